@@ -10,12 +10,19 @@ per GPU (BASELINE.json configs[1]), whole-job aggregate over N GPUs (weak scalin
 
 A step = SoTaskWrapModule.inference on one resident batch: encoder -> 24 TCN blocks -> mask -> decoder -> clamp.
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the roofline / cpu_baseline definitions).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of its own: the
+per-kernel roofline pass, the other fp32-class arithmetics, BASELINE configs 3 / 4 / 5 (`other_configs`) and the CPU
+baseline (each can still be left out with its --no-* option).  --dump-outputs DIR writes the output waveforms of the
+last timed step as DIR/enhanced.npy (float32; the inputs are seeded, so two builds can be compared output for output).
 """
 import argparse
 import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -132,11 +139,30 @@ def cpu_baseline(seconds_budget=75.0):
                               "sample": f"median of {one['runs']} timed runs of batch 1 x 4 s, torch.set_num_threads(1)"}}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, out):
+    """The output waveforms [B, L] of the last timed step as path/enhanced.npy, float32.  Above 64 MB (the gathered batch of 8
+    or more GPUs) a fixed, seeded sample of rows is written instead, the same rows on every run."""
+    y = out.detach().float().cpu().numpy()
+    if y.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (y.nbytes // y.shape[0])
+        y = y[np.sort(np.random.default_rng(0).choice(y.shape[0], keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "enhanced.npy"), np.ascontiguousarray(y))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra measurements: roofline pass, the other arithmetics, other_configs and the "
+                         "CPU baseline (off by default: a plain run only times the K steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output waveforms as DIR/enhanced.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
@@ -157,10 +183,14 @@ def main():
                          "operands scaled into fp16's range by powers of two -- against fp64 products and against the "
                          "reference's golden vectors its error is that of the exact fp32 MFMA path (config 2, pre-clamp "
                          "max-rel: 9.8e-7 vs 1.03e-6; tests/test_fp16x2.py).  bf16x3: three bf16 terms, six products, "
-                         "fp32-accurate by construction.  fp32: v_mfma_f32_* on fp32 operands.  The default run times "
+                         "fp32-accurate by construction.  fp32: v_mfma_f32_* on fp32 operands.  --full times "
                          "the other two as well and reports them in the same line.  bf16 (rounded operands) is not an "
                          "fp32 result and is labelled an experiment.")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_roofline = args.no_other_configs = args.no_cpu_baseline = True
 
     # `python bench.py --gpus N` on its own: start the N ranks as child processes (before anything here touches a GPU),
     # relay their output and leave with their status.  Under torch.distributed.run this is a no-op.
@@ -219,21 +249,26 @@ def main():
         return out
 
     def fence():
-        if overlap is not None:
-            overlap.flush()
+        last = overlap.flush() if overlap is not None else None
         torch.cuda.synchronize(dev)
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize(dev)
+        return last
 
     for _ in range(args.warmup):
         step()
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
-    fence()
+        out = step()
+    flushed = fence()
     elapsed = time.perf_counter() - t0
+    if flushed is not None:  # overlapped gather: the last step's result comes out of the flush
+        out = flushed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
+    del out, flushed
     rank_ms = [elapsed / args.steps * 1e3]
     if world > 1:
         mine = torch.tensor([elapsed], device=dev, dtype=torch.float64)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -11,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run(*extra):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", *extra], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", *extra],
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -21,7 +22,7 @@ def _run(*extra):
 
 @pytest.mark.parametrize("gemm", [None, "bf16x3", "fp32"])
 def test_bench_line(gemm):
-    d = _run(*(["--gemm", gemm] if gemm else []))
+    d = _run("--full", "--no-cpu-baseline", *(["--gemm", gemm] if gemm else []))
     if gemm is None:
         gemm = "fp16x2"  # the default arithmetic
         assert d["gemm"] == "fp16x2"
@@ -67,3 +68,30 @@ def test_bench_line(gemm):
     for k in ("dwconv", "free_encode", "free_decode"):
         assert 0.05 < r["hbm_bound_kernels"][k]["frac_of_8TBps"] < 1.0
 
+
+def test_plain_bench_line_times_only_the_steps_and_dumps_the_last_output(tmp_path):
+    """Without --full the line carries the headline fields only; --dump-outputs writes the last timed step's waveforms
+    of the seeded batch, the first of which is checked against the CPU oracle."""
+    d = _run("--dump-outputs", str(tmp_path))
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "gemm",
+                "config"):
+        assert key in d, key
+    assert d["steps"] == 2 and d["gemm"] == "fp16x2" and d["higher_is_better"] is True and d["unit"] == "samples/s"
+    assert abs(d["value"] - 32 * 64000 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    for key in ("roofline", "fp32_mfma_path", "bf16x3_path", "other_configs", "cpu_baseline"):
+        assert key not in d, key  # (--full)
+    y = np.load(tmp_path / "enhanced.npy")
+    assert y.dtype == np.float32 and y.shape == (32, 64000) and np.isfinite(y).all()
+    assert 0 < np.abs(y).max() <= 1.0  # the wrapper clamps its output waveforms
+    # row 0 against the CPU oracle, with the benchmark's model (seed 0) and input batch (seed 1234) rebuilt here
+    import torch
+    import cases
+    import puresound_amd.nnet as PA
+    from conftest import rel_max
+    from oracle import separator_oracle as O
+    torch.manual_seed(0)
+    model = cases.build(PA.NS, "cfg2_full").eval()
+    sd = {k: v.detach().float() for k, v in model.state_dict().items()}
+    noisy = (torch.rand(32, 64000, generator=torch.Generator().manual_seed(1234)) * 2 - 1) * 0.5
+    ref = O.inference(noisy[:1], sd, cases.oracle_cfg("cfg2_full"))
+    assert rel_max(y[:1], ref.numpy()) < 1e-4
