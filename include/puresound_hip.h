@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PS_ABI_VERSION 21
+#define PS_ABI_VERSION 22
 
 #define PS_E_INVALID (-1)     /* bad shape / null pointer / unsupported combination */
 #define PS_E_ALIGN (-2)       /* ldt or a pointer violates the alignment contract */
@@ -54,7 +54,7 @@ const char* ps_last_error(void);
  * ps_profile_read synchronises the recorded events and returns the summed duration and launch count
  * of one kernel family ("conv1x1", "dwconv", "free_encode", "free_decode", "embed_bias", "pad_rows",
  * "unpad_rows", "frame", "complex_mask", "istft_ola", "attn_stats_pool", "lstm", "lstm_cell", "chan_layernorm", "unfold_taps", "gated_product", "segment_overlap",
- * "film_conv", "lstm_gates_cell", "proj_layernorm", "overlap_average", "stream_windows", "stream_overlap", "conv1x1_bf16", "unfold2d", "conv2d", "activation", "add", "magnitude", "real_mask", "norm_activation", "self_attention", "add_position",
+ * "film_conv", "lstm_gates_cell", "proj_layernorm", "overlap_average", "stream_windows", "stream_overlap", "conv2d_step", "istft_step", "stream_commit", "conv1x1_bf16", "unfold2d", "conv2d", "activation", "add", "magnitude", "real_mask", "norm_activation", "self_attention", "add_position",
  * "film_apply").  Not for use under stream capture. */
 int ps_debug_flags(int flags); /* test/profiling hooks; bits 0..7, 20..30: kernel-variant switches (named where they are
                                   tested); bits 8..19: cap of the conv1x1 persistent grid (0 = off); <0 reads; returns
@@ -495,7 +495,8 @@ int ps_overlap_average_f32(const float* tail, int ld_tail, const float* cur, flo
                            void* stream);
 
 /* The same harness for ALL hops of a chunk in two launches (replaces the hop-by-hop window shift and overlap-add of
- * DemoTseNet.streaming_inference_chunk, egs/tse/demo/utils.py:100-128; win = 2 * hop):
+ * DemoTseNet.streaming_inference_chunk, egs/tse/demo/utils.py:100-128; win = 2 * hop for the overlap-add, win >= hop for the
+ * windows -- the conv-STFT streamer slides an n_fft window by hop):
  *   ps_stream_windows_f32  wins[i][b * win + j] = sig_b[i * hop + j], sig_b = queue[b][hop .. win) ++ chunk[b][0 .. hops * hop)
  *                          (queue [B][win] = the previous window, chunk [B][hops * hop]) -- one "utterance" per hop for the
  *                          encoder;
@@ -505,6 +506,52 @@ int ps_overlap_average_f32(const float* tail, int ld_tail, const float* cur, flo
 int ps_stream_windows_f32(const float* queue, const float* chunk, float* wins, int B, int hops, int win, int hop, void* stream);
 int ps_stream_overlap_f32(const float* frames, const float* wins, float* tail, float* blocks, float* queue, int B, int hops,
                           int win, int hop, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Streaming the causal conv-STFT U-Net maskers (DPCRN / DPARN, egs/ns ns_*_v0_causal) one hop at a time for B streams
+ * (puresound_amd/streaming/spectral.py).  The streams are the frame axis: one hop's activation of an offline [N][CH][F][ld]
+ * tensor is [1][CH][F][ldB], ldB = ps_padded_frames(B).  Previous frames live in per-source history RINGS [R][CH][F][ldB]
+ * (slot R-1 = frame t-1, slot R-d = frame t-d; zeroed at the start of a session, which is the causal zero padding), and
+ * `counter` is a device int = the index t of the frame being computed, advanced by ps_stream_commit_f32 -- so one captured
+ * graph replays every hop: no launch argument depends on t.
+ *
+ * ps_conv2d_step_f32: y[m][fo][b] = act( bias[m] + sum_k W[m][k] X[k][fo][b] ), k = (ci, jf, jt) = (ci*kf + jf)*kt + jt over
+ *   the C1 channels of source 1 then the C2 of source 2 (the decoder's torch.cat([x, skip], 1); C2 = 0: one source), b < B:
+ *     transposed = 0 (ZeroPad2d((kt-1)*dt, 0) + Conv2d, unet.py:112-128 with delay 0):
+ *        fi = fo*stride_f + jf*dil_f - pad_f,           frame t - (kt-1-jt)*dil_t
+ *     transposed = 1 (ConvTranspose2d trimmed to T, transpose_delay=False, unet.py:139-165,252-256):
+ *        fi = (fo + pad_f - jf*dil_f) / stride_f when divisible,  frame t - jt*dil_t
+ *   X = 0 for fi outside [0, Fin); frame t is x1 / x2 [C][Fin][ld], frame t-d (d >= 1) is slot R-d of ring1 / ring2
+ *   ([R][C][Fin][ld]; R >= (kt-1)*dil_t).  wt: packed as ps_conv1x1_f32 over K = (C1+C2)*kf*kt (eval BatchNorm2d folded in
+ *   by the caller); act 0 none, 1 relu, 2 prelu (one shared slope).  Exact fp32 products.  Writes y[m][fo][b] for b < B
+ *   only (y [M][Fout][ld]; its pad frames are left as they are).
+ * ps_istft_step_f32: ConvSTFT.inverse (lobe/encoder.py:432-454) one frame per stream.  flush = 0: t = *counter,
+ *   acc[j] = tail[b][j] + frames[j][b] * window[j] / n_fft (tail term 0 for j >= n_fft-hop),
+ *   out[b][j] = constrain( acc[j] / S(t*hop + j) ) for j < hop, tail[b][:] = acc[hop .. n_fft);
+ *   flush = 1 (after the last frame, T = *counter): out[b][j] = constrain( tail[b][j] / S(T*hop + j) ) for j < n_fft-hop.
+ *   S(g) = sum of window[g - u*hop]^2 over the frames 0 <= u <= min(g/hop, T-1) covering sample g, applied where > 1e-10 --
+ *   the window sum of ps_istft_ola_f32, edge frames included, summed in the same order.  frames [n_fft][ldf] (b < B read),
+ *   tail [B][n_fft-hop],
+ *   out row stride ld_out; out_mode PS_OUT_*.  n_fft % hop == 0, n_fft <= 8192 (n_fft = hop: no tail, flush emits nothing).
+ * ps_stream_commit_f32: for each of the n_pairs <= PS_MAX_RING_PAIRS entries of the HOST array pairs_host (copied into the
+ *   kernel arguments): ring[r] = ring[r+1] for r < slots-1, then ring[slots-1] = src (`count` floats per slot, a multiple of
+ *   4, 16-byte aligned; slots = 1 is a plain copy: the window queue, carried recurrent states); then *counter += 1
+ *   (counter may be NULL).  One launch per hop. */
+#define PS_MAX_RING_PAIRS 32
+typedef struct ps_ring_pair {
+  const float* src;
+  float* ring;
+  int64_t count;
+  int slots;
+  int reserved;
+} ps_ring_pair;
+int ps_conv2d_step_f32(const float* x1, const float* ring1, int C1, int R1, const float* x2, const float* ring2, int C2, int R2,
+                       const float* wt, const float* bias, float* y, int M, int Fin, int B, int ld, int kf, int kt,
+                       int stride_f, int dil_f, int dil_t, int pad_f, int Fout, int transposed, int act, const float* slope,
+                       void* stream);
+int ps_istft_step_f32(const float* frames, int ldf, const float* window, float* tail, float* out, int ld_out,
+                      const int* counter, int B, int n_fft, int hop, int out_mode, int flush, void* stream);
+int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs, int* counter, void* stream);
 
 /* One cell update per (unit, frame) from COMPLETE gate pre-activations gates [N][D*4H][ld_gates] (W_ih x + W_hh h + both
  * biases: the streaming step puts [x; h] on the K axis of one ps_conv1x1_f32):  c' = sig(f) c + sig(i) tanh(g) in

@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PURESOUND_HIP_LIB: an experimental build of the same library (tools/build_variant.sh); kernel experiments only
 LIB_PATH = os.environ.get("PURESOUND_HIP_LIB") or os.path.join(_HERE, "libpuresound_hip.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 PS_NORM_NONE, PS_NORM_GLOBAL, PS_NORM_AFFINE = 0, 1, 2
 PS_ACT = {"linear": 0, "relu": 1, "sigmoid": 2}
@@ -49,6 +49,13 @@ class GatesCell(C.Structure):
 class ProjLnCell(C.Structure):
     _fields_ = [(k, _vp) for k in ("x", "wt", "bias", "gamma", "beta", "res", "y", "gamma2", "beta2", "y2", "x_copy")] + [
         ("eps", C.c_float), ("eps2", C.c_float)]
+
+
+PS_MAX_RING_PAIRS = 32
+
+
+class RingPair(C.Structure):
+    _fields_ = [("src", _vp), ("ring", _vp), ("count", C.c_int64), ("slots", C.c_int), ("reserved", C.c_int)]
 
 
 class LstmArgs(C.Structure):
@@ -140,6 +147,10 @@ SIGNATURES = {
     "ps_overlap_average_f32": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "ps_stream_windows_f32": (C.c_int, [_vp, _vp, _vp] + [C.c_int] * 4 + [_vp]),
     "ps_stream_overlap_f32": (C.c_int, [_vp] * 5 + [C.c_int] * 4 + [_vp]),
+    "ps_conv2d_step_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp] + [C.c_int] * 13
+                           + [_vp, _vp]),
+    "ps_istft_step_f32": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp] + [C.c_int] * 5 + [_vp]),
+    "ps_stream_commit_f32": (C.c_int, [C.POINTER(RingPair), C.c_int, _vp, _vp]),
     "ps_unfold2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp] + [C.c_int] * 14 + [_vp]),
     "ps_conv2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 16 + [_vp, _vp]),
     "ps_conv2d_stats_parts": (C.c_int, [C.c_int] * 3),

@@ -745,9 +745,9 @@ extern "C" int ps_overlap_average_f32(const float* tail, int ld_tail, const floa
 
 extern "C" int ps_stream_windows_f32(const float* queue, const float* chunk, float* wins, int B, int hops, int win,
                                      int hop, void* stream) {
-  if (!queue || !chunk || !wins || B <= 0 || hops <= 0 || hop <= 0 || win != 2 * hop ||
+  if (!queue || !chunk || !wins || B <= 0 || hops <= 0 || hop <= 0 || win < hop ||
       (long long)B * hops * win > 0x7fffffffLL) {
-    set_error("ps_stream_windows_f32: bad argument (B=%d hops=%d win=%d hop=%d; win must be 2 * hop)", B, hops, win, hop);
+    set_error("ps_stream_windows_f32: bad argument (B=%d hops=%d win=%d hop=%d; win must be >= hop)", B, hops, win, hop);
     return PS_E_INVALID;
   }
   LaunchTimer timer("stream_windows", (hipStream_t)stream);

@@ -11,8 +11,8 @@ from typing import Optional, Sequence
 import torch
 
 from . import _abi
-from ._abi import (F16x2Range, LstmArgs, Prologue, TcnBlock, check, lib, padded_frames, ptr, require_device, require_weight,
-                   stream_ptr)
+from ._abi import (F16x2Range, LstmArgs, Prologue, RingPair, TcnBlock, check, lib, padded_frames, ptr, require_device,
+                   require_weight, stream_ptr)
 
 
 def pack_wt(w: torch.Tensor) -> torch.Tensor:
@@ -847,7 +847,8 @@ def overlap_average(prev: torch.Tensor, cur: torch.Tensor, overlap: int) -> torc
 
 
 def stream_windows(queue: torch.Tensor, chunk: torch.Tensor, wins: torch.Tensor, hop: int) -> None:
-    """queue [B, 2 hop] ‖ chunk [B, hops * hop] -> wins [hops, B * 2 hop]: window i of stream b (ps_stream_windows_f32)."""
+    """queue [B, win] ‖ chunk [B, hops * hop] -> wins [hops, B * win]: window i of stream b = samples [i hop, i hop + win) of
+    queue[:, hop:] ‖ chunk (ps_stream_windows_f32; win >= hop)."""
     require_device(chunk, "stream_windows")
     b, win = queue.shape
     hops = chunk.shape[1] // hop
@@ -871,6 +872,75 @@ def stream_overlap(frames: torch.Tensor, wins: torch.Tensor, tail: torch.Tensor,
 
 
 ACT_KINDS = {"none": 0, "relu": 1, "prelu": 2, "mish": 3, "sigmoid": 4, "tanh": 5}
+
+
+def conv2d_step(x1: torch.Tensor, ring1: Optional[torch.Tensor], x2: Optional[torch.Tensor], ring2: Optional[torch.Tensor],
+                wt: torch.Tensor, bias: Optional[torch.Tensor], m: int, b: int, f_out: int, kf: int, kt: int, stride_f: int,
+                dil_f: int, dil_t: int, pad_f: int, transposed: bool, act: str = "none", slope: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One causal frame of a Conv2d / ConvTranspose2d for b streams (ps_conv2d_step_f32): current frames x1 [1, C1, F, ld]
+    (+ x2 [1, C2, F, ld]), previous frames from the rings [R, C, F, ld] (slot R - d = frame t - d) -> [1, m, f_out, ld]
+    (columns b..ld of `out` are not written)."""
+    require_device(x1, "conv2d_step")
+    _, c1, f_in, ld = x1.shape
+    c2 = 0 if x2 is None else x2.shape[1]
+    for src, ring in ((x1, ring1), (x2, ring2)):
+        if src is None:
+            continue
+        if not src.is_contiguous() or src.shape[0] != 1 or (src.shape[2], src.shape[3]) != (f_in, ld):
+            raise RuntimeError("conv2d_step: the sources must be contiguous [1, C, F, ld] with one F and ld")
+        if ring is not None and (not ring.is_contiguous() or tuple(ring.shape[1:]) != tuple(src.shape[1:])):
+            raise RuntimeError("conv2d_step: a ring must be a contiguous [R, C, F, ld] of its source's frame shape")
+    y = out if out is not None else torch.zeros(1, m, f_out, ld, dtype=torch.float32, device=x1.device)
+    if tuple(y.shape) != (1, m, f_out, ld) or not y.is_contiguous():
+        raise RuntimeError(f"conv2d_step: out must be a contiguous {(1, m, f_out, ld)} tensor")
+    r1 = 0 if ring1 is None else ring1.shape[0]
+    r2 = 0 if ring2 is None else ring2.shape[0]
+    check(lib().ps_conv2d_step_f32(ptr(x1), ptr(ring1), c1, r1, ptr(x2), ptr(ring2), c2, r2, ptr(wt), ptr(bias), ptr(y), m,
+                                   f_in, b, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, f_out, int(transposed), ACT_KINDS[act],
+                                   ptr(slope), stream_ptr(x1.device)), "ps_conv2d_step_f32")
+    return y
+
+
+def istft_step(frames: Optional[torch.Tensor], window: torch.Tensor, tail: torch.Tensor, out: torch.Tensor,
+               counter: torch.Tensor, hop: int, out_mode: str = "none", flush: bool = False) -> torch.Tensor:
+    """Synthesis of frame t = counter[0] of every stream (ps_istft_step_f32): frames padded [1, n_fft, ldB] -> out [B, hop]
+    (a row view of a wider buffer is fine), overlap-add tail [B, n_fft - hop] updated in place; flush: the tail's samples
+    after the last frame -> out [B, n_fft - hop]."""
+    require_device(tail, "istft_step")
+    b, keep = tail.shape
+    n_fft = keep + hop
+    if not tail.is_contiguous() or out.dim() != 2 or out.shape[0] != b or out.stride(1) != 1 \
+            or out.shape[1] != (keep if flush else hop) or counter.dtype != torch.int32:
+        raise RuntimeError("istft_step: tail [B, n_fft - hop] contiguous, out [B, hop] (flush: [B, n_fft - hop]) with unit "
+                           "column stride, int32 counter expected")
+    ldf = 0
+    if flush and keep == 0:
+        return out
+    if not flush:
+        if frames is None or frames.shape[:2] != (1, n_fft) or not frames.is_contiguous():
+            raise RuntimeError("istft_step: frames must be a contiguous [1, n_fft, ldB] tensor")
+        ldf = frames.shape[2]
+    check(lib().ps_istft_step_f32(ptr(frames), ldf, ptr(window), ptr(tail), ptr(out), out.stride(0), ptr(counter), b, n_fft,
+                                  hop, _abi.PS_OUT[out_mode], int(flush), stream_ptr(tail.device)), "ps_istft_step_f32")
+    return out
+
+
+def commit_table(pairs: Sequence[tuple]) -> "C.Array[RingPair]":
+    """[(src, ring), ...] -> the host table of ps_stream_commit_f32 (ring [R, *src.shape]: R slots of src's size)."""
+    if not 0 < len(pairs) <= _abi.PS_MAX_RING_PAIRS:
+        raise RuntimeError(f"commit_table: 1 .. {_abi.PS_MAX_RING_PAIRS} pairs")
+    tab = (RingPair * len(pairs))()
+    for e, (src, ring) in zip(tab, pairs):
+        if not (src.is_contiguous() and ring.is_contiguous()) or ring.numel() % src.numel():
+            raise RuntimeError("commit_table: contiguous src and ring, the ring a whole number of src-sized slots")
+        e.src, e.ring, e.count, e.slots = ptr(src), ptr(ring), src.numel(), ring.numel() // src.numel()
+    return tab
+
+
+def stream_commit(table: "C.Array[RingPair]", counter: Optional[torch.Tensor], device: torch.device) -> None:
+    """Shift every ring of the table by one frame (newest = its source) and advance the frame counter (ps_stream_commit_f32)."""
+    check(lib().ps_stream_commit_f32(table, len(table), ptr(counter), stream_ptr(device)), "ps_stream_commit_f32")
 
 
 def unfold2d(x1: torch.Tensor, x2: Optional[torch.Tensor], t: int, f_out: int, kf: int, kt: int, stride_f: int,

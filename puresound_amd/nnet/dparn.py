@@ -62,6 +62,24 @@ class DPARNblock2D(PlanCache, nn.Module):
         y, _ = lstm_path(y, frames, *p["inter"], q=f, q_stride=ld, steps=t, step_stride=1, amax=amax, skip=inter_skip)
         return y.view(n, ch, f, ld)
 
+    def forward_step(self, x: torch.Tensor, b: int, h0: torch.Tensor, c0: torch.Tensor, state_out: tuple) -> torch.Tensor:
+        """One frame of b streams (streaming/spectral.py), exact fp32 arithmetic (the caller's plans): the intra attention
+        layers, Linear + LayerNorm + skip as offline with t = b; the inter LSTM one step per (f, b) sequence from the carried
+        states h0 / c0 [1, H, F*ld] into state_out."""
+        if self.gemm_precision != "fp32":
+            raise RuntimeError("DPARNblock2D.forward_step: exact fp32 plans only")
+        p = self._plan_get(x.device, self._build)
+        n, ch, f, ld = x.shape
+        y = x.view(n, ch, f * ld)
+        frames = (f - 1) * ld + b
+        a = self.intra_atten1.forward_padded(y, frames, b, 1, f, ld)
+        a = self.intra_atten2.forward_padded(a, frames, b, 1, f, ld)
+        fn = p["fc_norm"]
+        y, _ = hip.proj_layernorm(a, frames, p["fc"]["wt"], p["fc"]["bias"], ch, fn["gamma"], fn["beta"], fn["eps"], y)
+        y, _ = lstm_path(y, frames, *p["inter"], q=frames, q_stride=1, steps=1, step_stride=0, h0=h0, c0=c0,
+                         state_out=state_out)
+        return y.view(n, ch, f, ld)
+
     def forward(self, x: torch.Tensor, intra_skip: bool = True, inter_skip: bool = True) -> torch.Tensor:
         hip.require_device(x, "DPARNblock2D.forward")
         n, ch, f, t = x.shape

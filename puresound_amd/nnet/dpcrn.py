@@ -46,6 +46,21 @@ class DPRNNblock2D(PlanCache, nn.Module):
         y, _ = lstm_path(y, frames, *p["inter"], q=f, q_stride=ld, steps=t, step_stride=1, amax=amax, skip=inter_skip)
         return y.view(n, ch, f, ld)
 
+    def forward_step(self, x: torch.Tensor, b: int, h0: torch.Tensor, c0: torch.Tensor, state_out: tuple) -> torch.Tensor:
+        """One frame of b streams (streaming/spectral.py): x [1, CH, F, ld] with the streams on the frame axis.  The intra
+        pass is the offline one with t = b (one sequence per stream along F); the inter LSTM takes one step per (f, b)
+        sequence from the carried states h0 / c0 [1, H, F*ld] and writes the new ones into state_out.  Exact fp32 plans."""
+        if self.gemm_precision != "fp32":
+            raise RuntimeError("DPRNNblock2D.forward_step: exact fp32 plans only")
+        p = self._plan_get(x.device, self._build)
+        n, ch, f, ld = x.shape
+        y = x.view(n, ch, f * ld)
+        frames = (f - 1) * ld + b
+        y, _ = lstm_path(y, frames, *p["intra"], q=b, q_stride=1, steps=f, step_stride=ld)
+        y, _ = lstm_path(y, frames, *p["inter"], q=frames, q_stride=1, steps=1, step_stride=0, h0=h0, c0=c0,
+                         state_out=state_out)
+        return y.view(n, ch, f, ld)
+
     def forward(self, x: torch.Tensor, intra_skip: bool = True, inter_skip: bool = True) -> torch.Tensor:
         hip.require_device(x, "DPRNNblock2D.forward")
         n, ch, f, t = x.shape

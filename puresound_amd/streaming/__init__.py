@@ -1,2 +1,4 @@
-"""Mirror of `puresound.streaming` (chunked / frame-by-frame forward of the SkiM masker)."""
+"""Mirror of `puresound.streaming` (chunked / frame-by-frame forward of the SkiM masker), and hop-by-hop streaming of the
+causal conv-STFT U-Net noise suppressors (spectral.py)."""
 from .skim_inference import StreamingSkiM  # noqa: F401
+from .spectral import StreamingSeparator  # noqa: F401
