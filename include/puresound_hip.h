@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PS_ABI_VERSION 22
+#define PS_ABI_VERSION 23
 
 #define PS_E_INVALID (-1)     /* bad shape / null pointer / unsupported combination */
 #define PS_E_ALIGN (-2)       /* ldt or a pointer violates the alignment contract */
@@ -56,12 +56,43 @@ const char* ps_last_error(void);
  * "unpad_rows", "frame", "complex_mask", "istft_ola", "attn_stats_pool", "lstm", "lstm_cell", "chan_layernorm", "unfold_taps", "gated_product", "segment_overlap",
  * "film_conv", "lstm_gates_cell", "proj_layernorm", "overlap_average", "stream_windows", "stream_overlap", "conv2d_step", "istft_step", "stream_commit", "conv1x1_bf16", "unfold2d", "conv2d", "activation", "add", "magnitude", "real_mask", "norm_activation", "self_attention", "add_position",
  * "film_apply").  Not for use under stream capture. */
-int ps_debug_flags(int flags); /* test/profiling hooks; bits 0..7, 20..30: kernel-variant switches (named where they are
-                                  tested); bits 8..19: cap of the conv1x1 persistent grid (0 = off); <0 reads; returns
-                                  the old value */
-int ps_debug_buffer(void* device_buffer); /* 6 x u64 per conv1x1 workgroup: s_memtime stamps + HW ids */
 int ps_profile_enable(int on);
 int ps_profile_read(const char* kernel, double* total_ms, int* launches);
+
+/* Test / profiling hooks, all 0 in production.  Each setter takes a value >= 0 to set (< 0 only reads) and returns the
+ * old value.  ps_debug_flags carries the PS_DBG_* switches below: each one makes one dispatcher take the kernel it names
+ * instead of its default, so that tests can reach fallback kernels the default dispatch does not pick for their shape.
+ * A switch keeps the bit its choice had when the flags also held the grid cap and the ablation mask; switches split off
+ * a bit that several dispatchers shared took free bits. */
+enum {
+  PS_DBG_DWCONV_WG = 1 << 0,  /* ps_dwconv_f32 / _io: the workgroup-synchronised kernel, not the wave-private one */
+  PS_DBG_ENCDEC_VALU = 1 << 7,  /* ps_free_encode_f32 / ps_free_decode_ws_f32: the VALU kernels, not the MFMA ones */
+  PS_DBG_POOL_THREE_PASS = 1 << 24,  /* ps_attn_stats_pool_*: the three-pass kernel, not the one-pass register one */
+  PS_DBG_CONV1X1_TILED = 1 << 4,  /* ps_conv1x1_f32: 256 x 128 tiles for rows of <= 64 frames too (no small kernel) */
+  PS_DBG_PROJ_LN_FRAMES16 = 1 << 25,  /* ps_proj_layernorm_*: the 16-frame kernel for long rows too */
+  PS_DBG_PROJ_LN_UNPIPELINED = 1 << 26,  /* ps_proj_layernorm_*: the unpipelined row kernel at K = 64, M = 128 */
+  PS_DBG_GEMM_TWO_BARRIER = 1 << 5,  /* bf16 / fp16x2 GEMM: the two-barrier ping-pong kernel, not the interleaved one */
+  PS_DBG_GEMM_NO_PAIR = 1 << 6,  /* bf16 / fp16x2 GEMM: no m-tile pairing of the interleaved / register-B grids */
+  PS_DBG_GEMM_NO_RB = 1 << 22,  /* fp16x2 GEMM: the interleaved kernel, not the register-B one */
+  PS_DBG_GEMM_SIMPLE = 1 << 27,  /* bf16 / fp16x2 GEMM: the simple tiled kernel, no persistent one */
+  PS_DBG_GEMM_ANY_SIZE = 1 << 28,  /* bf16 / fp16x2 GEMM: the persistent kernels at any launch size */
+  PS_DBG_GEMM_WIDE_TILE = 1 << 29,  /* bf16 / fp16x2 GEMM: the simple kernel keeps 256 x 128 tiles on small launches */
+  PS_DBG_LSTM_SCALAR = 1 << 1,  /* ps_lstm_f32 / _f16x2_f32: the per-sequence VALU kernel, not the MFMA ones */
+  PS_DBG_LSTM_WIDE = 1 << 2,  /* ps_lstm_f32 / _f16x2_f32: 16 sequences per workgroup whatever the batch */
+  PS_DBG_LSTM_M4 = 1 << 3,  /* ps_lstm_f32 / _f16x2_f32: 4 sequences per workgroup whatever the batch */
+  PS_DBG_LSTM_4B_STORES = 1 << 20,  /* LSTM kernels: 4-byte h' stores, no grouped steps (ps_lstm_f32's segment and fp16x2
+                                      4-sequence kernels, ps_lstm_fmajor_*'s 8- / 16-byte stores) */
+  PS_DBG_COOP_SABOTAGE = 1 << 17,  /* cooperative LSTM: slice 0 never arrives at a barrier (bounded-poll test) */
+  PS_DBG_COOP_SCATTER = 1 << 18,  /* cooperative LSTM: a group's slices on different XCDs */
+  PS_DBG_COOP_AGENT_FENCES = 1 << 19,  /* cooperative LSTM: agent-scope fences even when a group shares one XCD */
+  PS_DBG_ATTN_GENERAL = 1 << 23,  /* ps_self_attention_f32: the general kernel, not the register-score one */
+  PS_DBG_ATTN_NARROW = 1 << 21,  /* ps_self_attention_f32: 4 sequences per workgroup, not 8, at dh = 16 */
+  PS_DBG_CHAN_LN_THREE_PASS = 1 << 30  /* ps_chan_layernorm_f32: the three-pass kernel, not the register one */
+};
+int ps_debug_flags(int flags);  /* PS_DBG_* switches */
+int ps_debug_grid_cap(int cap);  /* cap of the conv1x1 / bf16 GEMM persistent grids (0 = off) */
+int ps_debug_ablate(int mask);  /* timing experiments (results are wrong): parts of the GEMM / LSTM kernels removed */
+int ps_debug_buffer(void* device_buffer);  /* 6 x u64 per conv1x1 workgroup: s_memtime stamps + HW ids */
 
 /* Number of doubles a stats buffer needs: partial (sum, sum-of-squares) slabs per utterance.
  * Stats are handed from the producing kernel to the consuming kernel as per-workgroup partials

@@ -4,6 +4,7 @@ There is no CPU fallback: if the library is missing or a call fails, a RuntimeEr
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional
@@ -13,11 +14,35 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PURESOUND_HIP_LIB: an experimental build of the same library (tools/build_variant.sh); kernel experiments only
 LIB_PATH = os.environ.get("PURESOUND_HIP_LIB") or os.path.join(_HERE, "libpuresound_hip.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 PS_NORM_NONE, PS_NORM_GLOBAL, PS_NORM_AFFINE = 0, 1, 2
 PS_ACT = {"linear": 0, "relu": 1, "sigmoid": 2}
 PS_OUT = {"linear": 0, "sigmoid": 1, "none": 2}
+
+# ps_debug_flags switches (include/puresound_hip.h names the kernel each one selects); tests and tools only
+PS_DBG_DWCONV_WG = 1 << 0
+PS_DBG_ENCDEC_VALU = 1 << 7
+PS_DBG_POOL_THREE_PASS = 1 << 24
+PS_DBG_CONV1X1_TILED = 1 << 4
+PS_DBG_PROJ_LN_FRAMES16 = 1 << 25
+PS_DBG_PROJ_LN_UNPIPELINED = 1 << 26
+PS_DBG_GEMM_TWO_BARRIER = 1 << 5
+PS_DBG_GEMM_NO_PAIR = 1 << 6
+PS_DBG_GEMM_NO_RB = 1 << 22
+PS_DBG_GEMM_SIMPLE = 1 << 27
+PS_DBG_GEMM_ANY_SIZE = 1 << 28
+PS_DBG_GEMM_WIDE_TILE = 1 << 29
+PS_DBG_LSTM_SCALAR = 1 << 1
+PS_DBG_LSTM_WIDE = 1 << 2
+PS_DBG_LSTM_M4 = 1 << 3
+PS_DBG_LSTM_4B_STORES = 1 << 20
+PS_DBG_COOP_SABOTAGE = 1 << 17
+PS_DBG_COOP_SCATTER = 1 << 18
+PS_DBG_COOP_AGENT_FENCES = 1 << 19
+PS_DBG_ATTN_GENERAL = 1 << 23
+PS_DBG_ATTN_NARROW = 1 << 21
+PS_DBG_CHAN_LN_THREE_PASS = 1 << 30
 
 _f = C.POINTER(C.c_float)
 _d = C.POINTER(C.c_double)
@@ -82,6 +107,8 @@ SIGNATURES = {
     "ps_abi_version": (C.c_int, []),
     "ps_last_error": (C.c_char_p, []),
     "ps_debug_flags": (C.c_int, [C.c_int]),
+    "ps_debug_grid_cap": (C.c_int, [C.c_int]),
+    "ps_debug_ablate": (C.c_int, [C.c_int]),
     "ps_debug_buffer": (C.c_int, [_vp]),
     "ps_profile_enable": (C.c_int, [C.c_int]),
     "ps_profile_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
@@ -205,6 +232,20 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"libpuresound_hip.so ABI {handle.ps_abi_version()} != binding {ABI_VERSION}")
         _lib = handle
     return _lib
+
+
+@contextlib.contextmanager
+def debug(flags: int = 0, grid_cap: int = 0, ablate: int = 0):
+    """Run the block with these debug settings (PS_DBG_* switches, persistent-grid cap, ablation mask) and restore the
+    previous ones on exit."""
+    L = lib()
+    old = (L.ps_debug_flags(flags), L.ps_debug_grid_cap(grid_cap), L.ps_debug_ablate(ablate))
+    try:
+        yield
+    finally:
+        L.ps_debug_flags(old[0])
+        L.ps_debug_grid_cap(old[1])
+        L.ps_debug_ablate(old[2])
 
 
 def check(rc: int, what: str) -> None:

@@ -15,6 +15,8 @@ namespace ps {
 
 static thread_local char g_err[512] = "";
 int g_debug_flags = 0;
+int g_debug_grid_cap = 0;
+int g_debug_ablate = 0;
 void* g_debug_buffer = nullptr;
 
 void set_error(const char* fmt, ...) {
@@ -74,11 +76,14 @@ int device_cus() {
 extern "C" int ps_abi_version(void) { return PS_ABI_VERSION; }
 extern "C" const char* ps_last_error(void) { return g_err; }
 
-extern "C" int ps_debug_flags(int flags) {
-  const int old = g_debug_flags;
-  if (flags >= 0) g_debug_flags = flags;
+static int swap_if_set(int& g, int v) {
+  const int old = g;
+  if (v >= 0) g = v;
   return old;
 }
+extern "C" int ps_debug_flags(int flags) { return swap_if_set(g_debug_flags, flags); }
+extern "C" int ps_debug_grid_cap(int cap) { return swap_if_set(g_debug_grid_cap, cap); }
+extern "C" int ps_debug_ablate(int mask) { return swap_if_set(g_debug_ablate, mask); }
 
 extern "C" int ps_debug_buffer(void* device_buffer) {
   g_debug_buffer = device_buffer;

@@ -208,14 +208,14 @@ extern "C" int ps_self_attention_f32(const float* qkv, float* out, int N, int E,
     return PS_E_INVALID;
   }
   AttArgs a{qkv, out, E, heads, Q, q_stride, L, pos_stride, ld, causal, 1.f / sqrtf((float)dh)};
-  // L <= 64 positions with a head dimension of 16 / 32 / 64: the register-score kernel (ps_debug_flags bit 23 keeps the
+  // L <= 64 positions with a head dimension of 16 / 32 / 64: the register-score kernel (PS_DBG_ATTN_GENERAL keeps the
   // general one; tests run both)
   // (8 sequences per workgroup when their K / V fit: a workgroup then uses 32 bytes of every 128-byte line it touches
-  //  instead of 16, and the L2 -> L1 fill traffic halves; ps_debug_flags bit 21 keeps 4)
+  //  instead of 16, and the L2 -> L1 fill traffic halves; PS_DBG_ATTN_NARROW keeps 4)
   const size_t lds64 = (size_t)2 * L * ATT_SQ * (dh + 4) * sizeof(float);
-  if (L <= 64 && (dh == 16 || dh == 32 || dh == 64) && lds64 <= 64 * 1024 && !(g_debug_flags & (1 << 23))) {
+  if (L <= 64 && (dh == 16 || dh == 32 || dh == 64) && lds64 <= 64 * 1024 && !dbg(PS_DBG_ATTN_GENERAL)) {
     LaunchTimer timer("self_attention", (hipStream_t)stream);
-    const bool wide = dh == 16 && 2 * lds64 <= 96 * 1024 && !(g_debug_flags & (1 << 21));
+    const bool wide = dh == 16 && 2 * lds64 <= 96 * 1024 && !dbg(PS_DBG_ATTN_NARROW);
     const int sq = wide ? 8 : ATT_SQ;
     dim3 g((((Q + sq - 1) / sq) + 7) / 8 * 8, heads, N);
     if (wide) {

@@ -615,8 +615,8 @@ extern "C" int ps_conv1x1_f32(const float* x, const float* wt, float* y, int N, 
       return PS_E_INVALID;
     }
   }
-  // short rows (streaming step, state rows): channel-split kernel instead of 256 x 128 tiles (debug bit 4 = off)
-  if (T <= 64 && !ostats && !(pro && pro->norm == PS_NORM_GLOBAL) && !(g_debug_flags & 16)) {
+  // short rows (streaming step, state rows): channel-split kernel instead of 256 x 128 tiles (PS_DBG_CONV1X1_TILED = off)
+  if (T <= 64 && !ostats && !(pro && pro->norm == PS_NORM_GLOBAL) && !dbg(PS_DBG_CONV1X1_TILED)) {
     conv1x1_small_launch(x, wt, y, N, K, M, T, ldt, pro, bias, bias_n, res, (hipStream_t)stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -668,9 +668,9 @@ extern "C" int ps_conv1x1_f32(const float* x, const float* wt, float* y, int N, 
   if (a.nsteps < 2) a.nsteps = 2;  // the residual prefetch needs a K-step before the draining one
   a.stamps = (unsigned long long*)g_debug_buffer;
   int grid = a.ntiles < persistent_grid() ? a.ntiles : persistent_grid();
-  // test hook (ps_debug_flags bits 8..23): cap the persistent grid so that a workgroup's run spans many
+  // test hook (ps_debug_grid_cap): cap the persistent grid so that a workgroup's run spans many
   // tiles / utterances even on small problems
-  if ((g_debug_flags >> 8) & 0xfff) grid = grid < ((g_debug_flags >> 8) & 0xfff) ? grid : ((g_debug_flags >> 8) & 0xfff);
+  if (g_debug_grid_cap && grid > g_debug_grid_cap) grid = g_debug_grid_cap;
   const bool tr = a.pro.norm != PS_NORM_NONE || a.pro.prelu || a.pro.pre_relu || a.pro.post_tanh;
   {
     LaunchTimer timer("conv1x1", (hipStream_t)stream);

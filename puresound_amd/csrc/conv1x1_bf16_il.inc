@@ -669,7 +669,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_bf16_il_kernel(BfArgs a) {
       constexpr int mi = decltype(mi_c)::value, q = decltype(q_c)::value;
       if constexpr (q == 0 && mi < 3) read_afrags(sa, bic<mi + 1>{});  // requested before this row block's MFMAs issue
       __builtin_amdgcn_sched_barrier(0);
-#ifdef PS_PP_STAMPS  // (diagnostic build: ps_debug_flags bits 24 / 26 ablate the MFMAs / the chunks)
+#ifdef PS_PP_STAMPS  // (diagnostic build: ps_debug_ablate 1 / 4 removes the MFMAs / the chunks)
       const bool do_chunk = !(a.ablate & 4);
       if (!(a.ablate & 1))
 #else

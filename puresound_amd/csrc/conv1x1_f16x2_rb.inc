@@ -674,7 +674,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x2_rb_kernel(BfArgs a) {
       constexpr int rb = decltype(rb_c)::value;
       if constexpr (rb + AD < 16) read_afrags(sa, bic<(rb + AD) % 16>{});
       __builtin_amdgcn_sched_barrier(0);
-#ifdef PS_PP_STAMPS  // (diagnostic build: ps_debug_flags bits 24 / 26 ablate the MFMAs / the chunks)
+#ifdef PS_PP_STAMPS  // (diagnostic build: ps_debug_ablate 1 / 4 removes the MFMAs / the chunks)
       const bool do_chunk = !(a.ablate & 4);
       if (!(a.ablate & 1))
 #else

@@ -896,13 +896,13 @@ extern "C" int ps_proj_layernorm_amax_f32(const float* x, const float* wt, const
     return PS_E_UNSUPPORTED;
   }
   ProjLnArgs a{x, wt, bias, gamma, beta, res, y, gamma2, beta2, y2, x_copy, res_inside, eps, eps2, K, (K + 15) / 16 * 16, M, T, ldt, N, y_amax};
-  // long rows without the streaming step's extras: the row kernel (ps_debug_flags bit 4 keeps the 16-frame kernel: tests
-  // compare the two on the same data)
+  // long rows without the streaming step's extras: the row kernel (PS_DBG_PROJ_LN_FRAMES16 keeps the 16-frame kernel:
+  // tests compare the two on the same data)
   const int kp = (K + 15) / 16 * 16;
   const int nb = M <= 128 ? 4 : 8;
   const size_t lds = ((size_t)kp * (nb * 32 + 32) + 3 * nb * 32) * sizeof(float);
   if (!y2 && !x_copy && T >= 128 && M % 4 == 0 && lds <= 128 * 1024 && (long long)(M > K ? M : K) * ldt * 4 < (1ll << 31) &&
-      !(g_debug_flags & 16)) {
+      !dbg(PS_DBG_PROJ_LN_FRAMES16)) {
     LaunchTimer timer("proj_layernorm", (hipStream_t)stream);
     const long long tiles = (long long)((T + 127) / 128) * N;
     // one persistent workgroup per CU (the kernel holds a tile's accumulators AND its residual values: 256 registers, one
@@ -911,7 +911,7 @@ extern "C" int ps_proj_layernorm_amax_f32(const float* x, const float* wt, const
     const long long per_cu = nb == 4 ? (lds <= 76 * 1024 ? 2 : 1) : 1;
     const long long slots = (long long)device_cus() * per_cu;
     dim3 grid((unsigned)(tiles < slots ? tiles : slots));
-    if (K == 64 && M == 128 && !(g_debug_flags & (1 << 21))) {  // (debug bit 21: the unpipelined kernel, for the tests)
+    if (K == 64 && M == 128 && !dbg(PS_DBG_PROJ_LN_UNPIPELINED)) {  // (else the unpipelined kernel, for the tests)
       const long long slots2 = (long long)device_cus() * 2;  // (three per CU, 168 registers and 11 spills: 44.9 us against 42.5)
       const size_t lds64 = ((size_t)64 * (4 * 32 + 32) + 3 * 4 * 32) * sizeof(float);
       hipLaunchKernelGGL(proj_layernorm_rows64_kernel, dim3((unsigned)(tiles < slots2 ? tiles : slots2)), dim3(256), lds64,

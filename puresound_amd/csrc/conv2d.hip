@@ -6,10 +6,10 @@
 //   conv:        B_fo[k][t] = x[n][ci][fo*sf + jf*df - pf][t + jt*dt - pt]
 //   transposed:  B_fo[k][t] = x[n][ci][(fo + pf - jf*df)/sf][t + pt - jt*dt]   (when divisible)       0 outside the input
 //
-// A workgroup owns one output frequency row fo of one utterance, 128 frames and MB*32 output channels; wave w owns
-// frames [32w, 32w+32) of the tile and all its channels (MB accumulators of v_mfma_f32_32x32x2_f32), so every B element is
-// needed by exactly one wave and goes from global memory to its lane without LDS.  The k -> (source row, time shift)
-// table of this fo lives in LDS.  Weights come from the packed transposed layout of ps_conv1x1_f32 (L2 resident).
+// conv2d_lds_kernel: a workgroup owns one output frequency row fo of one utterance, 128 frames and MB*32 output channels;
+// wave w owns frames [32w, 32w+32) of the tile and all its channels (MB accumulators of v_mfma_f32_32x32x2_f32), so every
+// B element is needed by exactly one wave and goes from global memory to its lane without LDS.  The k -> (source row, time
+// shift) table of this fo lives in LDS.  Weights come from the packed transposed layout of ps_conv1x1_f32.
 // Eval BatchNorm2d is folded into W / bias by the caller; the activation is the epilogue.
 #include <type_traits>
 
@@ -42,114 +42,10 @@ __device__ __forceinline__ float act_apply(float u, int kind, float s) {
   }
 }
 
-template <int MB>
-__global__ __launch_bounds__(256) void conv2d_kernel(Conv2dArgs a) {
-  // dynamic LDS, 2 * Kp ints (round 4: the static 32 KiB tables held a CU to five workgroups whatever K was)
-  extern __shared__ int c2d_tab[];
-  int* const tab_off = c2d_tab;            // element offset of the source row inside the utterance (bit 30: second source), -1 = zero row
-  int* const tab_shift = c2d_tab + a.Kp;  // frame shift
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int lr = lane & 31, lk = lane >> 5;
-  const int t0 = blockIdx.x * 128, fo = blockIdx.y;
-  const int mtiles = (a.M + 32 * MB - 1) / (32 * MB);
-  const int n = blockIdx.z / mtiles, m0 = (blockIdx.z % mtiles) * 32 * MB;
-
-  for (int k = tid; k < a.Kp; k += 256) {
-    int off = -1, sh = 0;
-    if (k < a.K) {
-      const int jt = k % a.kt, jf = (k / a.kt) % a.kf, ci = k / (a.kt * a.kf);
-      int fi;
-      bool ok = true;
-      if (!a.transposed) {
-        fi = fo * a.sf + jf * a.df - a.pf;
-        sh = jt * a.dt - a.pt;
-      } else {
-        const int num = fo + a.pf - jf * a.df;
-        ok = num >= 0 && num % a.sf == 0;
-        fi = num / a.sf;
-        sh = a.pt - jt * a.dt;
-      }
-      if (ok && fi >= 0 && fi < a.Fin)
-        off = ci < a.C1 ? (ci * a.Fin + fi) * a.ld : (((ci - a.C1) * a.Fin + fi) * a.ld) | (1 << 30);
-    }
-    tab_off[k] = off;
-    tab_shift[k] = sh;
-  }
-  __syncthreads();
-
-  const float* x1n = a.x1 + (size_t)n * a.C1 * a.Fin * a.ld;
-  const float* x2n = a.x2 ? a.x2 + (size_t)n * a.C2 * a.Fin * a.ld : a.x1;
-  const int tcol = t0 + 32 * w + lr;
-  f32x16 acc[MB];
-#pragma unroll
-  for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[mb][r] = 0.f;
-
-  // Operands of C2D_UN k-pairs per batch; the loads of batch i + 1 are issued before the MFMAs of batch i (round 4: with
-  // load -> wait -> MFMA in sequence the kernel ran at a third of the fp32 MFMA rate, every wave waiting out an L2 round
-  // trip per batch).
-  const int npairs = a.Kp / 2;
-  float av[2][C2D_UN][MB], bv[2][C2D_UN];
-  auto fetch = [&](int p0, auto buf_c) {
-    constexpr int buf = decltype(buf_c)::value;
-#pragma unroll
-    for (int u = 0; u < C2D_UN; ++u) {
-      const int k = 2 * (p0 + u) + lk;  // Kp is a multiple of 16 = 2 * C2D_UN: always < Kp
-      const int off = tab_off[k];
-      const int ti = tcol + tab_shift[k];
-      const bool ok = off >= 0 && ti >= 0 && ti < a.Tin;
-      const float* src = (off & (1 << 30)) ? x2n : x1n;
-      const int idx = ok ? (off & ((1 << 30) - 1)) + ti : 0;
-      const float v = src[idx];   // unconditional load of a valid address, masked afterwards
-      bv[buf][u] = ok ? v : 0.f;
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb) {
-        const int m = m0 + 32 * mb + lr;  // the packed weight is zero padded to 256 rows per tile
-        av[buf][u][mb] = a.wt[((size_t)(m >> 8) * a.Kp + k) * 256 + (m & 255)];
-      }
-    }
-  };
-  auto multiply = [&](auto buf_c) {
-    constexpr int buf = decltype(buf_c)::value;
-#pragma unroll
-    for (int u = 0; u < C2D_UN; ++u)
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb)
-        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[buf][u][mb], bv[buf][u], acc[mb], 0, 0, 0);
-  };
-  using b0 = std::integral_constant<int, 0>;
-  using b1 = std::integral_constant<int, 1>;
-  fetch(0, b0{});
-  for (int p0 = 0; p0 < npairs; p0 += 2 * C2D_UN) {
-    if (p0 + C2D_UN < npairs) fetch(p0 + C2D_UN, b1{});
-    multiply(b0{});
-    if (p0 + C2D_UN < npairs) {
-      if (p0 + 2 * C2D_UN < npairs) fetch(p0 + 2 * C2D_UN, b0{});
-      multiply(b1{});
-    }
-  }
-
-  const float s = a.slope ? a.slope[0] : 0.f;
-  if (tcol < a.ld) {
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + 32 * mb + (r & 3) + 8 * (r >> 2) + 4 * lk;
-        if (m < a.M) {
-          float v = acc[mb][r] + (a.bias ? a.bias[m] : 0.f);
-          v = act_apply(v, a.act, s);
-          a.y[(((size_t)n * a.M + m) * a.Fout + fo) * a.ld + tcol] = tcol < a.T ? v : 0.f;
-        }
-      }
-  }
-}
-
 // ---- round 4: weights through LDS, valid taps only ------------------------------------------------------------------------
-// conv2d_kernel above reads its A operand (weights) from global memory in every wave: 4 waves x MB x 256 bytes per k-pair and
-// workgroup, every workgroup of the launch the same matrix -- at 32 x 4 s of ns_dpcrn_v0 that is ~30 TB/s asked of the L2s,
-// and the ten convolutions ran at 40-60 TFLOP/s of the 157 the fp32 matrix pipe has (profiles/r04_dpcrn_conv2d_before.txt).
+// The round-3 kernel (since retired) read its A operand (weights) from global memory in every wave: 4 waves x MB x 256
+// bytes per k-pair and workgroup, every workgroup of the launch the same matrix -- at 32 x 4 s of ns_dpcrn_v0 that is
+// ~30 TB/s asked of the L2s, and the ten convolutions ran at 40-60 TFLOP/s of the 157 the fp32 matrix pipe has (profiles/r04_dpcrn_conv2d_before.txt).
 // Here a workgroup stages 32 k of its channel tile in LDS (double buffered, one barrier per chunk) and the four waves read
 // their fragments from there.  The k -> (source row, shift) table keeps only the taps that exist for this output row: a
 // transposed convolution with stride 2 uses every second frequency tap, and rows at the edge lose the taps outside the
@@ -723,13 +619,12 @@ static int conv2d_launch(const float* x1, int C1, const float* x2, int C2, const
   dim3 grid(ld / 128, Fout, N * mtiles);
   {
     LaunchTimer timer("conv2d", (hipStream_t)stream);
-    const bool old_kernel = (g_debug_flags & (1 << 23)) != 0 && !ostats;  // (bit 23: the round-3 kernel; tests run both)
     // <= 4 output channels: the row-block kernel when its table fits (span = input rows feeding 8 output rows)
     const int span = transposed ? ((C2D_R - 1) + (kf - 1) * dil_f) / stride_f + 2 : (C2D_R - 1) * stride_f + (kf - 1) * dil_f + 1;
     const long long nent = (long long)(C1 + C2) * span * kt;
     const int mm = M <= 2 ? 2 : 4;
     const size_t rows_lds = (size_t)((nent + 3) / 4 * 4) * 2 * sizeof(int) + (size_t)nent * C2D_R * mm * sizeof(float);
-    if (M <= 4 && !old_kernel && !ostats && N <= 65535 && rows_lds <= 150 * 1024 && (Fout + C2D_R - 1) / C2D_R <= 65535) {
+    if (M <= 4 && !ostats && N <= 65535 && rows_lds <= 150 * 1024 && (Fout + C2D_R - 1) / C2D_R <= 65535) {
       dim3 rgrid((ld + 511) / 512, (Fout + C2D_R - 1) / C2D_R, N);
       static bool lds_raised = false;  // (dynamic LDS above 64 KiB has to be allowed per kernel, once)
       if (!lds_raised) {
@@ -741,7 +636,7 @@ static int conv2d_launch(const float* x1, int C1, const float* x2, int C2, const
         hipLaunchKernelGGL((conv2d_rows_kernel<2>), rgrid, dim3(256), rows_lds, (hipStream_t)stream, a, span, (int)nent);
       else
         hipLaunchKernelGGL((conv2d_rows_kernel<4>), rgrid, dim3(256), rows_lds, (hipStream_t)stream, a, span, (int)nent);
-    } else if (!old_kernel) {
+    } else {
       const int Kq = (Kp + 31) / 32 * 32;
       const size_t as = 32 * mb + (mb > 1 ? 32 : 0);
       const size_t lds = (size_t)3 * Kq * sizeof(int) + 2 * C2D_KC * as * sizeof(float);
@@ -751,14 +646,6 @@ static int conv2d_launch(const float* x1, int C1, const float* x2, int C2, const
         hipLaunchKernelGGL((conv2d_lds_kernel<2>), grid, dim3(256), lds, (hipStream_t)stream, a);
       else
         hipLaunchKernelGGL((conv2d_lds_kernel<4>), grid, dim3(256), lds, (hipStream_t)stream, a);
-    } else {
-      const size_t lds = (size_t)2 * Kp * sizeof(int);
-      if (mb == 1)
-        hipLaunchKernelGGL((conv2d_kernel<1>), grid, dim3(256), lds, (hipStream_t)stream, a);
-      else if (mb == 2)
-        hipLaunchKernelGGL((conv2d_kernel<2>), grid, dim3(256), lds, (hipStream_t)stream, a);
-      else
-        hipLaunchKernelGGL((conv2d_kernel<4>), grid, dim3(256), lds, (hipStream_t)stream, a);
     }
   }
   hipError_t e = hipGetLastError();

@@ -488,11 +488,11 @@ static int dwconv_any(const void* x_any, int x_bf16, const float* w, const float
     hipStream_t st = (hipStream_t)stream;
     const bool small = (P - 1) * dilation + 8 <= DW_SMALLHALO;
     const bool wave_ok = P == 3 && 2 * dilation <= 256 &&
-                         DW_FRAMES / 4 + ((left + 3) / 4 * 4 + 2 * dilation - left + 3) / 4 <= 64 * DWW_NV && !(g_debug_flags & 1);
+                         DW_FRAMES / 4 + ((left + 3) / 4 * 4 + 2 * dilation - left + 3) / 4 <= 64 * DWW_NV && !dbg(PS_DBG_DWCONV_WG);
     if (amax) {  // (ps_dwconv_amax_f32: fp32 rows, the wave-private kernel's shapes)
       if (aligned) hipLaunchKernelGGL((dwconv_wave_kernel<true, false, true>), grid, dim3(256), 0, st, a);
       else hipLaunchKernelGGL((dwconv_wave_kernel<false, false, true>), grid, dim3(256), 0, st, a);
-    } else if (x_bf16 && y_bf16 && wave_ok) {  // (bit 0 keeps the workgroup-synchronised kernel: tests run both)
+    } else if (x_bf16 && y_bf16 && wave_ok) {  // (PS_DBG_DWCONV_WG keeps the workgroup-synchronised kernel)
       if (aligned) hipLaunchKernelGGL((dwconv_wave_kernel<true, true>), grid, dim3(256), 0, st, a);
       else hipLaunchKernelGGL((dwconv_wave_kernel<false, true>), grid, dim3(256), 0, st, a);
     } else if (x_bf16 || y_bf16) {
@@ -512,7 +512,7 @@ static int dwconv_any(const void* x_any, int x_bf16, const float* w, const float
       }
 #undef PS_DW
     } else if (P == 3 && 2 * dilation <= 256 && DW_FRAMES / 4 + ((left + 3) / 4 * 4 + 2 * dilation - left + 3) / 4 <= 64 * DWW_NV &&
-               !(g_debug_flags & 1)) {  // (ps_debug_flags bit 0 keeps the workgroup-synchronised kernel: tests run both)
+               !dbg(PS_DBG_DWCONV_WG)) {  // (PS_DBG_DWCONV_WG keeps the workgroup-synchronised kernel: tests run both)
       if (aligned) hipLaunchKernelGGL((dwconv_wave_kernel<true>), grid, dim3(256), 0, st, a);
       else hipLaunchKernelGGL((dwconv_wave_kernel<false>), grid, dim3(256), 0, st, a);
     } else if (P == 3 && aligned && small)

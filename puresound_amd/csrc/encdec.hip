@@ -608,9 +608,9 @@ extern "C" int ps_free_encode_f32(const float* wav, const float* w, float* feats
   dim3 grid((T + 255) / 256, (C + cchunk - 1) / cchunk, N);
   hipStream_t s = (hipStream_t)stream;
   LaunchTimer timer("free_encode", s);
-  // long rows of the benchmark's filterbank: the matrix-pipe kernel (ps_debug_flags bit 0 keeps the VALU kernels of
-  // rounds 1-2: tests run both)
-  if (win == 32 && hop == 16 && C % 32 == 0 && T >= 64 && !(g_debug_flags & 1)) {
+  // long rows of the benchmark's filterbank: the matrix-pipe kernel (PS_DBG_ENCDEC_VALU keeps the VALU kernels of rounds
+  // 1-2: tests run both)
+  if (win == 32 && hop == 16 && C % 32 == 0 && T >= 64 && !dbg(PS_DBG_ENCDEC_VALU)) {
     dim3 g((T + 32 * EM_TILES - 1) / (32 * EM_TILES), (C + 127) / 128, N);
     hipLaunchKernelGGL(free_encode_mfma_kernel, g, dim3(256), 0, s, wav, w, feats, L, C, T, ldt, relu);
     return check_launch("ps_free_encode_f32");
@@ -667,10 +667,10 @@ extern "C" int ps_free_decode_ws_f32(const float* feats, const float* mask, int 
                                      int N, int C, int T, int ldt, int win, int hop, int out_mode, void* workspace,
                                      size_t workspace_bytes, void* stream) {
   const size_t need = ps_free_decode_workspace_bytes(N, T, win, hop);
-  // the matrix-pipe kernel: the benchmark's filterbank on long rows, with the side buffer it needs (ps_debug_flags
-  // bit 0 keeps the VALU kernel; so does a missing or short workspace)
+  // the matrix-pipe kernel: the benchmark's filterbank on long rows, with the side buffer it needs (PS_DBG_ENCDEC_VALU
+  // keeps the VALU kernel; so does a missing or short workspace)
   if (need == 0 || !workspace || workspace_bytes < need || T < 64 || N > 65535 || ((uintptr_t)out & 15) ||
-      ((uintptr_t)workspace & 15) || C % (2 * ps::DM_UC) || (long long)C * ldt * 4 >= (1ll << 31) || (g_debug_flags & 1))
+      ((uintptr_t)workspace & 15) || C % (2 * ps::DM_UC) || (long long)C * ldt * 4 >= (1ll << 31) || dbg(PS_DBG_ENCDEC_VALU))
     return ps_free_decode_f32(feats, mask, mask_act, w, out, N, C, T, ldt, win, hop, out_mode, stream);
   if (!feats || !w || !out || C <= 0 || ldt < T) {
     set_error("ps_free_decode_ws_f32: bad argument (N=%d C=%d T=%d)", N, C, T);

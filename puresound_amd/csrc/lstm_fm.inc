@@ -27,7 +27,7 @@
 struct LstmFm {
   ps_lstm_args a;
   int ldm;    // floats between consecutive frames of gx (>= D*4H)
-  int ablate; // profiling only (ps_debug_flags bits 24..): 1 = no h' stores
+  int ablate; // profiling only (ps_debug_ablate): 1 = no h' stores
   int nblk;   // blocks of 16 sequences per utterance
   int total;  // N * nblk
 };

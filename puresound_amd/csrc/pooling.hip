@@ -203,8 +203,8 @@ extern "C" int ps_attn_stats_pool_len_f32(const float* logits, const float* x, c
   }
   {
     LaunchTimer timer("attn_stats_pool", (hipStream_t)stream);
-    // rows that fit 16 values per thread: one pass over memory (ps_debug_flags bit 0 keeps the three-pass kernel: tests)
-    if (T <= 4096 && ldt % 4 == 0 && !(((uintptr_t)logits | (uintptr_t)x) & 15) && !(g_debug_flags & 1))
+    // rows that fit 16 values per thread: one pass over memory (PS_DBG_POOL_THREE_PASS keeps the three-pass kernel: tests)
+    if (T <= 4096 && ldt % 4 == 0 && !(((uintptr_t)logits | (uintptr_t)x) & 15) && !dbg(PS_DBG_POOL_THREE_PASS))
       hipLaunchKernelGGL(attn_stats_pool_reg_kernel, dim3(C, N), dim3(256), 0, (hipStream_t)stream, logits, x, lengths,
                          out, C, T, ldt, eps);
     else

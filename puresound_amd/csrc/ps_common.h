@@ -15,7 +15,10 @@ constexpr int kTileT = 128;  // padded-row granule: ldt % kTileT == 0
 
 void set_error(const char* fmt, ...);
 extern void* g_debug_buffer;  // ps_debug_buffer(): where diagnostic stamps go (NULL in production)
-extern int g_debug_flags;  // ps_debug_flags(): kernel ablation switches for profiling builds, 0 in production
+extern int g_debug_flags;     // ps_debug_flags(): PS_DBG_* kernel switches (tests)
+extern int g_debug_grid_cap;  // ps_debug_grid_cap(): cap of the persistent GEMM grids, 0 = none (tests, experiments)
+extern int g_debug_ablate;    // ps_debug_ablate(): parts of kernels removed for timing experiments (wrong results)
+inline bool dbg(int sw) { return (sw & g_debug_flags) != 0; }
 
 // Compute units of the CURRENT device (hipGetDevice), cached per device id: a process that drives several GPUs -- one
 // per thread, or hipSetDevice between calls -- gets each device's own count.

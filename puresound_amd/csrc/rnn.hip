@@ -1210,7 +1210,7 @@ extern "C" int ps_lstm_fmajor_h256_f16x2_f32(const ps_lstm_args* args, int ldm, 
   const long long seqs = (long long)a.N * a.Q;
   dim3 grid((unsigned)((seqs + 15) / 16), 1, a.D);
   const bool pairs = a.step_stride == 1 && a.q_stride % 2 == 0 && a.ldt % 2 == 0 && !((uintptr_t)a.hout & 7) &&
-                     (a.D == 1 || a.steps % 2 == 0) && !(g_debug_flags & (1 << 20));
+                     (a.D == 1 || a.steps % 2 == 0) && !dbg(PS_DBG_LSTM_4B_STORES);
   {
     LaunchTimer timer("lstm", (hipStream_t)stream);
     if (a.H == 256 && pairs)
@@ -1284,8 +1284,8 @@ extern "C" int ps_lstm_fmajor_coop_f16x2_f32(const ps_lstm_args* args, int ldm, 
   wv = wv < 0 ? -wv : wv;
   const size_t hx = align_up((size_t)2 * a.D * groups * 2 * 16 * (a.H + 8) * sizeof(_Float16), 256);
   LstmCoop k{a, ldm, whh_image, {acc_scale[0], a.D > 1 ? acc_scale[1] : acc_scale[0]}, (_Float16*)workspace,
-             (unsigned*)((char*)workspace + hx), groups, (g_debug_flags & (1 << 19)) ? 0 : 1, (g_debug_flags & (1 << 18)) ? 1 : 0,
-             (g_debug_flags & (1 << 17)) ? 1 : 0, 0, a.D, (int)((g_debug_flags >> 24) & 15)};
+             (unsigned*)((char*)workspace + hx), groups, dbg(PS_DBG_COOP_AGENT_FENCES) ? 0 : 1, dbg(PS_DBG_COOP_SCATTER) ? 1 : 0,
+             dbg(PS_DBG_COOP_SABOTAGE) ? 1 : 0, 0, a.D, g_debug_ablate};
   if (!(k.up[0] > 0.f) || !(k.up[1] > 0.f)) {
     set_error("ps_lstm_fmajor_coop_f16x2_f32: accumulator scales must be positive");
     return PS_E_INVALID;
@@ -1300,9 +1300,9 @@ extern "C" int ps_lstm_fmajor_coop_f16x2_f32(const ps_lstm_args* args, int ldm, 
     for (int d0 = 0; d0 < (per_direction ? a.D : 1); ++d0) {
     if (per_direction) k.d0 = d0, k.nd = 1;
     dim3 grid((unsigned)((k.nd * groups + 7) / 8 * (a.H / (16 * wv)) * 8));
-    // (the streamed kernel's rule for 8-byte h' stores; bit 20 keeps the 4-byte ones: tests run both)
+    // (the streamed kernel's rule for 8-byte h' stores; PS_DBG_LSTM_4B_STORES keeps the 4-byte ones: tests run both)
     const bool pairs = a.step_stride == 1 && a.q_stride % 2 == 0 && a.ldt % 2 == 0 && !((uintptr_t)a.hout & 7) &&
-                       (a.D == 1 || a.steps % 2 == 0) && !(g_debug_flags & (1 << 20));
+                       (a.D == 1 || a.steps % 2 == 0) && !dbg(PS_DBG_LSTM_4B_STORES);
 #define PS_COOP(HH, WW)                                                                                            \
   if (pairs)                                                                                                       \
     hipLaunchKernelGGL((lstm_coop_kernel<HH, WW, 2>), grid, dim3(64 * WW), 0, (hipStream_t)stream, k);             \
@@ -1337,7 +1337,7 @@ extern "C" int ps_lstm_fmajor_f16x2_f32(const ps_lstm_args* args, int ldm, void*
     return args ? PS_E_UNSUPPORTED : PS_E_INVALID;
   }
   const ps_lstm_args& a = *args;
-  LstmFm k{a, ldm, (g_debug_flags >> 24) & 15, (a.Q + 15) / 16, 0};
+  LstmFm k{a, ldm, g_debug_ablate, (a.Q + 15) / 16, 0};
   k.total = a.N * k.nblk;
   // one workgroup per CU (148 KiB of LDS), the directions side by side; a multiple of 8 for the XCD-aware block order
   int cap = device_cus() / a.D / 8 * 8;
@@ -1347,7 +1347,7 @@ extern "C" int ps_lstm_fmajor_f16x2_f32(const ps_lstm_args* args, int ldm, void*
   const int sp = (a.steps + 3) / 4 * 4;
   const bool contig = a.step_stride == 1 && a.q_stride % 4 == 0 && a.ldt % 4 == 0 && !((uintptr_t)a.hout & 15) &&
                       (a.steps % 4 == 0 || (a.D == 1 && (long long)(a.Q - 1) * a.q_stride + sp <= a.ldt)) &&
-                      !(g_debug_flags & (1 << 20));  // (bit 20: 4-byte h' stores for consecutive frames too; tests run both)
+                      !dbg(PS_DBG_LSTM_4B_STORES);  // (PS_DBG_LSTM_4B_STORES: 4-byte h' stores for consecutive frames too; tests run both)
   {
     LaunchTimer timer("lstm", (hipStream_t)stream);
     if (contig)
@@ -1435,7 +1435,7 @@ static int lstm_launch(const ps_lstm_args* args, void* stream, bool f16x2) {
   const int threads = (4 * a.H + 63) / 64 * 64;
   const size_t lds = (size_t)5 * a.H * sizeof(f32x4);
   dim3 grid((a.Q + LS - 1) / LS, a.N, a.D);
-  if ((a.H == 64 || a.H == 128) && !(g_debug_flags & 2)) {
+  if ((a.H == 64 || a.H == 128) && !dbg(PS_DBG_LSTM_SCALAR)) {
     const long long seqs = (long long)a.N * a.Q;
     // 16-byte step groups: steps are consecutive frames starting on a 16-byte boundary.  A forward-only pass may end
     // in a partial group: it reads / writes up to 3 frames past its last step, which must still lie inside the row
@@ -1445,13 +1445,13 @@ static int lstm_launch(const ps_lstm_args* args, void* stream, bool f16x2) {
     const bool tail_ok = a.steps % 4 == 0 || (a.D == 1 && (long long)(a.Q - 1) * a.q_stride + steps4 <= a.ldt);
     const bool contig = a.step_stride == 1 && tail_ok && a.q_stride % 4 == 0 && a.ldt % 4 == 0 &&
                         !((uintptr_t)a.gx & 15) && !((uintptr_t)a.hout & 15);
-    // 16 sequences per workgroup when there are enough sequences to fill the chip that way (debug bit 2 / 3 force one)
-    const bool wide = (g_debug_flags & 4) ? true : (g_debug_flags & 8) ? false : (a.H == 64 && contig && seqs >= 16 * 256);
+    // 16 sequences per workgroup when there are enough sequences to fill the chip that way (PS_DBG_LSTM_WIDE / _M4 force one)
+    const bool wide = dbg(PS_DBG_LSTM_WIDE) ? true : dbg(PS_DBG_LSTM_M4) ? false : (a.H == 64 && contig && seqs >= 16 * 256);
     LaunchTimer timer("lstm", (hipStream_t)stream);
     if (wide) {
       dim3 mgrid((unsigned)((seqs + 15) / 16), 1, a.D);
       // whole segments of 20 consecutive frames (DPRNN's intra pass at K = 20): all steps fetched up front
-      const bool seg = a.H == 64 && contig && a.steps == 20 && !(g_debug_flags & (1 << 20));
+      const bool seg = a.H == 64 && contig && a.steps == 20 && !dbg(PS_DBG_LSTM_4B_STORES);
       if (seg && f16x2 && a.D == 1)
         hipLaunchKernelGGL((lstm_seg_f16x2_kernel<64, 20, false>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
       else if (seg && f16x2)
@@ -1470,7 +1470,7 @@ static int lstm_launch(const ps_lstm_args* args, void* stream, bool f16x2) {
       dim3 mgrid((unsigned)(((seqs + 3) / 4 + 7) / 8 * 8), 1, a.D);  // multiple of 8: see the XCD-aware group order
       if (a.H == 64 && contig)
         hipLaunchKernelGGL((lstm_m4_kernel<64, true>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
-      else if (a.H == 64 && f16x2 && !(g_debug_flags & (1 << 20)))
+      else if (a.H == 64 && f16x2 && !dbg(PS_DBG_LSTM_4B_STORES))
         hipLaunchKernelGGL(lstm_m4_f16x2_kernel, mgrid, dim3(256), 0, (hipStream_t)stream, k);
       else if (a.H == 64)
         hipLaunchKernelGGL((lstm_m4_kernel<64, false>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
@@ -1504,11 +1504,11 @@ extern "C" int ps_chan_layernorm_f32(const float* x, const float* gamma, const f
     // few frames (streaming step, state rows): split the channels 16 ways instead of 4 to shorten the serial walk
     if ((long long)((T + 63) / 64) * N < 64)
       hipLaunchKernelGGL((chan_layernorm_kernel<16>), dim3((T + 63) / 64, N), dim3(1024), 0, (hipStream_t)stream, a);
-    else if (C <= 64 && !(g_debug_flags & (1 << 23)))  // (bit 23: the three-pass kernel; tests run both)
+    else if (C <= 64 && !dbg(PS_DBG_CHAN_LN_THREE_PASS))  // (else the three-pass kernel; tests run both)
       hipLaunchKernelGGL((chan_layernorm_reg_kernel<16>), dim3((T + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, a);
-    else if (C <= 128 && !(g_debug_flags & (1 << 23)))
+    else if (C <= 128 && !dbg(PS_DBG_CHAN_LN_THREE_PASS))
       hipLaunchKernelGGL((chan_layernorm_reg_kernel<32>), dim3((T + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, a);
-    else if (C <= 256 && !(g_debug_flags & (1 << 23)))
+    else if (C <= 256 && !dbg(PS_DBG_CHAN_LN_THREE_PASS))
       hipLaunchKernelGGL((chan_layernorm_reg_kernel<64>), dim3((T + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, a);
     else
       hipLaunchKernelGGL((chan_layernorm_kernel<4>), dim3((T + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, a);

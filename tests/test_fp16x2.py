@@ -102,19 +102,17 @@ def test_fp16x2_gemm_is_as_close_to_fp64_as_the_fp32_kernel(dev, n, k, m, t, mod
     e32 = float((y32[..., :t].cpu().double() - ref).pow(2).mean().sqrt()) / rms
     wf, we = H.pack_wt_f16x2(w.to(dev))
     first = None
-    # 0 = the persistent interleaved kernel where the launch is large enough, bit 27 = the one-tile-per-workgroup
-    # kernel (256 x 32 tiles for small grids), bits 27 | 29 = its 256 x 128 tile
-    # bit 7 = the one-wave-per-SIMD persistent kernel (conv1x1_f16x2_w1.inc) instead of the interleaved one, bit 28 = a
-    # persistent kernel at any launch size (where the shape allows one)
-    # bit 22 = the interleaved kernel where the default is the register-B kernel (conv1x1_f16x2_rb.inc: K % 32 == 0, M % 256 == 0)
-    for flags in (0, 1 << 27, (1 << 27) | (1 << 29), 128, 1 << 28, 128 | (1 << 28), 1 << 22, (1 << 22) | (1 << 28)):
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    # 0 = the persistent interleaved kernel where the launch is large enough, SIMPLE = the one-tile-per-workgroup
+    # kernel (256 x 32 tiles for small grids), SIMPLE | WIDE_TILE = its 256 x 128 tile, ANY_SIZE = a persistent kernel
+    # at any launch size (where the shape allows one), NO_RB = the interleaved kernel where the default is the
+    # register-B kernel (conv1x1_f16x2_rb.inc: K % 32 == 0, M % 256 == 0)
+    simple, wide, any_size, no_rb = (_abi.PS_DBG_GEMM_SIMPLE, _abi.PS_DBG_GEMM_WIDE_TILE, _abi.PS_DBG_GEMM_ANY_SIZE,
+                                     _abi.PS_DBG_GEMM_NO_RB)
+    for flags in (0, simple, simple | wide, any_size, no_rb, no_rb | any_size):
+        with _abi.debug(flags):
             y, st, am = H.conv1x1_f16x2(xd, t, wf, we, m, pro, b.to(dev), None, resd, want_stats=want, want_amax=True,
                                         **kw)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         got = y[..., :t].cpu().double()
         assert torch.isfinite(got).all()
         err = float((got - ref).pow(2).mean().sqrt()) / rms

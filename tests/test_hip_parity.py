@@ -13,6 +13,7 @@ import cases
 from conftest import rel_max
 from detweights import det_state_dict, det_wave
 from oracle import separator_oracle as O
+from puresound_amd import _abi
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -73,13 +74,11 @@ def test_free_encode(H, dev, n, length, c, win, hop, relu):
     w = _rand((c, 1, win), 2, -0.2, 0.2)
     ref = O.free_encode(wav, w, hop, relu)
     from puresound_amd import _abi
-    for flags in (0, 1):  # 0: the matrix-pipe kernel where the shape allows it (32 / 16, C % 32 == 0, T >= 64); bit 0: VALU kernel
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    # 0: the matrix-pipe kernel where the shape allows it (32 / 16, C % 32 == 0, T >= 64); ENCDEC_VALU: the VALU kernel
+    for flags in (0, _abi.PS_DBG_ENCDEC_VALU):
+        with _abi.debug(flags):
             feats, t = H.free_encode(wav.to(dev), w.to(dev), hop, relu)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         assert t == ref.shape[-1] == (length - win) // hop + 1
         assert rel_max(feats[..., :t].cpu().numpy(), ref.numpy()) < 1e-5, flags
 
@@ -103,15 +102,13 @@ def test_free_decode(H, dev, n, c, t, win, hop, mask_act, out_mode):
     if out_mode != "none":
         ref = O.output_constrain(ref, out_mode)
     from puresound_amd import _abi
-    for flags in (0, 1):  # 0: the matrix-pipe kernel + boundary fix-up where the shape allows it (32 / 16, T >= 64); bit 0: VALU
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    # 0: the matrix-pipe kernel + boundary fix-up where the shape allows it (32 / 16, T >= 64); ENCDEC_VALU: the VALU kernel
+    for flags in (0, _abi.PS_DBG_ENCDEC_VALU):
+        with _abi.debug(flags):
             out = H.free_decode(H.pad_rows(feats.to(dev)), t, w.to(dev), hop, H.pad_rows(mask.to(dev)), mask_act, out_mode)
             # no-mask variant == module-level FreeEncDec.inverse
             out2 = H.free_decode(H.pad_rows(feats.to(dev)), t, w.to(dev), hop)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         assert out.shape == ref.shape
         assert rel_max(out.cpu().numpy(), ref.numpy()) < 2e-5, flags
         assert rel_max(out2.cpu().numpy(), O.free_decode(feats, w, hop).numpy()) < 2e-5, flags
@@ -184,14 +181,11 @@ def test_dwconv(H, dev, p, dil, causal, n, h, t):
     stats = torch.stack([x.double().sum((1, 2)), (x.double() ** 2).sum((1, 2))], -1).reshape(n, 1, 2).to(dev)
     g_d, b_d, s_d = gamma.to(dev), beta.to(dev), slope.to(dev)
     pro = H.make_prologue(_abi.PS_NORM_GLOBAL, True, stats, h * t, 1e-8, g_d, b_d, s_d)
-    # 0: the wave-private kernel where the shape allows it (P = 3, halo <= 256), bit 0: the workgroup-synchronised kernel
-    for flags in (0, 1):
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    # 0: the wave-private kernel where the shape allows it (P = 3, halo <= 256), DWCONV_WG: the workgroup-synchronised kernel
+    for flags in (0, _abi.PS_DBG_DWCONV_WG):
+        with _abi.debug(flags):
             y, st = H.dwconv(H.pad_rows(x.to(dev)), t, w.to(dev), b.to(dev), dil, left, pro, want_stats=True)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         assert rel_max(y[..., :t].cpu().numpy(), ref.numpy()) < 1e-5, flags
         s = st.sum(1).cpu().numpy()
         np.testing.assert_allclose(s[:, 0], ref.double().sum((1, 2)).numpy(), rtol=1e-5, atol=1e-3)
@@ -214,14 +208,11 @@ def test_conv1x1_long_runs_across_utterances(H, dev, grid_cap):
     g_d, b_d, s_d = gamma.to(dev), beta.to(dev), slope.to(dev)
     pro = H.make_prologue(_abi.PS_NORM_GLOBAL, True, stats, k * t, 1e-8, g_d, b_d, s_d)
     xd, wd, bd, bnd, rd = H.pad_rows(x.to(dev)), H.pack_wt(w.to(dev)), b.to(dev), bn.to(dev), H.pad_rows(res.to(dev))
-    old = H.lib().ps_debug_flags(grid_cap << 8)
-    try:
+    with _abi.debug(grid_cap=grid_cap):
         y, st = H.conv1x1(xd, t, wd, m, pro, bd, bnd, None, want_stats=True)
         y2, _ = H.conv1x1(xd, t, wd, m, pro, bd, bnd, rd)
         y3, _ = H.conv1x1(xd, t, wd, m, None, bd, bnd, rd)
         torch.cuda.synchronize()
-    finally:
-        H.lib().ps_debug_flags(old)
     assert rel_max(y[..., :t].cpu().numpy(), ref.numpy()) < 2e-5
     assert rel_max(y2[..., :t].cpu().numpy(), (ref + res).numpy()) < 2e-5
     ref3 = torch.matmul(w, x) + b.reshape(1, -1, 1) + bn.reshape(n, m, 1) + res
@@ -298,7 +289,8 @@ def test_wrapper_inference_matches_reference_golden(PA, dev, golden_dir, name):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,c,t", [(2, 24, 77), (3, 512, 249), (1, 40, 1500), (2, 16, 3999), (1, 8, 4096), (1, 8, 5000)])
 def test_attn_stats_pool_kernel(H, dev, n, c, t):
-    """rows of <= 4096 frames: the one-pass kernel (rows in registers); debug bit 0 / longer rows: the three-pass kernel."""
+    """rows of <= 4096 frames: the one-pass kernel (rows in registers); PS_DBG_POOL_THREE_PASS / longer rows: the three-pass
+    kernel."""
     from puresound_amd import _abi
     logits = _rand((n, c, t), 31, -3.0, 3.0)
     x = _rand((n, c, t), 32)
@@ -306,13 +298,10 @@ def test_attn_stats_pool_kernel(H, dev, n, c, t):
     mean = (a * x.double()).sum(2)
     std = torch.sqrt((a * (x.double() - mean.unsqueeze(2)) ** 2).sum(2).clamp(1e-12))
     ref = torch.cat((mean, std), 1).float().numpy()
-    for flags in (0, 1):
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    for flags in (0, _abi.PS_DBG_POOL_THREE_PASS):
+        with _abi.debug(flags):
             out = H.attn_stats_pool(H.pad_rows(logits.to(dev)), H.pad_rows(x.to(dev)), t)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         assert out.shape == (n, 2 * c)
         assert rel_max(out.cpu().numpy(), ref) < 2e-5, flags
 
@@ -577,17 +566,15 @@ def test_lstm_kernel(H, dev, hid, bi, mode):
     gx, _ = H.conv1x1(H.pad_rows(x.to(dev)), t, p["wih"], p["rows"], None, p["bias"])
     to_state = lambda v: H.pad_rows(v.reshape(d, n, q, hid).permute(1, 0, 3, 2).reshape(n, d * hid, q).to(dev))  # noqa: E731
     back = lambda v: v[..., :q].cpu().reshape(n, d, hid, q).permute(1, 0, 3, 2).reshape(d, n * q, hid)  # noqa: E731
-    # debug flags pick the kernel variant for H = 64 / 128: 0 = by shape, 4 = 16 sequences per workgroup
-    # (16x16x4 MFMA), 8 = 4 sequences per workgroup (4x4x1 MFMA), 2 = the generic VALU kernel
+    # debug switches pick the kernel variant for H = 64 / 128: 0 = by shape, LSTM_WIDE = 16 sequences per workgroup
+    # (16x16x4 MFMA), LSTM_M4 = 4 sequences per workgroup (4x4x1 MFMA), LSTM_SCALAR = the generic VALU kernel
     from puresound_amd import _abi
-    for flags in ((0, 4, 8, 2) if hid in (64, 128) else (0,)):
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    variants = (0, _abi.PS_DBG_LSTM_WIDE, _abi.PS_DBG_LSTM_M4, _abi.PS_DBG_LSTM_SCALAR)
+    for flags in (variants if hid in (64, 128) else (0,)):
+        with _abi.debug(flags):
             hout, (hl, cl) = H.lstm(gx, p["whh_t"], hid, d, q, qs, steps, ss, to_state(h0), to_state(c0),
                                     want_state=True)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         got = hout[..., :t].cpu().transpose(1, 2).reshape(n, s, k, d * hid)
         got = got.reshape(n * s, k, -1) if mode == "intra" else got.permute(0, 2, 1, 3).reshape(n * k, s, -1)
         assert rel_max(got.numpy(), ref.numpy()) < 2e-5, flags
@@ -598,7 +585,7 @@ def test_lstm_kernel(H, dev, hid, bi, mode):
 @pytest.mark.parametrize("bi,wscale", [(False, 1.0), (True, 1.0), (False, 1.5), (False, 1e-3)])
 def test_lstm_whole_segment_kernel(H, dev, bi, wscale):
     """Intra pass at K = 20 (BASELINE config 4's shape): the whole-segment kernel (all 20 steps of 16 sequences held in
-    registers, h' staged in LDS) against the oracle and against the 4-step-group kernel it replaces (debug bit 20); 18 sequences = one full and one ragged workgroup, both directions, initial and final states."""
+    registers, h' staged in LDS) against the oracle and against the 4-step-group kernel it replaces (PS_DBG_LSTM_4B_STORES); 18 sequences = one full and one ragged workgroup, both directions, initial and final states."""
     from puresound_amd.nnet._plans import lstm_plan
     from puresound_amd import _abi
     hid, n, c, k, s = 64, 2, 12, 20, 9
@@ -620,14 +607,12 @@ def test_lstm_whole_segment_kernel(H, dev, bi, wscale):
     outs = []
     tol = 2e-5
     # (flags, f16x2): whole-segment fp32, the 4-step-group kernel, whole-segment with the fp16x2 recurrent product
-    for flags, f16x2 in ((4, False), (4 | 1 << 20, False), (4, True)):
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    wide = _abi.PS_DBG_LSTM_WIDE
+    for flags, f16x2 in ((wide, False), (wide | _abi.PS_DBG_LSTM_4B_STORES, False), (wide, True)):
+        with _abi.debug(flags):
             hout, (hl, cl) = H.lstm(gx, p["whh_t"], hid, d, s, k, k, 1, to_state(h0), to_state(c0), want_state=True,
                                     f16x2=f16x2)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         got = hout[..., :t].cpu().transpose(1, 2).reshape(n * s, k, d * hid)
         e = (rel_max(got.numpy(), ref.numpy()), rel_max(back(hl).numpy(), hn.numpy()), rel_max(back(cl).numpy(), cn.numpy()))
         assert max(e) < tol, (flags, f16x2, e)
@@ -700,15 +685,12 @@ def test_chan_layernorm_kernel(H, dev, n, c, t):
     y = H.chan_layernorm(H.pad_rows(x.to(dev)), t, g.to(dev), b.to(dev), 1e-8, slope=slope.to(dev), sigmoid=True,
                          mul=H.pad_rows(mul.to(dev)))
     assert rel_max(y[..., :t].cpu().numpy(), ref.numpy()) < 2e-5
-    # C <= 256 runs with the thread's channels in registers (one pass over x); debug bit 23 keeps the three-pass kernel: the
-    # same sums in the same order, bit for bit
+    # C <= 256 runs with the thread's channels in registers (one pass over x); PS_DBG_CHAN_LN_THREE_PASS keeps the three-pass
+    # kernel: the same sums in the same order, bit for bit
     from puresound_amd import _abi
-    old = _abi.lib().ps_debug_flags(1 << 23)
-    try:
+    with _abi.debug(_abi.PS_DBG_CHAN_LN_THREE_PASS):
         y3 = H.chan_layernorm(H.pad_rows(x.to(dev)), t, g.to(dev), b.to(dev), 1e-8, slope=slope.to(dev), sigmoid=True,
                               mul=H.pad_rows(mul.to(dev)))
-    finally:
-        _abi.lib().ps_debug_flags(old)
     assert torch.equal(y3[..., :t], y[..., :t])
 
 
@@ -902,7 +884,7 @@ def test_fused_streaming_step_kernels(H, dev):
 @pytest.mark.parametrize("res_inside", [False, True])
 def test_proj_layernorm_on_long_rows(H, dev, n, k, m, t, res_inside):
     """ps_proj_layernorm_f32 on the offline paths' long rows: the row kernel (32 frames x all channels per wave,
-    v_mfma_f32_32x32x2_f32) and, with ps_debug_flags bit 4, the 16-frame kernel of the streaming step -- both against
+    v_mfma_f32_32x32x2_f32) and, with PS_DBG_PROJ_LN_FRAMES16, the 16-frame kernel of the streaming step -- both against
     res + LN(W x + b) / LN(W x + b + res) in fp64."""
     from puresound_amd import _abi
     hx, res = _rand((n, k, t), 210), _rand((n, m, t), 211)
@@ -917,15 +899,13 @@ def test_proj_layernorm_on_long_rows(H, dev, n, k, m, t, res_inside):
     if not res_inside:
         ref = ref + res.double()
     outs = []
-    # 0: by shape (K = 64, M = 128: the pipelined row kernel), bit 21: the unpipelined row kernel, 16: the 16-frame kernel
-    for flags in (0, 1 << 21, 16):
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    # 0: by shape (K = 64, M = 128: the pipelined row kernel), PROJ_LN_UNPIPELINED: the unpipelined row kernel,
+    # PROJ_LN_FRAMES16: the 16-frame kernel
+    for flags in (0, _abi.PS_DBG_PROJ_LN_UNPIPELINED, _abi.PS_DBG_PROJ_LN_FRAMES16):
+        with _abi.debug(flags):
             y, _ = H.proj_layernorm(H.pad_rows(hx.to(dev)), t, H.pack_wt(wp.to(dev)), bp.to(dev), m, g1.to(dev), b1.to(dev),
                                     1e-5, H.pad_rows(res.to(dev)), res_inside=res_inside)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         assert rel_max(y[..., :t].cpu().double().numpy(), ref.numpy()) < 2e-5, flags
         outs.append(y[..., :t].cpu())
     assert rel_max(outs[0].numpy(), outs[2].numpy()) < 1e-5
@@ -971,19 +951,16 @@ def test_conv1x1_bf16_planes(H, dev, planes, tol, n, k, m, t, mode):
     want = mode in ("norm_stats", "stats", "stats_bias_n")
     if res is not None:
         ref = ref + res.double()
-    # flag bit 27 = simple kernel only (small grids take its 256 x 32 tile), bit 29 = keep its 256 x 128 tile,
-    # bit 28 = the persistent ping-pong kernel at any size
-    # bit 30 = the single-wave-per-SIMD experiment (where the launch is large enough for it)
-    # bit 5 (32) = the two-barrier ping-pong kernel instead of the interleaved one-barrier kernel
-    for flags in (0, 32, 1 << 27, (1 << 27) | (1 << 29), 1 << 28, (1 << 28) | 32, 1 << 30):
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    # SIMPLE = simple kernel only (small grids take its 256 x 32 tile), WIDE_TILE = keep its 256 x 128 tile,
+    # ANY_SIZE = the persistent ping-pong kernel at any size,
+    # TWO_BARRIER = the two-barrier ping-pong kernel instead of the interleaved one-barrier kernel
+    simple, any_size, two = _abi.PS_DBG_GEMM_SIMPLE, _abi.PS_DBG_GEMM_ANY_SIZE, _abi.PS_DBG_GEMM_TWO_BARRIER
+    for flags in (0, two, simple, simple | _abi.PS_DBG_GEMM_WIDE_TILE, any_size, any_size | two):
+        with _abi.debug(flags):
             y, st = H.conv1x1_bf16(H.pad_rows(x.to(dev)), t, H.pack_wt_bf16(w.to(dev), planes), m, pro, b.to(dev),
                                    None if bias_n is None else bias_n.to(dev),
                                    None if res is None else H.pad_rows(res.to(dev)), want_stats=want)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         assert rel_max(y[..., :t].cpu().double().numpy(), ref.numpy()) < tol, flags
         # the two kernels round and accumulate identically (only the residual enters at the other end of the sum)
         if flags == 0:
@@ -1125,10 +1102,8 @@ def test_unfold2d_kernel(H, dev, transposed):
                                                 (True, 2, 40, 24), (False, 40, 20, 12), (True, 100, 30, 34), (True, 32, 16, 16)])
 def test_conv2d_implicit_gemm_kernel(H, dev, transposed, m, c1, c2):
     """ps_conv2d_f32 against torch's Conv2d / ConvTranspose2d: the LDS-staged kernel (weights through LDS, compacted tap
-    table; several 32-k chunks at the larger channel counts), the <= 4-channel kernel (m = 2: the mask layer) and the round-3
-    kernel (debug bit 23)."""
+    table; several 32-k chunks at the larger channel counts) and the <= 4-channel kernel (m = 2: the mask layer)."""
     import torch.nn.functional as F
-    from puresound_amd import _abi
     n, f, t = 2, 11, 150
     x1, x2 = _rand((n, c1, f, t), 151), _rand((n, c2, f, t), 152)
     x = torch.cat([x1, x2], 1)
@@ -1145,19 +1120,11 @@ def test_conv2d_implicit_gemm_kernel(H, dev, transposed, m, c1, c2):
         ref = F.conv_transpose2d(x, w, b, stride=(sf, 1), padding=(kf // 2, 0), output_padding=(op, 0))[..., (kt - 1):]
         w2, shift = w.permute(1, 0, 2, 3).reshape(m, -1), kt - 1
     ref = torch.where(ref >= 0, ref, 0.2 * ref)
-    outs = []
-    for flags in (0, 1 << 23):
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
-            y = H.conv2d(pad(x1), pad(x2), H.pack_wt(w2.contiguous().to(dev)), b.to(dev), m, t, ref.shape[2], kf, kt, sf, 1, 1,
-                         kf // 2, shift, transposed, "prelu", slope.to(dev))
-            torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
-        assert rel_max(y[..., :t].cpu().numpy(), ref.numpy()) < 2e-5, flags
-        assert float(y[..., t:].abs().max()) == 0.0
-        outs.append(y)
-    assert rel_max(outs[0].cpu().numpy(), outs[1].cpu().numpy()) < 1e-5
+    y = H.conv2d(pad(x1), pad(x2), H.pack_wt(w2.contiguous().to(dev)), b.to(dev), m, t, ref.shape[2], kf, kt, sf, 1, 1,
+                 kf // 2, shift, transposed, "prelu", slope.to(dev))
+    torch.cuda.synchronize()
+    assert rel_max(y[..., :t].cpu().numpy(), ref.numpy()) < 2e-5
+    assert float(y[..., t:].abs().max()) == 0.0
 
 
 UNET_CASES = [n for n, c in cases.CASES.items() if c["kind"] == "unet"]
@@ -1291,19 +1258,19 @@ def test_fbank_encoder_matches_reference_golden(PA, dev, golden_dir, name):
     assert rel_max(y.cpu().numpy(), g["feats"]) < TOL
 
 
-@pytest.mark.parametrize("e,heads,f,t,flags", [(16, 4, 9, 13, 0), (64, 4, 9, 13, 0), (64, 4, 9, 13, 1 << 23), (64, 4, 9, 13, 1 << 21), (128, 8, 64, 37, 0), (128, 8, 64, 37, 1 << 21),
-                                               (64, 2, 20, 9, 0), (64, 1, 30, 6, 0), (64, 1, 30, 6, 1 << 23)])
+@pytest.mark.parametrize("e,heads,f,t,flags", [
+    (16, 4, 9, 13, 0), (64, 4, 9, 13, 0), (64, 4, 9, 13, _abi.PS_DBG_ATTN_GENERAL), (64, 4, 9, 13, _abi.PS_DBG_ATTN_NARROW),
+    (128, 8, 64, 37, 0), (128, 8, 64, 37, _abi.PS_DBG_ATTN_NARROW),
+    (64, 2, 20, 9, 0), (64, 1, 30, 6, 0), (64, 1, 30, 6, _abi.PS_DBG_ATTN_GENERAL)])
 def test_self_attention_kernel(H, dev, e, heads, f, t, flags):
     """ps_self_attention_f32 / ps_add_position_f32 against the oracle's multi-head attention, both sequence layouts
     (positions contiguous in time; positions strided over frequency rows as in DPARN), with and without causal mask.
-    Head dimensions 16 / 32 / 64 with at most 64 positions take the register-score kernel (debug bit 23: the general one);
+    Head dimensions 16 / 32 / 64 with at most 64 positions take the register-score kernel (PS_DBG_ATTN_GENERAL: the
+    general one; PS_DBG_ATTN_NARROW: 4 sequences per workgroup at dh = 16);
     (128, 8, 64, 37) is the DPARN bottleneck's shape with a ragged last workgroup."""
     from puresound_amd import _abi
-    old_flags = _abi.lib().ps_debug_flags(flags)
-    try:
+    with _abi.debug(flags):
         _self_attention_case(H, dev, e, heads, f, t)
-    finally:
-        _abi.lib().ps_debug_flags(old_flags)
 
 
 def _self_attention_case(H, dev, e, heads, f, t):
@@ -1350,13 +1317,10 @@ def test_lstm_kernel_row_sequences_with_partial_step_group(H, dev, hid, t):
     ld = xp.shape[-1]
     frames = (f - 1) * ld + t
     gx, _ = H.conv1x1(xp.view(n, c, f * ld), frames, p["wih"], p["rows"], None, p["bias"])
-    for flags in (0, 4, 8, 2):
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    for flags in (0, _abi.PS_DBG_LSTM_WIDE, _abi.PS_DBG_LSTM_M4, _abi.PS_DBG_LSTM_SCALAR):
+        with _abi.debug(flags):
             hout, _ = H.lstm(gx, p["whh_t"], hid, 1, f, ld, t, 1)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         got = hout.view(n, hid, f, ld)[..., :t].cpu().permute(0, 2, 3, 1).reshape(n * f, t, hid)
         assert rel_max(got.numpy(), ref.numpy()) < 2e-5, flags
 

@@ -187,6 +187,19 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_abi.SIGNATURES) == declared, "ctypes binding and header disagree"
 
 
+def test_debug_switches_are_distinct_bits_and_match_the_binding():
+    hdr = open(os.path.join(ROOT, "include", "puresound_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    names = re.findall(r"\b(PS_DBG_\w+)\s*=", hdr)
+    values = {n: 1 << int(b) for n, b in re.findall(r"\b(PS_DBG_\w+)\s*=\s*1\s*<<\s*(\d+)\s*[,}]", hdr)}
+    assert len(names) >= 20 and sorted(values) == sorted(names), "every PS_DBG_* switch is written 1 << bit"
+    assert len(set(values.values())) == len(values), "two switches share a bit"
+    assert all(v < 1 << 31 for v in values.values())
+    for n, v in values.items():
+        assert getattr(_abi, n) == v, n
+    assert sorted(k for k in vars(_abi) if k.startswith("PS_DBG_")) == sorted(values)
+
+
 def test_abi_host_side_helpers_need_no_gpu():
     lib = _abi.lib()
     assert lib.ps_abi_version() == _abi.ABI_VERSION

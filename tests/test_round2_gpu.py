@@ -10,6 +10,7 @@ import cases
 from conftest import rel_max
 from detweights import det_state_dict, det_wave
 from oracle import separator_oracle as O
+from puresound_amd import _abi
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -286,7 +287,7 @@ def test_mask_functions_and_magphase_on_the_device(PA, dev, golden_dir):
 
 
 # ---- bf16 activation rows (BASELINE "bf16" configurations: bf16 storage, fp32 accumulation) ---------------------------
-@pytest.mark.parametrize("flags", [0, 1 << 28, 1 << 27])
+@pytest.mark.parametrize("flags", [0, _abi.PS_DBG_GEMM_ANY_SIZE, _abi.PS_DBG_GEMM_SIMPLE])
 @pytest.mark.parametrize("n,k,m,t,mode,xb,yb", [(8, 512, 256, 3999, "stats", False, True),
                                                 (8, 256, 256, 3999, "norm_stats", True, True),
                                                 (8, 256, 512, 3999, "norm_res", True, False),
@@ -310,14 +311,11 @@ def test_conv1x1_bf16_rows_equal_the_fp32_row_kernel_on_rounded_data(dev, flags,
     want = mode in ("norm_stats", "stats")
     wb = H.pack_wt_bf16(w.to(dev), 1)
     xp = H.pad_rows(x.to(dev))
-    old = _abi.lib().ps_debug_flags(flags)
-    try:
+    with _abi.debug(flags):
         y_ref, st_ref = H.conv1x1_bf16(xp, t, wb, m, pro, b.to(dev), None, res, want_stats=want)
         y, st = H.conv1x1_bf16(xp.bfloat16() if xb else xp, t, wb, m, pro, b.to(dev), None, res, want_stats=want,
                                out_dtype=torch.bfloat16 if yb else torch.float32)
         torch.cuda.synchronize()
-    finally:
-        _abi.lib().ps_debug_flags(old)
     assert y.dtype == (torch.bfloat16 if yb else torch.float32)
     want_y = y_ref[..., :t].bfloat16() if yb else y_ref[..., :t]
     assert torch.equal(y[..., :t], want_y)
@@ -339,16 +337,13 @@ def test_dwconv_bf16_rows(dev, dil, causal):
     left = 2 * dil if causal else dil
     xp = H.pad_rows(x.to(dev))
     y_ref, st_ref = H.dwconv(xp, t, w.to(dev), b.to(dev), dil, left, pro, True)
-    # (True, True) twice: the wave-private kernel (round 4: bf16 rows there too) and, with ps_debug_flags bit 0, the
+    # (True, True) twice: the wave-private kernel (round 4: bf16 rows there too) and, with PS_DBG_DWCONV_WG, the
     # workgroup-synchronised one
-    for xb, yb, flags in ((True, True, 0), (True, True, 1), (True, False, 0), (False, True, 0)):
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+    for xb, yb, flags in ((True, True, 0), (True, True, _abi.PS_DBG_DWCONV_WG), (True, False, 0), (False, True, 0)):
+        with _abi.debug(flags):
             y, st = H.dwconv(xp.bfloat16() if xb else xp, t, w.to(dev), b.to(dev), dil, left, pro, True,
                              out_dtype=torch.bfloat16 if yb else torch.float32)
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         # (the instantiations may contract their multiply-adds differently: equal to one fp32 rounding, i.e. the bf16
         #  results differ in at most the last bit of a few elements)
         if yb:

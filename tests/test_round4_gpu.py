@@ -7,6 +7,7 @@ import cases
 from conftest import rel_max
 from detweights import det_state_dict, det_wave
 from oracle import separator_oracle as O
+from puresound_amd import _abi
 
 pytestmark = pytest.mark.gpu
 
@@ -39,12 +40,13 @@ def _l2rel(a, b):
     return float(np.linalg.norm(a - b) / np.linalg.norm(b))
 
 
-@pytest.mark.parametrize("n,k,m,t,flags", [(2, 256, 512, 300, 0), (8, 256, 512, 3999, 0), (8, 256, 512, 3999, 1 << 27),
+@pytest.mark.parametrize("n,k,m,t,flags", [(2, 256, 512, 300, 0), (8, 256, 512, 3999, 0),
+                                           (8, 256, 512, 3999, _abi.PS_DBG_GEMM_SIMPLE),
                                            (3, 64, 96, 700, 0)])
 def test_bf16_gemm_with_bf16_residual_and_output_rows(dev, n, k, m, t, flags):
     """ps_conv1x1_bf16_io with y_bf16 and a residual: the residual is bf16 rows too (out_conv of a block whose residual
-    stream is stored in bf16), on the persistent kernel (large launches) and the one-tile-per-workgroup kernel (bit 27 /
-    small launches).  Reference: fp64 product of the bf16-rounded operands + the bf16 residual, rounded to bf16 once."""
+    stream is stored in bf16), on the persistent kernel (large launches) and the one-tile-per-workgroup kernel
+    (PS_DBG_GEMM_SIMPLE / small launches).  Reference: fp64 product of the bf16-rounded operands + the bf16 residual, rounded to bf16 once."""
     from puresound_amd import _abi, hip as H
     x, w, b = _rand((n, k, t), 401), _rand((m, k), 402, -0.1, 0.1), _rand((m,), 403)
     res = _rand((n, m, t), 404)
@@ -54,12 +56,9 @@ def test_bf16_gemm_with_bf16_residual_and_output_rows(dev, n, k, m, t, flags):
     pro = H.make_prologue(_abi.PS_NORM_GLOBAL, True, keep[0], k * t, 1e-8, keep[1], keep[2], keep[3])
     xd = H.pad_rows(x.to(dev)).to(torch.bfloat16)
     rd = H.pad_rows(res.to(dev)).to(torch.bfloat16)
-    old = _abi.lib().ps_debug_flags(flags)
-    try:
+    with _abi.debug(flags):
         y, _ = H.conv1x1_bf16(xd, t, H.pack_wt_bf16(w.to(dev), 1), m, pro, b.to(dev), None, rd, out_dtype=torch.bfloat16)
         torch.cuda.synchronize()
-    finally:
-        _abi.lib().ps_debug_flags(old)
     assert y.dtype == torch.bfloat16
     xb = xd[..., :t].float().cpu().double()
     a = O.prelu(O.glob_ln(xb, gamma.double(), beta.double()), slope.double())   # statistics are those of the fp32 x: close
@@ -137,8 +136,7 @@ def test_conv1x1_f16x2_frame_major_is_the_row_major_result_transposed(H, dev):
     n, k, t = 2, 128, 300
     x = H.pad_rows(_rand4((n, k, t), 401).to(dev))
     ldt = x.shape[-1]
-    old = _abi.lib().ps_debug_flags(1 << 28)   # the register-B kernel at any size
-    try:
+    with _abi.debug(_abi.PS_DBG_GEMM_ANY_SIZE):   # the register-B kernel at any size
         for m in (512, 1024):
             w = _rand4((m, k), 402 + m, -0.3, 0.3).to(dev)
             b = _rand4((m,), 403, -0.5, 0.5).to(dev)
@@ -152,8 +150,6 @@ def test_conv1x1_f16x2_frame_major_is_the_row_major_result_transposed(H, dev):
             assert torch.equal(y_fm.transpose(1, 2), y_rm), m
             ref = torch.einsum("mk,nkt->nmt", w.double().cpu(), x[..., :t].double().cpu()) + b.double().cpu()[None, :, None]
             assert rel_max(y_rm[..., :t].cpu().numpy(), ref.numpy()) < 2e-6
-    finally:
-        _abi.lib().ps_debug_flags(old)
     # a launch that fills the chip: 512 workgroups, the four m-tiles of a frame tile on four workgroups of one XCD
     n2, t2, m2 = 8, 2000, 1024
     x2 = H.pad_rows(_rand4((n2, k, t2), 405).to(dev))
@@ -258,7 +254,8 @@ def test_dpcrn_preset_takes_the_frame_major_recurrence(PA, dev):
     assert not torch.equal(outs[True], outs[False])   # (the two paths are different kernels)
 
 
-@pytest.mark.parametrize("n,k,t,flags", [(2, 128, 300, 1 << 28), (3, 256, 1000, 1 << 28), (16, 256, 2000, 0)])
+@pytest.mark.parametrize("n,k,t,flags", [(2, 128, 300, _abi.PS_DBG_GEMM_ANY_SIZE), (3, 256, 1000, _abi.PS_DBG_GEMM_ANY_SIZE),
+                                         (16, 256, 2000, 0)])
 def test_gemm_with_layernorm_epilogue(H, dev, n, k, t, flags):
     """ps_conv1x1_f16x2_ln_f32: y = res + LayerNorm_128(W x + b) in one launch (the projection behind a recurrence, |x| < 1)
     against float64 and against the two-launch path it replaces (fp16x2 GEMM, then ps_chan_layernorm_f32)."""
@@ -276,16 +273,13 @@ def test_gemm_with_layernorm_epilogue(H, dev, n, k, t, flags):
     w256[:c] = w
     wf, we = H.pack_wt_f16x2(w256.to(dev))
     wf1, we1 = H.pack_wt_f16x2(w.to(dev))
-    old = _abi.lib().ps_debug_flags(flags)
-    try:
+    with _abi.debug(flags):
         assert H.conv1x1_f16x2_ln_ok(n, k, c, t)
         y = H.conv1x1_f16x2_ln(xp, t, wf, we, c, b.to(dev), g.to(dev), be.to(dev), 1e-5, rp, x_bound=1.0)
         y_nores = H.conv1x1_f16x2_ln(xp, t, wf, we, c, None, g.to(dev), be.to(dev), 1e-5, None, x_bound=1.0)
         p2, _, _ = H.conv1x1_f16x2(xp, t, wf1, we1, c, None, b.to(dev), x_bound=1.0)
         y2 = H.chan_layernorm(p2, t, g.to(dev), be.to(dev), 1e-5, res=rp)
         torch.cuda.synchronize()
-    finally:
-        _abi.lib().ps_debug_flags(old)
     assert rel_max(y[..., :t].cpu().numpy(), ref.numpy()) < 5e-6
     assert rel_max(y[..., :t].cpu().numpy(), y2[..., :t].cpu().numpy()) < 5e-6
     p0 = torch.einsum("mk,nkt->nmt", w.double(), x.double())
@@ -347,29 +341,30 @@ def test_lstm_h256_streamed_weights_kernel(H, dev, bi, n, s, k, shift, wscale, h
     old_coop = H.COOP_LSTM
     H.COOP_LSTM = bool(coop)
     H._COOP_LAST[0] = None
-    # bit 19: the memory model's agent-scope fences at every barrier; bit 18: a cluster's slices on consecutive workgroup ids,
-    # i.e. on different XCDs -- the kernel must notice (more than one bit in the cluster's mask) and take those fences itself
-    # bit 20: 4-byte h' stores where the launch qualifies for 8-byte ones
-    old_flags = _abi.lib().ps_debug_flags({"agent-scope fences": 1 << 19, "scattered": 1 << 18, "4-byte stores": 1 << 20}.get(coop, 0))
+    # COOP_AGENT_FENCES: the memory model's agent-scope fences at every barrier; COOP_SCATTER: a cluster's slices on
+    # consecutive workgroup ids, i.e. on different XCDs -- the kernel must notice (more than one bit in the cluster's mask)
+    # and take those fences itself; LSTM_4B_STORES: 4-byte h' stores where the launch qualifies for 8-byte ones
+    switch = {"agent-scope fences": _abi.PS_DBG_COOP_AGENT_FENCES, "scattered": _abi.PS_DBG_COOP_SCATTER,
+              "4-byte stores": _abi.PS_DBG_LSTM_4B_STORES}.get(coop, 0)
     try:
-        _lstm_h256_case(H, dev, bi, n, s, k, shift, wscale, hid)
-        if coop:
-            assert H._COOP_LAST[0] is not None, "the cooperative kernel did not run"
-            d, groups = 2 if bi else 1, (n * s + 15) // 16
-            assert H.coop_lstm_error_word(d, groups, hid) == 0
-            ids = H.coop_lstm_xcd_ids(d, groups, hid)   # the XCD every slice ran on, and per cluster the OR of 1 << XCD
-            masks = H.coop_lstm_xcd_masks(d, groups, hid)
-            for row, m in zip(ids.tolist(), masks.tolist()):
-                assert m == sum(1 << x for x in set(row)), (row, m)
-            if coop == "scattered":
-                assert all(len(set(row)) > 1 for row in ids.tolist()), ids    # (different XCDs: the heavy barrier was taken)
-            elif coop is True or coop == "4-byte stores":
-                assert all(len(set(row)) == 1 for row in ids.tolist()), ids   # alone on the chip: one XCD per cluster
-        else:
-            assert H._COOP_LAST[0] is None
+        with _abi.debug(switch):
+            _lstm_h256_case(H, dev, bi, n, s, k, shift, wscale, hid)
+            if coop:
+                assert H._COOP_LAST[0] is not None, "the cooperative kernel did not run"
+                d, groups = 2 if bi else 1, (n * s + 15) // 16
+                assert H.coop_lstm_error_word(d, groups, hid) == 0
+                ids = H.coop_lstm_xcd_ids(d, groups, hid)   # the XCD every slice ran on, and per cluster the OR of 1 << XCD
+                masks = H.coop_lstm_xcd_masks(d, groups, hid)
+                for row, m in zip(ids.tolist(), masks.tolist()):
+                    assert m == sum(1 << x for x in set(row)), (row, m)
+                if coop == "scattered":
+                    assert all(len(set(row)) > 1 for row in ids.tolist()), ids    # (different XCDs: the heavy barrier was taken)
+                elif coop is True or coop == "4-byte stores":
+                    assert all(len(set(row)) == 1 for row in ids.tolist()), ids   # alone on the chip: one XCD per cluster
+            else:
+                assert H._COOP_LAST[0] is None
     finally:
         H.COOP_LSTM = old_coop
-        _abi.lib().ps_debug_flags(old_flags)
 
 
 def _lstm_h256_case(H, dev, bi, n, s, k, shift, wscale, hid):
@@ -786,7 +781,7 @@ def test_bn_block_in_fp16x2_over_input_scales(PA, dev, scale, dilation):
 
 
 def test_cooperative_lstm_gives_up_loudly(H, dev):
-    """A group barrier that one slice never reaches (ps_debug_flags bit 17) runs into its bound instead of spinning for
+    """A group barrier that one slice never reaches (PS_DBG_COOP_SABOTAGE) runs into its bound instead of spinning for
     ever: the launch ends, the error word is set and the result is NaN from the first step on -- and the next launch is fine."""
     import torch.nn as nn
     from puresound_amd import _abi
@@ -802,20 +797,18 @@ def test_cooperative_lstm_gives_up_loudly(H, dev):
     assert H.COOP_LSTM
     good, _ = H.lstm_fmajor_h256(gx_fm, img, scale, 1, 1, k, k, 1)
     assert H.coop_lstm_error_word(1, 1, hid) == 0 and torch.isfinite(good[..., :k]).all()
-    old = _abi.lib().ps_debug_flags(1 << 17)
-    try:
+    with _abi.debug(_abi.PS_DBG_COOP_SABOTAGE):
         bad, _ = H.lstm_fmajor_h256(gx_fm, img, scale, 1, 1, k, k, 1)
         torch.cuda.synchronize()
-    finally:
-        _abi.lib().ps_debug_flags(old)
     assert H.coop_lstm_error_word(1, 1, hid) == 1
     assert torch.isnan(bad[..., :k]).all()
     again, _ = H.lstm_fmajor_h256(gx_fm, img, scale, 1, 1, k, k, 1)
     assert H.coop_lstm_error_word(1, 1, hid) == 0 and torch.equal(again[..., :k], good[..., :k])
 
 
-@pytest.mark.parametrize("flags,what", [(0, "light barrier, 8-byte stores"), (1 << 20, "light barrier, 4-byte stores"),
-                                        (1 << 19, "agent-scope fences")])
+@pytest.mark.parametrize("flags,what", [(0, "light barrier, 8-byte stores"),
+                                        (_abi.PS_DBG_LSTM_4B_STORES, "light barrier, 4-byte stores"),
+                                        (_abi.PS_DBG_COOP_AGENT_FENCES, "agent-scope fences")])
 @pytest.mark.parametrize("d", [1, 2])
 def test_cooperative_lstm_many_groups_back_to_back(H, dev, flags, what, d):
     """SkiM's segment-LSTM launch (864 sequences x 150 steps, H = 256: 54 groups x 4 slices on 216 CUs) eight times back to
@@ -834,12 +827,9 @@ def test_cooperative_lstm_many_groups_back_to_back(H, dev, flags, what, d):
         H.COOP_LSTM = False
         ref, _ = H.lstm_fmajor_h256(gx, img, scale, d, q, steps, steps, 1)
         H.COOP_LSTM = True
-        old = _abi.lib().ps_debug_flags(flags)
-        try:
+        with _abi.debug(flags):
             outs = [H.lstm_fmajor_h256(gx, img, scale, d, q, steps, steps, 1)[0] for _ in range(8)]
             torch.cuda.synchronize()
-        finally:
-            _abi.lib().ps_debug_flags(old)
         groups = (n * q + 15) // 16
         assert H.coop_lstm_error_word(d, groups, hid) == 0
         diffs = [float((o[..., :t] - ref[..., :t]).abs().max()) for o in outs]

@@ -27,38 +27,37 @@ for name, (K, M, pro, res) in shapes.items():
     flop = 2.0 * N * T * K * M
     res_line = []
     for fname, f in flags.items():
-        lib.ps_debug_flags(f)
-        for _ in range(3):
-            hip.conv1x1(x, T, wt, M, p, bias, None, r, want_stats=not res, out=y)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        reps = 10
-        e0.record()
-        for _ in range(reps):
-            hip.conv1x1(x, T, wt, M, p, bias, None, r, want_stats=not res, out=y)
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) / reps * 1e3
-        res_line.append(f"{fname}={us:.0f}us")
-    lib.ps_debug_flags(0)
-    # flags: 0 = default (interleaved one-barrier persistent kernel), 32 = two-barrier ping-pong kernel, bit 27 = simple kernel,
-    # bit 30 = single-wave experiment; extra flag bits from the command line are OR-ed in (kernel experiments)
-    extra = int(sys.argv[1], 0) if len(sys.argv) > 1 else 0
-    for planes, abl in ((3, 0), (3, 32), (1, 0), (1, 32)):
-        lib.ps_debug_flags(abl | (extra if abl == 0 else 0))
-        wb = hip.pack_wt_bf16(torch.randn(M, K, device=dev) * 0.05, planes)
-        for _ in range(3):
-            hip.conv1x1_bf16(x, T, wb, M, p, bias, None, r, want_stats=not res, out=y)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            hip.conv1x1_bf16(x, T, wb, M, p, bias, None, r, want_stats=not res, out=y)
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) / 10 * 1e3
-        res_line.append(f"bf16x{planes}/{ {0: 'il', 32: 'pp'}.get(abl, 'simple') }={us:.0f}us ({flop / us / 1e6 * (6 if planes == 3 else 1) / 2500:.2f})")
-    lib.ps_debug_flags(0)
+        with _abi.debug(f):
+            for _ in range(3):
+                hip.conv1x1(x, T, wt, M, p, bias, None, r, want_stats=not res, out=y)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            reps = 10
+            e0.record()
+            for _ in range(reps):
+                hip.conv1x1(x, T, wt, M, p, bias, None, r, want_stats=not res, out=y)
+            e1.record()
+            torch.cuda.synchronize()
+            us = e0.elapsed_time(e1) / reps * 1e3
+            res_line.append(f"{fname}={us:.0f}us")
+    # 0 = default (interleaved one-barrier persistent kernel), GEMM_TWO_BARRIER = two-barrier ping-pong kernel; switches
+    # from the command line (PS_DBG_* names without the prefix, comma-separated) are OR-ed into the default leg
+    extra = sum(getattr(_abi, "PS_DBG_" + s) for s in (sys.argv[1] if len(sys.argv) > 1 else "").split(",") if s)
+    two = _abi.PS_DBG_GEMM_TWO_BARRIER
+    for planes, abl in ((3, 0), (3, two), (1, 0), (1, two)):
+        with _abi.debug(abl | (extra if abl == 0 else 0)):
+            wb = hip.pack_wt_bf16(torch.randn(M, K, device=dev) * 0.05, planes)
+            for _ in range(3):
+                hip.conv1x1_bf16(x, T, wb, M, p, bias, None, r, want_stats=not res, out=y)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                hip.conv1x1_bf16(x, T, wb, M, p, bias, None, r, want_stats=not res, out=y)
+            e1.record()
+            torch.cuda.synchronize()
+            us = e0.elapsed_time(e1) / 10 * 1e3
+            res_line.append(f"bf16x{planes}/{ {0: 'il', two: 'pp'}.get(abl, 'simple') }={us:.0f}us ({flop / us / 1e6 * (6 if planes == 3 else 1) / 2500:.2f})")
     wf, we = hip.pack_wt_f16x2(torch.randn(M, K, device=dev) * 0.05)
     kw = dict(x_bound=1000.0) if pro else dict(x_amax=hip.absmax(x, T))
     for _ in range(3):

@@ -107,8 +107,8 @@ def cfg4_data_parallel(args, world):
 def dpcrn(args):
     """The real egs/ns model (ns_dpcrn_v0_causal: conv-STFT 512/128 + DPCRN + complex mask + iSTFT), 32 x 4 s."""
     dev = "cuda:0"
-    if os.environ.get("PS_FLAGS"):   # experiments: ps_debug_flags for the whole run
-        _abi.lib().ps_debug_flags(int(os.environ["PS_FLAGS"], 0))
+    if os.environ.get("PS_FLAGS"):   # experiments: PS_DBG_* switches (names without the prefix, comma-separated)
+        _abi.lib().ps_debug_flags(sum(getattr(_abi, "PS_DBG_" + s) for s in os.environ["PS_FLAGS"].split(",") if s))
     model = cases.build(PA.NS, os.environ.get("PS_NS_CASE", "ns_dpcrn_short")).eval()
     model.load_state_dict(det_state_dict(model))
     model.to(dev)
@@ -163,7 +163,7 @@ if __name__ == "__main__":
     ap.add_argument("--streams", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=500)
     ap.add_argument("--profile", action="store_true")
-    ap.add_argument("--flags", type=int, default=0, help="ps_debug_flags (kernel variant switches)")
+    ap.add_argument("--flags", default="", help="kernel variant switches: PS_DBG_* names without the prefix, comma-separated")
     ap.add_argument("--gemm", default="fp32", choices=["fp32", "fp16x2", "bf16x3", "bf16"],
                     help="arithmetic of the LSTM input projections (per module: masker.set_gemm_precision)")
     a = ap.parse_args()
@@ -174,7 +174,7 @@ if __name__ == "__main__":
     if launch.launch_probe("bench_recurrent.py"):
         raise SystemExit(0)
     if a.flags:
-        _abi.lib().ps_debug_flags(a.flags)
+        _abi.lib().ps_debug_flags(sum(getattr(_abi, "PS_DBG_" + s) for s in a.flags.split(",") if s))
     if "cfg4" in a.which:
         cfg4(a)
     if "cfg5" in a.which:

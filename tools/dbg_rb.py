@@ -1,4 +1,4 @@
-"""Debug: the rb kernel (ps_debug_flags bit 22) against the exact-fp32 GEMM on one shape; where do they differ?"""
+"""Debug: the rb kernel (PS_DBG_GEMM_NO_RB switches it off) against the exact-fp32 GEMM on one shape; where do they differ?"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,11 +15,11 @@ parts = lib.ps_dwconv_stats_parts(K, T)
 st = torch.zeros(N, parts, 2, dtype=torch.float64, device=dev); st[:, 0, 1] = float(K * T)
 p = hip.make_prologue(_abi.PS_NORM_GLOBAL, True, st, K * T, 1e-8, g, b, sl)
 ref, _ = hip.conv1x1(x, T, hip.pack_wt(w), M, p, bias, None, r, want_stats=False)
-for flags in (0, 1 << 22):
-    lib.ps_debug_flags(flags)
-    y = torch.full((N, M, ldt), float("nan"), device=dev)
-    yy, _, amx = hip.conv1x1_f16x2(x, T, wb, we, M, p, bias, None, r, want_stats=False, out=y, want_amax=True, x_bound=1000.0)
-    torch.cuda.synchronize(); lib.ps_debug_flags(0)
+for flags in (0, _abi.PS_DBG_GEMM_NO_RB):
+    with _abi.debug(flags):
+        y = torch.full((N, M, ldt), float("nan"), device=dev)
+        yy, _, amx = hip.conv1x1_f16x2(x, T, wb, we, M, p, bias, None, r, want_stats=False, out=y, want_amax=True, x_bound=1000.0)
+        torch.cuda.synchronize()
     d = (yy[:, :, :T] - ref[:, :, :T]).abs()
     bad = d > 1e-3
     print(f"flags {flags:#x}: max err {float(d.max()):.3e}  bad {int(bad.sum())} of {bad.numel()}  nan {int(torch.isnan(yy[:, :, :T]).sum())}")

@@ -55,14 +55,12 @@ for xs in (1.0, 1e-3, 300.0):
         outs["fp32"] = hip.conv1x1(x, T, hip.pack_wt(w), M, p, bias, None, r, want_stats=not res)[0]
         outs["bf16x3"] = hip.conv1x1_bf16(x, T, hip.pack_wt_bf16(w, 3), M, p, bias, None, r, want_stats=not res)[0]
         wf, we = hip.pack_wt_f16x2(w)
-        lib.ps_debug_flags(0)
         outs["fp16x2/default range"] = hip.conv1x1_f16x2(x, T, wf, we, M, p, bias, None, r, want_stats=not res)[0]
         # the range a caller would give: a bound behind the norm, the producer's maxima for raw rows
         kw = dict(x_bound=float(gbs[0].abs().max()) * (K * T) ** 0.5 + float(gbs[1].abs().max())) if pro else dict(x_amax=hip.absmax(x, T))
         outs["fp16x2"], _, am = hip.conv1x1_f16x2(x, T, wf, we, M, p, bias, None, r, want_stats=not res, want_amax=True, **kw)
-        lib.ps_debug_flags(1 << 27)
-        outs["fp16x2/simple"], _, am2 = hip.conv1x1_f16x2(x, T, wf, we, M, p, bias, None, r, want_stats=not res, want_amax=True, **kw)
-        lib.ps_debug_flags(0)
+        with _abi.debug(_abi.PS_DBG_GEMM_SIMPLE):
+            outs["fp16x2/simple"], _, am2 = hip.conv1x1_f16x2(x, T, wf, we, M, p, bias, None, r, want_stats=not res, want_amax=True, **kw)
         ymax = outs["fp16x2"][:, :, :T].abs().amax((1, 2))
         assert torch.equal(am.amax(1), ymax) and torch.equal(am2.amax(1), outs["fp16x2/simple"][:, :, :T].abs().amax((1, 2))), (am.amax(1), ymax)
         line = f"x scale {xs:g} {name}:"

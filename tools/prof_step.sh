@@ -1,6 +1,7 @@
 #!/bin/bash
-# kernel-trace averages of the benchmark's step (tools/step_time.py) for a list of ps_debug_flags values (GPU box):
-#   tools/prof_step.sh 0 0x400000
+# kernel-trace averages of the benchmark's step (tools/step_time.py) for a list of PS_FLAGS values (PS_DBG_* names
+# without the prefix, comma-separated; "" = the default dispatch) (GPU box):
+#   tools/prof_step.sh "" GEMM_NO_RB
 root=$(pwd); cd /tmp && export TMPDIR=/tmp && cd "$root"
 for f in "$@"; do
   out=gpurun_out/prof_step; rm -rf $out

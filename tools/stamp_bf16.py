@@ -7,7 +7,7 @@ dev = torch.device("cuda:0"); lib = _abi.lib()
 N, T = 32, 3999; ldt = _abi.padded_frames(T)
 shapes = {"in": (512, 256, False, False), "pw": (256, 256, True, False), "out": (256, 512, True, True)}
 ABL = int(sys.argv[1]) if len(sys.argv) > 1 else 0
-lib.ps_debug_flags(ABL << 24)
+lib.ps_debug_ablate(ABL)
 for planes in (3, 1):
     for name, (K, M, pro, res) in shapes.items():
         x = torch.randn(N, K, ldt, device=dev); wb = hip.pack_wt_bf16(torch.randn(M, K, device=dev) * 0.05, planes)
@@ -25,7 +25,7 @@ for planes in (3, 1):
         hip.conv1x1_bf16(x, T, wb, M, p, bias, None, r, want_stats=not res, out=y)
         torch.cuda.synchronize(); lib.ps_debug_buffer(None)
         s = buf.cpu().numpy().reshape(nwg, 6).astype(np.int64)
-        if not (lib.ps_debug_flags(-1) & (1 << 27)):  # ping-pong kernel: one record per (workgroup, half)
+        if not (lib.ps_debug_flags(-1) & _abi.PS_DBG_GEMM_SIMPLE):  # ping-pong kernel: one record per (workgroup, half)
             s = s[:512]
             for h in (0, 1):
                 q = s[h::2]

@@ -1,6 +1,6 @@
 """Cycle buckets of conv1x1_bf16_il_kernel per (workgroup, half) from a -DPS_PP_STAMPS build (s_memtime):
 interval body (MFMAs + chunks) / wait + barrier / drain.  Run on the GPU box:
-  make -C puresound_amd/csrc clean all EXTRA=-DPS_PP_STAMPS && python tools/stamp_il.py [extra debug flags]"""
+  make -C puresound_amd/csrc clean all EXTRA=-DPS_PP_STAMPS && python tools/stamp_il.py [PS_DBG_* names without the prefix, comma-separated]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -8,8 +8,7 @@ from puresound_amd import hip, _abi
 dev = torch.device("cuda:0"); lib = _abi.lib()
 N, T = 32, 3999; ldt = _abi.padded_frames(T)
 shapes = {"in": (512, 256, False, False), "pw": (256, 256, True, False), "out": (256, 512, True, True)}
-extra = int(sys.argv[1], 0) if len(sys.argv) > 1 else 0
-lib.ps_debug_flags(extra)
+lib.ps_debug_flags(sum(getattr(_abi, "PS_DBG_" + s) for s in (sys.argv[1] if len(sys.argv) > 1 else "").split(",") if s))
 for planes in (3, 2, 1):
     for name, (K, M, pro, res) in shapes.items():
         x = torch.randn(N, K, ldt, device=dev)

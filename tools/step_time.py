@@ -1,5 +1,6 @@
 """The benchmark's step (config 2, 32 x 4 s, fp16x2 by default) with the library's per-launch hipEvents: ms per step and
-average launch of each kernel family.  PURESOUND_HIP_LIB=tools/_variants/X.so python tools/step_time.py [gemm] [steps]"""
+average launch of each kernel family.  PURESOUND_HIP_LIB=tools/_variants/X.so python tools/step_time.py [gemm] [steps]
+PS_FLAGS: comma-separated PS_DBG_* names without the prefix; PS_CAP: persistent-grid cap."""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -13,7 +14,8 @@ lib = _abi.lib()
 model = bench.build_model(dev)
 model.masker.set_gemm_precision(gemm)
 model.hip_streams = int(os.environ.get("PS_STREAMS", "1"))
-lib.ps_debug_flags((int(os.environ.get("PS_CAP", "0")) << 8) | int(os.environ.get("PS_FLAGS", "0"), 0))
+lib.ps_debug_flags(sum(getattr(_abi, "PS_DBG_" + s) for s in os.environ.get("PS_FLAGS", "").split(",") if s))
+lib.ps_debug_grid_cap(int(os.environ.get("PS_CAP", "0")))
 g = torch.Generator().manual_seed(1234)
 noisy = ((torch.rand(bench.B_PER_GPU, bench.L, generator=g) * 2 - 1) * 0.5).to(dev)
 for _ in range(5):

@@ -14,7 +14,7 @@ for gemm in sys.argv[1:] or ["fp32", "bf16x3", "bf16"]:
         model.masker.set_gemm_precision(gemm)
     from puresound_amd import _abi
     for streams, cap in ((1, 0), (2, 0), (2, 128), (2, 160), (4, 64), (4, 128), (3, 96)):
-        _abi.lib().ps_debug_flags(cap << 8)
+        _abi.lib().ps_debug_grid_cap(cap)
         model.hip_streams = streams
         for _ in range(5):
             model.inference(noisy)

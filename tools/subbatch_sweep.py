@@ -9,7 +9,7 @@ dev = torch.device("cuda:0")
 model = bench.build_model(dev)
 model.hip_streams = 1
 from puresound_amd import _abi
-_abi.lib().ps_debug_flags(int(os.environ.get("PS_FLAGS", "0"), 0))
+_abi.lib().ps_debug_flags(sum(getattr(_abi, "PS_DBG_" + s) for s in os.environ.get("PS_FLAGS", "").split(",") if s))  # (PS_DBG_* names)
 x = ((torch.rand(32, 64000) * 2 - 1) * 0.5).to(dev)
 for gemm in ("fp16x2",):
     model.masker.set_gemm_precision(gemm)
