@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PS_ABI_VERSION 23
+#define PS_ABI_VERSION 24
 
 #define PS_E_INVALID (-1)     /* bad shape / null pointer / unsupported combination */
 #define PS_E_ALIGN (-2)       /* ldt or a pointer violates the alignment contract */
@@ -583,6 +583,32 @@ int ps_conv2d_step_f32(const float* x1, const float* ring1, int C1, int R1, cons
 int ps_istft_step_f32(const float* frames, int ldf, const float* window, float* tail, float* out, int ld_out,
                       const int* counter, int B, int n_fft, int hop, int out_mode, int flush, void* stream);
 int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs, int* counter, void* stream);
+
+/* k causal frames of the time-domain Conv-TasNet (FreeEncDec + causal ConvTasNet) for B streams at once
+ * (puresound_amd/streaming/tcn.py).  Column n = f * B + b of a [C][ld] row tensor is frame f < k of the chunk, stream b < B;
+ * `counter` is a device int = the absolute index t0 of the chunk's first frame, advanced by ps_stream_commit_frames_f32, so
+ * one captured graph per chunk length replays every chunk.
+ *
+ * ps_dwconv_step_f32: the causal depthwise convolution of a TCN block (ps_dwconv_f32 with left = (P-1)*dilation):
+ *   y[h][n] = bias[h] + sum_j w[h][j] a(t0 + f - (P-1-j)*dilation), a = PReLU(affine(x)) through `pro` (norm PS_NORM_NONE
+ *   or PS_NORM_AFFINE, PReLU with one shared slope; NULL = identity).  Frames of the chunk come from x [H][ld]; earlier frames
+ *   g >= 0 from ring slot g % R ([R][H][B], activated values); frames g < 0 are 0 (the zero padding after the prologue).
+ *   Every activated frame of the chunk is stored in its slot (t0 + f) % R.  R >= (P-1)*dilation + k.  Writes y[h][n] for
+ *   n < k*B only.  Exact fp32 products.
+ * ps_free_decode_step_f32: FreeEncDec.inverse (a transposed convolution, stride hop) for the chunk's k frames per stream:
+ *   frame f adds s[j] = sum_c w[c][j] feats[c][n] act(mask[c][n]) (w [C][win], mask NULL = 1, act PS_ACT_*) to the samples
+ *   [f*hop + j] after the stream's tail [B][win - hop]; out[b][f*hop + i] = constrain(sample) for i < hop (out row stride
+ *   ld_out, out_mode PS_OUT_*), the last win - hop samples become the new tail.  flush = 1: out[b][i] = constrain(tail[b][i]),
+ *   i < win - hop (nothing when win = hop).  win % hop == 0, win <= 256.  ws: ps_free_decode_step_workspace_bytes(B, k, win)
+ *   bytes of scratch (the k frames' synthesis products; not read by flush).
+ * ps_stream_commit_frames_f32: ps_stream_commit_f32 with *counter += frames (frames >= 1). */
+int ps_dwconv_step_f32(const float* x, float* ring, int R, const int* counter, const float* w, const float* b, float* y, int H,
+                       int B, int k, int ld, int P, int dilation, const ps_prologue* pro, void* stream);
+size_t ps_free_decode_step_workspace_bytes(int B, int k, int win);
+int ps_free_decode_step_f32(const float* feats, const float* mask, int mask_act, int ld, const float* w, float* tail,
+                            float* out, int ld_out, int B, int k, int C, int win, int hop, int out_mode, int flush, float* ws,
+                            size_t ws_bytes, void* stream);
+int ps_stream_commit_frames_f32(const ps_ring_pair* pairs_host, int n_pairs, int* counter, int frames, void* stream);
 
 /* One cell update per (unit, frame) from COMPLETE gate pre-activations gates [N][D*4H][ld_gates] (W_ih x + W_hh h + both
  * biases: the streaming step puts [x; h] on the K axis of one ps_conv1x1_f32):  c' = sig(f) c + sig(i) tanh(g) in

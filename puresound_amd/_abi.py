@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PURESOUND_HIP_LIB: an experimental build of the same library (tools/build_variant.sh); kernel experiments only
 LIB_PATH = os.environ.get("PURESOUND_HIP_LIB") or os.path.join(_HERE, "libpuresound_hip.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 PS_NORM_NONE, PS_NORM_GLOBAL, PS_NORM_AFFINE = 0, 1, 2
 PS_ACT = {"linear": 0, "relu": 1, "sigmoid": 2}
@@ -178,6 +178,10 @@ SIGNATURES = {
                            + [_vp, _vp]),
     "ps_istft_step_f32": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp] + [C.c_int] * 5 + [_vp]),
     "ps_stream_commit_f32": (C.c_int, [C.POINTER(RingPair), C.c_int, _vp, _vp]),
+    "ps_dwconv_step_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp] + [C.c_int] * 6 + [C.POINTER(Prologue), _vp]),
+    "ps_free_decode_step_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "ps_free_decode_step_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp] + [C.c_int] * 8 + [_vp, C.c_size_t, _vp]),
+    "ps_stream_commit_frames_f32": (C.c_int, [C.POINTER(RingPair), C.c_int, _vp, C.c_int, _vp]),
     "ps_unfold2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp] + [C.c_int] * 14 + [_vp]),
     "ps_conv2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 16 + [_vp, _vp]),
     "ps_conv2d_stats_parts": (C.c_int, [C.c_int] * 3),

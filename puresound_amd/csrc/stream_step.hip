@@ -7,6 +7,7 @@
 // ps_conv2d_step_f32  one frame of a causal Conv2d / ConvTranspose2d, previous frames from history rings (VALU tile GEMM)
 // ps_istft_step_f32   synthesis of one frame per stream (window, / n_fft, overlap-add into the tail, / window sum)
 // ps_stream_commit_f32   the history commit behind every hop: rings shift by one frame, the counter advances
+// ps_stream_commit_frames_f32   the same commit with the counter advanced by k frames (the Conv-TasNet streamer's chunk)
 #include "ps_common.h"
 
 namespace ps {
@@ -188,17 +189,17 @@ __global__ __launch_bounds__(256) void istft_step_kernel(const float* __restrict
 // ---------------------------------------------------------------------------------------------------------------------
 // ps_stream_commit_f32.  Pair p: ring[r] <- ring[r + 1] for r < R - 1, ring[R - 1] <- src (R slots of `count` floats; R = 1
 // is a plain copy: the window queue, carried LSTM states).  One thread owns one float4 column of a pair across all its slots,
-// so the shift needs no ordering between threads.  Thread 0 of workgroup (0, 0) advances the counter; nothing else in the
-// launch reads it.
+// so the shift needs no ordering between threads.  Thread 0 of workgroup (0, 0) advances the counter by `advance` frames;
+// nothing else in the launch reads it.
 // ---------------------------------------------------------------------------------------------------------------------
 struct CommitTable {
   ps_ring_pair p[PS_MAX_RING_PAIRS];
 };
 
-__global__ __launch_bounds__(256) void stream_commit_kernel(CommitTable tab, int* counter) {
+__global__ __launch_bounds__(256) void stream_commit_kernel(CommitTable tab, int* counter, int advance) {
   const ps_ring_pair& q = tab.p[blockIdx.y];
   const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (counter && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) counter[0] += 1;
+  if (counter && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) counter[0] += advance;
   if (i >= q.count) return;
   for (int r = 0; r + 1 < q.slots; ++r)
     *reinterpret_cast<f32x4*>(q.ring + (size_t)r * q.count + i) =
@@ -270,9 +271,10 @@ extern "C" int ps_istft_step_f32(const float* frames, int ldf, const float* wind
   return step_launched("ps_istft_step_f32");
 }
 
-extern "C" int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs, int* counter, void* stream) {
+static int stream_commit(const char* who, const ps_ring_pair* pairs_host, int n_pairs, int* counter, int advance,
+                         void* stream) {
   if (!pairs_host || n_pairs <= 0 || n_pairs > PS_MAX_RING_PAIRS) {
-    set_error("ps_stream_commit_f32: 1 .. %d pairs (got %d)", PS_MAX_RING_PAIRS, n_pairs);
+    set_error("%s: 1 .. %d pairs (got %d)", who, PS_MAX_RING_PAIRS, n_pairs);
     return PS_E_INVALID;
   }
   CommitTable tab{};
@@ -281,8 +283,8 @@ extern "C" int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs,
     const ps_ring_pair& q = pairs_host[p];
     if (!q.src || !q.ring || q.count <= 0 || q.count % 4 || q.slots <= 0 || ((uintptr_t)q.src & 15) ||
         ((uintptr_t)q.ring & 15) || q.count > ((int64_t)1 << 40)) {
-      set_error("ps_stream_commit_f32: pair %d: 16-byte aligned src / ring, count a positive multiple of 4 (got %lld), "
-                "slots >= 1 (got %d)", p, (long long)q.count, q.slots);
+      set_error("%s: pair %d: 16-byte aligned src / ring, count a positive multiple of 4 (got %lld), "
+                "slots >= 1 (got %d)", who, p, (long long)q.count, q.slots);
       return PS_E_INVALID;
     }
     tab.p[p] = q;
@@ -290,10 +292,24 @@ extern "C" int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs,
   }
   const int64_t blocks = (most / 4 + 255) / 256;
   if (blocks > 0x7fffffffLL) {
-    set_error("ps_stream_commit_f32: pair too large");
+    set_error("%s: pair too large", who);
     return PS_E_INVALID;
   }
   LaunchTimer timer("stream_commit", (hipStream_t)stream);
-  hipLaunchKernelGGL(stream_commit_kernel, dim3((unsigned)blocks, n_pairs), dim3(256), 0, (hipStream_t)stream, tab, counter);
-  return step_launched("ps_stream_commit_f32");
+  hipLaunchKernelGGL(stream_commit_kernel, dim3((unsigned)blocks, n_pairs), dim3(256), 0, (hipStream_t)stream, tab, counter,
+                     advance);
+  return step_launched(who);
+}
+
+extern "C" int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs, int* counter, void* stream) {
+  return stream_commit("ps_stream_commit_f32", pairs_host, n_pairs, counter, 1, stream);
+}
+
+extern "C" int ps_stream_commit_frames_f32(const ps_ring_pair* pairs_host, int n_pairs, int* counter, int frames,
+                                           void* stream) {
+  if (frames <= 0) {
+    set_error("ps_stream_commit_frames_f32: frames >= 1 (got %d)", frames);
+    return PS_E_INVALID;
+  }
+  return stream_commit("ps_stream_commit_frames_f32", pairs_host, n_pairs, counter, frames, stream);
 }

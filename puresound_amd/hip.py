@@ -943,6 +943,66 @@ def stream_commit(table: "C.Array[RingPair]", counter: Optional[torch.Tensor], d
     check(lib().ps_stream_commit_f32(table, len(table), ptr(counter), stream_ptr(device)), "ps_stream_commit_f32")
 
 
+def stream_commit_frames(table: "C.Array[RingPair]", counter: torch.Tensor, frames: int, device: torch.device) -> None:
+    """ps_stream_commit_f32 with the frame counter advanced by `frames` (ps_stream_commit_frames_f32)."""
+    check(lib().ps_stream_commit_frames_f32(table, len(table), ptr(counter), int(frames), stream_ptr(device)),
+          "ps_stream_commit_frames_f32")
+
+
+def dwconv_step(x: torch.Tensor, ring: torch.Tensor, counter: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor],
+                dilation: int, streams: int, frames: int, pro: Optional[Prologue] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal depthwise convolution of `frames` new frames of `streams` streams (ps_dwconv_step_f32): x [1, H, ld] (column
+    f * streams + b), w [H, 1, P]; earlier frames from ring [R, H, streams] (slot g % R = frame g, activated values; the
+    chunk's frames are stored there too), frame index of column 0 = counter[0] -> y [1, H, ld] (columns past
+    frames * streams are not written)."""
+    require_device(x, "dwconv_step")
+    _, h, ld = x.shape
+    p = w.shape[-1]
+    if not (x.is_contiguous() and ring.is_contiguous()) or ring.dim() != 3 or tuple(ring.shape[1:]) != (h, streams) \
+            or counter.dtype != torch.int32:
+        raise RuntimeError("dwconv_step: contiguous x [1, H, ld] and ring [R, H, streams], int32 counter expected")
+    y = out if out is not None else torch.zeros_like(x)
+    if y.shape != x.shape or not y.is_contiguous():
+        raise RuntimeError("dwconv_step: out must be a contiguous tensor of x's shape")
+    check(lib().ps_dwconv_step_f32(ptr(x), ptr(ring), ring.shape[0], ptr(counter), ptr(w), ptr(b), ptr(y), h, streams, frames,
+                                   ld, p, dilation, C.byref(pro) if pro is not None else None, stream_ptr(x.device)),
+          "ps_dwconv_step_f32")
+    return y
+
+
+def free_decode_step(feats: Optional[torch.Tensor], mask: Optional[torch.Tensor], w: torch.Tensor, tail: torch.Tensor,
+                     out: torch.Tensor, hop: int, frames: int = 0, mask_act: str = "linear", out_mode: str = "linear",
+                     flush: bool = False) -> torch.Tensor:
+    """FreeEncDec's decoder for `frames` new frames of B streams (ps_free_decode_step_f32): feats / mask [1, C, ld] (column
+    f * B + b), w [C, 1, win], overlap-add tail [B, win - hop] updated in place -> out [B, frames * hop] (a row view of a
+    wider buffer is fine); flush: the tail's samples -> out [B, win - hop]."""
+    require_device(tail, "free_decode_step")
+    b, keep = tail.shape
+    win = w.shape[-1]
+    if keep != win - hop or not tail.is_contiguous() or out.dim() != 2 or out.shape[0] != b or out.stride(1) != 1 \
+            or out.shape[1] != (keep if flush else frames * hop):
+        raise RuntimeError("free_decode_step: tail [B, win - hop] contiguous, out [B, frames * hop] (flush: [B, win - hop]) "
+                           "with unit column stride expected")
+    ld, c = 0, w.shape[0]
+    if flush and keep == 0:
+        return out
+    if not flush:
+        require_weight(w, tail, "free_decode_step")
+        for t in (feats, mask):
+            if t is not None and (t.dim() != 3 or t.shape[:2] != (1, c) or not t.is_contiguous()):
+                raise RuntimeError(f"free_decode_step: feats / mask must be contiguous [1, {c}, ld] tensors")
+        ld = feats.shape[2]
+        if mask is not None and mask.shape != feats.shape:
+            raise RuntimeError("free_decode_step: feats and mask of one shape expected")
+    ws_bytes = 0 if flush else lib().ps_free_decode_step_workspace_bytes(b, frames, win)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=tail.device) if ws_bytes else None
+    check(lib().ps_free_decode_step_f32(ptr(feats), ptr(mask), _abi.PS_ACT[mask_act], ld, ptr(w), ptr(tail), ptr(out),
+                                        out.stride(0), b, frames, c, win, hop, _abi.PS_OUT[out_mode], int(flush), ptr(ws),
+                                        ws_bytes, stream_ptr(tail.device)), "ps_free_decode_step_f32")
+    return out
+
+
 def unfold2d(x1: torch.Tensor, x2: Optional[torch.Tensor], t: int, f_out: int, kf: int, kt: int, stride_f: int,
              dil_f: int, dil_t: int, pad_f: int, pad_t: int, transposed: bool, t_in: Optional[int] = None) -> torch.Tensor:
     """x1 [N,C1,F,ld] (+ x2 [N,C2,F,ld]) -> tap rows [N, (C1+C2)*kf*kt, f_out*ld] for the Conv2d / ConvTranspose2d GEMM."""
