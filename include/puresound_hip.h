@@ -27,6 +27,8 @@
 extern "C" {
 #endif
 
+/* Raised when an existing signature, struct or constant changes.  A pull request that only ADDS entry points keeps the number: a
+ * binding made for this number still loads and runs against the newer library (the *_slots_f32 entry points came in at 24). */
 #define PS_ABI_VERSION 24
 
 #define PS_E_INVALID (-1)     /* bad shape / null pointer / unsupported combination */
@@ -601,7 +603,18 @@ int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs, int* count
  *   ld_out, out_mode PS_OUT_*), the last win - hop samples become the new tail.  flush = 1: out[b][i] = constrain(tail[b][i]),
  *   i < win - hop (nothing when win = hop).  win % hop == 0, win <= 256.  ws: ps_free_decode_step_workspace_bytes(B, k, win)
  *   bytes of scratch (the k frames' synthesis products; not read by flush).
- * ps_stream_commit_frames_f32: ps_stream_commit_f32 with *counter += frames (frames >= 1). */
+ * ps_stream_commit_frames_f32: ps_stream_commit_f32 with *counter += frames (frames >= 1).
+ *
+ * Slots: streams that begin and end on their own while the session runs.  span [B][2] (device int, 8-byte aligned) holds per
+ * stream the absolute frame indices (birth, death); frame g of stream b is LIVE iff span[b][0] <= g < span[b][1], an idle
+ * column has an empty span.  The column may hold anything while it is not live (inf / NaN included).
+ * ps_dwconv_step_slots_f32: ps_dwconv_step_f32 where a tap reads frame g, from the chunk or from the ring, iff g is live in
+ *   its stream, and reads an exact 0 otherwise (as for g < 0: a zero after the prologue).  Every activated frame of the
+ *   chunk is still stored in its ring slot; ring slots of dead frames are never read, so the ring needs no clearing when a
+ *   stream begins.
+ * ps_free_decode_step_slots_f32: ps_free_decode_step_f32 (never the flush) where frame f of the chunk, g = *counter + f,
+ *   adds its synthesis product iff g is live in its stream (a dead frame adds an exact 0, its columns are not read).  The
+ *   tail of one stream is flushed by ps_free_decode_step_f32(flush = 1) with B = 1 on that stream's row. */
 int ps_dwconv_step_f32(const float* x, float* ring, int R, const int* counter, const float* w, const float* b, float* y, int H,
                        int B, int k, int ld, int P, int dilation, const ps_prologue* pro, void* stream);
 size_t ps_free_decode_step_workspace_bytes(int B, int k, int win);
@@ -609,6 +622,12 @@ int ps_free_decode_step_f32(const float* feats, const float* mask, int mask_act,
                             float* out, int ld_out, int B, int k, int C, int win, int hop, int out_mode, int flush, float* ws,
                             size_t ws_bytes, void* stream);
 int ps_stream_commit_frames_f32(const ps_ring_pair* pairs_host, int n_pairs, int* counter, int frames, void* stream);
+int ps_dwconv_step_slots_f32(const float* x, float* ring, int R, const int* counter, const int* span, const float* w,
+                             const float* b, float* y, int H, int B, int k, int ld, int P, int dilation, const ps_prologue* pro,
+                             void* stream);
+int ps_free_decode_step_slots_f32(const float* feats, const float* mask, int mask_act, int ld, const float* w, float* tail,
+                                  float* out, int ld_out, const int* span, const int* counter, int B, int k, int C, int win,
+                                  int hop, int out_mode, float* ws, size_t ws_bytes, void* stream);
 
 /* One cell update per (unit, frame) from COMPLETE gate pre-activations gates [N][D*4H][ld_gates] (W_ih x + W_hh h + both
  * biases: the streaming step puts [x; h] on the K axis of one ps_conv1x1_f32):  c' = sig(f) c + sig(i) tanh(g) in

@@ -182,6 +182,10 @@ SIGNATURES = {
     "ps_free_decode_step_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "ps_free_decode_step_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp] + [C.c_int] * 8 + [_vp, C.c_size_t, _vp]),
     "ps_stream_commit_frames_f32": (C.c_int, [C.POINTER(RingPair), C.c_int, _vp, C.c_int, _vp]),
+    "ps_dwconv_step_slots_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp] + [C.c_int] * 6
+                                 + [C.POINTER(Prologue), _vp]),
+    "ps_free_decode_step_slots_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]
+                                      + [C.c_int] * 6 + [_vp, C.c_size_t, _vp]),
     "ps_unfold2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp] + [C.c_int] * 14 + [_vp]),
     "ps_conv2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 16 + [_vp, _vp]),
     "ps_conv2d_stats_parts": (C.c_int, [C.c_int] * 3),

@@ -949,13 +949,19 @@ def stream_commit_frames(table: "C.Array[RingPair]", counter: torch.Tensor, fram
           "ps_stream_commit_frames_f32")
 
 
+def _check_span(span: torch.Tensor, streams: int, like: torch.Tensor, who: str) -> None:
+    if span.dtype != torch.int32 or tuple(span.shape) != (streams, 2) or not span.is_contiguous() or span.device != like.device:
+        raise RuntimeError(f"{who}: span must be a contiguous int32 [{streams}, 2] tensor (birth, death) on {like.device}")
+
+
 def dwconv_step(x: torch.Tensor, ring: torch.Tensor, counter: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor],
                 dilation: int, streams: int, frames: int, pro: Optional[Prologue] = None,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None, span: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Causal depthwise convolution of `frames` new frames of `streams` streams (ps_dwconv_step_f32): x [1, H, ld] (column
     f * streams + b), w [H, 1, P]; earlier frames from ring [R, H, streams] (slot g % R = frame g, activated values; the
     chunk's frames are stored there too), frame index of column 0 = counter[0] -> y [1, H, ld] (columns past
-    frames * streams are not written)."""
+    frames * streams are not written).  span int32 [streams, 2]: ps_dwconv_step_slots_f32, a tap reads frame g of stream b
+    iff span[b, 0] <= g < span[b, 1]."""
     require_device(x, "dwconv_step")
     _, h, ld = x.shape
     p = w.shape[-1]
@@ -965,18 +971,27 @@ def dwconv_step(x: torch.Tensor, ring: torch.Tensor, counter: torch.Tensor, w: t
     y = out if out is not None else torch.zeros_like(x)
     if y.shape != x.shape or not y.is_contiguous():
         raise RuntimeError("dwconv_step: out must be a contiguous tensor of x's shape")
+    pro_ref = C.byref(pro) if pro is not None else None
+    if span is not None:
+        _check_span(span, streams, x, "dwconv_step")
+        check(lib().ps_dwconv_step_slots_f32(ptr(x), ptr(ring), ring.shape[0], ptr(counter), ptr(span), ptr(w), ptr(b), ptr(y),
+                                             h, streams, frames, ld, p, dilation, pro_ref, stream_ptr(x.device)),
+              "ps_dwconv_step_slots_f32")
+        return y
     check(lib().ps_dwconv_step_f32(ptr(x), ptr(ring), ring.shape[0], ptr(counter), ptr(w), ptr(b), ptr(y), h, streams, frames,
-                                   ld, p, dilation, C.byref(pro) if pro is not None else None, stream_ptr(x.device)),
+                                   ld, p, dilation, pro_ref, stream_ptr(x.device)),
           "ps_dwconv_step_f32")
     return y
 
 
 def free_decode_step(feats: Optional[torch.Tensor], mask: Optional[torch.Tensor], w: torch.Tensor, tail: torch.Tensor,
                      out: torch.Tensor, hop: int, frames: int = 0, mask_act: str = "linear", out_mode: str = "linear",
-                     flush: bool = False) -> torch.Tensor:
+                     flush: bool = False, span: Optional[torch.Tensor] = None,
+                     counter: Optional[torch.Tensor] = None) -> torch.Tensor:
     """FreeEncDec's decoder for `frames` new frames of B streams (ps_free_decode_step_f32): feats / mask [1, C, ld] (column
     f * B + b), w [C, 1, win], overlap-add tail [B, win - hop] updated in place -> out [B, frames * hop] (a row view of a
-    wider buffer is fine); flush: the tail's samples -> out [B, win - hop]."""
+    wider buffer is fine); flush: the tail's samples -> out [B, win - hop].  span int32 [B, 2] with the int32 frame counter:
+    ps_free_decode_step_slots_f32, frame f adds its product iff span[b, 0] <= counter[0] + f < span[b, 1] (not with flush)."""
     require_device(tail, "free_decode_step")
     b, keep = tail.shape
     win = w.shape[-1]
@@ -997,6 +1012,15 @@ def free_decode_step(feats: Optional[torch.Tensor], mask: Optional[torch.Tensor]
             raise RuntimeError("free_decode_step: feats and mask of one shape expected")
     ws_bytes = 0 if flush else lib().ps_free_decode_step_workspace_bytes(b, frames, win)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=tail.device) if ws_bytes else None
+    if span is not None:
+        _check_span(span, b, tail, "free_decode_step")
+        if flush or counter is None or counter.dtype != torch.int32 or counter.device != tail.device:
+            raise RuntimeError("free_decode_step: a span goes with the int32 device frame counter and never with flush")
+        check(lib().ps_free_decode_step_slots_f32(ptr(feats), ptr(mask), _abi.PS_ACT[mask_act], ld, ptr(w), ptr(tail), ptr(out),
+                                                  out.stride(0), ptr(span), ptr(counter), b, frames, c, win, hop,
+                                                  _abi.PS_OUT[out_mode], ptr(ws), ws_bytes, stream_ptr(tail.device)),
+              "ps_free_decode_step_slots_f32")
+        return out
     check(lib().ps_free_decode_step_f32(ptr(feats), ptr(mask), _abi.PS_ACT[mask_act], ld, ptr(w), ptr(tail), ptr(out),
                                         out.stride(0), b, frames, c, win, hop, _abi.PS_OUT[out_mode], int(flush), ptr(ws),
                                         ws_bytes, stream_ptr(tail.device)), "ps_free_decode_step_f32")

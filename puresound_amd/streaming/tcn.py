@@ -19,6 +19,12 @@ depends on the frame index, so one captured graph per chunk length replays every
 Arithmetic: exact fp32 products throughout, whatever the model's gemm_precision.  The streamer packs its own weights from
 the parameters, so the model's own setting and plans are left as they were.  The embedding is computed once per stream by
 the model's speaker branch (inference_tse_embedding), in the model's own arithmetic.
+
+Slots (init_slots / open / end / close): a session of fixed capacity B whose columns begin and end streams of their own while
+it runs.  Per slot the device holds a span (birth, death) of absolute frame indices; frame g of column b is live iff
+birth[b] <= g < death[b].  ps_dwconv_step_slots_f32 reads a frame that is not live as 0 (the rule for g < 0, per column) and
+ps_free_decode_step_slots_f32 adds nothing for it; everything else in a hop is column-wise, so dead columns compute values
+nobody reads.  A slot's output is the offline output of its stream delayed by latency_samples, whatever the other slots do.
 """
 from typing import Dict, List, Optional
 
@@ -34,6 +40,9 @@ from .spectral import StreamingSeparator
 
 #: frames per launch at most: step_chunk splits longer chunks (the rings hold (P-1)*dilation + K_MAX frames)
 K_MAX = 16
+INT32_MAX = 2 ** 31 - 1
+#: a slot session stops here: the device frame counter is an int32, and a launch reads up to K_MAX frames past it
+FRAME_LIMIT = INT32_MAX - K_MAX
 
 
 def check_streamable(model) -> None:
@@ -89,6 +98,12 @@ class StreamingConvTasNet:
     s = StreamingConvTasNet(model); s.init_streams(B, enroll); s.step(hop [B, hop]) -> [B, hop] or None while the first
     window fills; s.step_chunk([B, k*hop]) -> what k step() calls return, concatenated; s.flush() -> the last win - hop
     samples.
+
+    Slots, for streams that begin and end on their own: s.init_slots(capacity); s.open(slot, enroll [L']); every
+    s.step / s.step_chunk([capacity, k*hop]) -> [capacity, k*hop] from the first hop on (idle slots: constrain(0));
+    s.end(slot, hops) when the stream has `hops` more hops of input; s.close(slot) -> the last win - hop samples, and the
+    slot is idle again.  What a slot returned from open to close, then close's samples, is the offline output of its stream
+    after latency_samples samples of constrain(0): slot_output_range(L, win, hop).
     """
 
     def __init__(self, model: SoTaskWrapModule):
@@ -103,6 +118,7 @@ class StreamingConvTasNet:
         self._mask_act = model.mask_constraint.lower()
         self._out_mode = model.output_constraint.lower()
         self.streams = None
+        self._span = self._slots = None
         self._drop_weights()
 
     @property
@@ -111,6 +127,13 @@ class StreamingConvTasNet:
         return self.win_length - self.hop_length
 
     output_length = staticmethod(StreamingSeparator.output_length)
+
+    @staticmethod
+    def slot_output_range(samples: int, win: int, hop: int) -> range:
+        """The indices of y that hold model.inference(x, e) for a stream x of `samples` = k * hop samples in a slot, y = every
+        output of the slot from open() on ‖ close(): the offline output after the latency, win - hop samples."""
+        n = StreamingSeparator.output_length(samples, win, hop)
+        return range(win - hop, win - hop + n["emitted"] + n["flushed"])
 
     # -- weights ------------------------------------------------------------------------------------------------------
     _signature = StreamingSeparator._signature
@@ -174,10 +197,17 @@ class StreamingConvTasNet:
             if any(m.tcn_with_embed):
                 dvec = model.inference_tse_embedding(enroll)[..., 0].float().contiguous()   # [B, E]
                 self._emb = hip.l2_normalize(dvec) if m.embed_norm else dvec
+        self._new_session(b, dev, use_graph)
+
+    def _new_session(self, b: int, dev: torch.device, use_graph: bool) -> None:
+        """Zeroed state of b columns (self._emb is set by the caller)."""
+        m = self.model.masker
         self.streams, self.device, self._use_graph = b, dev, bool(use_graph)
         self._hops = 0
         self.frames = 0
         self._finished = False
+        self._span = None        # int32 [B, 2] (birth, death) in a slot session
+        self._slots = None       # per slot None (idle) or dict(hops fed, total hops once end() was called)
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
         self._blocks: List[TCN] = [blk for stack in m.tcn_list for blk in stack]
         # one circular ring of activated depthwise inputs per block: (P-1)*dilation frames of history plus a chunk
@@ -187,6 +217,128 @@ class StreamingConvTasNet:
         self._counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self._io: Dict[int, tuple] = {}
         self._bufs: Dict[int, dict] = {}
+
+    @torch.no_grad()
+    def init_slots(self, capacity: int, use_graph: bool = True) -> None:
+        """Start a slot session of `capacity` columns, every slot idle (every state zeroed); open() starts a stream."""
+        if int(capacity) < 1:
+            raise ValueError("init_slots: capacity >= 1")
+        model, m = self.model, self.model.masker
+        self._check_parameters()
+        self._graphs = {}
+        dev = next(model.parameters()).device
+        b = int(capacity)
+        self._emb = None
+        if model.speaker_net is not None and any(m.tcn_with_embed):
+            self._emb = torch.zeros(b, m.embed_dim, dtype=torch.float32, device=dev)
+        self._new_session(b, dev, use_graph)
+        self._span = torch.zeros(b, 2, dtype=torch.int32, device=dev)
+        self._slots = [None] * b
+
+    @property
+    def active(self) -> List[int]:
+        """The slots that carry a stream (opened and not yet closed)."""
+        return [] if self._slots is None else [i for i, st in enumerate(self._slots) if st is not None]
+
+    def _slot(self, slot: int, what: str, idle: bool) -> int:
+        """Check that `slot` names a slot of this slot session that is idle / carries a stream -> its index."""
+        name = f"StreamingConvTasNet.{what}"
+        if self.streams is None or self._slots is None:
+            raise RuntimeError(f"{name}: not a slot session; call init_slots() (an init_streams() session starts and ends "
+                               f"all its streams at once, with flush())")
+        if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.streams:
+            raise IndexError(f"{name}: slot {slot!r} is out of range; this session has slots 0 .. {self.streams - 1}")
+        if idle and self._slots[slot] is not None:
+            raise RuntimeError(f"{name}: slot {slot} carries a stream; close({slot}) it first, or take one of the idle slots "
+                               f"{[i for i, st in enumerate(self._slots) if st is None]}")
+        if not idle and self._slots[slot] is None:
+            raise RuntimeError(f"{name}: slot {slot} is idle; open({slot}) starts a stream in it")
+        return slot
+
+    @torch.no_grad()
+    def open(self, slot: int, enroll: Optional[torch.Tensor] = None) -> None:
+        """Start a stream in the idle slot `slot`: its first input hop is the first hop of the next step / step_chunk call.
+        enroll [L'] or [1, L'] on the model's device, required iff the model has a speaker_net; its embedding is computed
+        here, once.  No synchronisation, no captured graph is touched."""
+        name = "StreamingConvTasNet.open"
+        slot = self._slot(slot, "open", idle=True)
+        model, m = self.model, self.model.masker
+        if (enroll is not None) != (model.speaker_net is not None):
+            raise ValueError(f"{name}: an enrolment [L'] is required iff the model has a speaker_net (this one has "
+                             f"{'one: pass enroll' if model.speaker_net is not None else 'none: pass no enroll'})")
+        if enroll is not None:
+            hip.require_device(enroll, name)
+            if enroll.device != self.device:
+                raise RuntimeError(f"{name}: the enrolment is on {enroll.device}, the session on {self.device}; move it with "
+                                   f".to({str(self.device)!r})")
+            enroll = enroll[None] if enroll.dim() == 1 else enroll
+            if enroll.dim() != 2 or enroll.shape[0] != 1:
+                raise ValueError(f"{name}: enroll must be [L'] or [1, L'] (one stream), got {tuple(enroll.shape)}")
+        if self.frames + self.prime_hops > FRAME_LIMIT:
+            raise RuntimeError(f"{name}: the session is at its limit of {FRAME_LIMIT} frames (an int32 frame counter); close "
+                               f"the streams and call init_slots() for a new session")
+        self._check_parameters()
+        if self._emb is not None:
+            dvec = model.inference_tse_embedding(enroll)[..., 0].float().contiguous()   # [1, E]
+            dvec = (hip.l2_normalize(dvec) if m.embed_norm else dvec)[0]
+            self._emb[slot] = dvec
+            c = m.input_dim
+            for bufs in self._bufs.values():           # (chunk lengths created later read self._emb)
+                for r in bufs["res"]:
+                    r[0, c:, slot:bufs["n"]:self.streams] = dvec[:, None]
+        self._queue[slot].zero_()
+        self._tail[slot].zero_()
+        # frames counter .. counter + prime_hops - 1 see a partly filled window: dead.  (device-side add: no read-back)
+        self._span[slot, 0:1] = self._counter + self.prime_hops
+        self._span[slot, 1:2] = INT32_MAX
+        self._slots[slot] = dict(hops=0, total=None)
+
+    def _needs(self, st: dict, more: int, what: str, slot: int) -> None:
+        """flush()'s rule per slot: a stream that ends after fewer than win samples has no frame."""
+        need = self.win_length // self.hop_length
+        if st["hops"] + more < need:
+            raise RuntimeError(f"StreamingConvTasNet.{what}: the stream in slot {slot} would end after "
+                               f"{(st['hops'] + more) * self.hop_length} samples, and a stream needs {self.win_length} (no "
+                               f"complete frame yet): step {need - st['hops'] - more} more hops of it first")
+
+    @torch.no_grad()
+    def end(self, slot: int, hops: int) -> None:
+        """The stream in `slot` has `hops` >= 0 more hops of input: frames after them are dead, whatever the caller pads the
+        rest of a chunk with, and the slot's later output hops drain its overlap-add tail."""
+        slot = self._slot(slot, "end", idle=False)
+        st = self._slots[slot]
+        if not isinstance(hops, int) or hops < 0:
+            raise ValueError(f"StreamingConvTasNet.end: hops = {hops!r}: the whole hops of input still to come, >= 0")
+        if st["total"] is not None:
+            raise RuntimeError(f"StreamingConvTasNet.end: slot {slot} was ended already ({st['total'] - st['hops']} hops to "
+                               f"go); close({slot}) frees it")
+        self._needs(st, hops, "end", slot)
+        self._span[slot, 1:2] = self._counter + hops
+        st["total"] = st["hops"] + hops
+
+    @torch.no_grad()
+    def close(self, slot: int) -> torch.Tensor:
+        """-> [win - hop]: what is left of the slot's overlap-add tail, through the output constraint; the slot is idle
+        again.  Without an earlier end() the stream ends now."""
+        slot = self._slot(slot, "close", idle=False)
+        st = self._slots[slot]
+        if st["total"] is None:
+            self._needs(st, 0, "close", slot)
+        elif st["hops"] < st["total"]:
+            raise RuntimeError(f"StreamingConvTasNet.close: end({slot}, ..) announced {st['total'] - st['hops']} more hops of "
+                               f"input; step them first")
+        self._check_parameters()
+        if self._packs is None:
+            self._build_packs(self.device)
+        if st["total"] is None:
+            self.end(slot, 0)
+        out = torch.empty(1, self.win_length - self.hop_length, dtype=torch.float32, device=self.device)
+        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail[slot:slot + 1], out, self.hop_length,
+                             out_mode=self._out_mode, flush=True)
+        self._tail[slot].zero_()
+        self._span[slot].zero_()
+        self._slots[slot] = None
+        return out[0]
 
     def _state(self) -> List[torch.Tensor]:
         return [self._queue, self._tail, self._counter] + self._rings
@@ -225,7 +377,7 @@ class StreamingConvTasNet:
         y1, _ = hip.conv1x1(x[:, :c + p["E"]], n, p["in_wt"], h, out=bufs["y1"])
         src, pro = settle(y1, "in", bufs["a1"])
         y2 = hip.dwconv_step(src, self._rings[i], self._counter, p["dw_w"], p["dw_b"], p["dilation"], self.streams, hops, pro,
-                             out=bufs["y2"])
+                             out=bufs["y2"], span=self._span)
         src, pro = settle(y2, "dw", bufs["a2"])
         y3, _ = hip.conv1x1(src, n, p["pw_wt"], h, pro, p["pw_b"], out=bufs["y3"])
         src, pro = settle(y3, "pw", bufs["a3"])
@@ -248,7 +400,8 @@ class StreamingConvTasNet:
             y = x0 if i % 2 == 0 else x1
             self._block(i, p, x, y, bufs, hops)
             x = y
-        hip.free_decode_step(feats[:, :c], x[:, :c], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode)
+        hip.free_decode_step(feats[:, :c], x[:, :c], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode,
+                             span=self._span, counter=self._counter if self._span is not None else None)
         hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
 
     def _run_piece(self, piece: torch.Tensor) -> torch.Tensor:
@@ -272,11 +425,19 @@ class StreamingConvTasNet:
 
     def _run(self, chunk: torch.Tensor) -> torch.Tensor:
         """Whole hops past the priming -> their output samples, in pieces of at most K_MAX hops."""
+        k = chunk.shape[1] // self.hop_length
+        if self._slots is not None and self.frames + k > FRAME_LIMIT:
+            raise RuntimeError(f"StreamingConvTasNet: {self.frames} + {k} frames pass this session's limit of {FRAME_LIMIT} "
+                               f"(2**31 - 1 - K_MAX: the device frame counter is an int32); close the streams and call "
+                               f"init_slots() for a new session")
         self._check_parameters()
         if self._packs is None:
             self._build_packs(self.device)
         step = K_MAX * self.hop_length
         outs = [self._run_piece(chunk[:, i:i + step]) for i in range(0, chunk.shape[1], step)]
+        for st in self._slots or ():
+            if st is not None:
+                st["hops"] = st["hops"] + k if st["total"] is None else min(st["hops"] + k, st["total"])
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
     def _capture(self, hops: int) -> torch.cuda.CUDAGraph:
@@ -301,7 +462,7 @@ class StreamingConvTasNet:
 
     def _check_input(self, x: torch.Tensor, what: str) -> int:
         if self.streams is None:
-            raise RuntimeError(f"StreamingConvTasNet.{what}: call init_streams() first")
+            raise RuntimeError(f"StreamingConvTasNet.{what}: call init_streams() first (or init_slots())")
         if self._finished:
             raise RuntimeError(f"StreamingConvTasNet.{what}: the streams were flushed; call init_streams() for new ones")
         hip.require_device(x, f"StreamingConvTasNet.{what}")
@@ -316,7 +477,7 @@ class StreamingConvTasNet:
         window fills (the first win / hop - 1 hops)."""
         if self._check_input(hop, "step") != 1:
             raise ValueError(f"StreamingConvTasNet.step: one hop of {self.hop_length} samples per stream")
-        if self._hops < self.prime_hops:
+        if self._slots is None and self._hops < self.prime_hops:
             self._prime(hop)
             return None
         return self._run(hop)
@@ -325,6 +486,8 @@ class StreamingConvTasNet:
     def step_chunk(self, chunk: torch.Tensor) -> torch.Tensor:
         """chunk [B, k*hop_length] -> what k step() calls return, concatenated ([B, 0] when every hop only primes)."""
         k = self._check_input(chunk, "step_chunk")
+        if self._slots is not None:      # no priming phase: a slot's first prime_hops frames are dead by its span
+            return self._run(chunk) if k else chunk.new_zeros(self.streams, 0)
         i = 0
         while i < k and self._hops < self.prime_hops:
             self._prime(chunk[:, i * self.hop_length:(i + 1) * self.hop_length])
@@ -338,6 +501,9 @@ class StreamingConvTasNet:
         """The last win - hop_length samples of every stream ([B, win - hop_length]); the streams are then finished."""
         if self.streams is None or self._finished:
             raise RuntimeError("StreamingConvTasNet.flush: no open streams")
+        if self._slots is not None:
+            raise RuntimeError("StreamingConvTasNet.flush: a slot session ends its streams one by one: close(slot) returns a "
+                               "slot's last samples")
         if self.frames == 0:
             raise RuntimeError(f"StreamingConvTasNet.flush: no complete frame yet (a stream needs {self.win_length} samples)")
         self._check_parameters()
