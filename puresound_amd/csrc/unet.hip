@@ -106,7 +106,9 @@ __global__ __launch_bounds__(256) void norm_activation_kernel(NormActArgs a) {
     rstd = (float)(1.0 / sqrt(var + (double)a.pro.eps));
   }
   const int ch = row / a.rows_per_channel;
-  const float sc = a.pro.gamma[ch] * rstd, sh = a.pro.beta[ch] - (float)mean * sc;
+  // the mean is taken off in fp64 before the gain: a shift beta - mean * gain folded in fp32 costs half an ulp of mean * gain,
+  // which at a mean far from zero is more than the whole result's budget
+  const float sc = a.pro.gamma[ch] * rstd, sh = a.pro.beta[ch];
   const float s = a.slope ? a.slope[0] : 0.f;
   const int t = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (t >= a.ld) return;
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(256) void norm_activation_kernel(NormActArgs a) {
   f32x4 v = *reinterpret_cast<const f32x4*>(p);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    float u = v[e] * sc + sh;
+    float u = (float)((double)v[e] - mean) * sc + sh;
     switch (a.kind) {
       case 1: u = relu_keep_nan(u); break;
       case 2: u = u >= 0.f ? u : s * u; break;
@@ -138,14 +140,13 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
   double sa = 0.0, sq = 0.0;
   for (int r = p; r < rows; r += kRowStatsParts) {
     const float* row = x + ((size_t)n * rows + r) * ld;
-    float fa = 0.f, fq = 0.f;  // (a row's share per thread is short: fp32 inside, fp64 across rows)
+    // fp64 all the way (the product of two floats is exact in fp64): with a mean far from zero the variance is the small
+    // difference E[x^2] - mean^2, and fp32 squares lose it (x ~ 100: 4e-8 of sum x^2 is 1e-3 of the variance)
     for (int t = threadIdx.x; t < T; t += 256) {
-      const float v = row[t];
-      fa += v;
-      fq += v * v;
+      const double v = row[t];
+      sa += v;
+      sq += v * v;
     }
-    sa += fa;
-    sq += fq;
   }
   block_sum2(sa, sq, red);
   if (threadIdx.x == 0) {

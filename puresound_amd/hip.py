@@ -493,21 +493,35 @@ RNN_KINDS = {"RNN": 0, "GRU": 2}
 
 
 def rnn(gx: torch.Tensor, whh_t: torch.Tensor, kind: str, hidden: int, dirs: int, q: int, q_stride: int, steps: int,
-        step_stride: int, bhn: Optional[torch.Tensor] = None) -> torch.Tensor:
+        step_stride: int, bhn: Optional[torch.Tensor] = None, h0: Optional[torch.Tensor] = None, want_state: bool = False):
     """ps_rnn_f32: the recurrence of nn.RNN (tanh) / nn.GRU over pre-activations gx padded [N, D*G, ldt] (G = H or 3H) ->
-    hout [N, D*H, ldt]; zero initial state."""
+    hout [N, D*H, ldt].  h0: initial state in the state layout [N, D*H, ldq >= Q] (None = zeros); want_state: returns
+    (hout, h_last) with h_last in the same layout (ldq of h0, else padded_frames(Q))."""
     require_device(gx, "rnn")
     n, rows, ldt = gx.shape
     g = (3 if kind == "GRU" else 1) * hidden
     if kind not in RNN_KINDS or rows != dirs * g or tuple(whh_t.shape) != (dirs, hidden, g):
         raise RuntimeError("rnn: kind RNN / GRU, gx [N, D*G, ldt], whh_t [D, H, G]")
+    if bhn is not None and (tuple(bhn.shape) != (dirs, hidden) or not bhn.is_contiguous()):
+        raise RuntimeError("rnn: bhn must be a contiguous [D, H] tensor")
+    ldq = 0
+    if h0 is not None:
+        require_device(h0, "rnn")
+        if h0.dim() != 3 or tuple(h0.shape[:2]) != (n, dirs * hidden) or h0.shape[2] < q or not h0.is_contiguous():
+            raise RuntimeError("rnn: h0 must be a contiguous state tensor [N, D*H, ldq >= Q]")
+        ldq = h0.shape[2]
+    h_last = None
+    if want_state:
+        ldq = ldq or padded_frames(q)
+        h_last = torch.zeros(n, dirs * hidden, ldq, dtype=torch.float32, device=gx.device)
     hout = torch.empty(n, dirs * hidden, ldt, dtype=torch.float32, device=gx.device)
     a = LstmArgs()
     a.gx, a.whh_t, a.hout = ptr(gx), ptr(whh_t), ptr(hout)
+    a.h0, a.h_last = ptr(h0), ptr(h_last)
     a.N, a.H, a.D, a.Q, a.q_stride, a.steps, a.step_stride = n, hidden, dirs, q, q_stride, steps, step_stride
-    a.ldt, a.ldq, a.state_shift = ldt, 0, 0
+    a.ldt, a.ldq, a.state_shift = ldt, ldq, 0
     check(lib().ps_rnn_f32(C.byref(a), RNN_KINDS[kind], ptr(bhn), stream_ptr(gx.device)), "ps_rnn_f32")
-    return hout
+    return (hout, h_last) if want_state else hout
 
 
 def _lstm_fmajor_args(gx_fm: torch.Tensor, whh_t: torch.Tensor, hout, hidden, dirs, q, q_stride, steps, step_stride):
@@ -689,8 +703,11 @@ def unfold_taps(x: torch.Tensor, t: int, taps: int, dilation: int, left: int, sc
     require_device(x, "unfold_taps")
     n, k, ldt = x.shape
     e = 0 if embed is None else embed.shape[1]
-    t_out = t if t_out is None else t_out
     y = torch.empty(n, taps * (k + e), ldt, dtype=torch.float32, device=x.device)
+    if t_out is None:
+        check(lib().ps_unfold_taps_f32(ptr(x), ptr(y), n, k, t, ldt, taps, dilation, left, ptr(scale), ptr(shift), ptr(embed), e,
+                                       stream_ptr(x.device)), "ps_unfold_taps_f32")
+        return y
     check(lib().ps_unfold_taps_out_f32(ptr(x), ptr(y), n, k, t, t_out, ldt, taps, dilation, left, ptr(scale), ptr(shift),
                                        ptr(embed), e, stream_ptr(x.device)), "ps_unfold_taps_out_f32")
     return y
