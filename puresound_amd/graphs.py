@@ -3,8 +3,8 @@
 At one or a few utterances per call a Conv-TasNet forward is ~100 launches of 15-35 us each and a fifth of its wall
 time is launch gaps.  Every kernel of the path is enqueued on the caller's stream through the C ABI and allocates
 through torch's caching allocator only, so `torch.cuda.graph` (a hipGraph on ROCm) can capture the call as it is;
-a replay then costs one launch.  (The streaming harness captures its frame step the same way,
-puresound_amd/streaming/skim_inference.py.)
+a replay then costs one launch.  (The streaming classes of puresound_amd/streaming capture their hop and chunk bodies
+through the same `capture`.)
 
     fast = GraphedInference(model)           # SoTaskWrapModule / SiMoTaskWrapModule, on the GPU, eval()
     enhanced = fast(noisy)                    # first call per input shape: 3 eager warm-ups + capture; then replay
@@ -45,6 +45,26 @@ def _cached_tensors(model: torch.nn.Module) -> list:
                 walk(v, 0)
     walk(hip._EYE, 0)
     return out
+
+
+def capture(body, device, state=(), warmups: int = 1) -> tuple:
+    """Run body() `warmups` times on a side stream (plans, workspaces and library handles come into being outside the
+    capture), copy the saved values back into the tensors of `state`, capture body() once -> (graph, what body returned
+    inside the capture).  A capture records launches and runs none, so `state` holds the saved values afterwards too."""
+    state = list(state)
+    saved = [t.clone() for t in state]
+    side = torch.cuda.Stream(device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        for _ in range(warmups):
+            body()
+    torch.cuda.current_stream(device).wait_stream(side)
+    for t, v in zip(state, saved):
+        t.copy_(v)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = body()
+    return graph, out
 
 
 class GraphedInference:
@@ -100,15 +120,7 @@ class GraphedInference:
             static_in = noisy.clone()
             static_enroll = None if enroll is None else enroll.clone()
             args = (static_in,) if static_enroll is None else (static_in, static_enroll)
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):  # plans, scratch buffers and library handles exist before the capture
-                for _ in range(3):
-                    self.model.inference(*args)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                static_out = self.model.inference(*args)
+            graph, static_out = capture(lambda: self.model.inference(*args), dev, warmups=3)
             entry = (graph, static_in, static_enroll, static_out, _cached_tensors(self.model))
             self._graphs[key] = entry
         graph, static_in, static_enroll, static_out, _pinned = entry

@@ -30,11 +30,18 @@ FMAJOR_LSTM = os.environ.get("PS_FMAJOR_LSTM", "1") == "1"      # 0: H = 128 rec
 _PLANES = {"fp32": 0, "bf16": 1, "bf16x3": 3, "fp16x2": 2}
 
 
-def param_signature(module: nn.Module, device) -> tuple:
-    sig = [(t.data_ptr(), t._version) for t in list(module.parameters()) + list(module.buffers())]
-    sig.append(module.training)
-    sig.append(str(device))
-    return tuple(sig)
+def tensor_signature(module: nn.Module) -> tuple:
+    """Cheap fingerprint of every parameter / buffer: a changed value (in-place edit, load_state_dict, .to(device)) changes
+    the version counter or the data pointer.  What a captured graph or a weight pack is checked against, by the streaming
+    classes at every call: hence one walk over the module tree, not parameters() and then buffers()."""
+    return tuple((t.data_ptr(), t._version) for m in module.modules() for tensors in (m._parameters, m._buffers)
+                 for t in tensors.values() if t is not None)
+
+
+def param_signature(module: nn.Module) -> tuple:
+    """tensor_signature and the training switch: the key of a packed plan (the caller appends the device and its own
+    arithmetic switches)."""
+    return tensor_signature(module) + (module.training,)
 
 
 class PlanCache:
@@ -68,7 +75,7 @@ class PlanCache:
         return state
 
     def _plan_get(self, device, builder):
-        sig = param_signature(self, device) + (self.gemm_precision,)
+        sig = param_signature(self) + (str(device), self.gemm_precision)
         if self._plan is None or self._plan_sig != sig:
             self._plan = builder(device)
             self._plan_sig = sig

@@ -15,6 +15,7 @@ import torch.nn as nn
 from .. import hip
 from ..ops import op_module, same_shape
 from .._abi import PS_NORM_AFFINE, PS_NORM_GLOBAL, TcnBlock, ptr
+from ._plans import param_signature
 from .lobe.cnn import DepthwiseSeparableConv1d
 from .lobe.norm import ChanLN, GlobLN, get_norm, norm_plan
 
@@ -36,16 +37,6 @@ class _PlanCache:
             if k in state:
                 state[k] = None
         return state
-
-
-def _param_signature(module: nn.Module):
-    """Cheap fingerprint of every parameter/buffer: a changed value (in-place edit, load_state_dict,
-    .to(device)) changes the version counter or the data pointer, which invalidates the packed plan."""
-    sig = []
-    for t in list(module.parameters()) + list(module.buffers()):
-        sig.append((t.data_ptr(), t._version))
-    sig.append(module.training)
-    return tuple(sig)
 
 
 @op_module("tcn_block_fwd", same_shape, cpu="tcn_block")
@@ -109,7 +100,7 @@ class TCN(_PlanCache, nn.Module):
     def plan(self, device: torch.device) -> dict:
         planes = self.gemm_planes_for_plan()
         hb = bool(self.hidden_bf16) and planes == 1 and self.kernel == 3 and 2 * self.dilation + 8 <= 288
-        sig = (_param_signature(self), str(device), planes, hb, bool(self.stream_bf16))
+        sig = (param_signature(self), str(device), planes, hb, bool(self.stream_bf16))
         if self._plan is not None and self._plan_sig == sig:
             return self._plan
         if self.training and self.dconv[1].p > 0:
@@ -278,7 +269,7 @@ class GatedTCN(_PlanCache, nn.Module):
         return w.permute(0, 2, 1).reshape(w.shape[0], -1).contiguous()
 
     def plan(self, device: torch.device) -> dict:
-        sig = (_param_signature(self), str(device))
+        sig = (param_signature(self), str(device))
         if self._plan is not None and self._plan_sig == sig:
             return self._plan
         if self.training and (self.left_conv[3].p > 0 or self.right_conv[3].p > 0):

@@ -21,6 +21,8 @@ import torch
 import torch.nn as nn
 
 from .. import hip
+from ..graphs import capture
+from ..nnet._plans import tensor_signature
 from ..nnet.lobe.encoder import FreeEncDec
 from .skim_inference import StreamingSkiM
 
@@ -91,54 +93,25 @@ class DemoTseNet(nn.Module):
         self.queue[:, self.hop_size:] = chunk
         # embedding terms of the FiLM layers: refreshed in place when the embeddings change
         self._check_parameters()
-        self._refresh_embedding(embed)
+        m._set_embedding(embed)
         if not self._use_graph:
             gen = self._hop_body()
         else:
             if self._graph is None:
-                saved = [t.clone() for t in m._seg_h + m._seg_c]
-                s = torch.cuda.Stream(chunk.device)
-                s.wait_stream(torch.cuda.current_stream(chunk.device))
-                with torch.cuda.stream(s):
-                    self._hop_body()
-                torch.cuda.current_stream(chunk.device).wait_stream(s)
-                for t, v in zip(m._seg_h + m._seg_c, saved):
-                    t.copy_(v)
-                self._graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._graph):
-                    self._gen = self._hop_body()
-                for t, v in zip(m._seg_h + m._seg_c, saved):
-                    t.copy_(v)
+                self._graph, self._gen = capture(self._hop_body, chunk.device, m._seg_h + m._seg_c)
             self._graph.replay()
             gen = self._gen
-        m.frames_counter += 1
-        if m.frames_counter % m.seg_size == 0:
-            m.update_mem_lstm()
-            m.reset_seg_lstm_status()
-            m.frames_counter = 0
+        m._end_of_frame()
         return gen.clone()
 
     def _check_parameters(self) -> None:
         """A captured graph replays the kernel plans' pointers: drop every graph when a parameter was updated."""
-        sig = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        sig = tensor_signature(self)
         if sig != self._sig:
             self._graph = None
             self._chunk_graphs = {}
             self._sig = sig
-            self.masker._embed_key = None  # the per-frame conditioning terms were made with the old weights
-
-    def _refresh_embedding(self, embed: torch.Tensor) -> None:
-        m = self.masker
-        key = (embed.data_ptr(), embed._version, tuple(embed.shape))
-        if key != m._embed_key:
-            if m._embed_static is None:
-                m._embed_static = embed.detach().reshape(m.streams, -1).float().clone()
-            else:
-                m._embed_static.copy_(embed.reshape(m.streams, -1))
-            m._embed_key = key
-            for f in m.seg_input_fusion:
-                if f is not None:
-                    f.set_per_frame_condition(m._embed_static, m.embed_norm)
+            self.masker._forget_embedding()
 
     def _chunk_body(self, hops: int, updates: tuple):
         """`hops` hops on the static buffers; the Mem-LSTM update + block-0 reset behind every hop listed in `updates`
@@ -249,19 +222,7 @@ class DemoTseNet(nn.Module):
         hops, updates = key
         m = self.masker
         state = m._seg_h + m._seg_c + [t for pair in m._mem_h + m._mem_c for t in pair] + [self.queue, self._tail]
-        saved = [t.clone() for t in state]
-        s = torch.cuda.Stream(device)
-        s.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(s):          # warm-up outside the capture: plans, per-frame embedding terms
-            self._chunk_body(hops, updates)
-        torch.cuda.current_stream(device).wait_stream(s)
-        for t, v in zip(state, saved):
-            t.copy_(v)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._chunk_body(hops, updates)
-        for t, v in zip(state, saved):
-            t.copy_(v)
+        g, _ = capture(lambda: self._chunk_body(hops, updates), device, state)   # (the warm-up: plans, embedding terms)
         while len(self._chunk_graphs) >= self._CHUNK_GRAPH_CAP:
             self._chunk_graphs.pop(next(iter(self._chunk_graphs)))
         self._chunk_graphs[key] = g
@@ -297,7 +258,7 @@ class DemoTseNet(nn.Module):
         if embed.dim() == 1:
             embed = embed.unsqueeze(0)
         self._check_parameters()
-        self._refresh_embedding(embed)
+        m._set_embedding(embed)
         b, h = m.streams, self.hop_size
         updates = self._updates_in_chunk(m.frames_counter, hops)
         if self._tail is None or getattr(self, "_chunk_in", None) is None or self._chunk_in.shape != (b, hops * h):

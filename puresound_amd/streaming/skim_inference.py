@@ -13,7 +13,8 @@ from typing import List, Optional, Tuple
 import torch
 
 from .. import hip
-from ..nnet._plans import lstm_path
+from ..graphs import capture
+from ..nnet._plans import lstm_path, tensor_signature
 from ..nnet.lobe.trivial import FiLM
 from ..nnet.skim import SkiM
 
@@ -354,51 +355,54 @@ class StreamingSkiM(SkiM):
         self._x_in[0, :, :b].copy_(x.reshape(b, self.input_size).t())
         # a parameter update (load_state_dict, an in-place edit) rebuilds the kernel plans: the captured graph replays the
         # old pointers and the per-frame conditioning terms were made with the old weights -- both are redone
-        sig = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        sig = tensor_signature(self)
         if sig != self._graph_sig:
             self._graph = None
             self._graph_sig = sig
-            self._embed_key = None
+            self._forget_embedding()
         if embed is not None:
-            key = (embed.data_ptr(), embed._version, tuple(embed.shape))
-            if key != self._embed_key:
-                if self._embed_static is None:
-                    self._embed_static = embed.detach().reshape(b, -1).float().clone()
-                else:
-                    self._embed_static.copy_(embed.reshape(b, -1))
-                self._embed_key = key
-                for m in getattr(self, "seg_input_fusion", []):
-                    if m is not None:
-                        m.set_per_frame_condition(self._embed_static, self.embed_norm)
+            self._set_embedding(embed)
         elif self._embed_static is not None:
             raise RuntimeError("step_frame: the stream was started with an embedding; keep passing it")
         if not self._use_graph:
             out = self._frame_body()
         else:
             if self._graph is None:
-                # warm up once eagerly on a side stream (fills plan caches / per-frame embedding terms), then capture
-                saved = [t.clone() for t in self._seg_h + self._seg_c]
-                s = torch.cuda.Stream(x.device)
-                s.wait_stream(torch.cuda.current_stream(x.device))
-                with torch.cuda.stream(s):
-                    self._frame_body()
-                torch.cuda.current_stream(x.device).wait_stream(s)
-                for t, v in zip(self._seg_h + self._seg_c, saved):
-                    t.copy_(v)
-                self._graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._graph):
-                    self._out = self._frame_body()
-                for t, v in zip(self._seg_h + self._seg_c, saved):
-                    t.copy_(v)
+                # the warm-up fills plan caches / per-frame embedding terms
+                self._graph, self._out = capture(self._frame_body, x.device, self._seg_h + self._seg_c)
             self._graph.replay()
             out = self._out
         res = out[0, :, :b].t().reshape(b, -1, 1).clone()
+        self._end_of_frame()
+        return res
+
+    def _forget_embedding(self) -> None:
+        """The next _set_embedding recomputes the per-frame conditioning terms (they were made with weights that changed)."""
+        self._embed_key = None
+
+    def _set_embedding(self, embed: torch.Tensor) -> None:
+        """embed [B, E]: the FiLM layers' embedding terms, refreshed in place when the embeddings change (the static copy
+        keeps its address: a captured graph reads it)."""
+        key = (embed.data_ptr(), embed._version, tuple(embed.shape))
+        if key == self._embed_key:
+            return
+        if self._embed_static is None:
+            self._embed_static = embed.detach().reshape(self.streams, -1).float().clone()
+        else:
+            self._embed_static.copy_(embed.reshape(self.streams, -1))
+        self._embed_key = key
+        for m in getattr(self, "seg_input_fusion", []):
+            if m is not None:
+                m.set_per_frame_condition(self._embed_static, self.embed_norm)
+
+    def _end_of_frame(self) -> None:
+        """Count the frame; at a segment boundary block i's state goes through Mem-LSTM i to block i+1, block 0 starts
+        afresh and the counter wraps (skim_inference.py:205-218)."""
         self.frames_counter += 1
         if self.frames_counter % self.seg_size == 0:
             self.update_mem_lstm()
             self.reset_seg_lstm_status()
             self.frames_counter = 0
-        return res
 
     @torch.no_grad()
     def update_mem_lstm(self):

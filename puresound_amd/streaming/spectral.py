@@ -18,9 +18,11 @@ graph replays every hop; `step_chunk` captures one graph per chunk length.
 Arithmetic: exact fp32 products throughout, whatever the model's gemm_precision.  The streamer keeps its own fp32 kernel
 plans and swaps them into the masker's modules only while it builds or runs a hop, so the model's own setting and plans
 are left as they were.
+The session around the kernels (priming, step / step_chunk / flush, eager run or graph replay, the capture) is HopSession's:
+streaming/_session.py.
 """
 import contextlib
-from typing import Dict, List, Optional
+from typing import List
 
 import torch
 
@@ -30,6 +32,7 @@ from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
 from ..nnet.dparn import DPARN
 from ..nnet.dpcrn import DPCRN
 from ..nnet.lobe.encoder import ConvEncDec
+from ._session import HopSession, check_on_device
 
 _SWAP = ("gemm_precision", "_plan", "_plan_sig")
 
@@ -82,13 +85,10 @@ def check_streamable(model) -> None:
     rows = 2 * (bins - (1 if model.drop_first_bin else 0))
     if ch0 * m.num_freq != rows or m.channels[0] != ch0:
         raise NotImplementedError(f"StreamingSeparator: the masker reads {ch0} x {m.num_freq} rows, the encoder gives {rows}")
-    devs = {t.device.type for t in list(model.parameters()) + list(model.buffers())}
-    if devs != {"cuda"}:
-        raise NotImplementedError(f"StreamingSeparator: the model's tensors are on {sorted(devs)}; streaming runs on a ROCm "
-                                  f"device only (move the model with .to(device))")
+    check_on_device(model, "StreamingSeparator")
 
 
-class StreamingSeparator:
+class StreamingSeparator(HopSession):
     """Hop-by-hop inference of a causal DPCRN / DPARN noise suppressor for B streams (see the module docstring).
 
     s = StreamingSeparator(model); s.init_streams(B); s.step(hop [B, hop]) -> [B, hop] or None while the analysis window
@@ -97,38 +97,20 @@ class StreamingSeparator:
 
     def __init__(self, model: SoTaskWrapModule):
         check_streamable(model)
-        if model.training:
-            raise RuntimeError("StreamingSeparator: the model is in training mode -- call .eval()")
-        self.model = model
         stft = model.encoder.encoder
-        self.n_fft, self.hop_length = int(stft.n_fft), int(stft.stride)
-        self.prime_hops = self.n_fft // self.hop_length - 1
-        self._pairing = model.mask_type.lower()
-        self._mask_act = model.mask_constraint.lower()
-        self._out_mode = model.output_constraint.lower()
         self._plan_mods = [m for m in model.masker.modules() if isinstance(m, PlanCache)]
-        self.streams = None
-        self._drop_weights()
-
-    @property
-    def latency_samples(self) -> int:
-        """Samples between a sample entering and its enhanced value leaving: the analysis window minus one hop."""
-        return self.n_fft - self.hop_length
+        super().__init__(model, stft.n_fft, stft.stride)
+        self.n_fft = self.window
+        self._pairing = model.mask_type.lower()
 
     # -- weights ------------------------------------------------------------------------------------------------------
-    def _signature(self) -> tuple:
-        return tuple((t.data_ptr(), t._version) for t in list(self.model.parameters()) + list(self.model.buffers()))
-
     def _drop_weights(self) -> None:
         """Forget graphs, fp32 plans and weight packs (they are rebuilt from the current parameters on next use)."""
-        self._graphs: Dict[int, tuple] = {}
+        super()._drop_weights()
         self._own = [{"gemm_precision": "fp32"} for _ in self._plan_mods]
-        self._packs = None
-        self._sig = self._signature()
 
-    def _check_parameters(self) -> None:
-        if self._signature() != self._sig:
-            self._drop_weights()
+    def _around_body(self):
+        return self._fp32_plans()
 
     @contextlib.contextmanager
     def _fp32_plans(self):
@@ -161,16 +143,11 @@ class StreamingSeparator:
         """Start `streams` new streams (every state zeroed)."""
         if int(streams) < 1:
             raise ValueError("init_streams: streams >= 1")
-        self._check_parameters()
-        self._graphs = {}
         m = self.model.masker
         dev = next(self.model.parameters()).device
         b = int(streams)
-        ldb = hip.padded_frames(b)
-        self.streams, self.device, self._ldb, self._use_graph = b, dev, ldb, bool(use_graph)
-        self._hops = 0
-        self.frames = 0
-        self._finished = False
+        self._begin(b, dev, use_graph)
+        self._ldb = ldb = hip.padded_frames(b)
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
         n = m.n_cnn
         ch0 = 2 if m.input_type.lower() == "ri" else 1
@@ -218,10 +195,6 @@ class StreamingSeparator:
         hid = [blk.inter_rnn.rnn.hidden_size for blk in blocks]
         fb = shapes["mid"][1]
         self._lstm = [tuple(z(1, h, fb * ldb) for _ in range(4)) for h in hid]   # h0, c0, h', c'
-        self._queue = z(b, self.n_fft)
-        self._tail = z(b, self.n_fft - self.hop_length)
-        self._counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._io: Dict[int, tuple] = {}
         if sum(r is not None for r in self._rings.values()) + 2 * len(blocks) + 1 > hip._abi.PS_MAX_RING_PAIRS:
             raise NotImplementedError("StreamingSeparator: more history buffers than one commit launch takes")
 
@@ -271,115 +244,5 @@ class StreamingSeparator:
                 pairs.append((wins[i], self._queue))
             hip.stream_commit(hip.commit_table(pairs), self._counter, self.device)
 
-    def _run(self, chunk: torch.Tensor) -> torch.Tensor:
-        """Whole hops past the priming -> their output samples [B, hops*hop] (graph replay or eager)."""
-        hops = chunk.shape[1] // self.hop_length
-        self._check_parameters()
-        if self._packs is None:
-            self._build_packs(self.device)
-        if hops not in self._io:
-            z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.device)  # noqa: E731
-            self._io[hops] = (z(self.streams, chunk.shape[1]), z(self.streams, chunk.shape[1]),
-                              z(hops, self.streams * self.n_fft))
-        self._io[hops][0].copy_(chunk)
-        if not self._use_graph:
-            with self._fp32_plans():
-                self._body(hops)
-        else:
-            g = self._graphs.get(hops)
-            if g is None:
-                g = self._capture(hops)
-            g.replay()
-        self._hops += hops
-        self.frames += hops
-        return self._io[hops][1].clone()
-
-    def _capture(self, hops: int):
-        """Warm up once eagerly on a side stream (builds the fp32 plans and their buffers), put the state back, capture."""
-        state = self._state()
-        saved = [t.clone() for t in state]
-        dev = self.device
-        with self._fp32_plans():
-            s = torch.cuda.Stream(dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                self._body(hops)
-            torch.cuda.current_stream(dev).wait_stream(s)
-            for t, v in zip(state, saved):
-                t.copy_(v)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._body(hops)
-        self._graphs[hops] = g
-        return g
-
-    def _prime(self, hop_in: torch.Tensor) -> None:
-        """A hop that only fills the analysis window: the queue slides, no model state moves."""
-        if 1 not in self._io:
-            self._io[1] = tuple(torch.zeros(*s, dtype=torch.float32, device=self.device)
-                                for s in ((self.streams, self.hop_length), (self.streams, self.hop_length),
-                                          (1, self.streams * self.n_fft)))
-        chunk, _, wins = self._io[1]
-        chunk.copy_(hop_in)
-        hip.stream_windows(self._queue, chunk, wins, self.hop_length)
-        self._queue.copy_(wins.view(self.streams, self.n_fft))
-        self._hops += 1
-
-    def _check_input(self, x: torch.Tensor, what: str) -> int:
-        if self.streams is None:
-            raise RuntimeError(f"StreamingSeparator.{what}: call init_streams() first")
-        if self._finished:
-            raise RuntimeError(f"StreamingSeparator.{what}: the streams were flushed; call init_streams() for new ones")
-        hip.require_device(x, f"StreamingSeparator.{what}")
-        if x.dim() != 2 or x.shape[0] != self.streams or x.shape[1] % self.hop_length:
-            raise ValueError(f"StreamingSeparator.{what}: expected [{self.streams}, k * {self.hop_length}] samples, "
-                             f"got {tuple(x.shape)}")
-        return x.shape[1] // self.hop_length
-
-    @torch.no_grad()
-    def step(self, hop: torch.Tensor) -> Optional[torch.Tensor]:
-        """hop [B, hop_length] new samples per stream -> [B, hop_length] enhanced samples, or None while the analysis window
-        fills (the first n_fft / hop - 1 hops)."""
-        if self._check_input(hop, "step") != 1:
-            raise ValueError(f"StreamingSeparator.step: one hop of {self.hop_length} samples per stream")
-        if self._hops < self.prime_hops:
-            self._prime(hop)
-            return None
-        return self._run(hop)
-
-    @torch.no_grad()
-    def step_chunk(self, chunk: torch.Tensor) -> torch.Tensor:
-        """chunk [B, k*hop_length] -> what k step() calls return, concatenated ([B, 0] when every hop only primes)."""
-        k = self._check_input(chunk, "step_chunk")
-        i = 0
-        while i < k and self._hops < self.prime_hops:
-            self._prime(chunk[:, i * self.hop_length:(i + 1) * self.hop_length])
-            i += 1
-        if i == k:
-            return chunk.new_zeros(self.streams, 0)
-        return self._run(chunk[:, i * self.hop_length:])
-
-    @torch.no_grad()
-    def flush(self) -> torch.Tensor:
-        """The last n_fft - hop_length samples of every stream ([B, n_fft - hop_length]); the streams are then finished."""
-        if self.streams is None or self._finished:
-            raise RuntimeError("StreamingSeparator.flush: no open streams")
-        if self.frames == 0:
-            raise RuntimeError(f"StreamingSeparator.flush: no complete frame yet (a stream needs {self.n_fft} samples)")
-        self._check_parameters()
-        if self._packs is None:
-            self._build_packs(self.device)
-        out = torch.empty(self.streams, self.n_fft - self.hop_length, dtype=torch.float32, device=self.device)
+    def _flush_into(self, out: torch.Tensor) -> None:
         hip.istft_step(None, self._packs["window"], self._tail, out, self._counter, self.hop_length, self._out_mode, flush=True)
-        self._finished = True
-        return out
-
-    @staticmethod
-    def output_length(samples: int, n_fft: int, hop: int) -> Dict[str, int]:
-        """Length bookkeeping of a stream of `samples` = k * hop input samples: priming hops, samples the steps emit, samples
-        flush() returns (their sum is the offline output length (T - 1) * hop + n_fft, T = (samples - n_fft) // hop + 1)."""
-        if samples % hop or n_fft % hop or samples < n_fft:
-            raise ValueError("output_length: whole hops, n_fft a multiple of hop, at least one window")
-        prime = n_fft // hop - 1
-        frames = samples // hop - prime
-        return dict(prime_hops=prime, frames=frames, emitted=frames * hop, flushed=n_fft - hop)

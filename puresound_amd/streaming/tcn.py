@@ -25,6 +25,8 @@ it runs.  Per slot the device holds a span (birth, death) of absolute frame indi
 birth[b] <= g < death[b].  ps_dwconv_step_slots_f32 reads a frame that is not live as 0 (the rule for g < 0, per column) and
 ps_free_decode_step_slots_f32 adds nothing for it; everything else in a hop is column-wise, so dead columns compute values
 nobody reads.  A slot's output is the offline output of its stream delayed by latency_samples, whatever the other slots do.
+The session around the kernels (priming, step / step_chunk / flush, eager run or graph replay, the capture) is HopSession's:
+streaming/_session.py.
 """
 from typing import Dict, List, Optional
 
@@ -36,7 +38,7 @@ from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
 from ..nnet.conv_tasnet import TCN, ConvTasNet
 from ..nnet.lobe.encoder import FreeEncDec
 from ..nnet.lobe.norm import ChanLN, norm_plan
-from .spectral import StreamingSeparator
+from ._session import HopSession, check_on_device
 
 #: frames per launch at most: step_chunk splits longer chunks (the rings hold (P-1)*dilation + K_MAX frames)
 K_MAX = 16
@@ -86,13 +88,10 @@ def check_streamable(model) -> None:
         dsc = blk.dconv[0]
         if any(a.weight.numel() != 1 for a in (blk.in_conv[2], dsc.depthwise[2], dsc.pointwise[2])):
             raise NotImplementedError(f"{name}: PReLU with per-channel slopes is not on the HIP path")
-    devs = {t.device.type for t in list(model.parameters()) + list(model.buffers())}
-    if devs != {"cuda"}:
-        raise NotImplementedError(f"{name}: the model's tensors are on {sorted(devs)}; streaming runs on a ROCm device only "
-                                  f"(move the model with .to(device))")
+    check_on_device(model, name)
 
 
-class StreamingConvTasNet:
+class StreamingConvTasNet(HopSession):
     """Hop-by-hop inference of a causal Conv-TasNet separator / speaker extractor for B streams (see the module docstring).
 
     s = StreamingConvTasNet(model); s.init_streams(B, enroll); s.step(hop [B, hop]) -> [B, hop] or None while the first
@@ -106,45 +105,23 @@ class StreamingConvTasNet:
     after latency_samples samples of constrain(0): slot_output_range(L, win, hop).
     """
 
+    max_hops = K_MAX
+    _how_to_start = "call init_streams() first (or init_slots())"
+
     def __init__(self, model: SoTaskWrapModule):
         check_streamable(model)
-        if model.training:
-            raise RuntimeError("StreamingConvTasNet: the model is in training mode -- call .eval()")
-        self.model = model
-        enc = model.encoder
-        self.win_length, self.hop_length = int(enc.win_length), int(enc.hop_length)
-        self.n_fft = self.win_length       # (the analysis window, under the name the shared helpers read)
-        self.prime_hops = self.win_length // self.hop_length - 1
-        self._mask_act = model.mask_constraint.lower()
-        self._out_mode = model.output_constraint.lower()
-        self.streams = None
+        super().__init__(model, model.encoder.win_length, model.encoder.hop_length)
+        self.win_length = self.window
         self._span = self._slots = None
-        self._drop_weights()
-
-    @property
-    def latency_samples(self) -> int:
-        """Samples between a sample entering and its value leaving: the analysis window minus one hop."""
-        return self.win_length - self.hop_length
-
-    output_length = staticmethod(StreamingSeparator.output_length)
 
     @staticmethod
     def slot_output_range(samples: int, win: int, hop: int) -> range:
         """The indices of y that hold model.inference(x, e) for a stream x of `samples` = k * hop samples in a slot, y = every
         output of the slot from open() on ‖ close(): the offline output after the latency, win - hop samples."""
-        n = StreamingSeparator.output_length(samples, win, hop)
+        n = HopSession.output_length(samples, win, hop)
         return range(win - hop, win - hop + n["emitted"] + n["flushed"])
 
     # -- weights ------------------------------------------------------------------------------------------------------
-    _signature = StreamingSeparator._signature
-    _check_parameters = StreamingSeparator._check_parameters
-
-    def _drop_weights(self) -> None:
-        """Forget graphs and weight packs (they are rebuilt from the current parameters on next use)."""
-        self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
-        self._packs = None
-        self._sig = self._signature()
-
     def _build_packs(self, dev: torch.device) -> None:
         """Weights packed for the kernels (eval BatchNorm1d folded to scale / shift), held by the streamer: a captured
         graph keeps reading these tensors."""
@@ -185,8 +162,6 @@ class StreamingConvTasNet:
         if (enroll is not None) != (model.speaker_net is not None):
             raise ValueError("StreamingConvTasNet.init_streams: an enrolment [streams, L'] is required iff the model has a "
                              "speaker_net")
-        self._check_parameters()
-        self._graphs = {}
         dev = next(model.parameters()).device
         b = int(streams)
         self._emb = None
@@ -202,20 +177,13 @@ class StreamingConvTasNet:
     def _new_session(self, b: int, dev: torch.device, use_graph: bool) -> None:
         """Zeroed state of b columns (self._emb is set by the caller)."""
         m = self.model.masker
-        self.streams, self.device, self._use_graph = b, dev, bool(use_graph)
-        self._hops = 0
-        self.frames = 0
-        self._finished = False
+        self._begin(b, dev, use_graph)
         self._span = None        # int32 [B, 2] (birth, death) in a slot session
         self._slots = None       # per slot None (idle) or dict(hops fed, total hops once end() was called)
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
         self._blocks: List[TCN] = [blk for stack in m.tcn_list for blk in stack]
         # one circular ring of activated depthwise inputs per block: (P-1)*dilation frames of history plus a chunk
         self._rings = [z((blk.kernel - 1) * blk.dilation + K_MAX, blk.hid_channels, b) for blk in self._blocks]
-        self._queue = z(b, self.win_length)
-        self._tail = z(b, self.win_length - self.hop_length)
-        self._counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._io: Dict[int, tuple] = {}
         self._bufs: Dict[int, dict] = {}
 
     @torch.no_grad()
@@ -224,8 +192,6 @@ class StreamingConvTasNet:
         if int(capacity) < 1:
             raise ValueError("init_slots: capacity >= 1")
         model, m = self.model, self.model.masker
-        self._check_parameters()
-        self._graphs = {}
         dev = next(model.parameters()).device
         b = int(capacity)
         self._emb = None
@@ -327,9 +293,7 @@ class StreamingConvTasNet:
         elif st["hops"] < st["total"]:
             raise RuntimeError(f"StreamingConvTasNet.close: end({slot}, ..) announced {st['total'] - st['hops']} more hops of "
                                f"input; step them first")
-        self._check_parameters()
-        if self._packs is None:
-            self._build_packs(self.device)
+        self._ready()
         if st["total"] is None:
             self.end(slot, 0)
         out = torch.empty(1, self.win_length - self.hop_length, dtype=torch.float32, device=self.device)
@@ -404,113 +368,31 @@ class StreamingConvTasNet:
                              span=self._span, counter=self._counter if self._span is not None else None)
         hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
 
-    def _run_piece(self, piece: torch.Tensor) -> torch.Tensor:
-        """At most K_MAX whole hops past the priming -> their output samples [B, hops*hop] (graph replay or eager)."""
-        hops = piece.shape[1] // self.hop_length
-        if hops not in self._io:
-            z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.device)  # noqa: E731
-            self._io[hops] = (z(self.streams, piece.shape[1]), z(self.streams, piece.shape[1]),
-                              z(hops, self.streams * self.win_length))
-        self._io[hops][0].copy_(piece)
-        if not self._use_graph:
-            self._body(hops)
-        else:
-            g = self._graphs.get(hops)
-            if g is None:
-                g = self._capture(hops)
-            g.replay()
-        self._hops += hops
-        self.frames += hops
-        return self._io[hops][1].clone()
-
     def _run(self, chunk: torch.Tensor) -> torch.Tensor:
-        """Whole hops past the priming -> their output samples, in pieces of at most K_MAX hops."""
+        """In a slot session: the frame limit before the chunk, the hops each slot's stream was fed after it."""
         k = chunk.shape[1] // self.hop_length
         if self._slots is not None and self.frames + k > FRAME_LIMIT:
             raise RuntimeError(f"StreamingConvTasNet: {self.frames} + {k} frames pass this session's limit of {FRAME_LIMIT} "
                                f"(2**31 - 1 - K_MAX: the device frame counter is an int32); close the streams and call "
                                f"init_slots() for a new session")
-        self._check_parameters()
-        if self._packs is None:
-            self._build_packs(self.device)
-        step = K_MAX * self.hop_length
-        outs = [self._run_piece(chunk[:, i:i + step]) for i in range(0, chunk.shape[1], step)]
+        out = super()._run(chunk)
         for st in self._slots or ():
             if st is not None:
                 st["hops"] = st["hops"] + k if st["total"] is None else min(st["hops"] + k, st["total"])
-        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+        return out
 
-    def _capture(self, hops: int) -> torch.cuda.CUDAGraph:
-        """Warm up once eagerly on a side stream (allocates what the launches need), put the state back, capture."""
-        state = self._state()
-        saved = [t.clone() for t in state]
-        dev = self.device
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            self._body(hops)
-        torch.cuda.current_stream(dev).wait_stream(s)
-        for t, v in zip(state, saved):
-            t.copy_(v)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._body(hops)
-        self._graphs[hops] = g
-        return g
+    def _priming(self) -> bool:
+        """(a slot session has no priming phase: a slot's first prime_hops frames are dead by its span)"""
+        return self._slots is None and super()._priming()
 
-    _prime = StreamingSeparator._prime
-
-    def _check_input(self, x: torch.Tensor, what: str) -> int:
-        if self.streams is None:
-            raise RuntimeError(f"StreamingConvTasNet.{what}: call init_streams() first (or init_slots())")
-        if self._finished:
-            raise RuntimeError(f"StreamingConvTasNet.{what}: the streams were flushed; call init_streams() for new ones")
-        hip.require_device(x, f"StreamingConvTasNet.{what}")
-        if x.dim() != 2 or x.shape[0] != self.streams or x.shape[1] % self.hop_length:
-            raise ValueError(f"StreamingConvTasNet.{what}: expected [{self.streams}, k * {self.hop_length}] samples, "
-                             f"got {tuple(x.shape)}")
-        return x.shape[1] // self.hop_length
-
-    @torch.no_grad()
-    def step(self, hop: torch.Tensor) -> Optional[torch.Tensor]:
-        """hop [B, hop_length] new samples per stream -> [B, hop_length] output samples, or None while the first analysis
-        window fills (the first win / hop - 1 hops)."""
-        if self._check_input(hop, "step") != 1:
-            raise ValueError(f"StreamingConvTasNet.step: one hop of {self.hop_length} samples per stream")
-        if self._slots is None and self._hops < self.prime_hops:
-            self._prime(hop)
-            return None
-        return self._run(hop)
-
-    @torch.no_grad()
-    def step_chunk(self, chunk: torch.Tensor) -> torch.Tensor:
-        """chunk [B, k*hop_length] -> what k step() calls return, concatenated ([B, 0] when every hop only primes)."""
-        k = self._check_input(chunk, "step_chunk")
-        if self._slots is not None:      # no priming phase: a slot's first prime_hops frames are dead by its span
-            return self._run(chunk) if k else chunk.new_zeros(self.streams, 0)
-        i = 0
-        while i < k and self._hops < self.prime_hops:
-            self._prime(chunk[:, i * self.hop_length:(i + 1) * self.hop_length])
-            i += 1
-        if i == k:
-            return chunk.new_zeros(self.streams, 0)
-        return self._run(chunk[:, i * self.hop_length:])
+    def _flush_into(self, out: torch.Tensor) -> None:
+        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail, out, self.hop_length, out_mode=self._out_mode,
+                             flush=True)
 
     @torch.no_grad()
     def flush(self) -> torch.Tensor:
         """The last win - hop_length samples of every stream ([B, win - hop_length]); the streams are then finished."""
-        if self.streams is None or self._finished:
-            raise RuntimeError("StreamingConvTasNet.flush: no open streams")
         if self._slots is not None:
             raise RuntimeError("StreamingConvTasNet.flush: a slot session ends its streams one by one: close(slot) returns a "
                                "slot's last samples")
-        if self.frames == 0:
-            raise RuntimeError(f"StreamingConvTasNet.flush: no complete frame yet (a stream needs {self.win_length} samples)")
-        self._check_parameters()
-        if self._packs is None:
-            self._build_packs(self.device)
-        out = torch.empty(self.streams, self.win_length - self.hop_length, dtype=torch.float32, device=self.device)
-        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail, out, self.hop_length, out_mode=self._out_mode,
-                             flush=True)
-        self._finished = True
-        return out
+        return super().flush()
