@@ -629,6 +629,36 @@ int ps_free_decode_step_slots_f32(const float* feats, const float* mask, int mas
                                   float* out, int ld_out, const int* span, const int* counter, int B, int k, int C, int win,
                                   int hop, int out_mode, float* ws, size_t ws_bytes, void* stream);
 
+/* k causal frames of ONE block of the causal dual-path RNN (DPRNN with causal = True, seg_overlap = False; dprnn.py:10-191)
+ * for B streams in one launch (puresound_amd/streaming/dprnn.py).  Columns as above: x, y [C][ld], column f * B + b; `counter`
+ * (device int, read and never written) = the absolute index of the chunk's first frame.  Frame g = *counter + f is position
+ * p = g % K of its segment.  Per frame and stream:
+ *   intra: gates = W [x ; h] + b with (h, c) = (h_intra, c_intra)[.][b], read as 0 when p == 0; LSTM cell (gates i, f, g, o);
+ *          v = x + LN(P h' + b_p); (h', c') -> (h_intra, c_intra) [H][ldb], in place;
+ *   inter: the same on v with (h, c) = slot p of h_bank / c_bank [K][H][ldb], written back to slot p;
+ *          y = v + LN(P h'' + b_p).  The other K - 1 slots are not touched by that frame.
+ * ps_dprnn_pass (a HOST struct, copied into the kernel arguments): wt [C + H][4H] = [W_ih | W_hh] transposed (k-major, gate
+ * rows in nn.LSTM's order), bias [4H] = b_ih + b_hh, pt [H][C] = the projection's weight transposed, pbias [C], gamma / beta
+ * [C] and eps of the nn.LayerNorm (biased variance over the C channels of one frame).
+ * Exact fp32 products and fp32 sums, every sum of a column in one fixed order: a stream's values are bit-identical for every
+ * B, whatever the other columns hold and however the frames are split into launches.  A workgroup owns 16 columns and needs
+ * (2 C + 6 H) * 64 bytes of LDS: ps_dprnn_block_step_ok(C, H, K) = 1 where that fits 64 KiB (C, H, K >= 1), else
+ * PS_E_UNSUPPORTED, which ps_dprnn_block_step_f32 then returns too, writing nothing.  x != y; k * B <= ld; B <= ldb. */
+typedef struct ps_dprnn_pass {
+  const float* wt;
+  const float* bias;
+  const float* pt;
+  const float* pbias;
+  const float* gamma;
+  const float* beta;
+  float eps;
+  int reserved;
+} ps_dprnn_pass;
+int ps_dprnn_block_step_ok(int C, int H, int K);
+int ps_dprnn_block_step_f32(const float* x, float* y, const int* counter, const ps_dprnn_pass* intra,
+                            const ps_dprnn_pass* inter, float* h_intra, float* c_intra, float* h_bank, float* c_bank, int C,
+                            int H, int K, int B, int k, int ld, int ldb, void* stream);
+
 /* One cell update per (unit, frame) from COMPLETE gate pre-activations gates [N][D*4H][ld_gates] (W_ih x + W_hh h + both
  * biases: the streaming step puts [x; h] on the K axis of one ps_conv1x1_f32):  c' = sig(f) c + sig(i) tanh(g) in
  * place in c [N][D*H][ld_state], h' = sig(o) tanh(c') into h [N][D*H][ld_state].  (SegLSTM with a one-frame

@@ -83,6 +83,10 @@ class RingPair(C.Structure):
     _fields_ = [("src", _vp), ("ring", _vp), ("count", C.c_int64), ("slots", C.c_int), ("reserved", C.c_int)]
 
 
+class DprnnPass(C.Structure):
+    _fields_ = [(k, _vp) for k in ("wt", "bias", "pt", "pbias", "gamma", "beta")] + [("eps", C.c_float), ("reserved", C.c_int)]
+
+
 class LstmArgs(C.Structure):
     _fields_ = [("gx", _vp), ("whh_t", _vp), ("h0", _vp), ("c0", _vp), ("hout", _vp), ("h_last", _vp),
                 ("c_last", _vp)] + [(k, C.c_int) for k in ("N", "H", "D", "Q", "q_stride", "steps", "step_stride",
@@ -186,6 +190,9 @@ SIGNATURES = {
                                  + [C.POINTER(Prologue), _vp]),
     "ps_free_decode_step_slots_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]
                                       + [C.c_int] * 6 + [_vp, C.c_size_t, _vp]),
+    "ps_dprnn_block_step_ok": (C.c_int, [C.c_int] * 3),
+    "ps_dprnn_block_step_f32": (C.c_int, [_vp, _vp, _vp, C.POINTER(DprnnPass), C.POINTER(DprnnPass)] + [_vp] * 4
+                                + [C.c_int] * 7 + [_vp]),
     "ps_unfold2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp] + [C.c_int] * 14 + [_vp]),
     "ps_conv2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 16 + [_vp, _vp]),
     "ps_conv2d_stats_parts": (C.c_int, [C.c_int] * 3),

@@ -1044,6 +1044,55 @@ def free_decode_step(feats: Optional[torch.Tensor], mask: Optional[torch.Tensor]
     return out
 
 
+def dprnn_block_step_ok(c: int, hidden: int, seg: int) -> bool:
+    """Whether ps_dprnn_block_step_f32 has a kernel for (C, H, K)."""
+    return lib().ps_dprnn_block_step_ok(int(c), int(hidden), int(seg)) == 1
+
+
+def pack_dprnn_pass(lstm, proj, norm, device: torch.device) -> dict:
+    """One pass of a DPRNN block (a unidirectional one-layer nn.LSTM, its nn.Linear, its nn.LayerNorm) -> the fp32 tensors of
+    a ps_dprnn_pass and the struct pointing at them (keep the dict alive while launches read it)."""
+    f32 = lambda t: t.detach().to(dtype=torch.float32, device=device)  # noqa: E731
+    p = dict(wt=torch.cat([f32(lstm.weight_ih_l0), f32(lstm.weight_hh_l0)], dim=1).t().contiguous(),   # [C + H, 4H]
+             bias=(f32(lstm.bias_ih_l0) + f32(lstm.bias_hh_l0)).contiguous(),
+             pt=f32(proj.weight).t().contiguous(), pbias=f32(proj.bias).contiguous(),                   # [H, C]
+             gamma=f32(norm.weight).contiguous(), beta=f32(norm.bias).contiguous())
+    s = _abi.DprnnPass()
+    for key, t in p.items():
+        setattr(s, key, ptr(t))
+    s.eps = float(norm.eps)
+    p["struct"] = s
+    return p
+
+
+def dprnn_block_step(x: torch.Tensor, counter: torch.Tensor, intra: dict, inter: dict, h_intra: torch.Tensor,
+                     c_intra: torch.Tensor, h_bank: torch.Tensor, c_bank: torch.Tensor, streams: int, frames: int,
+                     out: torch.Tensor) -> torch.Tensor:
+    """One causal DPRNN block on `frames` new frames of `streams` streams (ps_dprnn_block_step_f32): x [1, C, ld] (column
+    f * streams + b) -> out [1, C, ld] (columns past frames * streams are not written); intra / inter from pack_dprnn_pass;
+    intra state h_intra / c_intra [H, ldb] and the inter banks h_bank / c_bank [K, H, ldb] (slot p = position p of a segment),
+    updated in place; frame index of column 0 = counter[0], position = index % K."""
+    require_device(x, "dprnn_block_step")
+    _, c, ld = x.shape
+    k_seg, hidden, ldb = h_bank.shape
+    for t, shape in ((h_intra, (hidden, ldb)), (c_intra, (hidden, ldb)), (c_bank, (k_seg, hidden, ldb))):
+        require_weight(t, x, "dprnn_block_step")
+        if tuple(t.shape) != shape:
+            raise RuntimeError("dprnn_block_step: states [H, ldb] and banks [K, H, ldb] of one H and ldb expected")
+    require_weight(h_bank, x, "dprnn_block_step")
+    if not (x.is_contiguous() and out.is_contiguous()) or out.shape != x.shape or out.dtype != torch.float32 \
+            or counter.dtype != torch.int32 or counter.device != x.device:
+        raise RuntimeError("dprnn_block_step: contiguous fp32 x and out [1, C, ld], an int32 counter on their device expected")
+    if tuple(intra["wt"].shape) != (c + hidden, 4 * hidden) or tuple(inter["wt"].shape) != (c + hidden, 4 * hidden) \
+            or tuple(intra["pt"].shape) != (hidden, c) or tuple(inter["pt"].shape) != (hidden, c) \
+            or intra["wt"].device != x.device or inter["wt"].device != x.device:
+        raise RuntimeError(f"dprnn_block_step: passes packed for C = {c}, H = {hidden} on {x.device} expected")
+    check(lib().ps_dprnn_block_step_f32(ptr(x), ptr(out), ptr(counter), C.byref(intra["struct"]), C.byref(inter["struct"]),
+                                        ptr(h_intra), ptr(c_intra), ptr(h_bank), ptr(c_bank), c, hidden, k_seg, streams,
+                                        frames, ld, ldb, stream_ptr(x.device)), "ps_dprnn_block_step_f32")
+    return out
+
+
 def unfold2d(x1: torch.Tensor, x2: Optional[torch.Tensor], t: int, f_out: int, kf: int, kt: int, stride_f: int,
              dil_f: int, dil_t: int, pad_f: int, pad_t: int, transposed: bool, t_in: Optional[int] = None) -> torch.Tensor:
     """x1 [N,C1,F,ld] (+ x2 [N,C2,F,ld]) -> tap rows [N, (C1+C2)*kf*kt, f_out*ld] for the Conv2d / ConvTranspose2d GEMM."""

@@ -1,0 +1,205 @@
+"""Streaming the causal time-domain DPRNN speaker extractor (FreeEncDec + DPRNN(causal=True), with or without
+embedding_free_tse: egs/tse veve_dprnn_v0_causal) on the HIP path, one hop at a time for B concurrent streams.
+
+The model is exactly causal in time.  A segment is K = seg_size consecutive frames (seg_overlap=False).  With causal=True both
+LSTMs of a block run forward only: the intra LSTM walks the K frames of a segment from a zero state, and the inter LSTM at
+position p = g % K of frame g continues from the state it left at position p of the previous segment -- for the first
+segment from zero, or, with embedding_free_tse, from the state the enrolment pass ended in at that position.  LayerNorm acts
+on one frame, and the zero padding to whole segments lies after the last frame.  So frame g needs frames <= g only, and the
+samples a stream returns, followed by flush(), equal `model.inference(noisy, enroll)`, win - hop samples late.
+
+Layout as tcn.py: the k frames of a chunk for the B streams are the N = k*B columns of the library's channel-major rows
+(column f*B + b = frame f, stream b).  Every dependency of a block is per stream, so one launch of ps_dprnn_block_step_f32
+(csrc/dprnn_step.hip) runs a whole block on a whole chunk: a workgroup owns 16 stream columns and walks their frames in order.
+Per block the device holds the intra state (h, c) [H, ldB] and two banks [K, H, ldB], slot p = the inter state at position p.
+A chunk is: stream_windows, frame, the encoder's conv1x1 (+ ReLU), n_blocks block launches, output_fc (a conv1x1 with a PReLU
+prologue), free_decode_step (two launches) and stream_commit_frames -- n_blocks + 7 or 8 launches whatever its length.  No
+launch argument depends on the frame index, so one captured graph per chunk length replays every chunk.
+
+Arithmetic: exact fp32 products throughout, whatever the model's gemm_precision; every sum of a stream's column has one fixed
+order (the two 1x1 convolutions always take ps_conv1x1_f32's tiled kernel: MIN_GEMM_COLUMNS), so a stream's output does not depend on B, on its neighbours or on how its hops are split into calls.  The streamer
+packs its own weights from the parameters; the model's own setting and plans are left as they were.  The enrolment states are
+computed once per session by the model's own offline pieces, in the model's own arithmetic.  The session around the kernels
+(priming, step / step_chunk / flush, eager run or graph replay, the capture) is HopSession's: streaming/_session.py.
+"""
+from typing import List, Optional
+
+import torch
+
+from .. import hip
+from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
+from ..nnet.dprnn import DPRNN
+from ..nnet.lobe.encoder import FreeEncDec
+from ._session import HopSession, check_on_device
+
+#: frames per launch at most: step_chunk splits longer chunks
+K_MAX = 16
+INT32_MAX = 2 ** 31 - 1
+#: a session stops here: the device frame counter is an int32, and a launch reads up to K_MAX frames past it
+FRAME_LIMIT = INT32_MAX - K_MAX
+#: the 1x1 convolutions always run on at least this many columns (the rows are at least 128 wide; the columns past the chunk
+#: hold values nobody reads): ps_conv1x1_f32 has another kernel, with another order of summation, for 64 columns or fewer,
+#: and a stream's bits must not depend on how many columns share its launch
+MIN_GEMM_COLUMNS = 65
+
+
+def check_streamable(model) -> None:
+    """Raise NotImplementedError naming the reason when `model` is not a configuration this streamer computes exactly."""
+    name = "StreamingDPRNN"
+    if not isinstance(model, SoTaskWrapModule):
+        raise NotImplementedError(f"{name}: a SoTaskWrapModule (got {type(model).__name__})")
+    if not isinstance(model.encoder, FreeEncDec):
+        raise NotImplementedError(f"{name}: encoder {type(model.encoder).__name__}: only the free encoder (FreeEncDec) streams "
+                                  f"here; conv-STFT models stream through StreamingSeparator")
+    win, hop = model.encoder.win_length, model.encoder.hop_length
+    if win % hop:
+        raise NotImplementedError(f"{name}: win = {win} is not a multiple of hop = {hop}")
+    if win % 4 or win > 256:
+        raise NotImplementedError(f"{name}: win = {win}: a multiple of 4 up to 256 (the window queue moves in float4 "
+                                  f"columns, the decoder keeps a window per stream in LDS)")
+    m = model.masker
+    if not isinstance(m, DPRNN):
+        raise NotImplementedError(f"{name}: masker {type(m).__name__}: DPRNN only (ConvTasNet streams through "
+                                  f"StreamingConvTasNet)")
+    if m.bi_direct:
+        raise NotImplementedError(f"{name}: the DPRNN is not causal (causal=False: bidirectional LSTMs read future frames)")
+    if m.seg_overlap:
+        raise NotImplementedError(f"{name}: seg_overlap=True (half-overlapped segments) does not stream here")
+    if m.embed_dim != 0 or any(f is not None for f in m.input_film):
+        raise NotImplementedError(f"{name}: FiLM-conditioned blocks (embed_dim = {m.embed_dim}) are out of scope")
+    if model.speaker_net is not None:
+        raise NotImplementedError(f"{name}: a speaker_net (an embedding-conditioned DPRNN) is out of scope; the enrolment "
+                                  f"enters through embedding_free_tse only")
+    if bool(model.embedding_free_tse) != bool(m.embedding_free_tse):
+        raise NotImplementedError(f"{name}: embedding_free_tse differs between the wrapper ({model.embedding_free_tse}) and "
+                                  f"the masker ({m.embedding_free_tse})")
+    if m.output_fc[0].weight.numel() != 1:
+        raise NotImplementedError(f"{name}: PReLU with per-channel slopes is not on the HIP path")
+    pair = (model.mask_type.lower(), model.f_type.lower())
+    if pair != ("real", "real"):
+        raise NotImplementedError(f"{name}: mask pairing {pair}: the free encoder uses (real, real) only")
+    if model.mask_constraint.lower() not in _MASK_ACTS:
+        raise NotImplementedError(f"{name}: mask_constraint {model.mask_constraint!r}")
+    if model.output_constraint.lower() not in ("linear", "sigmoid"):
+        raise NotImplementedError(f"{name}: output_constraint {model.output_constraint!r}: linear or sigmoid")
+    c = model.encoder.encoder.weight.shape[0]
+    if m.input_size != c or m.output_fc[1].out_channels != c:
+        raise NotImplementedError(f"{name}: shapes: the encoder has {c} channels, the DPRNN takes {m.input_size} and returns "
+                                  f"{m.output_fc[1].out_channels}; a mask per encoder channel is needed")
+    if not hip.dprnn_block_step_ok(m.input_size, m.hidden_size, m.seg_size):
+        raise NotImplementedError(f"{name}: shapes: ps_dprnn_block_step_f32 has no kernel for (C, H, K) = ({m.input_size}, "
+                                  f"{m.hidden_size}, {m.seg_size}): a tile of 16 streams needs (2 C + 6 H) * 64 bytes of LDS, "
+                                  f"64 KiB at most")
+    if model.training:
+        raise NotImplementedError(f"{name}: the model is in training mode -- call .eval()")
+    check_on_device(model, name)
+
+
+class StreamingDPRNN(HopSession):
+    """Hop-by-hop inference of a causal DPRNN separator / enrolment-seeded speaker extractor for B streams (see the module
+    docstring).
+
+    s = StreamingDPRNN(model); s.init_streams(B, enroll); s.step(hop [B, hop]) -> [B, hop] or None while the first window
+    fills; s.step_chunk([B, k*hop]) -> what k step() calls return, concatenated; s.flush() -> the last win - hop samples.
+    """
+
+    max_hops = K_MAX
+
+    def __init__(self, model: SoTaskWrapModule):
+        check_streamable(model)
+        super().__init__(model, model.encoder.win_length, model.encoder.hop_length)
+        self.win_length = self.window
+
+    # -- weights ------------------------------------------------------------------------------------------------------
+    def _build_packs(self, dev: torch.device) -> None:
+        """fp32 weights packed for the kernels, held by the streamer: a captured graph keeps reading these tensors."""
+        f32 = dict(dtype=torch.float32, device=dev)
+        enc, m = self.model.encoder, self.model.masker
+        blocks = [(hip.pack_dprnn_pass(m.intra_rnn[i], m.intra_proj[i], m.intra_norm[i], dev),
+                   hip.pack_dprnn_pass(m.inter_rnn[i], m.inter_proj[i], m.inter_norm[i], dev)) for i in range(m.n_blocks)]
+        slope = m.output_fc[0].weight.detach().to(**f32).contiguous()
+        self._packs = dict(enc_wt=hip.pack_wt(enc.encoder.weight.detach().to(**f32)[:, 0, :]),
+                           dec_w=enc.decoder.weight.detach().to(**f32).contiguous(), blocks=blocks,
+                           out_wt=hip.pack_wt(m.output_fc[1].weight.detach().to(**f32)),
+                           out_b=m.output_fc[1].bias.detach().to(**f32).contiguous(), out_slope=slope,
+                           out_pro=hip.make_prologue(0, True, None, 0.0, 0.0, None, None, slope))
+
+    # -- session ------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def init_streams(self, streams: int = 1, enroll: Optional[torch.Tensor] = None, use_graph: bool = True) -> None:
+        """Start `streams` new streams.  enroll [streams, L'] on the model's device: the enrolment of each stream, required iff
+        the model is embedding_free_tse; the inter-LSTM states its pass ends in are computed here, once, and seed the banks.
+        Every other state is zeroed."""
+        if int(streams) < 1:
+            raise ValueError("init_streams: streams >= 1")
+        model, m = self.model, self.model.masker
+        if (enroll is not None) != bool(model.embedding_free_tse):
+            raise ValueError("StreamingDPRNN.init_streams: an enrolment [streams, L'] is required iff the model is "
+                             "embedding_free_tse")
+        dev = next(model.parameters()).device
+        b = int(streams)
+        seeds = None
+        if enroll is not None:
+            hip.require_device(enroll, "StreamingDPRNN.init_streams")
+            if enroll.dim() != 2 or enroll.shape[0] != b:
+                raise ValueError(f"StreamingDPRNN.init_streams: enroll must be [{b}, L'], got {tuple(enroll.shape)}")
+            feats, te = model.encoder.encode_padded(enroll.contiguous(), m.padded_frames_needed)
+            seeds = m.hidden_states_padded(feats, te)       # per block (h, c) [B, H, ldq]: [b, :, p] = position p of stream b
+        self._begin(b, dev, use_graph)
+        k, h, ldb = m.seg_size, m.hidden_size, hip.padded_frames(b)
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        self._intra = [(z(h, ldb), z(h, ldb)) for _ in range(m.n_blocks)]
+        self._banks = [(z(k, h, ldb), z(k, h, ldb)) for _ in range(m.n_blocks)]
+        if seeds is not None:
+            for bank, seed in zip(self._banks, seeds):
+                for dst, src in zip(bank, seed):
+                    dst[:, :, :b] = src[:, :, :k].float().permute(2, 1, 0)
+        self._bufs = {}
+
+    def _state(self) -> List[torch.Tensor]:
+        return [self._queue, self._tail, self._counter] + [t for pair in self._intra + self._banks for t in pair]
+
+    # -- one chunk ----------------------------------------------------------------------------------------------------
+    def _buffers(self, hops: int) -> dict:
+        """Activation buffers of a `hops`-frame chunk: [1, C, ld] over N = hops * B columns."""
+        if hops not in self._bufs:
+            n = hops * self.streams
+            ld = hip.padded_frames(n)
+            c = self.model.masker.input_size
+            z = lambda: torch.zeros(1, c, ld, dtype=torch.float32, device=self.device)  # noqa: E731
+            self._bufs[hops] = dict(n=n, feats=z(), x0=z(), x1=z(), mask=z())
+        return self._bufs[hops]
+
+    def _body(self, hops: int) -> None:
+        """`hops` frames of every stream: input _io[hops][0] [B, hops*hop] -> output _io[hops][1] [B, hops*hop]."""
+        chunk, out, wins = self._io[hops]
+        hop, win, pk = self.hop_length, self.win_length, self._packs
+        bufs = self._buffers(hops)
+        c, n = self.model.masker.input_size, bufs["n"]
+        feats = bufs["feats"]
+        hip.stream_windows(self._queue, chunk, wins, hop)
+        frames, _ = hip.frame(wins.view(1, -1), win, win)               # [1, win, ld]: column f*B + b
+        cols = max(n, MIN_GEMM_COLUMNS)
+        hip.conv1x1(frames, cols, pk["enc_wt"], c, out=feats)
+        if self.model.encoder.output_active:
+            hip.activation_(feats, "relu", None, n)
+        x = feats
+        for i, (intra, inter) in enumerate(pk["blocks"]):
+            y = bufs["x0"] if i % 2 == 0 else bufs["x1"]
+            hip.dprnn_block_step(x, self._counter, intra, inter, *self._intra[i], *self._banks[i], self.streams, hops, out=y)
+            x = y
+        hip.conv1x1(x, cols, pk["out_wt"], c, pk["out_pro"], pk["out_b"], out=bufs["mask"])
+        hip.free_decode_step(feats, bufs["mask"], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode)
+        hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
+
+    def _run(self, chunk: torch.Tensor) -> torch.Tensor:
+        k = chunk.shape[1] // self.hop_length
+        if self.frames + k > FRAME_LIMIT:
+            raise RuntimeError(f"StreamingDPRNN: {self.frames} + {k} frames pass this session's limit of {FRAME_LIMIT} "
+                               f"(2**31 - 1 - K_MAX: the device frame counter is an int32); flush the streams and call "
+                               f"init_streams() for a new session")
+        return super()._run(chunk)
+
+    def _flush_into(self, out: torch.Tensor) -> None:
+        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail, out, self.hop_length, out_mode=self._out_mode,
+                             flush=True)
