@@ -829,9 +829,9 @@ def lstm_gates_cell_cells(cells: list, t: int, hidden: int) -> None:
           "ps_lstm_gates_cell_cells_f32")
 
 
-def proj_layernorm_cells(cells: list, t: int, m: int) -> None:
+def proj_layernorm_cells(cells: list, t: int, m: int, res_inside: bool = False) -> None:
     """cells: [dict(x, wt, bias, gamma, beta, eps, res, y, norm2 = (gamma2, beta2, eps2) | None, y2, x_copy), ...] -> one
-    launch: y = res + LN(W x + b) (+ y2 = LN2(y), + x_copy = x) per cell."""
+    launch: y = res + LN(W x + b), or LN(W x + b + res) with res_inside (+ y2 = LN2(y), + x_copy = x) per cell."""
     x0 = cells[0]["x"]
     require_device(x0, "proj_layernorm_cells")
     _, k, ldt = x0.shape
@@ -844,7 +844,7 @@ def proj_layernorm_cells(cells: list, t: int, m: int) -> None:
         a.res, a.y, a.gamma2, a.beta2 = ptr(c.get("res")), ptr(c["y"]), ptr(g2), ptr(b2)
         a.y2, a.x_copy = ptr(c.get("y2") if g2 is not None else None), ptr(c.get("x_copy"))
         a.eps, a.eps2 = float(c["eps"]), float(e2)
-    check(lib().ps_proj_layernorm_cells_f32(arr, len(cells), 0, k, m, t, ldt, stream_ptr(x0.device)),
+    check(lib().ps_proj_layernorm_cells_f32(arr, len(cells), int(res_inside), k, m, t, ldt, stream_ptr(x0.device)),
           "ps_proj_layernorm_cells_f32")
 
 

@@ -171,3 +171,100 @@ def stream_overlap(frames, tail, hop: int):
         blocks.append((prev + f[:, :hop]) * 0.5)
         prev = f[:, hop:]
     return np.concatenate(blocks, 1), prev
+
+
+# ---- short-row GEMM kernels (conv1x1_small.hip): 1x1 convolution, FiLM, gates + cell, projection + LayerNorm -------------
+def conv1x1_ref(x, w, bias=None, bias_n=None, res=None, pro=None):
+    """y[n] = W a[n] + bias (+ bias_n[n]) (+ res[n]), a = the prologue of x [N, K, T] in the kernel's order (small_transform):
+    ReLU-before -> norm -> PReLU -> tanh-after.  pro: dict of `pre_relu` (bool), `affine` = (gamma [K], beta [K]), `prelu` =
+    slope, `post_tanh` (bool); `glob` = (gamma, beta, eps) takes the norm's place with the per-utterance mean / biased
+    variance over [K, T] (the tiled kernel's global-norm prologue)."""
+    pro = pro or {}
+    a = x.double()
+    if pro.get("pre_relu"):
+        a = a.clamp(min=0)
+    if pro.get("affine") is not None:
+        g, b = pro["affine"]
+        a = a * g.double().reshape(1, -1, 1) + b.double().reshape(1, -1, 1)
+    if pro.get("glob") is not None:
+        g, b, eps = pro["glob"]
+        mean = a.mean(dim=(1, 2), keepdim=True)
+        var = ((a - mean) ** 2).mean(dim=(1, 2), keepdim=True)
+        a = (a - mean) / torch.sqrt(var + eps) * g.double().reshape(1, -1, 1) + b.double().reshape(1, -1, 1)
+    if pro.get("prelu") is not None:
+        a = torch.where(a >= 0, a, float(pro["prelu"]) * a)
+    if pro.get("post_tanh"):
+        a = torch.tanh(a)
+    y = torch.matmul(w.double(), a)
+    if bias is not None:
+        y = y + bias.double().reshape(1, -1, 1)
+    if bias_n is not None:
+        y = y + bias_n.double().unsqueeze(2)
+    if res is not None:
+        y = y + res.double()
+    return y
+
+
+def film_conv_ref(x, w_scale, w_bias, res_scale=None, res_bias=None):
+    """(Ws x + rs) * x + (Wb x + rb): x [N, C, T], Ws / Wb [C, C], rs / rb [N, C, T] or None."""
+    x = x.double()
+    scale, shift = torch.matmul(w_scale.double(), x), torch.matmul(w_bias.double(), x)
+    if res_scale is not None:
+        scale = scale + res_scale.double()
+    if res_bias is not None:
+        shift = shift + res_bias.double()
+    return scale * x + shift
+
+
+def gates_cell_ref(xh, w, bias, c):
+    """gates = W [x; h] + b with rows gate-major (i, f, g, o, H rows each, nn.LSTM's order); c' = sig(f) c + sig(i) tanh(g),
+    h' = sig(o) tanh(c').  xh [N, K, T], w [4H, K], bias [4H] or None, c [N, H, T] -> (c', h')."""
+    a = torch.matmul(w.double(), xh.double())
+    if bias is not None:
+        a = a + bias.double().reshape(1, -1, 1)
+    hid = w.shape[0] // 4
+    gi, gf, gg, go = (a[:, g * hid:(g + 1) * hid] for g in range(4))
+    c_new = torch.sigmoid(gf) * c.double() + torch.sigmoid(gi) * torch.tanh(gg)
+    return c_new, torch.sigmoid(go) * torch.tanh(c_new)
+
+
+def frame_layernorm(p, gamma, beta, eps):
+    """LayerNorm of every frame of p [N, M, T] over its M channels, two-pass biased variance -> (y, variance [N, 1, T])."""
+    mean = p.mean(1, keepdim=True)
+    var = ((p - mean) ** 2).mean(1, keepdim=True)
+    return (p - mean) / torch.sqrt(var + eps) * gamma.double().reshape(1, -1, 1) + beta.double().reshape(1, -1, 1), var
+
+
+def proj_layernorm_ref(x, w, bias, gamma, beta, eps, res=None, res_inside=False, norm2=None, with_var=False):
+    """y = res + LN(W x + b) or, res_inside, LN(W x + b + res); y2 = LN2(y) with norm2 = (gamma2, beta2, eps2), else None.
+    with_var: also the smallest per-frame variance either norm divides by (the conditioning of the comparison)."""
+    p = torch.matmul(w.double(), x.double())
+    if bias is not None:
+        p = p + bias.double().reshape(1, -1, 1)
+    if res is not None and res_inside:
+        p = p + res.double()
+    y, var = frame_layernorm(p, gamma, beta, eps)
+    if res is not None and not res_inside:
+        y = y + res.double()
+    y2, low = None, float(var.min())
+    if norm2 is not None:
+        y2, var2 = frame_layernorm(y, norm2[0], norm2[1], norm2[2])
+        low = min(low, float(var2.min()))
+    return (y, y2, low) if with_var else (y, y2)
+
+
+def film_pack_weights(w_scale, w_bias):
+    """[C, C] x 2 -> [2C, C] with rows (2c, 2c + 1) = (scale row c, bias row c): what ps_film_conv_f32 takes (then pack_wt)."""
+    c = w_scale.shape[0]
+    return torch.stack([w_scale, w_bias], 1).reshape(2 * c, -1)
+
+
+def film_pack_rows(res_scale, res_bias):
+    """[N, C, T] x 2 -> [N, 2C, T], rows paired like film_pack_weights."""
+    n, c, t = res_scale.shape
+    return torch.stack([res_scale, res_bias], 2).reshape(n, 2 * c, t)
+
+
+def gate_unit_major(hid: int):
+    """index [4H] taking gate-major rows (g H + u) to the unit-major order of ps_lstm_gates_cell_f32: row 4u + g."""
+    return (torch.arange(4).reshape(1, 4) * hid + torch.arange(hid).reshape(hid, 1)).reshape(-1)

@@ -101,7 +101,9 @@ def _wrappers():
 
 
 def _gpu_test_files():
-    return [p for p in sorted(glob.glob(os.path.join(ROOT, "tests", "test_*.py"))) if "pytest.mark.gpu" in open(p).read()]
+    # (the mark as a statement or decorator at the start of a line: this file only speaks of it)
+    return [p for p in sorted(glob.glob(os.path.join(ROOT, "tests", "test_*.py")))
+            if re.search(r"^(?:pytestmark\s*=\s*|@)pytest\.mark\.gpu\b", open(p).read(), flags=re.M)]
 
 
 def _hit_wrappers(calls):
@@ -144,3 +146,28 @@ def test_exempt_entries_launch_nothing():
         assert s in defs, f"no definition of {s} in csrc/"
         assert "hipLaunchKernelGGL" not in defs[s][1] and "<<<" not in defs[s][1], f"{s} launches a kernel: it needs a test"
     assert set(defs) >= entries, sorted(entries - set(defs))
+
+
+# ---- the debug switches: each PS_DBG_* makes a dispatcher take the kernel it names, so that tests can run both -----------------
+def _debug_switches():
+    hdr = re.sub(r"/\*.*?\*/", "", _read("include/puresound_hip.h"), flags=re.S)
+    return sorted(set(re.findall(r"\b(PS_DBG_[A-Z0-9_]+)\s*=\s*1\s*<<", hdr)))
+
+
+def _unnamed_switches(test_texts):
+    return [s for s in _debug_switches() if not any(re.search(rf"\b{s}\b", text) for text in test_texts)]
+
+
+def test_every_debug_switch_is_read_by_a_kernel_launcher_and_named_by_a_gpu_test():
+    """A switch no dispatcher reads is dead; a switch no gpu-marked test names leaves the kernel it selects (or the default it
+    switches off) without a comparison.  PS_DBG_COOP_SABOTAGE counts through the bounded-poll test that names it."""
+    switches = _debug_switches()
+    assert len(switches) >= 22 and "PS_DBG_CONV1X1_TILED" in switches and "PS_DBG_GEMM_NO_PAIR" in switches
+    csrc = "".join(open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, "puresound_amd", "csrc", "*")))
+                   if p.endswith((".hip", ".inc", ".h")))
+    unread = [s for s in switches if not re.search(rf"\b{s}\b", csrc)]
+    assert not unread, f"declared in include/puresound_hip.h, read nowhere in csrc/: {unread}"
+    abi_py = _read("puresound_amd/_abi.py")
+    assert not [s for s in switches if not re.search(rf"^{s} = ", abi_py, flags=re.M)], "puresound_amd/_abi.py lacks a switch"
+    unnamed = _unnamed_switches([open(p).read() for p in _gpu_test_files()])
+    assert not unnamed, f"debug switches that no gpu-marked test names: {unnamed}"

@@ -106,9 +106,18 @@ def test_fp16x2_gemm_is_as_close_to_fp64_as_the_fp32_kernel(dev, n, k, m, t, mod
     # kernel (256 x 32 tiles for small grids), SIMPLE | WIDE_TILE = its 256 x 128 tile, ANY_SIZE = a persistent kernel
     # at any launch size (where the shape allows one), NO_RB = the interleaved kernel where the default is the
     # register-B kernel (conv1x1_f16x2_rb.inc: K % 32 == 0, M % 256 == 0)
-    simple, wide, any_size, no_rb = (_abi.PS_DBG_GEMM_SIMPLE, _abi.PS_DBG_GEMM_WIDE_TILE, _abi.PS_DBG_GEMM_ANY_SIZE,
-                                     _abi.PS_DBG_GEMM_NO_RB)
-    for flags in (0, simple, simple | wide, any_size, no_rb, no_rb | any_size):
+    # NO_PAIR = the persistent grids without their m-tile pairing (workgroups 8 apart, one XCD, share a run of frame tiles).
+    # Where the default pairs, on a 256-CU device (conv1x1_bf16.hip, tiles_t = ceil(T / 128), tiles_m = ceil(M / 256),
+    # nsuper = ceil(tiles_t / 2) tiles_m N): only (8, 256, 512, 3999) of the shapes above has two m-tiles AND fills the grid --
+    #   register-B kernel (flags 0): ntiles = 32 * 2 * 8 = 512 = Gr = 2 x CUs (2 * 256), Gr % (8 tiles_m) = 512 % 16 = 0 -> pair_r = 1
+    #     (gp = 256 pairs for 256 frame tiles: one tile per pair, inside PP_MAXU utterances);
+    #   interleaved kernel (NO_RB): st_per = 16, nsuper = 16 * 2 * 8 = 256 = G, nsuper % 256 = 0, per = 1 -> pair_r = 16.
+    # The other two-m-tile shapes do not pair: (1, 256, 512, 300) has 6 tiles (Gr = 6, G = 4), (5, 48, 512, 3700) has
+    # nsuper = 150 = G != 256 and K % 32 != 0 (no register-B kernel).  So no_pair / no_rb | no_pair change the numbering at
+    # that one shape and are the defaults again elsewhere; placement only -- the same bits are expected, the bound is the loop's.
+    simple, wide, any_size, no_rb, no_pair = (_abi.PS_DBG_GEMM_SIMPLE, _abi.PS_DBG_GEMM_WIDE_TILE, _abi.PS_DBG_GEMM_ANY_SIZE,
+                                              _abi.PS_DBG_GEMM_NO_RB, _abi.PS_DBG_GEMM_NO_PAIR)
+    for flags in (0, simple, simple | wide, any_size, no_rb, no_rb | any_size, no_pair, no_rb | no_pair):
         with _abi.debug(flags):
             y, st, am = H.conv1x1_f16x2(xd, t, wf, we, m, pro, b.to(dev), None, resd, want_stats=want, want_amax=True,
                                         **kw)

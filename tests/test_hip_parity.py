@@ -954,8 +954,13 @@ def test_conv1x1_bf16_planes(H, dev, planes, tol, n, k, m, t, mode):
     # SIMPLE = simple kernel only (small grids take its 256 x 32 tile), WIDE_TILE = keep its 256 x 128 tile,
     # ANY_SIZE = the persistent ping-pong kernel at any size,
     # TWO_BARRIER = the two-barrier ping-pong kernel instead of the interleaved one-barrier kernel
+    # NO_PAIR = the interleaved kernel's grid without the m-tile pairing.  On a 256-CU device the default pairs where
+    # G == 256 && tiles_m == 2 && nsuper % 256 == 0 (conv1x1_bf16.hip; nsuper = ceil(ceil(T / 128) / 2) tiles_m N): of the
+    # shapes above only (8, 256, 512, 3999) -- st_per = 16, nsuper = 16 * 2 * 8 = 256 = G, per = 1, pair_r = 16; the other
+    # two-m-tile shapes have nsuper = 4 and 150, the rest one m-tile.  Placement only: held to the loop's own bounds.
     simple, any_size, two = _abi.PS_DBG_GEMM_SIMPLE, _abi.PS_DBG_GEMM_ANY_SIZE, _abi.PS_DBG_GEMM_TWO_BARRIER
-    for flags in (0, two, simple, simple | _abi.PS_DBG_GEMM_WIDE_TILE, any_size, any_size | two):
+    no_pair = _abi.PS_DBG_GEMM_NO_PAIR
+    for flags in (0, two, simple, simple | _abi.PS_DBG_GEMM_WIDE_TILE, any_size, any_size | two, no_pair):
         with _abi.debug(flags):
             y, st = H.conv1x1_bf16(H.pad_rows(x.to(dev)), t, H.pack_wt_bf16(w.to(dev), planes), m, pro, b.to(dev),
                                    None if bias_n is None else bias_n.to(dev),
