@@ -26,6 +26,32 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+int launch_status(const char* who) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
+    return (int)e;
+  }
+  return 0;
+}
+
+int check_prologue(const char* who, const ps_prologue* pro) {
+  if (!pro) return 0;
+  if (pro->norm == PS_NORM_GLOBAL && (!pro->stats || pro->parts <= 0 || pro->count <= 0 || !pro->gamma || !pro->beta)) {
+    set_error("%s: PS_NORM_GLOBAL prologue needs stats/parts/count/gamma/beta", who);
+    return PS_E_INVALID;
+  }
+  if (pro->norm == PS_NORM_AFFINE && (!pro->gamma || !pro->beta)) {
+    set_error("%s: PS_NORM_AFFINE prologue needs gamma/beta", who);
+    return PS_E_INVALID;
+  }
+  if (pro->prelu && !pro->slope) {
+    set_error("%s: prelu prologue needs slope", who);
+    return PS_E_INVALID;
+  }
+  return 0;
+}
+
 struct ProfRecord {
   const char* kernel;
   hipEvent_t start, stop;

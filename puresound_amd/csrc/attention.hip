@@ -180,15 +180,6 @@ __global__ __launch_bounds__(256) void add_position_kernel(const float* __restri
 
 using namespace ps;
 
-static int att_status(const char* who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
 extern "C" int ps_self_attention_f32(const float* qkv, float* out, int N, int E, int heads, int Q, int q_stride, int L,
                                      int pos_stride, int ld, int causal, void* stream) {
   if (!qkv || !out || N <= 0 || E <= 0 || heads <= 0 || E % heads || Q <= 0 || L <= 0 || q_stride < 0 ||
@@ -232,14 +223,14 @@ extern "C" int ps_self_attention_f32(const float* qkv, float* out, int N, int E,
       hipLaunchKernelGGL((self_attention_l64_kernel<32, ATT_SQ>), g, dim3(ATT_SQ * 64), lds64, (hipStream_t)stream, a);
     else
       hipLaunchKernelGGL((self_attention_l64_kernel<64, ATT_SQ>), g, dim3(ATT_SQ * 64), lds64, (hipStream_t)stream, a);
-    return att_status("ps_self_attention_f32");
+    return launch_status("ps_self_attention_f32");
   }
   {
     LaunchTimer timer("self_attention", (hipStream_t)stream);
     hipLaunchKernelGGL(self_attention_kernel, dim3((Q + ATT_SQ - 1) / ATT_SQ, heads, N), dim3(ATT_SQ * 64), lds,
                        (hipStream_t)stream, a);
   }
-  return att_status("ps_self_attention_f32");
+  return launch_status("ps_self_attention_f32");
 }
 
 extern "C" int ps_add_position_f32(const float* x, const float* pe, float* y, int N, int E, int Q, int q_stride, int L,
@@ -254,5 +245,5 @@ extern "C" int ps_add_position_f32(const float* x, const float* pe, float* y, in
     hipLaunchKernelGGL(add_position_kernel, dim3((Q + 255) / 256, L, N * E), dim3(256), 0, (hipStream_t)stream, x, pe, y,
                        E, Q, q_stride, pos_stride, ld);
   }
-  return att_status("ps_add_position_f32");
+  return launch_status("ps_add_position_f32");
 }

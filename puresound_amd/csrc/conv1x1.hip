@@ -600,30 +600,11 @@ extern "C" int ps_conv1x1_f32(const float* x, const float* wt, float* y, int N, 
     set_error("ps_conv1x1_f32: residual and output statistics cannot be combined (no Conv-TasNet stage needs both)");
     return PS_E_UNSUPPORTED;
   }
-  if (pro) {
-    if (pro->norm == PS_NORM_GLOBAL && (!pro->stats || pro->parts <= 0 || pro->count <= 0 || !pro->gamma ||
-                                        !pro->beta)) {
-      set_error("ps_conv1x1_f32: PS_NORM_GLOBAL prologue needs stats/parts/count/gamma/beta");
-      return PS_E_INVALID;
-    }
-    if (pro->norm == PS_NORM_AFFINE && (!pro->gamma || !pro->beta)) {
-      set_error("ps_conv1x1_f32: PS_NORM_AFFINE prologue needs gamma/beta");
-      return PS_E_INVALID;
-    }
-    if (pro->prelu && !pro->slope) {
-      set_error("ps_conv1x1_f32: prelu prologue needs slope");
-      return PS_E_INVALID;
-    }
-  }
+  if (const int rc = check_prologue("ps_conv1x1_f32", pro)) return rc;
   // short rows (streaming step, state rows): channel-split kernel instead of 256 x 128 tiles (PS_DBG_CONV1X1_TILED = off)
   if (T <= 64 && !ostats && !(pro && pro->norm == PS_NORM_GLOBAL) && !dbg(PS_DBG_CONV1X1_TILED)) {
     conv1x1_small_launch(x, wt, y, N, K, M, T, ldt, pro, bias, bias_n, res, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("ps_conv1x1_f32: launch failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    return 0;
+    return launch_status("ps_conv1x1_f32");
   }
   Conv1x1Args a{};
   a.x = x;
@@ -633,24 +614,7 @@ extern "C" int ps_conv1x1_f32(const float* x, const float* wt, float* y, int N, 
   a.bias_n = bias_n;
   a.res = res;
   a.ostats = ostats;
-  if (pro) {
-    a.pro = *pro;
-    if (a.pro.norm == PS_NORM_GLOBAL && (!a.pro.stats || a.pro.parts <= 0 || a.pro.count <= 0 || !a.pro.gamma ||
-                                         !a.pro.beta)) {
-      set_error("ps_conv1x1_f32: PS_NORM_GLOBAL prologue needs stats/parts/count/gamma/beta");
-      return PS_E_INVALID;
-    }
-    if (a.pro.norm == PS_NORM_AFFINE && (!a.pro.gamma || !a.pro.beta)) {
-      set_error("ps_conv1x1_f32: PS_NORM_AFFINE prologue needs gamma/beta");
-      return PS_E_INVALID;
-    }
-    if (a.pro.prelu && !a.pro.slope) {
-      set_error("ps_conv1x1_f32: prelu prologue needs slope");
-      return PS_E_INVALID;
-    }
-  } else {
-    a.pro.norm = PS_NORM_NONE;
-  }
+  if (pro) a.pro = *pro;  // (else zeroed: PS_NORM_NONE, no activation)
   a.K = K;
   a.M = M;
   a.T = T;
@@ -689,10 +653,5 @@ extern "C" int ps_conv1x1_f32(const float* x, const float* wt, float* y, int N, 
     else
       hipLaunchKernelGGL(conv1x1_raw, gr, bl, 0, st, a);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_conv1x1_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_conv1x1_f32");
 }

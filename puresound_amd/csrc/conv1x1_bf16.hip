@@ -1048,6 +1048,66 @@ __global__ __launch_bounds__(512, 1) void conv1x1_bf16_pp_kernel(BfArgs a) {
 
 static int bf16_cus() { return device_cus(); }
 
+// The shape-derived fields of a launch's arguments (all that rb_ok reads) and the debug hooks.
+static BfArgs make_args(int N, int K, int M, int T, int ldt) {
+  BfArgs a{};
+  a.K = K, a.M = M, a.T = T, a.ldt = ldt, a.N = N;
+  a.ksteps = (K + XB_K - 1) / XB_K;
+  a.tiles_t = (T + XB_T - 1) / XB_T;
+  a.tiles_m = (M + XB_M - 1) / XB_M;
+  a.ablate = g_debug_ablate;
+  a.stamps = (unsigned long long*)g_debug_buffer;
+  return a;
+}
+
+// PLANES = 2: range of the activations (see the header): a host-side bound, the producer's maxima, or the defaults.
+// Reads a.pro: set the prologue first.
+static void set_range(BfArgs& a, const ps_f16x2_range& rng, bool tr) {
+  int x_exp = (tr && a.pro.norm != PS_NORM_NONE) ? -2 : -4;
+  if (rng.x_bound > 0.f) {
+    int e;
+    frexpf(rng.x_bound, &e);  // bound < 2^e  ->  scaled below 2^15
+    x_exp = 15 - e;
+    x_exp = x_exp < -100 ? -100 : (x_exp > 100 ? 100 : x_exp);
+  }
+  a.xscale = ldexpf(1.f, x_exp);
+  a.winv = ldexpf(1.f, -rng.w_exp);
+  a.x_amax = rng.x_bound > 0.f ? nullptr : rng.x_amax;
+  a.x_amax_parts = rng.x_amax_parts;
+  a.y_amax = rng.y_amax;  // [N][ps_conv1x1_stats_parts(M, T)] partial maxima of |y| (the next GEMM's input range) or NULL
+  a.amax_mul = rng.amax_mul > 0.f ? rng.amax_mul : 0.f;
+  a.amax_add = rng.amax_add > 0.f ? rng.amax_add : 0.f;
+}
+
+// need_source: the entry has no default range (bf16 rows): a bound or the producer's maxima must be there
+static int check_range(const char* who, const ps_f16x2_range* rng, bool need_source) {
+  if (!rng || rng->w_exp < -100 || rng->w_exp > 100 || rng->x_bound < 0.f || (rng->x_amax && rng->x_amax_parts <= 0) ||
+      (need_source && !(rng->x_bound > 0.f) && !rng->x_amax)) {
+    set_error("%s: range descriptor missing or %s", who,
+              need_source ? "incomplete (w_exp within +-100 and x_bound > 0 or x_amax)"
+                          : "out of range (w_exp within +-100, x_bound >= 0)");
+    return PS_E_INVALID;
+  }
+  return 0;
+}
+
+// Calls f(TR, STATS, RES) with the launch's variant as std::bool_constant values: the template arguments of its kernel.
+// (Statistics and a residual never come together: the entries refuse that.)
+template <class F>
+static void with_variant(bool tr, bool stats, bool res, F&& f) {
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (tr) {
+    if (stats) f(yes, yes, no);
+    else if (res) f(yes, no, yes);
+    else f(yes, no, no);
+  } else {
+    if (stats) f(no, yes, no);
+    else if (res) f(no, no, yes);
+    else f(no, no, no);
+  }
+}
+
 // Can this launch run on the register-B kernel (conv1x1_f16x2_rb.inc)?  K a multiple of 32, M a multiple of 256, a
 // scale / shift + PReLU prologue at most, enough tiles for the chip and a workgroup's run inside PP_MAXU utterances.
 // Gr receives the grid.
@@ -1065,46 +1125,35 @@ static bool rb_ok(const BfArgs& a, int N, int* Gr_out) {
 }
 
 template <bool R16, bool FM = false, bool LNE = false>
-static void rb_launch(const BfArgs& a, int N, bool tr, int Gr, hipStream_t stream) {
+static void rb_launch(BfArgs a, int N, bool tr, int Gr, hipStream_t stream) {
   const bool stats = a.ostats != nullptr, res = a.res != nullptr;
-  BfArgs& b = const_cast<BfArgs&>(a);
-  b.groups = Gr / 2;
-  b.delay = 0;
+  a.groups = Gr / 2;
+  a.delay = 0;
   // two m-tiles: workgroups 8 apart share a run of frame tiles, one m-tile each (see the kernel); needs an even grid
   // whose halves get whole, equal runs
-  b.pair_r = ((a.tiles_m == 2 || a.tiles_m == 4) && Gr % (8 * a.tiles_m) == 0 && !dbg(PS_DBG_GEMM_NO_PAIR)) ? 1 : 0;
-  if (b.pair_r) {  // (a pair's / quad's run of frame tiles must stay within PP_MAXU utterances too)
+  a.pair_r = ((a.tiles_m == 2 || a.tiles_m == 4) && Gr % (8 * a.tiles_m) == 0 && !dbg(PS_DBG_GEMM_NO_PAIR)) ? 1 : 0;
+  if (a.pair_r) {  // (a pair's / quad's run of frame tiles must stay within PP_MAXU utterances too)
     const int gp = Gr / a.tiles_m;
     const long long fr = (long long)a.tiles_t * N, pw2 = (fr + gp - 1) / gp;
-    if ((pw2 + a.tiles_t - 2) / a.tiles_t + 1 > PP_MAXU) b.pair_r = 0;
+    if ((pw2 + a.tiles_t - 2) / a.tiles_t + 1 > PP_MAXU) a.pair_r = 0;
   }
-#define PS_RB(TRV, STV, RSV) \
-  hipLaunchKernelGGL((conv1x1_f16x2_rb_kernel<TRV, STV, RSV, R16>), dim3(Gr, 1), dim3(256), 0, stream, a)
+  const dim3 grid(Gr, 1), block(256);
   if constexpr (FM) {  // (split_gemm admits no prologue, residual or statistics here)
-    hipLaunchKernelGGL((conv1x1_f16x2_rb_kernel<false, false, false, false, true>), dim3(Gr, 1), dim3(256), 0, stream, a);
-    return;
-  }
-  if constexpr (LNE) {
+    hipLaunchKernelGGL((conv1x1_f16x2_rb_kernel<false, false, false, false, true>), grid, block, 0, stream, a);
+  } else if constexpr (LNE) {
     if (tr)
-      hipLaunchKernelGGL((conv1x1_f16x2_rb_kernel<true, false, false, false, false, true>), dim3(Gr, 1), dim3(256), 0, stream, a);
+      hipLaunchKernelGGL((conv1x1_f16x2_rb_kernel<true, false, false, false, false, true>), grid, block, 0, stream, a);
     else
-      hipLaunchKernelGGL((conv1x1_f16x2_rb_kernel<false, false, false, false, false, true>), dim3(Gr, 1), dim3(256), 0, stream, a);
-    return;
-  }
-  if (tr) {
-    if (stats) PS_RB(true, true, false);
-    else if (res) PS_RB(true, false, true);
-    else PS_RB(true, false, false);
+      hipLaunchKernelGGL((conv1x1_f16x2_rb_kernel<false, false, false, false, false, true>), grid, block, 0, stream, a);
   } else {
-    if (stats) PS_RB(false, true, false);
-    else if (res) PS_RB(false, false, true);
-    else PS_RB(false, false, false);
+    with_variant(tr, stats, res, [&](auto TR, auto ST, auto RS) {
+      hipLaunchKernelGGL((conv1x1_f16x2_rb_kernel<TR(), ST(), RS(), R16>), grid, block, 0, stream, a);
+    });
   }
-#undef PS_RB
 }
 
 template <int PLANES, bool XB = false, bool YB = false>
-static void bf16_launch(const BfArgs& a, int N, bool tr, hipStream_t stream) {
+static void bf16_launch(BfArgs a, int N, bool tr, hipStream_t stream) {
   const bool stats = a.ostats != nullptr, res = a.res != nullptr;
   // The ping-pong kernel needs enough supertiles to give every CU work, K-steps to pipeline over, and a bounded
   // utterance span per workgroup (prologue tables in LDS); everything else takes the simple kernel.  PS_DBG_GEMM_SIMPLE
@@ -1125,13 +1174,13 @@ static void bf16_launch(const BfArgs& a, int N, bool tr, hipStream_t stream) {
     // same time and the drains run at what HBM gives the whole chip at once (39 k cycles); four phases of workgroups
     // 16 k cycles apart shorten them by more than the offset costs at the end of the launch (248 -> 221 us at 32
     // utterances; the in / pointwise drains are issue-bound and gain nothing)
-    const_cast<BfArgs&>(a).delay = (PLANES >= 2 && res && per_wg >= 4) ? 16000 : 0;
-    const_cast<BfArgs&>(a).groups = 4;
+    a.delay = (PLANES >= 2 && res && per_wg >= 4) ? 16000 : 0;
+    a.groups = 4;
 #ifdef PS_TUNE  // tuning builds only: phase offset / phase count from the environment (res / stats / plain launches)
     {
       const char* key = res ? "PS_IL_DELAY_RES" : stats ? "PS_IL_DELAY_STATS" : "PS_IL_DELAY_PLAIN";
-      if (const char* v = getenv(key)) const_cast<BfArgs&>(a).delay = atoi(v);
-      if (const char* v = getenv("PS_IL_GROUPS")) const_cast<BfArgs&>(a).groups = atoi(v);
+      if (const char* v = getenv(key)) a.delay = atoi(v);
+      if (const char* v = getenv("PS_IL_GROUPS")) a.groups = atoi(v);
     }
 #endif
     // out_conv (two m-tiles) reads every activation tile twice, once per m-tile.  Workgroups go to the XCDs round robin
@@ -1141,7 +1190,7 @@ static void bf16_launch(const BfArgs& a, int N, bool tr, hipStream_t stream) {
     const int per = (int)(nsuper / (G > 0 ? G : 1));
     const bool pairable = G == 256 && a.tiles_m == 2 && nsuper % 256 == 0 && per > 0 && st_per % per == 0 &&
                           !dbg(PS_DBG_GEMM_NO_PAIR);
-    const_cast<BfArgs&>(a).pair_r = pairable ? st_per / per : 0;
+    a.pair_r = pairable ? st_per / per : 0;
     // fp16x2 on fp32 rows, K a multiple of 32, M a multiple of 256: the register-B kernel (conv1x1_f16x2_rb.inc) --
     // activations go from HBM to the MFMA operand registers without touching LDS, v_mfma_f32_16x16x32_f16, two workgroups
     // per CU.  Same-box comparison in the benchmark's step (profiles/r04_gemm_kernels_same_box.txt), out / in / pointwise:
@@ -1154,56 +1203,106 @@ static void bf16_launch(const BfArgs& a, int N, bool tr, hipStream_t stream) {
         return;
       }
     }
-#define PS_IL(TRV, STV, RSV) \
-  hipLaunchKernelGGL((conv1x1_bf16_il_kernel<PLANES, TRV, STV, RSV, XB, YB>), dim3(G, 1), dim3(512), 0, stream, a)
-    if (tr) {
-      if (stats) PS_IL(true, true, false);
-      else if (res) PS_IL(true, false, true);
-      else PS_IL(true, false, false);
-    } else {
-      if (stats) PS_IL(false, true, false);
-      else if (res) PS_IL(false, false, true);
-      else PS_IL(false, false, false);
-    }
-#undef PS_IL
+    with_variant(tr, stats, res, [&](auto TR, auto ST, auto RS) {
+      hipLaunchKernelGGL((conv1x1_bf16_il_kernel<PLANES, TR(), ST(), RS(), XB, YB>), dim3(G, 1), dim3(512), 0, stream, a);
+    });
     return;
   }
   if constexpr (PLANES != 2) if (pp && !XB && !YB) {  // (bf16 rows, fp16 terms: the interleaved kernel or the simple one)
-#define PS_PP(TRV, STV, RSV) \
-  hipLaunchKernelGGL((conv1x1_bf16_pp_kernel<PLANES, TRV, STV, RSV>), dim3(G, 1), dim3(512), 0, stream, a)
-    if (tr) {
-      if (stats) PS_PP(true, true, false);
-      else if (res) PS_PP(true, false, true);
-      else PS_PP(true, false, false);
-    } else {
-      if (stats) PS_PP(false, true, false);
-      else if (res) PS_PP(false, false, true);
-      else PS_PP(false, false, false);
-    }
-#undef PS_PP
+    with_variant(tr, stats, res, [&](auto TR, auto ST, auto RS) {
+      hipLaunchKernelGGL((conv1x1_bf16_pp_kernel<PLANES, TR(), ST(), RS()>), dim3(G, 1), dim3(512), 0, stream, a);
+    });
     return;
   }
   // launches that cannot fill the chip with 256 x 128 tiles (one or a few utterances) take 256 x 32 tiles: four times
   // the workgroups, a quarter of the staging and MFMA work each (PS_DBG_GEMM_WIDE_TILE keeps the wide tile)
   const bool narrow = 2 * (long long)a.tiles_t * a.tiles_m * N <= cus && !dbg(PS_DBG_GEMM_WIDE_TILE);
-  dim3 grid(narrow ? a.tiles_t * 4 : a.tiles_t, a.tiles_m, N);
-#define PS_BF(TRV, STV, RSV)                                                                                          \
-  do {                                                                                                                \
-    if (narrow)                                                                                                       \
-      hipLaunchKernelGGL((conv1x1_bf16_kernel<PLANES, TRV, STV, RSV, 32, XB, YB>), grid, dim3(256), 0, stream, a);    \
-    else                                                                                                              \
-      hipLaunchKernelGGL((conv1x1_bf16_kernel<PLANES, TRV, STV, RSV, XB_T, XB, YB>), grid, dim3(256), 0, stream, a);  \
-  } while (0)
-  if (tr) {
-    if (stats) PS_BF(true, true, false);
-    else if (res) PS_BF(true, false, true);
-    else PS_BF(true, false, false);
-  } else {
-    if (stats) PS_BF(false, true, false);
-    else if (res) PS_BF(false, false, true);
-    else PS_BF(false, false, false);
+  const dim3 grid(narrow ? a.tiles_t * 4 : a.tiles_t, a.tiles_m, N);
+  with_variant(tr, stats, res, [&](auto TR, auto ST, auto RS) {
+    if (narrow)
+      hipLaunchKernelGGL((conv1x1_bf16_kernel<PLANES, TR(), ST(), RS(), 32, XB, YB>), grid, dim3(256), 0, stream, a);
+    else
+      hipLaunchKernelGGL((conv1x1_bf16_kernel<PLANES, TR(), ST(), RS(), XB_T, XB, YB>), grid, dim3(256), 0, stream, a);
+  });
+}
+
+// Every entry but the LayerNorm one: validation, arguments, the kernel family of the arithmetic.  rng: planes = 2 only
+// (checked by the entry); fm_ld > 0: frame-major output (ps_conv1x1_f16x2_fmajor_f32).
+static int split_gemm(const void* x_any, int x_bf16, const void* wt_planes, const ps_f16x2_range* rng, void* y_any,
+                      int y_bf16, int N, int K, int M, int T, int ldt, int planes, const ps_prologue* pro,
+                      const float* bias, const float* bias_n, const float* res, double* ostats, void* stream,
+                      int fm_ld) {
+  const char* const who = "ps_conv1x1_bf16_f32";
+  const bool fmajor = fm_ld > 0;
+  const bool rows16 = planes == 2 && x_bf16 && y_bf16;  // ps_conv1x1_f16_rows
+  if ((x_bf16 || y_bf16) && planes != 1 && !rows16) {
+    set_error("ps_conv1x1_bf16_io: bf16 activation rows go with planes = 1 (got %d)", planes);
+    return PS_E_UNSUPPORTED;
   }
-#undef PS_BF
+  if (!x_any || !wt_planes || !y_any || N <= 0 || K <= 0 || M <= 0 || T <= 0 || N > 65535) {
+    set_error("%s: null pointer or non-positive size (N=%d K=%d M=%d T=%d)", who, N, K, M, T);
+    return PS_E_INVALID;
+  }
+  if (ldt < T || ldt % kTileT != 0 || ((uintptr_t)wt_planes & 15)) {
+    set_error("%s: ldt=%d must be a multiple of %d >= T=%d, weights 16-byte aligned", who, ldt, kTileT, T);
+    return PS_E_ALIGN;
+  }
+  if (res && ostats) {
+    set_error("%s: residual and output statistics cannot be combined", who);
+    return PS_E_UNSUPPORTED;
+  }
+  if (const int rc = check_prologue(who, pro)) return rc;
+  const bool tr = pro && (pro->norm != PS_NORM_NONE || pro->prelu || pro->pre_relu || pro->post_tanh);
+  if (tr && K > 512) {
+    set_error("%s: K=%d exceeds the 512 input channels the prologue keeps tables for", who, K);
+    return PS_E_UNSUPPORTED;
+  }
+  BfArgs a = make_args(N, K, M, T, ldt);
+  if (pro) a.pro = *pro;
+  a.x = (const float*)x_any;
+  a.wt = (const unsigned short*)wt_planes;
+  a.y = (float*)y_any;
+  a.bias = bias;
+  a.bias_n = bias_n;
+  a.res = res;
+  a.ostats = ostats;
+  a.x_bf16 = x_bf16 != 0;
+  a.y_bf16 = y_bf16 != 0;
+  {
+    LaunchTimer timer("conv1x1_bf16", (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (planes == 2) {
+      set_range(a, *rng, tr);
+      if (fmajor) {
+        int Gr = 0;
+        a.fm_ld = fm_ld;
+        if (tr || res || ostats || !rb_ok(a, N, &Gr) || fm_ld < M || fm_ld % 4 || (long long)fm_ld * ldt * 4 >= (1LL << 31)) {
+          set_error("ps_conv1x1_f16x2_fmajor_f32: this launch cannot run on the register-B kernel (ps_conv1x1_f16x2_fmajor_ok)");
+          return PS_E_UNSUPPORTED;
+        }
+        rb_launch<false, true>(a, N, false, Gr, st);
+      } else if (rows16) {
+        int Gr = 0;
+        if (!rb_ok(a, N, &Gr)) {
+          set_error("ps_conv1x1_f16_rows: this launch cannot run on the register-B kernel (ps_conv1x1_f16_rows_ok)");
+          return PS_E_UNSUPPORTED;
+        }
+        rb_launch<true>(a, N, tr, Gr, st);
+      } else {
+        bf16_launch<2>(a, N, tr, st);
+      }
+    } else if (planes == 3)
+      bf16_launch<3>(a, N, tr, st);
+    else if (a.x_bf16 && a.y_bf16)
+      bf16_launch<1, true, true>(a, N, tr, st);
+    else if (a.x_bf16)
+      bf16_launch<1, true, false>(a, N, tr, st);
+    else if (a.y_bf16)
+      bf16_launch<1, false, true>(a, N, tr, st);
+    else
+      bf16_launch<1>(a, N, tr, st);
+  }
+  return launch_status(who);
 }
 
 }  // namespace ps
@@ -1222,11 +1321,6 @@ extern "C" int ps_conv1x1_bf16_f32(const float* x, const void* wt_planes, float*
   return ps_conv1x1_bf16_io(x, 0, wt_planes, y, 0, N, K, M, T, ldt, planes, pro, bias, bias_n, res, ostats, stream);
 }
 
-static int split_gemm(const void* x_any, int x_bf16, const void* wt_planes, const ps_f16x2_range* rng, void* y_any,
-                      int y_bf16, int N, int K, int M, int T, int ldt, int planes, const ps_prologue* pro,
-                      const float* bias, const float* bias_n, const float* res, double* ostats, void* stream,
-                      int fm_ld = 0);
-
 extern "C" int ps_conv1x1_bf16_io(const void* x_any, int x_bf16, const void* wt_planes, void* y_any, int y_bf16, int N,
                                   int K, int M, int T, int ldt, int planes, const ps_prologue* pro, const float* bias,
                                   const float* bias_n, const float* res, double* ostats, void* stream) {
@@ -1235,17 +1329,14 @@ extern "C" int ps_conv1x1_bf16_io(const void* x_any, int x_bf16, const void* wt_
     return PS_E_INVALID;
   }
   return split_gemm(x_any, x_bf16, wt_planes, nullptr, y_any, y_bf16, N, K, M, T, ldt, planes, pro, bias, bias_n, res,
-                    ostats, stream);
+                    ostats, stream, 0);
 }
 
 extern "C" int ps_conv1x1_f16x2_f32(const float* x, const void* wt_planes, const ps_f16x2_range* rng, float* y, int N,
                                     int K, int M, int T, int ldt, const ps_prologue* pro, const float* bias,
                                     const float* bias_n, const float* res, double* ostats, void* stream) {
-  if (!rng || rng->w_exp < -100 || rng->w_exp > 100 || rng->x_bound < 0.f || (rng->x_amax && rng->x_amax_parts <= 0)) {
-    set_error("ps_conv1x1_f16x2_f32: range descriptor missing or out of range (w_exp within +-100, x_bound >= 0)");
-    return PS_E_INVALID;
-  }
-  return split_gemm(x, 0, wt_planes, rng, y, 0, N, K, M, T, ldt, 2, pro, bias, bias_n, res, ostats, stream);
+  if (const int rc = check_range("ps_conv1x1_f16x2_f32", rng, false)) return rc;
+  return split_gemm(x, 0, wt_planes, rng, y, 0, N, K, M, T, ldt, 2, pro, bias, bias_n, res, ostats, stream, 0);
 }
 
 extern "C" int ps_conv1x1_f16x2_fmajor_ok(int N, int K, int M, int T, int ldt, int ldm) {
@@ -1254,10 +1345,7 @@ extern "C" int ps_conv1x1_f16x2_fmajor_ok(int N, int K, int M, int T, int ldt, i
 
 extern "C" int ps_conv1x1_f16x2_fmajor_f32(const float* x, const void* wt_planes, const ps_f16x2_range* rng, float* y, int N,
                                            int K, int M, int T, int ldt, int ldm, const float* bias, void* stream) {
-  if (!rng || rng->w_exp < -100 || rng->w_exp > 100 || rng->x_bound < 0.f || (rng->x_amax && rng->x_amax_parts <= 0)) {
-    set_error("ps_conv1x1_f16x2_fmajor_f32: range descriptor missing or out of range (w_exp within +-100, x_bound >= 0)");
-    return PS_E_INVALID;
-  }
+  if (const int rc = check_range("ps_conv1x1_f16x2_fmajor_f32", rng, false)) return rc;
   if (ldm < M || ldm % 4) {
     set_error("ps_conv1x1_f16x2_fmajor_f32: ldm=%d must be a multiple of 4 >= M=%d", ldm, M);
     return PS_E_INVALID;
@@ -1270,10 +1358,7 @@ extern "C" int ps_conv1x1_f16x2_ln_ok(int N, int K, int C, int T) { return C == 
 extern "C" int ps_conv1x1_f16x2_ln_f32(const float* x, const void* wt_planes, const ps_f16x2_range* rng, float* y, int N, int K,
                                        int C, int T, int ldt, const ps_prologue* pro, const float* bias, const float* gamma,
                                        const float* beta, float eps, const float* res, int res_inside, void* stream) {
-  if (!rng || rng->w_exp < -100 || rng->w_exp > 100 || rng->x_bound < 0.f || (rng->x_amax && rng->x_amax_parts <= 0)) {
-    set_error("ps_conv1x1_f16x2_ln_f32: range descriptor missing or out of range (w_exp within +-100, x_bound >= 0)");
-    return PS_E_INVALID;
-  }
+  if (const int rc = check_range("ps_conv1x1_f16x2_ln_f32", rng, false)) return rc;
   if (!x || !wt_planes || !y || !gamma || !beta || N <= 0 || K <= 0 || T <= 0 || N > 65535 || !(eps >= 0.f)) {
     set_error("ps_conv1x1_f16x2_ln_f32: null pointer or non-positive size (N=%d K=%d C=%d T=%d)", N, K, C, T);
     return PS_E_INVALID;
@@ -1284,7 +1369,7 @@ extern "C" int ps_conv1x1_f16x2_ln_f32(const float* x, const void* wt_planes, co
               kTileT);
     return PS_E_UNSUPPORTED;
   }
-  BfArgs a{};
+  BfArgs a = make_args(N, K, 256, T, ldt);  // (the weight image has 256 rows, the upper 128 of them zero)
   bool tr = false;
   if (pro) {
     a.pro = *pro;
@@ -1296,25 +1381,8 @@ extern "C" int ps_conv1x1_f16x2_ln_f32(const float* x, const void* wt_planes, co
     }
   }
   a.x = x, a.wt = (const unsigned short*)wt_planes, a.y = y, a.bias = bias, a.res = res;
-  a.K = K, a.M = 256, a.T = T, a.ldt = ldt, a.N = N;  // (the weight image has 256 rows, the upper 128 of them zero)
-  a.ksteps = (K + XB_K - 1) / XB_K, a.tiles_t = (T + XB_T - 1) / XB_T, a.tiles_m = 1;
-  a.ablate = g_debug_ablate;
-  a.stamps = (unsigned long long*)g_debug_buffer;
   a.ln_gamma = gamma, a.ln_beta = beta, a.ln_eps = eps, a.ln_inside = res_inside && res ? 1 : 0;
-  int x_exp = (tr && a.pro.norm != PS_NORM_NONE) ? -2 : -4;
-  if (rng->x_bound > 0.f) {
-    int e;
-    frexpf(rng->x_bound, &e);
-    x_exp = 15 - e;
-    x_exp = x_exp < -100 ? -100 : (x_exp > 100 ? 100 : x_exp);
-  }
-  a.xscale = ldexpf(1.f, x_exp);
-  a.winv = ldexpf(1.f, -rng->w_exp);
-  a.x_amax = rng->x_bound > 0.f ? nullptr : rng->x_amax;
-  a.x_amax_parts = rng->x_amax_parts;
-  a.amax_mul = rng->amax_mul > 0.f ? rng->amax_mul : 0.f;
-  a.amax_add = rng->amax_add > 0.f ? rng->amax_add : 0.f;
-  a.y_amax = rng->y_amax;  // [N][ps_conv1x1_stats_parts(256, T)] partial maxima of |y| (the next GEMM's input range) or NULL
+  set_range(a, *rng, tr);
   int Gr = 0;
   if (!rb_ok(a, N, &Gr)) {
     set_error("ps_conv1x1_f16x2_ln_f32: this launch cannot run on the register-B kernel (ps_conv1x1_f16x2_ln_ok)");
@@ -1324,33 +1392,19 @@ extern "C" int ps_conv1x1_f16x2_ln_f32(const float* x, const void* wt_planes, co
     LaunchTimer timer("conv1x1_bf16", (hipStream_t)stream);
     rb_launch<false, false, true>(a, N, tr, Gr, (hipStream_t)stream);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_conv1x1_f16x2_ln_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_conv1x1_f16x2_ln_f32");
 }
 
 extern "C" int ps_conv1x1_f16_rows_ok(int N, int K, int M, int T) {
   if (N <= 0 || K <= 0 || M <= 0 || T <= 0) return 0;
-  BfArgs a{};
-  a.K = K, a.M = M, a.T = T;
-  a.ksteps = (K + XB_K - 1) / XB_K;
-  a.tiles_t = (T + XB_T - 1) / XB_T;
-  a.tiles_m = (M + XB_M - 1) / XB_M;
-  return rb_ok(a, N, nullptr) ? 1 : 0;
+  return rb_ok(make_args(N, K, M, T, /*ldt (no rows here; rb_ok does not read it)*/ 0), N, nullptr) ? 1 : 0;
 }
 
 extern "C" int ps_conv1x1_f16_rows(const void* x, const void* wt_planes, const ps_f16x2_range* rng, void* y, int N, int K,
                                    int M, int T, int ldt, const ps_prologue* pro, const float* bias, const float* bias_n,
                                    const void* res, double* ostats, void* stream) {
-  if (!rng || rng->w_exp < -100 || rng->w_exp > 100 || rng->x_bound < 0.f || (rng->x_amax && rng->x_amax_parts <= 0) ||
-      (!(rng->x_bound > 0.f) && !rng->x_amax)) {
-    set_error("ps_conv1x1_f16_rows: range descriptor missing or incomplete (w_exp within +-100 and x_bound > 0 or x_amax)");
-    return PS_E_INVALID;
-  }
-  return split_gemm(x, 1, wt_planes, rng, y, 1, N, K, M, T, ldt, 2, pro, bias, bias_n, (const float*)res, ostats, stream);
+  if (const int rc = check_range("ps_conv1x1_f16_rows", rng, true)) return rc;
+  return split_gemm(x, 1, wt_planes, rng, y, 1, N, K, M, T, ldt, 2, pro, bias, bias_n, (const float*)res, ostats, stream, 0);
 }
 
 // partial maxima of |x| per utterance for the fp16x2 GEMM's range: [N][PS_ABSMAX_PARTS]
@@ -1386,131 +1440,5 @@ extern "C" int ps_absmax_f32(const float* x, float* amax, int N, int C, int T, i
   }
   LaunchTimer timer("absmax", (hipStream_t)stream);
   hipLaunchKernelGGL(absmax_kernel, dim3(kAbsmaxParts, N), dim3(256), 0, (hipStream_t)stream, x, amax, C, T, ldt);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_absmax_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
-static int split_gemm(const void* x_any, int x_bf16, const void* wt_planes, const ps_f16x2_range* rng, void* y_any,
-                      int y_bf16, int N, int K, int M, int T, int ldt, int planes, const ps_prologue* pro,
-                      const float* bias, const float* bias_n, const float* res, double* ostats, void* stream,
-                      int fm_ld) {
-  const bool fmajor = fm_ld > 0;
-  const float* x = (const float*)x_any;
-  float* y = (float*)y_any;
-  const bool rows16 = planes == 2 && x_bf16 && y_bf16;  // ps_conv1x1_f16_rows
-  if ((x_bf16 || y_bf16) && planes != 1 && !rows16) {
-    set_error("ps_conv1x1_bf16_io: bf16 activation rows go with planes = 1 (got %d)", planes);
-    return PS_E_UNSUPPORTED;
-  }
-  if (!x || !wt_planes || !y || N <= 0 || K <= 0 || M <= 0 || T <= 0 || N > 65535) {
-    set_error("ps_conv1x1_bf16_f32: null pointer or non-positive size (N=%d K=%d M=%d T=%d)", N, K, M, T);
-    return PS_E_INVALID;
-  }
-  if (ldt < T || ldt % kTileT != 0 || ((uintptr_t)wt_planes & 15)) {
-    set_error("ps_conv1x1_bf16_f32: ldt=%d must be a multiple of %d >= T=%d, weights 16-byte aligned", ldt, kTileT, T);
-    return PS_E_ALIGN;
-  }
-  if (res && ostats) {
-    set_error("ps_conv1x1_bf16_f32: residual and output statistics cannot be combined");
-    return PS_E_UNSUPPORTED;
-  }
-  bool tr = false;
-  BfArgs a{};
-  if (pro) {
-    a.pro = *pro;
-    tr = pro->norm != PS_NORM_NONE || pro->prelu || pro->pre_relu || pro->post_tanh;
-    if (pro->norm == PS_NORM_GLOBAL && (!pro->stats || pro->parts <= 0 || pro->count <= 0 || !pro->gamma || !pro->beta)) {
-      set_error("ps_conv1x1_bf16_f32: PS_NORM_GLOBAL prologue needs stats/parts/count/gamma/beta");
-      return PS_E_INVALID;
-    }
-    if (pro->norm == PS_NORM_AFFINE && (!pro->gamma || !pro->beta)) {
-      set_error("ps_conv1x1_bf16_f32: PS_NORM_AFFINE prologue needs gamma/beta");
-      return PS_E_INVALID;
-    }
-    if (pro->prelu && !pro->slope) {
-      set_error("ps_conv1x1_bf16_f32: prelu prologue needs slope");
-      return PS_E_INVALID;
-    }
-  }
-  if (tr && K > 512) {
-    set_error("ps_conv1x1_bf16_f32: K=%d exceeds the 512 input channels the prologue keeps tables for", K);
-    return PS_E_UNSUPPORTED;
-  }
-  a.x = x;
-  a.wt = (const unsigned short*)wt_planes;
-  a.y = y;
-  a.bias = bias;
-  a.bias_n = bias_n;
-  a.res = res;
-  a.ostats = ostats;
-  a.K = K;
-  a.M = M;
-  a.T = T;
-  a.ldt = ldt;
-  a.ksteps = (K + XB_K - 1) / XB_K;
-  a.tiles_t = (T + XB_T - 1) / XB_T;
-  a.tiles_m = (M + XB_M - 1) / XB_M;
-  a.N = N;
-  a.ablate = g_debug_ablate;
-  a.stamps = (unsigned long long*)g_debug_buffer;
-  a.x_bf16 = x_bf16 != 0;
-  a.y_bf16 = y_bf16 != 0;
-  {
-    LaunchTimer timer("conv1x1_bf16", (hipStream_t)stream);
-    hipStream_t st = (hipStream_t)stream;
-    if (planes == 2) {
-      // range of the activations (see the header): a host-side bound, the producer's maxima, or the defaults
-      int x_exp = (tr && a.pro.norm != PS_NORM_NONE) ? -2 : -4;
-      if (rng->x_bound > 0.f) {
-        int e;
-        frexpf(rng->x_bound, &e);  // bound < 2^e  ->  scaled below 2^15
-        x_exp = 15 - e;
-        x_exp = x_exp < -100 ? -100 : (x_exp > 100 ? 100 : x_exp);
-      }
-      a.xscale = ldexpf(1.f, x_exp);
-      a.winv = ldexpf(1.f, -rng->w_exp);
-      a.x_amax = rng->x_bound > 0.f ? nullptr : rng->x_amax;
-      a.x_amax_parts = rng->x_amax_parts;
-      a.y_amax = rng->y_amax;
-      a.amax_mul = rng->amax_mul > 0.f ? rng->amax_mul : 0.f;
-      a.amax_add = rng->amax_add > 0.f ? rng->amax_add : 0.f;
-      if (fmajor) {
-        int Gr = 0;
-        a.fm_ld = fm_ld;
-        if (tr || res || ostats || !rb_ok(a, N, &Gr) || fm_ld < M || fm_ld % 4 || (long long)fm_ld * ldt * 4 >= (1LL << 31)) {
-          set_error("ps_conv1x1_f16x2_fmajor_f32: this launch cannot run on the register-B kernel (ps_conv1x1_f16x2_fmajor_ok)");
-          return PS_E_UNSUPPORTED;
-        }
-        rb_launch<false, true>(a, N, false, Gr, st);
-      } else if (rows16) {
-        int Gr = 0;
-        if (!rb_ok(a, N, &Gr)) {
-          set_error("ps_conv1x1_f16_rows: this launch cannot run on the register-B kernel (ps_conv1x1_f16_rows_ok)");
-          return PS_E_UNSUPPORTED;
-        }
-        rb_launch<true>(a, N, tr, Gr, st);
-      } else {
-        bf16_launch<2>(a, N, tr, st);
-      }
-    } else if (planes == 3)
-      bf16_launch<3>(a, N, tr, st);
-    else if (a.x_bf16 && a.y_bf16)
-      bf16_launch<1, true, true>(a, N, tr, st);
-    else if (a.x_bf16)
-      bf16_launch<1, true, false>(a, N, tr, st);
-    else if (a.y_bf16)
-      bf16_launch<1, false, true>(a, N, tr, st);
-    else
-      bf16_launch<1>(a, N, tr, st);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_conv1x1_bf16_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_absmax_f32");
 }

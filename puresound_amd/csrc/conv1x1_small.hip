@@ -704,15 +704,6 @@ int conv1x1_small_launch(const float* x, const float* wt, float* y, int N, int K
 
 using namespace ps;
 
-static int small_status(const char* who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
 static int fused_launch(const char* who, int epi, FusedArgs& fa, int N, hipStream_t stream) {
   const SmallArgs& a = fa.g;
   const int ncb = a.T <= 16 ? 1 : a.T <= 32 ? 2 : 4;
@@ -751,7 +742,7 @@ extern "C" int ps_film_conv_f32(const float* x, const float* wt_pairs, const flo
   fa.g.T = T;
   fa.g.ldt = ldt;
   fused_launch("film_conv", 1, fa, N, (hipStream_t)stream);
-  return small_status("ps_film_conv_f32");
+  return launch_status("ps_film_conv_f32");
 }
 
 extern "C" int ps_lstm_gates_cell_f32(const float* xh, const float* wt_units, const float* bias_units, float* c,
@@ -773,7 +764,7 @@ extern "C" int ps_lstm_gates_cell_f32(const float* xh, const float* wt_units, co
   fa.h_out = h;
   fa.ld_state = ld_state;
   fused_launch("lstm_gates_cell", 2, fa, N, (hipStream_t)stream);
-  return small_status("ps_lstm_gates_cell_f32");
+  return launch_status("ps_lstm_gates_cell_f32");
 }
 
 // ---- the cells of a streaming anti-diagonal as one launch each (N = 1 per cell, shapes shared) -------------------------
@@ -795,7 +786,7 @@ static int fused_cells_launch(const char* who, int epi, const FusedCells& fc, in
     PS_FUSED(4)
   }
 #undef PS_FUSED
-  return small_status(who);
+  return launch_status(who);
 }
 
 extern "C" int ps_film_conv_cells_f32(const ps_film_cell* cells, int ncells, int C, int T, int ldt, void* stream) {
@@ -869,7 +860,7 @@ extern "C" int ps_proj_layernorm_cells_f32(const ps_projln_cell* cells, int ncel
     hipLaunchKernelGGL((proj_layernorm_cells_kernel<8>), grid, dim3(256), 0, s, pc);
   else
     hipLaunchKernelGGL((proj_layernorm_cells_kernel<16>), grid, dim3(256), 0, s, pc);
-  return small_status("ps_proj_layernorm_cells_f32");
+  return launch_status("ps_proj_layernorm_cells_f32");
 }
 
 extern "C" int ps_proj_layernorm_amax_parts(int T) { return T > 0 ? 4 * ((T + 127) / 128) : 0; }
@@ -932,7 +923,7 @@ extern "C" int ps_proj_layernorm_amax_f32(const float* x, const float* wt, const
       else
         hipLaunchKernelGGL((proj_layernorm_rows_kernel<8>), grid, dim3(256), lds, (hipStream_t)stream, a);
     }
-    return small_status("ps_proj_layernorm_f32");
+    return launch_status("ps_proj_layernorm_f32");
   }
   if (y_amax) {
     set_error("ps_proj_layernorm_amax_f32: the maxima are an output of the row kernel only (T >= 128, no second norm / copy, "
@@ -949,5 +940,5 @@ extern "C" int ps_proj_layernorm_amax_f32(const float* x, const float* wt, const
     else
       hipLaunchKernelGGL((proj_layernorm_kernel<16>), dim3((T + 15) / 16, N), dim3(256), 0, (hipStream_t)stream, a);
   }
-  return small_status("ps_proj_layernorm_f32");
+  return launch_status("ps_proj_layernorm_f32");
 }

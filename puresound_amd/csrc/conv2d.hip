@@ -550,12 +550,7 @@ extern "C" int ps_conv2d_f16x2_f32(const float* x1, int C1, const float* x2, int
     else
       hipLaunchKernelGGL((conv2d_f16x2_kernel<4>), grid, dim3(256), lds, (hipStream_t)stream, fa);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_conv2d_f16x2_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_conv2d_f16x2_f32");
 }
 
 extern "C" int ps_conv2d_stats_parts(int M, int Fout, int ld) {
@@ -648,10 +643,5 @@ static int conv2d_launch(const float* x1, int C1, const float* x2, int C2, const
         hipLaunchKernelGGL((conv2d_lds_kernel<4>), grid, dim3(256), lds, (hipStream_t)stream, a);
     }
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_conv2d_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_conv2d_f32");
 }

@@ -204,10 +204,5 @@ extern "C" int ps_dprnn_block_step_f32(const float* x, float* y, const int* coun
   LaunchTimer timer("dprnn_block_step", (hipStream_t)stream);
   hipLaunchKernelGGL(dprnn_block_step_kernel, dim3((B + DP_TB - 1) / DP_TB), dim3(DP_THREADS), dprnn_lds_bytes(C, H),
                      (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status(who);
 }

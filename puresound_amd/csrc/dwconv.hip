@@ -526,10 +526,5 @@ static int dwconv_any(const void* x_any, int x_bf16, const float* w, const float
     else
       hipLaunchKernelGGL((dwconv_kernel<0, false>), grid, dim3(256), 0, st, a);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_dwconv_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_dwconv_f32");
 }

@@ -548,15 +548,6 @@ __global__ __launch_bounds__(256) void embed_bias_kernel(const float* __restrict
   }
 }
 
-static int check_launch(const char* who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
 }  // namespace ps
 
 using namespace ps;
@@ -574,7 +565,7 @@ extern "C" int ps_pad_rows_f32(const float* src, float* dst, int64_t rows, int T
     hipLaunchKernelGGL(pad_rows_kernel, dim3((ldt + 255) / 256, (unsigned)nr), dim3(256), 0, (hipStream_t)stream,
                        src + r0 * T, dst + r0 * ldt, nr, T, ldt);
   }
-  return check_launch("ps_pad_rows_f32");
+  return launch_status("ps_pad_rows_f32");
 }
 
 extern "C" int ps_unpad_rows_f32(const float* src, float* dst, int64_t rows, int T, int ldt, void* stream) {
@@ -589,7 +580,7 @@ extern "C" int ps_unpad_rows_f32(const float* src, float* dst, int64_t rows, int
     hipLaunchKernelGGL(unpad_rows_kernel, dim3((T + 255) / 256, (unsigned)nr), dim3(256), 0, (hipStream_t)stream,
                        src + r0 * ldt, dst + r0 * T, nr, T, ldt);
   }
-  return check_launch("ps_unpad_rows_f32");
+  return launch_status("ps_unpad_rows_f32");
 }
 
 extern "C" int ps_free_encode_f32(const float* wav, const float* w, float* feats, int N, int L, int C, int win,
@@ -613,7 +604,7 @@ extern "C" int ps_free_encode_f32(const float* wav, const float* w, float* feats
   if (win == 32 && hop == 16 && C % 32 == 0 && T >= 64 && !dbg(PS_DBG_ENCDEC_VALU)) {
     dim3 g((T + 32 * EM_TILES - 1) / (32 * EM_TILES), (C + 127) / 128, N);
     hipLaunchKernelGGL(free_encode_mfma_kernel, g, dim3(256), 0, s, wav, w, feats, L, C, T, ldt, relu);
-    return check_launch("ps_free_encode_f32");
+    return launch_status("ps_free_encode_f32");
   }
   if (win == 32)
     hipLaunchKernelGGL(free_encode_kernel<32>, grid, dim3(256), 0, s, wav, w, feats, L, C, win, hop, T, ldt, relu,
@@ -624,7 +615,7 @@ extern "C" int ps_free_encode_f32(const float* wav, const float* w, float* feats
   else
     hipLaunchKernelGGL(free_encode_kernel<0>, grid, dim3(256), 0, s, wav, w, feats, L, C, win, hop, T, ldt, relu,
                        cchunk);
-  return check_launch("ps_free_encode_f32");
+  return launch_status("ps_free_encode_f32");
 }
 
 extern "C" int ps_free_decode_f32(const float* feats, const float* mask, int mask_act, const float* w, float* out,
@@ -655,7 +646,7 @@ extern "C" int ps_free_decode_f32(const float* feats, const float* mask, int mas
     hipLaunchKernelGGL(free_decode_generic_kernel, dim3((Lout + 255) / 256, N), dim3(256), 0, s, feats, mask,
                        mask_act, w, out, C, T, ldt, win, hop, out_mode);
   }
-  return check_launch("ps_free_decode_f32");
+  return launch_status("ps_free_decode_f32");
 }
 
 extern "C" size_t ps_free_decode_workspace_bytes(int N, int T, int win, int hop) {
@@ -688,7 +679,7 @@ extern "C" int ps_free_decode_ws_f32(const float* feats, const float* mask, int 
   const long long fix = (long long)N * (ntiles - 1) * 16;
   hipLaunchKernelGGL(free_decode_fixup_kernel<false>, dim3((unsigned)((fix + 255) / 256)), dim3(256), 0, s, out,
                      (const float*)workspace, T, ntiles, N, out_mode, ps::DecodeScore{});
-  return check_launch("ps_free_decode_ws_f32");
+  return launch_status("ps_free_decode_ws_f32");
 }
 
 extern "C" int ps_free_decode_moments_parts(int N, int C, int T, int ldt, int win, int hop) {
@@ -728,7 +719,7 @@ extern "C" int ps_free_decode_moments_f32(const float* feats, const float* mask,
                      out, (float*)workspace, C, T, ldt, ntiles, out_mode, sc);
   hipLaunchKernelGGL(free_decode_fixup_kernel<true>, dim3(((ntiles - 1) * 16 + 255) / 256, N), dim3(256), 0, s, out,
                      (const float*)workspace, T, ntiles, N, out_mode, sc);
-  return check_launch("ps_free_decode_moments_f32");
+  return launch_status("ps_free_decode_moments_f32");
 }
 
 extern "C" int ps_overlap_average_f32(const float* tail, int ld_tail, const float* cur, float* out, int B, int win,
@@ -740,7 +731,7 @@ extern "C" int ps_overlap_average_f32(const float* tail, int ld_tail, const floa
   LaunchTimer timer("overlap_average", (hipStream_t)stream);
   hipLaunchKernelGGL(overlap_average_kernel, dim3((win + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, tail,
                      ld_tail, cur, out, win, overlap);
-  return check_launch("ps_overlap_average_f32");
+  return launch_status("ps_overlap_average_f32");
 }
 
 extern "C" int ps_stream_windows_f32(const float* queue, const float* chunk, float* wins, int B, int hops, int win,
@@ -753,7 +744,7 @@ extern "C" int ps_stream_windows_f32(const float* queue, const float* chunk, flo
   LaunchTimer timer("stream_windows", (hipStream_t)stream);
   hipLaunchKernelGGL(stream_windows_kernel, dim3((hops * B * win + 255) / 256), dim3(256), 0, (hipStream_t)stream, queue,
                      chunk, wins, B, hops, win, hop);
-  return check_launch("ps_stream_windows_f32");
+  return launch_status("ps_stream_windows_f32");
 }
 
 extern "C" int ps_stream_overlap_f32(const float* frames, const float* wins, float* tail, float* blocks, float* queue,
@@ -765,7 +756,7 @@ extern "C" int ps_stream_overlap_f32(const float* frames, const float* wins, flo
   LaunchTimer timer("stream_overlap", (hipStream_t)stream);
   hipLaunchKernelGGL(stream_overlap_kernel, dim3((B * win + 255) / 256), dim3(256), 0, (hipStream_t)stream, frames, wins,
                      tail, blocks, queue, B, hops, win, hop);
-  return check_launch("ps_stream_overlap_f32");
+  return launch_status("ps_stream_overlap_f32");
 }
 
 extern "C" int ps_embed_bias_f32(const float* dvec, const float* w_embed, float* bias_n, int N, int E, int M,
@@ -777,5 +768,5 @@ extern "C" int ps_embed_bias_f32(const float* dvec, const float* w_embed, float*
   LaunchTimer timer("embed_bias", (hipStream_t)stream);
   hipLaunchKernelGGL(embed_bias_kernel, dim3((M + 3) / 4, N), dim3(256), 0, (hipStream_t)stream, dvec, w_embed,
                      bias_n, E, M, normalize);
-  return check_launch("ps_embed_bias_f32");
+  return launch_status("ps_embed_bias_f32");
 }

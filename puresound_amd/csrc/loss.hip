@@ -54,10 +54,5 @@ extern "C" int ps_wave_moments_f64(const float* a, const float* b, double* parti
     hipLaunchKernelGGL(wave_moments_kernel, dim3(chunks, N), dim3(256), 0, (hipStream_t)stream, a, b, partials, L, lda,
                        ldb, chunks);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_wave_moments_f64: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_wave_moments_f64");
 }

@@ -186,12 +186,7 @@ extern "C" int ps_attn_weights_f32(const float* logits, const float* lengths, fl
     LaunchTimer timer("attn_weights", (hipStream_t)stream);
     hipLaunchKernelGGL(attn_weights_kernel, dim3(C, N), dim3(256), 0, (hipStream_t)stream, logits, lengths, out, C, T, ldt);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_attn_weights_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_attn_weights_f32");
 }
 
 extern "C" int ps_attn_stats_pool_len_f32(const float* logits, const float* x, const float* lengths, float* out, int N,
@@ -211,12 +206,7 @@ extern "C" int ps_attn_stats_pool_len_f32(const float* logits, const float* x, c
       hipLaunchKernelGGL(attn_stats_pool_kernel, dim3(C, N), dim3(256), 0, (hipStream_t)stream, logits, x, lengths, out,
                          C, T, ldt, eps);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_attn_stats_pool_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_attn_stats_pool_f32");
 }
 
 extern "C" int ps_attn_stats_pool_f32(const float* logits, const float* x, float* out, int N, int C, int T, int ldt,

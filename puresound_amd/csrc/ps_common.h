@@ -14,6 +14,10 @@ constexpr int kWave = 64;
 constexpr int kTileT = 128;  // padded-row granule: ldt % kTileT == 0
 
 void set_error(const char* fmt, ...);
+// After enqueueing: 0, or the HIP error code, with "<who>: ..." and the HIP error string as the last error.
+int launch_status(const char* who);
+// The prologue rules the conv1x1 entries share (pro may be NULL): 0 or PS_E_INVALID.
+int check_prologue(const char* who, const ps_prologue* pro);
 extern void* g_debug_buffer;  // ps_debug_buffer(): where diagnostic stamps go (NULL in production)
 extern int g_debug_flags;     // ps_debug_flags(): PS_DBG_* kernel switches (tests)
 extern int g_debug_grid_cap;  // ps_debug_grid_cap(): cap of the persistent GEMM grids, 0 = none (tests, experiments)

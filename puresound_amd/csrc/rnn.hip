@@ -997,15 +997,6 @@ __global__ __launch_bounds__(256) void film_apply_kernel(const float* __restrict
   *reinterpret_cast<f32x4*>(y + xo) = sv * xv + bv;
 }
 
-static int launch_status(const char* who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
 // ---- the 4-sequence recurrence with the product W_hh h in two fp16 terms (ps_lstm_f16x2_f32, inter-segment pass) --------
 // The step of lstm_m4_kernel is a dependent chain: 64 v_mfma_f32_4x4x1_f32 (512 cycles of issue), the cell, one LDS
 // exchange.  v_mfma_f32_4x4x4_f16 takes four k per issue: with W_hh 2^e = hi + lo once per workgroup and h 2^10 = hi +
@@ -1222,12 +1213,7 @@ extern "C" int ps_lstm_fmajor_h256_f16x2_f32(const ps_lstm_args* args, int ldm, 
     else
       hipLaunchKernelGGL((lstm_fm_h256_kernel<192, 1>), grid, dim3(384), 0, (hipStream_t)stream, k);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_lstm_fmajor_h256_f16x2_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_lstm_fmajor_h256_f16x2_f32");
 }
 
 // the cooperative kernel: the streamed kernel's shapes, few enough sequence groups that every slice of every group gets a CU
@@ -1293,7 +1279,6 @@ extern "C" int ps_lstm_fmajor_coop_f16x2_f32(const ps_lstm_args* args, int ldm, 
   // (a kernel, not hipMemsetAsync: inside a replayed graph a memset node does not have to go through the L2 the counters'
   //  atomics work in -- the first graph replays of this launch computed with the previous replay's counts)
   hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, k.sync, (int)((need - hx) / sizeof(unsigned)));
-  hipError_t e;
   {
     LaunchTimer timer("lstm", (hipStream_t)stream);
     // clusters (direction, group) in rounds of 8, one per XCD; H / 32 slices each
@@ -1320,12 +1305,7 @@ extern "C" int ps_lstm_fmajor_coop_f16x2_f32(const ps_lstm_args* args, int ldm, 
     }
 #undef PS_COOP
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_lstm_fmajor_coop_f16x2_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_lstm_fmajor_coop_f16x2_f32");
 }
 
 extern "C" int ps_lstm_fmajor_ok(const ps_lstm_args* args, int ldm) { return args && lstm_fmajor_fits(*args, ldm) ? 1 : 0; }
@@ -1355,12 +1335,7 @@ extern "C" int ps_lstm_fmajor_f16x2_f32(const ps_lstm_args* args, int ldm, void*
     else
       hipLaunchKernelGGL((lstm_fm_f16x2_kernel<false>), grid, dim3(512), 0, (hipStream_t)stream, k);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_lstm_fmajor_f16x2_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_lstm_fmajor_f16x2_f32");
 }
 
 extern "C" int ps_rnn_f32(const ps_lstm_args* args, int kind, const float* bhn, void* stream) {

@@ -139,15 +139,6 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
   out[(size_t)n * Lout + g] = acc;
 }
 
-static int launched(const char* who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
 }  // namespace ps
 
 using namespace ps;
@@ -162,7 +153,7 @@ extern "C" int ps_frame_f32(const float* wav, float* frames, int N, int L, int w
   LaunchTimer timer("frame", (hipStream_t)stream);
   hipLaunchKernelGGL(frame_kernel, dim3((ldt / 4 + 255) / 256, win, N), dim3(256), 0, (hipStream_t)stream, wav,
                      frames, L, win, hop, T, ldt);
-  return launched("ps_frame_f32");
+  return launch_status("ps_frame_f32");
 }
 
 extern "C" int ps_complex_mask_f32(const float* feats, const float* mask, float* out, int N, int half, int ldt,
@@ -175,7 +166,7 @@ extern "C" int ps_complex_mask_f32(const float* feats, const float* mask, float*
   LaunchTimer timer("complex_mask", (hipStream_t)stream);
   hipLaunchKernelGGL(complex_mask_kernel, dim3((ldt / 4 + 255) / 256, half, N), dim3(256), 0, (hipStream_t)stream,
                      feats, mask, out, half, ldt, mask_act);
-  return launched("ps_complex_mask_f32");
+  return launch_status("ps_complex_mask_f32");
 }
 
 extern "C" int ps_polar_mask_f32(const float* feats, const float* mask, float* out, int N, int half, int ldt,
@@ -187,7 +178,7 @@ extern "C" int ps_polar_mask_f32(const float* feats, const float* mask, float* o
   LaunchTimer timer("polar_mask", (hipStream_t)stream);
   hipLaunchKernelGGL(polar_mask_kernel, dim3((ldt / 4 + 255) / 256, half, N), dim3(256), 0, (hipStream_t)stream, feats,
                      mask, out, half, ldt);
-  return launched("ps_polar_mask_f32");
+  return launch_status("ps_polar_mask_f32");
 }
 
 extern "C" int ps_magphase_f32(const float* spec, float* out, int N, int half, int ldt, int take_sqrt, void* stream) {
@@ -198,7 +189,7 @@ extern "C" int ps_magphase_f32(const float* spec, float* out, int N, int half, i
   LaunchTimer timer("magphase", (hipStream_t)stream);
   hipLaunchKernelGGL(magphase_kernel, dim3((ldt / 4 + 255) / 256, half, N), dim3(256), 0, (hipStream_t)stream, spec, out,
                      half, ldt, take_sqrt);
-  return launched("ps_magphase_f32");
+  return launch_status("ps_magphase_f32");
 }
 
 extern "C" int ps_real_mask_f32(const float* feats, const float* mask, float* out, int64_t rows, int ldt, int mask_act,
@@ -215,7 +206,7 @@ extern "C" int ps_real_mask_f32(const float* feats, const float* mask, float* ou
     hipLaunchKernelGGL(real_mask_kernel, dim3((ldt / 4 + 255) / 256, (unsigned)nr), dim3(256), 0, (hipStream_t)stream,
                        feats + r0 * ldt, mask + r0 * ldt, out + r0 * ldt, ldt, mask_act);
   }
-  return launched("ps_real_mask_f32");
+  return launch_status("ps_real_mask_f32");
 }
 
 extern "C" int ps_istft_ola_f32(const float* frames, const float* window, float* out, int N, int n_fft, int hop,
@@ -229,7 +220,7 @@ extern "C" int ps_istft_ola_f32(const float* frames, const float* window, float*
   LaunchTimer timer("istft_ola", (hipStream_t)stream);
   hipLaunchKernelGGL(istft_ola_kernel, dim3((Lout + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, frames,
                      window, out, n_fft, hop, T, ldt, out_mode);
-  return launched("ps_istft_ola_f32");
+  return launch_status("ps_istft_ola_f32");
 }
 
 // Magnitude lobe (lobe/trivial.py:21-59) on the [re rows; im rows] channel layout: y[h] = sqrt(re[h+d]^2 + im[h+d]^2 + 1e-8)
@@ -265,12 +256,7 @@ extern "C" int ps_magnitude_f32(const float* x, float* y, int N, int half, int d
     hipLaunchKernelGGL(magnitude_kernel, dim3((T + 255) / 256, half - drop_first, N), dim3(256), 0, (hipStream_t)stream, x,
                        y, half, drop_first, T, ldt, log1p);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_magnitude_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_magnitude_f32");
 }
 
 // SpecAugment's masked fill (lobe/trivial.py:306-335 of the reference: torchaudio.functional.mask_along_axis picks the
@@ -304,10 +290,5 @@ extern "C" int ps_fill_span_f32(const float* x, float* y, int N, int rows, int l
   LaunchTimer timer("fill_span", (hipStream_t)stream);
   hipLaunchKernelGGL(ps::fill_span_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y,
                      rows, ld, axis, lo, hi, value, total);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ps_fill_span_f32: launch failed: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return launch_status("ps_fill_span_f32");
 }

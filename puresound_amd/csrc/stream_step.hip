@@ -207,15 +207,6 @@ __global__ __launch_bounds__(256) void stream_commit_kernel(CommitTable tab, int
   *reinterpret_cast<f32x4*>(q.ring + (size_t)(q.slots - 1) * q.count + i) = *reinterpret_cast<const f32x4*>(q.src + i);
 }
 
-static int step_launched(const char* who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
 }  // namespace ps
 
 using namespace ps;
@@ -252,7 +243,7 @@ extern "C" int ps_conv2d_step_f32(const float* x1, const float* ring1, int C1, i
   else
     hipLaunchKernelGGL((conv2d_step_kernel<64, 64>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, (hipStream_t)stream,
                        a);
-  return step_launched("ps_conv2d_step_f32");
+  return launch_status("ps_conv2d_step_f32");
 }
 
 extern "C" int ps_istft_step_f32(const float* frames, int ldf, const float* window, float* tail, float* out, int ld_out,
@@ -268,7 +259,7 @@ extern "C" int ps_istft_step_f32(const float* frames, int ldf, const float* wind
   LaunchTimer timer("istft_step", (hipStream_t)stream);
   hipLaunchKernelGGL(istft_step_kernel, dim3(B), dim3(256), (size_t)n_fft * sizeof(float), (hipStream_t)stream, frames, ldf,
                      window, tail, out, ld_out, counter, n_fft, hop, out_mode, flush);
-  return step_launched("ps_istft_step_f32");
+  return launch_status("ps_istft_step_f32");
 }
 
 static int stream_commit(const char* who, const ps_ring_pair* pairs_host, int n_pairs, int* counter, int advance,
@@ -298,7 +289,7 @@ static int stream_commit(const char* who, const ps_ring_pair* pairs_host, int n_
   LaunchTimer timer("stream_commit", (hipStream_t)stream);
   hipLaunchKernelGGL(stream_commit_kernel, dim3((unsigned)blocks, n_pairs), dim3(256), 0, (hipStream_t)stream, tab, counter,
                      advance);
-  return step_launched(who);
+  return launch_status(who);
 }
 
 extern "C" int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs, int* counter, void* stream) {

@@ -207,15 +207,6 @@ __global__ __launch_bounds__(256) void free_decode_flush_kernel(const float* __r
   out[(size_t)b * ld_out + s] = dec_constrain(tail[i], out_mode);
 }
 
-static int tcn_step_launched(const char* who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
 }  // namespace ps
 
 using namespace ps;
@@ -256,7 +247,7 @@ static int dwconv_step_launch(const char* who, bool slots, const float* x, float
     hipLaunchKernelGGL(dwconv_step_slots_kernel, dim3((N + 255) / 256, H), dim3(256), 0, (hipStream_t)stream, a, span);
   else
     hipLaunchKernelGGL(dwconv_step_kernel, dim3((N + 255) / 256, H), dim3(256), 0, (hipStream_t)stream, a);
-  return tcn_step_launched(who);
+  return launch_status(who);
 }
 
 extern "C" int ps_dwconv_step_f32(const float* x, float* ring, int R, const int* counter, const float* w, const float* b,
@@ -299,7 +290,7 @@ static int free_decode_step_launch(const char* who, const float* feats, const fl
     if (keep == 0) return 0;  // win = hop: nothing overlaps the last frame
     hipLaunchKernelGGL(free_decode_flush_kernel, dim3((B * keep + 255) / 256), dim3(256), 0, (hipStream_t)stream, tail, out,
                        ld_out, B, keep, out_mode);
-    return tcn_step_launched(who);
+    return launch_status(who);
   }
   const dim3 grid((B + DEC_SB - 1) / DEC_SB, k, (win + DEC_JW - 1) / DEC_JW);
   if (span)
@@ -310,7 +301,7 @@ static int free_decode_step_launch(const char* who, const float* feats, const fl
                        C, win);
   hipLaunchKernelGGL(free_decode_ola_kernel, dim3((B * hop + 255) / 256), dim3(256), 0, (hipStream_t)stream, ws, tail, out,
                      ld_out, B, k, win, hop, out_mode);
-  return tcn_step_launched(who);
+  return launch_status(who);
 }
 
 extern "C" int ps_free_decode_step_f32(const float* feats, const float* mask, int mask_act, int ld, const float* w,

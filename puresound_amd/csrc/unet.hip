@@ -162,15 +162,6 @@ __global__ __launch_bounds__(256) void add_rows_kernel(const float* __restrict__
   reinterpret_cast<f32x4*>(y)[i] = reinterpret_cast<const f32x4*>(a)[i] + reinterpret_cast<const f32x4*>(b)[i];
 }
 
-static int unet_status(const char* who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
 }  // namespace ps
 
 using namespace ps;
@@ -198,7 +189,7 @@ extern "C" int ps_unfold2d_f32(const float* x1, int C1, const float* x2, int C2,
       hipLaunchKernelGGL(unfold2d_kernel, dim3((ld + 255) / 256, Fout, (unsigned)(nb * K)), dim3(256), 0, (hipStream_t)stream, a);
     }
   }
-  return unet_status("ps_unfold2d_f32");
+  return launch_status("ps_unfold2d_f32");
 }
 
 extern "C" int ps_activation_f32(float* x, int kind, const float* slope, int64_t rows, int T, int ld, void* stream) {
@@ -214,7 +205,7 @@ extern "C" int ps_activation_f32(float* x, int kind, const float* slope, int64_t
     hipLaunchKernelGGL(activation_kernel, dim3((ld / 4 + 255) / 256, (unsigned)nr), dim3(256), 0, (hipStream_t)stream,
                        x + r0 * ld, slope, kind, T, ld);
   }
-  return unet_status("ps_activation_f32");
+  return launch_status("ps_activation_f32");
 }
 
 extern "C" int ps_add_f32(const float* a, const float* b, float* y, int64_t count, void* stream) {
@@ -227,7 +218,7 @@ extern "C" int ps_add_f32(const float* a, const float* b, float* y, int64_t coun
   const size_t n4 = (size_t)count / 4;
   LaunchTimer timer("add", (hipStream_t)stream);
   hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, y, n4);
-  return unet_status("ps_add_f32");
+  return launch_status("ps_add_f32");
 }
 
 extern "C" int ps_row_stats_parts(void) { return ps::kRowStatsParts; }
@@ -242,7 +233,7 @@ extern "C" int ps_row_stats_f64(const float* x, double* stats, int N, int rows, 
     LaunchTimer timer("row_stats", (hipStream_t)stream);
     hipLaunchKernelGGL(row_stats_kernel, dim3(kRowStatsParts, N), dim3(256), 0, (hipStream_t)stream, x, stats, rows, T, ld);
   }
-  return unet_status("ps_row_stats_f64");
+  return launch_status("ps_row_stats_f64");
 }
 
 extern "C" int ps_norm_activation_f32(float* x, const ps_prologue* pro, double corr_sum, double corr_sq,
@@ -262,5 +253,5 @@ extern "C" int ps_norm_activation_f32(float* x, const ps_prologue* pro, double c
     hipLaunchKernelGGL(norm_activation_kernel, dim3((ld / 4 + 255) / 256, rows_per_utt, N), dim3(256), 0,
                        (hipStream_t)stream, a);
   }
-  return unet_status("ps_norm_activation_f32");
+  return launch_status("ps_norm_activation_f32");
 }

@@ -5,6 +5,7 @@ memory and streams only; all arithmetic happens in the HIP kernels.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Sequence
 
@@ -227,21 +228,40 @@ def conv1x1(x: torch.Tensor, t: int, wt: torch.Tensor, m: int, pro: Optional[Pro
     return y, stats
 
 
+def _split_planes(rest: torch.Tensor, dtype: torch.dtype, planes: int) -> list:
+    """fp32 `rest` -> `planes` tensors of `dtype`: each holds the rounding of what the planes before it left over."""
+    out = []
+    for _ in range(planes):
+        h = rest.to(dtype)
+        out.append(h)
+        rest = rest - h.float()
+    return out
+
+
+def _f16_weight_exponent(w: torch.Tensor, who: str) -> int:
+    """w_exp that puts max |2^w_exp w| into [2^13, 2^14) (0 for an all-zero weight); reads the maximum back to the host."""
+    wmax = float(w.detach().abs().max())
+    if not (wmax < float("inf")):
+        raise ValueError(f"{who}: the weight holds inf / NaN")
+    return 13 - math.frexp(wmax)[1] + 1 if wmax > 0 else 0  # frexp: wmax = f * 2^e, f in [0.5, 1)
+
+
+def _plane_image(w: torch.Tensor, dtype: torch.dtype, planes: int) -> torch.Tensor:
+    """[M, K] fp32 -> the conv1x1 plane image [ceil(M/256)][ceil(K/16)][planes][256][16], zero padded"""
+    m, k = w.shape
+    mt, ks = (m + 255) // 256, (k + 15) // 16
+    rest = torch.zeros(mt * 256, ks * 16, dtype=torch.float32, device=w.device)
+    rest[:m, :k] = w
+    img = torch.stack(_split_planes(rest, dtype, planes), 0).reshape(planes, mt, 256, ks, 16)
+    return img.permute(1, 3, 0, 2, 4).contiguous()
+
+
 def pack_wt_bf16(w: torch.Tensor, planes: int) -> torch.Tensor:
     """[M,K] (or [M,K,1]) fp32 weight -> bf16 plane image [ceil(M/256)][ceil(K/16)][planes][256][16] for
     ps_conv1x1_bf16_f32: plane p holds bf16 of what the planes before it left over (planes = 1: plain rounding)."""
     if w.dim() == 3:
         w = w[:, :, 0]
-    m, k = w.shape
-    mt, ks = (m + 255) // 256, (k + 15) // 16
-    rest = torch.zeros(mt * 256, ks * 16, dtype=torch.float32, device=w.device)
-    rest[:m, :k] = w.detach().float()
-    out = torch.empty(mt, ks, planes, 256, 16, dtype=torch.bfloat16, device=w.device)
-    for p in range(planes):
-        h = rest.to(torch.bfloat16)
-        out[:, :, p] = h.reshape(mt, 256, ks, 16).permute(0, 2, 1, 3)
-        rest = rest - h.float()
-    return out.contiguous()
+    return _plane_image(w.detach().float(), torch.bfloat16, planes)
 
 
 def pack_wt_f16x2(w: torch.Tensor) -> tuple[torch.Tensor, int]:
@@ -250,21 +270,16 @@ def pack_wt_f16x2(w: torch.Tensor) -> tuple[torch.Tensor, int]:
     (Reads the maximum back to the host: plan-build time only.)"""
     if w.dim() == 3:
         w = w[:, :, 0]
-    m, k = w.shape
-    wmax = float(w.detach().abs().max())
-    if not (wmax < float("inf")):
-        raise ValueError("pack_wt_f16x2: the weight holds inf / NaN")
-    import math
-    w_exp = 13 - math.frexp(wmax)[1] + 1 if wmax > 0 else 0  # frexp: wmax = f * 2^e, f in [0.5, 1)
-    mt, ks = (m + 255) // 256, (k + 15) // 16
-    rest = torch.zeros(mt * 256, ks * 16, dtype=torch.float32, device=w.device)
-    rest[:m, :k] = torch.ldexp(w.detach().float(), torch.tensor(w_exp, device=w.device))
-    out = torch.empty(mt, ks, 2, 256, 16, dtype=torch.float16, device=w.device)
-    for p in range(2):
-        h = rest.to(torch.float16)
-        out[:, :, p] = h.reshape(mt, 256, ks, 16).permute(0, 2, 1, 3)
-        rest = rest - h.float()
-    return out.contiguous(), w_exp
+    w_exp = _f16_weight_exponent(w, "pack_wt_f16x2")
+    return _plane_image(torch.ldexp(w.detach().float(), torch.tensor(w_exp, device=w.device)), torch.float16, 2), w_exp
+
+
+def _f16x2_range(w_exp: int, x_bound: float, x_amax: Optional[torch.Tensor], y_amax: Optional[torch.Tensor],
+                 amax_map: Optional[tuple] = None) -> F16x2Range:
+    rng = F16x2Range(int(w_exp), float(x_bound), ptr(x_amax), x_amax.shape[1] if x_amax is not None else 0, ptr(y_amax))
+    if amax_map is not None:
+        rng.amax_mul, rng.amax_add = float(amax_map[0]), float(amax_map[1])
+    return rng
 
 
 def conv1x1_f16x2(x: torch.Tensor, t: int, wt_planes: torch.Tensor, w_exp: int, m: int,
@@ -291,9 +306,7 @@ def conv1x1_f16x2(x: torch.Tensor, t: int, wt_planes: torch.Tensor, w_exp: int, 
         require_device(x_amax, "conv1x1_f16x2 (x_amax)")
         if x_amax.dim() != 2 or x_amax.shape[0] != n or not x_amax.is_contiguous():
             raise ValueError(f"conv1x1_f16x2: x_amax must be a contiguous [N={n}, parts] tensor, got {tuple(x_amax.shape)}")
-    rng = F16x2Range(int(w_exp), float(x_bound), ptr(x_amax), x_amax.shape[1] if x_amax is not None else 0, ptr(amax))
-    if amax_map is not None:
-        rng.amax_mul, rng.amax_add = float(amax_map[0]), float(amax_map[1])
+    rng = _f16x2_range(w_exp, x_bound, x_amax, amax, amax_map)
     check(lib().ps_conv1x1_f16x2_f32(ptr(x), ptr(wt_planes), C.byref(rng), ptr(y), n, k, m, t, ldt,
                                      C.byref(pro) if pro is not None else None, ptr(bias), ptr(bias_n), ptr(res),
                                      ptr(stats), stream_ptr(x.device)), "ps_conv1x1_f16x2_f32")
@@ -322,7 +335,7 @@ def conv1x1_f16x2_fmajor(x: torch.Tensor, t: int, wt_planes: torch.Tensor, w_exp
     n, k, ldt = x.shape
     ldm = fmajor_ld(m)
     y = torch.empty(n, ldt, ldm, dtype=torch.float32, device=x.device)[..., :m]
-    rng = F16x2Range(int(w_exp), float(x_bound), ptr(x_amax), x_amax.shape[1] if x_amax is not None else 0, None)
+    rng = _f16x2_range(w_exp, x_bound, x_amax, None)
     check(lib().ps_conv1x1_f16x2_fmajor_f32(ptr(x), ptr(wt_planes), C.byref(rng), ptr(y), n, k, m, t, ldt, ldm, ptr(bias),
                                             stream_ptr(x.device)), "ps_conv1x1_f16x2_fmajor_f32")
     return y
@@ -347,7 +360,7 @@ def conv1x1_f16x2_ln(x: torch.Tensor, t: int, wt_planes: torch.Tensor, w_exp: in
     if res is not None and (tuple(res.shape) != (n, c, ldt) or not res.is_contiguous()):
         raise ValueError(f"conv1x1_f16x2_ln: the residual must be a contiguous {(n, c, ldt)} tensor")
     amax = torch.zeros(n, lib().ps_conv1x1_stats_parts(256, t), dtype=torch.float32, device=x.device) if want_amax else None
-    rng = F16x2Range(int(w_exp), float(x_bound), ptr(x_amax), x_amax.shape[1] if x_amax is not None else 0, ptr(amax))
+    rng = _f16x2_range(w_exp, x_bound, x_amax, amax)
     check(lib().ps_conv1x1_f16x2_ln_f32(ptr(x), ptr(wt_planes), C.byref(rng), ptr(y), n, k, c, t, ldt,
                                         C.byref(pro) if pro is not None else None, ptr(bias), ptr(gamma), ptr(beta), float(eps),
                                         ptr(res), int(res_inside), stream_ptr(x.device)), "ps_conv1x1_f16x2_ln_f32")
@@ -444,6 +457,33 @@ def attn_weights(logits: torch.Tensor, t: int, lengths: Optional[torch.Tensor] =
     return out
 
 
+def _lstm_state_args(who: str, a: LstmArgs, n: int, rows: int, q: int, h0, c0, want_state: bool, state_out, device):
+    """Fills a.h0 / c0 / h_last / c_last / ldq of an LSTM launch; returns the final-state pair (h, c) or None.  All state
+    tensors of one launch share the row stride ldq (the kernels read and write every one of them with it)."""
+    ldq = padded_frames(q)
+    for name, t in (("h0", h0), ("c0", c0)):
+        if t is not None and (tuple(t.shape[:2]) != (n, rows) or t.shape[2] < q or not t.is_contiguous()):
+            raise RuntimeError(f"{who}: {name} must be a contiguous state tensor [N, D*H, ldq >= Q]")
+    if h0 is not None:
+        ldq = h0.shape[2]
+    elif c0 is not None:
+        ldq = c0.shape[2]
+    if (h0 is not None and c0 is not None) and h0.shape[2] != c0.shape[2]:
+        raise RuntimeError(f"{who}: h0 and c0 must share ldq")
+    h_last = c_last = None
+    if state_out is not None:
+        h_last, c_last = state_out
+        if h_last.shape[2] != ldq and (h0 is not None or c0 is not None):
+            raise RuntimeError(f"{who}: state_out must share ldq with h0/c0")
+        ldq = h_last.shape[2]
+    elif want_state:
+        h_last = torch.zeros(n, rows, ldq, dtype=torch.float32, device=device)
+        c_last = torch.zeros_like(h_last)
+    a.h0, a.c0, a.h_last, a.c_last = ptr(h0), ptr(c0), ptr(h_last), ptr(c_last)
+    a.ldq = ldq
+    return (h_last, c_last) if h_last is not None else None
+
+
 def lstm(gx: torch.Tensor, whh_t: torch.Tensor, hidden: int, dirs: int, q: int, q_stride: int, steps: int,
          step_stride: int, h0: Optional[torch.Tensor] = None, c0: Optional[torch.Tensor] = None,
          want_state: bool = False, state_shift: int = 0, state_out: Optional[tuple] = None, f16x2: bool = False,
@@ -460,33 +500,14 @@ def lstm(gx: torch.Tensor, whh_t: torch.Tensor, hidden: int, dirs: int, q: int, 
         raise RuntimeError("lstm: out must be a contiguous [N, D*H, ldt] tensor")
     a = LstmArgs()
     a.gx, a.whh_t, a.hout = ptr(gx), ptr(whh_t), ptr(hout)
-    ldq = padded_frames(q)
-    for name, t in (("h0", h0), ("c0", c0)):
-        if t is not None and (tuple(t.shape[:2]) != (n, dirs * hidden) or t.shape[2] < q or not t.is_contiguous()):
-            raise RuntimeError(f"lstm: {name} must be a contiguous state tensor [N, D*H, ldq >= Q]")
-    if h0 is not None:
-        ldq = h0.shape[2]
-    elif c0 is not None:
-        ldq = c0.shape[2]
-    if (h0 is not None and c0 is not None) and h0.shape[2] != c0.shape[2]:
-        raise RuntimeError("lstm: h0 and c0 must share ldq")
-    h_last = c_last = None
-    if state_out is not None:
-        h_last, c_last = state_out
-        if h_last.shape[2] != ldq and (h0 is not None or c0 is not None):
-            raise RuntimeError("lstm: state_out must share ldq with h0/c0")
-        ldq = h_last.shape[2]
-    elif want_state:
-        h_last = torch.zeros(n, dirs * hidden, ldq, dtype=torch.float32, device=gx.device)
-        c_last = torch.zeros_like(h_last)
-    a.h0, a.c0, a.h_last, a.c_last = ptr(h0), ptr(c0), ptr(h_last), ptr(c_last)
+    state = _lstm_state_args("lstm", a, n, dirs * hidden, q, h0, c0, want_state, state_out, gx.device)
     a.N, a.H, a.D, a.Q, a.q_stride, a.steps, a.step_stride = n, hidden, dirs, q, q_stride, steps, step_stride
-    a.ldt, a.ldq, a.state_shift = ldt, ldq, state_shift
+    a.ldt, a.state_shift = ldt, state_shift
     if f16x2:
         check(lib().ps_lstm_f16x2_f32(C.byref(a), stream_ptr(gx.device)), "ps_lstm_f16x2_f32")
     else:
         check(lib().ps_lstm_f32(C.byref(a), stream_ptr(gx.device)), "ps_lstm_f32")
-    return (hout, (h_last, c_last)) if h_last is not None else (hout, None)
+    return hout, state
 
 
 RNN_KINDS = {"RNN": 0, "GRU": 2}
@@ -563,7 +584,6 @@ def lstm_fmajor(gx_fm: torch.Tensor, whh_t: torch.Tensor, hidden: int, dirs: int
 def pack_whh_h256(whh_t: torch.Tensor):
     """weight_hh^T [D, H, 4H], H = 256 or 192 -> (fp16 image [D, H/32, H/32, 2, 4, 2, 64, 8], acc scales [D] as a Python list)
     for lstm_fmajor_h256 (layout: include/puresound_hip.h).  Reads the maxima back to the host: plan-build time only."""
-    import math
     d, hh, g = whh_t.shape
     if hh not in (256, 192) or g != 4 * hh:
         raise ValueError("pack_whh_h256: whh_t must be [D, H, 4H] with H = 256 or 192")
@@ -576,13 +596,7 @@ def pack_whh_h256(whh_t: torch.Tensor):
             raise ValueError("pack_whh_h256: the weight holds inf / NaN")
         ex = max(math.frexp(wmax)[1], -27) if wmax > 0 else 0
         sc = math.ldexp(1.0, 13 - ex)
-        rest = w * sc
-        planes = []
-        for _ in range(2):
-            hp = rest.to(torch.float16)
-            planes.append(hp)
-            rest = rest - hp.float()
-        pl = torch.stack(planes, 0)                                 # [pl, 4H, H]
+        pl = torch.stack(_split_planes(w * sc, torch.float16, 2), 0)  # [pl, 4H, H]
         pl = pl.reshape(2, 4, nw, 2, 16, nw, 4, 8)                  # pl, g, w, rb, row, ks, kg, e
         pl = pl.permute(2, 5, 3, 1, 0, 6, 4, 7)                     # w, ks, rb, g, pl, kg, row, e
         imgs.append(pl.reshape(nw, nw, 2, 4, 2, 64, 8))
@@ -612,24 +626,9 @@ def lstm_fmajor_h256(gx_fm: torch.Tensor, whh_image: torch.Tensor, acc_scale, di
     hout = out if out is not None else torch.empty(n, dirs * hidden, ldt, dtype=torch.float32, device=gx_fm.device)
     a = LstmArgs()
     a.gx, a.whh_t, a.hout = ptr(gx_fm), None, ptr(hout)
-    ldq = padded_frames(q)
-    for name, t in (("h0", h0), ("c0", c0)):
-        if t is not None and (tuple(t.shape[:2]) != (n, dirs * hidden) or t.shape[2] < q or not t.is_contiguous()):
-            raise RuntimeError(f"lstm_fmajor_h256: {name} must be a contiguous state tensor [N, D*H, ldq >= Q]")
-    if h0 is not None:
-        ldq = h0.shape[2]
-    elif c0 is not None:
-        ldq = c0.shape[2]
-    h_last = c_last = None
-    if state_out is not None:
-        h_last, c_last = state_out
-        ldq = h_last.shape[2]
-    elif want_state:
-        h_last = torch.zeros(n, dirs * hidden, ldq, dtype=torch.float32, device=gx_fm.device)
-        c_last = torch.zeros_like(h_last)
-    a.h0, a.c0, a.h_last, a.c_last = ptr(h0), ptr(c0), ptr(h_last), ptr(c_last)
+    state = _lstm_state_args("lstm_fmajor_h256", a, n, dirs * hidden, q, h0, c0, want_state, state_out, gx_fm.device)
     a.N, a.H, a.D, a.Q, a.q_stride, a.steps, a.step_stride = n, hidden, dirs, q, q_stride, steps, step_stride
-    a.ldt, a.ldq, a.state_shift = ldt, ldq, state_shift
+    a.ldt, a.state_shift = ldt, state_shift
     sc = (C.c_float * 2)(float(acc_scale[0]), float(acc_scale[-1]))
     # few sequence groups (a speaker LSTM over all frames, SkiM's Mem-LSTMs): the cooperative kernel -- W_hh resident in the
     # registers of H / 32 CUs per group -- instead of streaming 1 MiB of it through one CU every step
@@ -642,7 +641,7 @@ def lstm_fmajor_h256(gx_fm: torch.Tensor, whh_image: torch.Tensor, acc_scale, di
     else:
         check(lib().ps_lstm_fmajor_h256_f16x2_f32(C.byref(a), ldm, ptr(whh_image), sc, stream_ptr(gx_fm.device)),
               "ps_lstm_fmajor_h256_f16x2_f32")
-    return (hout, (h_last, c_last)) if h_last is not None else (hout, None)
+    return hout, state
 
 
 COOP_LSTM = os.environ.get("PS_COOP_LSTM", "1") != "0"   # 0: always the streamed-weight kernel
@@ -656,21 +655,27 @@ def _coop_slices(dirs: int, groups: int, hidden: int) -> int:
     return hidden // 32 if rounds * (hidden // 32) <= cus else hidden // 64
 
 
+def _coop_layout(dirs: int, groups: int, hidden: int) -> tuple[int, int, int]:
+    """int32 indices into the cooperative LSTM's workspace (lstm_coop.inc: the h exchange, then D * groups barrier
+    counters): (error word, first XCD id, first XCD mask)."""
+    hx = (2 * dirs * groups * 2 * 16 * (hidden + 8) * 2 + 255) // 256 * 256
+    err = hx // 4 + dirs * groups
+    return err, err + 1, err + 1 + dirs * groups * _coop_slices(dirs, groups, hidden)
+
+
 def coop_lstm_error_word(dirs: int, groups: int, hidden: int) -> int:
     """The error word of the last cooperative LSTM launch's workspace (1 = a group barrier gave up waiting); synchronises."""
     ws = _COOP_LAST[0]
     if ws is None:
         return 0
-    hx = (2 * dirs * groups * 2 * 16 * (hidden + 8) * 2 + 255) // 256 * 256
-    return int(ws.view(torch.int32)[hx // 4 + dirs * groups])
+    return int(ws.view(torch.int32)[_coop_layout(dirs, groups, hidden)[0]])
 
 
 def coop_lstm_xcd_ids(dirs: int, groups: int, hidden: int) -> torch.Tensor:
     """[D * groups, slices]: the XCD every slice of the last cooperative launch ran on (the light group barrier needs each
     row constant: tests check it on the target part)."""
     ws = _COOP_LAST[0]
-    hx = (2 * dirs * groups * 2 * 16 * (hidden + 8) * 2 + 255) // 256 * 256
-    first = hx // 4 + dirs * groups + 1
+    first = _coop_layout(dirs, groups, hidden)[1]
     ns = _coop_slices(dirs, groups, hidden)
     return ws.view(torch.int32)[first:first + dirs * groups * ns].reshape(dirs * groups, ns).cpu()
 
@@ -678,8 +683,7 @@ def coop_lstm_xcd_ids(dirs: int, groups: int, hidden: int) -> torch.Tensor:
 def coop_lstm_xcd_masks(dirs: int, groups: int, hidden: int) -> torch.Tensor:
     """[D * groups]: per cluster the OR of 1 << XCD over its slices (one bit = the cluster took the light barrier)."""
     ws = _COOP_LAST[0]
-    hx = (2 * dirs * groups * 2 * 16 * (hidden + 8) * 2 + 255) // 256 * 256
-    first = hx // 4 + dirs * groups + 1 + dirs * groups * _coop_slices(dirs, groups, hidden)
+    first = _coop_layout(dirs, groups, hidden)[2]
     return ws.view(torch.int32)[first:first + dirs * groups].cpu()
 
 
@@ -1126,22 +1130,14 @@ def conv2d(x1: torch.Tensor, x2: Optional[torch.Tensor], wt: torch.Tensor, bias:
 def pack_conv2d_f16x2(w2: torch.Tensor):
     """[M, K] fp32 (BatchNorm folded) -> (image of 2^w_exp W for ps_conv2d_f16x2_f32, w_exp); layout: include/puresound_hip.h.
     Reads the maximum back to the host: plan-build time only."""
-    import math
     m, k = w2.shape
-    wmax = float(w2.detach().abs().max())
-    if not (wmax < float("inf")):
-        raise ValueError("pack_conv2d_f16x2: the weight holds inf / NaN")
-    w_exp = 13 - math.frexp(wmax)[1] + 1 if wmax > 0 else 0
+    w_exp = _f16_weight_exponent(w2, "pack_conv2d_f16x2")
     mt = 32 if m <= 32 else 64 if m <= 64 else 128
     tiles, nch = (m + mt - 1) // mt, (k + 31) // 32
     rest = torch.zeros(tiles * mt, nch * 32, dtype=torch.float32, device=w2.device)
     rest[:m, :k] = torch.ldexp(w2.detach().float(), torch.tensor(w_exp, device=w2.device))
-    planes = []
-    for _ in range(2):
-        hp = rest.to(torch.float16)
-        planes.append(hp)
-        rest = rest - hp.float()
-    img = torch.stack(planes, 0).reshape(2, tiles, mt // 16, 16, nch, 4, 8)      # pl, tile, rb, row, chunk, kg, e
+    img = torch.stack(_split_planes(rest, torch.float16, 2), 0)
+    img = img.reshape(2, tiles, mt // 16, 16, nch, 4, 8)                         # pl, tile, rb, row, chunk, kg, e
     img = img.permute(1, 4, 0, 2, 5, 3, 6).contiguous()                          # tile, chunk, pl, rb, kg, row, e
     return img, w_exp
 

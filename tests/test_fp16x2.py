@@ -139,6 +139,123 @@ def test_fp16x2_gemm_is_as_close_to_fp64_as_the_fp32_kernel(dev, n, k, m, t, mod
             np.testing.assert_allclose(s[:, 1], (got * got).sum((1, 2)).numpy(), rtol=1e-5)
 
 
+def _small_case(mode, m, dev, rows16=False):
+    """N = 2, K = 64 (four K-steps: the persistent kernels' minimum; a multiple of 32 for the register-B kernel), T = 129
+    (two frame tiles, the second one partial); mode: "plain" / "stats" / "res", "affine" in front for a scale / shift +
+    PReLU prologue.  -> operands, the range to hand over, the fp64 result and sum_k |w| |f(x)| per output"""
+    from puresound_amd import _abi, hip as H
+    n, k, t = 2, 64, 129
+    x = _rand((n, k, t), 141) + 0.2
+    res = _rand((n, m, t), 146) if mode.endswith("res") else None
+    if rows16:
+        x, res = x.bfloat16().float(), None if res is None else res.bfloat16().float()
+    w, b = _rand((m, k), 142, -0.2, 0.2), _rand((m,), 143)
+    gamma, beta, slope = _rand((k,), 144, 0.5, 1.5), _rand((k,), 145, -0.2, 0.2), torch.tensor([0.2])
+    a, pro, keep = x.double(), None, None
+    bound = float(x.abs().max())
+    if mode.startswith("affine"):
+        a = O.prelu(gamma.double().reshape(1, -1, 1) * a + beta.double().reshape(1, -1, 1), slope.double())
+        keep = (gamma.to(dev), beta.to(dev), slope.to(dev))
+        pro = H.make_prologue(_abi.PS_NORM_AFFINE, True, None, 0.0, 0.0, keep[0], keep[1], keep[2])
+        bound = float(gamma.abs().max()) * bound + float(beta.abs().max())
+    ref = torch.matmul(w.double(), a) + b.double().reshape(1, -1, 1)
+    if res is not None:
+        ref = ref + res.double()
+    return x, w, b, pro, keep, res, bound, ref, torch.matmul(w.double().abs(), a.abs()), t
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["res", "affine"])
+@pytest.mark.parametrize("kernel", ["narrow", "wide", "il", "rb"])
+def test_fp16x2_variants_the_large_shapes_leave_out(dev, kernel, mode):
+    """The shapes above reach (prologue, statistics, residual) = (0,0,0), (0,1,0), (1,1,0), (1,0,1) on the one-tile,
+    the interleaved and the register-B kernel.  Here the other two -- a residual without a prologue (two m-tiles) and a
+    prologue alone -- on each of them and both tiles of the first, forced at a small size: SIMPLE (256 x 32 tiles while
+    2 * tiles <= CUs; with WIDE_TILE 256 x 128), ANY_SIZE (register-B: K % 32 == 0, M % 256 == 0), ANY_SIZE | NO_RB
+    (interleaved).  Same bounds as there."""
+    from puresound_amd import _abi, hip as H
+    flags = {"narrow": _abi.PS_DBG_GEMM_SIMPLE, "wide": _abi.PS_DBG_GEMM_SIMPLE | _abi.PS_DBG_GEMM_WIDE_TILE,
+             "il": _abi.PS_DBG_GEMM_ANY_SIZE | _abi.PS_DBG_GEMM_NO_RB, "rb": _abi.PS_DBG_GEMM_ANY_SIZE}[kernel]
+    m = 512 if mode == "res" else 256
+    x, w, b, pro, keep, res, bound, ref, _, t = _small_case(mode, m, dev)
+    xd = H.pad_rows(x.to(dev))
+    resd = None if res is None else H.pad_rows(res.to(dev))
+    y32, _ = H.conv1x1(xd, t, H.pack_wt(w.to(dev)), m, pro, b.to(dev), None, resd)
+    rms = float(ref.pow(2).mean().sqrt())
+    e32 = float((y32[..., :t].cpu().double() - ref).pow(2).mean().sqrt()) / rms
+    wf, we = H.pack_wt_f16x2(w.to(dev))
+    with _abi.debug(flags):
+        y, _, am = H.conv1x1_f16x2(xd, t, wf, we, m, pro, b.to(dev), None, resd, want_amax=True, x_bound=bound)
+        torch.cuda.synchronize()
+    got = y[..., :t].cpu().double()
+    assert torch.isfinite(got).all()
+    err = float((got - ref).pow(2).mean().sqrt()) / rms
+    assert err < 1.5 * e32 + 1e-8, (err, e32)
+    assert rel_max(got.numpy(), ref.numpy()) < 4e-6
+    assert torch.equal(am.amax(1).cpu(), y[..., :t].abs().amax((1, 2)).cpu())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("res_inside", [False, True])
+def test_gemm_with_layernorm_epilogue_behind_a_prologue(dev, res_inside):
+    """ps_conv1x1_f16x2_ln_f32 with a scale / shift + PReLU prologue (the register-B kernel's TR = 1 LayerNorm variant;
+    test_gemm_with_layernorm_epilogue runs the TR = 0 one) against fp64, at that test's bound."""
+    import torch.nn.functional as F
+    from puresound_amd import _abi, hip as H
+    c = 128
+    x, w, b, pro, keep, res, bound, p, _, t = _small_case("affine_res", c, dev)
+    g, be = _rand((c,), 147, 0.5, 1.5), _rand((c,), 148, -0.3, 0.3)
+    p = p - res.double()   # W f(x) + b
+    ln = lambda v: F.layer_norm(v.transpose(1, 2), (c,), g.double(), be.double(), 1e-5).transpose(1, 2)
+    ref = ln(p + res.double()) if res_inside else res.double() + ln(p)
+    w256 = torch.zeros(256, w.shape[1])
+    w256[:c] = w
+    wf, we = H.pack_wt_f16x2(w256.to(dev))
+    with _abi.debug(_abi.PS_DBG_GEMM_ANY_SIZE):
+        assert H.conv1x1_f16x2_ln_ok(2, w.shape[1], c, t)
+        y = H.conv1x1_f16x2_ln(H.pad_rows(x.to(dev)), t, wf, we, c, b.to(dev), g.to(dev), be.to(dev), 1e-5,
+                               H.pad_rows(res.to(dev)), x_bound=bound, pro=pro, res_inside=res_inside)
+        torch.cuda.synchronize()
+    assert rel_max(y[..., :t].cpu().numpy(), ref.numpy()) < 5e-6
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["plain", "stats", "res", "affine", "affine_stats", "affine_res"])
+def test_f16_rows_gemm_in_every_variant(dev, mode):
+    """ps_conv1x1_f16_rows (bf16 rows, one fp16 term per operand, the register-B kernel) called directly in all six
+    (prologue, statistics, residual) variants; the masker reaches three of them (ps_conv_tasnet_bf16_rows).  Against the
+    fp64 product of the same bf16 rows at the bounds of test_bf16_gemm_with_bf16_residual_and_output_rows (one bf16
+    rounding of the result).  The statistics are those of the fp32 values before that rounding: every output is within
+    E = 1.01 * 2^-10 sum_k |w| |f(x)| of the fp64 one (2^-11 per fp16 operand; 1 % for their cross term and the fp32
+    accumulation), so the sums are within sum E and sum (2 |y| E + E^2)."""
+    import ctypes as C
+    from puresound_amd import _abi, hip as H
+    m = 512 if mode.endswith("res") else 256
+    x, w, b, pro, keep, res, bound, ref, absprod, t = _small_case(mode, m, dev, rows16=True)
+    n, k = x.shape[:2]
+    xd = H.pad_rows(x.to(dev)).bfloat16()
+    rd = None if res is None else H.pad_rows(res.to(dev)).bfloat16()
+    wf, we = H.pack_wt_f16x2(w.to(dev))
+    y = torch.empty(n, m, xd.shape[-1], dtype=torch.bfloat16, device=dev)
+    bd = b.to(dev)
+    st = torch.zeros(n, _abi.lib().ps_conv1x1_stats_parts(m, t), 2, dtype=torch.float64, device=dev) if mode.endswith("stats") else None
+    rng = _abi.F16x2Range(int(we), bound, None, 0, None)
+    with _abi.debug(_abi.PS_DBG_GEMM_ANY_SIZE):
+        assert _abi.lib().ps_conv1x1_f16_rows_ok(n, k, m, t)
+        _abi.check(_abi.lib().ps_conv1x1_f16_rows(_abi.ptr(xd), _abi.ptr(wf), C.byref(rng), _abi.ptr(y), n, k, m, t, xd.shape[-1],
+                                                  C.byref(pro) if pro is not None else None, _abi.ptr(bd), None, _abi.ptr(rd),
+                                                  _abi.ptr(st), _abi.stream_ptr(dev)), "ps_conv1x1_f16_rows")
+        torch.cuda.synchronize()
+    got = y[..., :t].float().cpu().double()
+    assert torch.isfinite(got).all()
+    assert float(np.linalg.norm(got.numpy() - ref.numpy()) / np.linalg.norm(ref.numpy())) < 6e-3
+    assert rel_max(got.numpy(), ref.numpy()) < 2e-2
+    if st is not None:
+        s, e = st.sum(1).cpu().numpy(), absprod * (1.01 * 2.0 ** -10)
+        assert (np.abs(s[:, 0] - ref.sum((1, 2)).numpy()) <= e.sum((1, 2)).numpy()).all()
+        assert (np.abs(s[:, 1] - (ref ** 2).sum((1, 2)).numpy()) <= (2 * ref.abs() * e + e * e).sum((1, 2)).numpy()).all()
+
+
 @pytest.mark.gpu
 def test_fp16x2_default_range_and_its_loud_failure(dev):
     """Without a range from the caller the kernel scales raw rows by 2^-4: fine around unit scale, coarser for tiny

@@ -979,6 +979,86 @@ def test_conv1x1_bf16_planes(H, dev, planes, tol, n, k, m, t, mode):
             np.testing.assert_allclose(s[:, 1], (got ** 2).sum((1, 2)).numpy(), rtol=1e-6)
 
 
+def _small_gemm_case(mode, m, dev, H, round_x=False):
+    """N = 2, K = 64 (four K-steps: the persistent kernels' minimum), T = 129 (two frame tiles, the second one partial):
+    operands, prologue, residual and the fp64 result of one (prologue, statistics, residual) variant"""
+    n, k, t = 2, 64, 129
+    x = _rand((n, k, t), 131) + 0.2
+    if round_x:
+        x = x.bfloat16().float()
+    w, b = _rand((m, k), 132, -0.2, 0.2), _rand((m,), 133)
+    gamma, beta, slope = _rand((k,), 134, 0.5, 1.5), _rand((k,), 135, -0.2, 0.2), torch.tensor([0.2])
+    a, pro, keep = x.double(), None, None
+    g64, b64 = gamma.double().reshape(1, -1, 1), beta.double().reshape(1, -1, 1)
+    if mode.startswith("affine"):
+        a = O.prelu(g64 * a + b64, slope.double())
+        keep = (gamma.to(dev), beta.to(dev), slope.to(dev))
+        pro = H.make_prologue(_abi.PS_NORM_AFFINE, True, None, 0.0, 0.0, keep[0], keep[1], keep[2])
+    elif mode == "relu_tanh":
+        a = torch.tanh(g64 * torch.relu(a) + b64)
+        keep = (gamma.to(dev), beta.to(dev))
+        pro = H.make_prologue(_abi.PS_NORM_AFFINE, False, None, 0.0, 0.0, keep[0], keep[1], None, pre_relu=True, post_tanh=True)
+    ref = torch.matmul(w.double(), a) + b.double().reshape(1, -1, 1)
+    res = _rand((n, m, t), 136) if mode.endswith("res") else None
+    if round_x and res is not None:
+        res = res.bfloat16().float()
+    if res is not None:
+        ref = ref + res.double()
+    return x, w, b, pro, keep, res, ref, t
+
+
+# kernel -> the switches that force it at this size (256 CUs; conv1x1_bf16.hip, bf16_launch): ANY_SIZE lets the two
+# supertiles of this launch onto a persistent kernel -- the interleaved one, or the two-barrier ping-pong kernel with
+# TWO_BARRIER or a ReLU / tanh prologue; SIMPLE gives 256 x 32 tiles (2 * tiles <= CUs), with WIDE_TILE 256 x 128
+_SMALL_GEMM_KERNELS = {"il": _abi.PS_DBG_GEMM_ANY_SIZE, "pp": _abi.PS_DBG_GEMM_ANY_SIZE | _abi.PS_DBG_GEMM_TWO_BARRIER,
+                       "pp_by_prologue": _abi.PS_DBG_GEMM_ANY_SIZE, "narrow": _abi.PS_DBG_GEMM_SIMPLE,
+                       "wide": _abi.PS_DBG_GEMM_SIMPLE | _abi.PS_DBG_GEMM_WIDE_TILE}
+
+
+@pytest.mark.parametrize("planes,tol", [(3, 2e-6), (1, 2e-2)])
+@pytest.mark.parametrize("kernel,mode", [("il", "plain"), ("il", "res"), ("il", "affine"), ("pp", "plain"), ("pp", "res"),
+                                         ("pp", "affine"), ("pp_by_prologue", "relu_tanh"), ("narrow", "res"),
+                                         ("wide", "res")])
+def test_conv1x1_bf16_variants_the_large_shapes_leave_out(H, dev, planes, tol, kernel, mode):
+    """test_conv1x1_bf16_planes reaches (prologue, statistics, residual) = (0,1,0), (1,1,0), (1,0,1) on every kernel and
+    (0,0,0), (1,0,0) on the one-tile kernel only.  Here: the remaining instantiations -- a residual without a prologue
+    everywhere (two m-tiles), no extra at all and a prologue alone on the two persistent kernels, and the two-barrier
+    kernel as the default dispatch reaches it (ReLU / tanh prologue) -- against the fp64 product, at that test's bounds."""
+    x, w, b, pro, keep, res, ref, t = _small_gemm_case(mode, 512 if mode == "res" else 256, dev, H)
+    with _abi.debug(_SMALL_GEMM_KERNELS[kernel]):
+        y, _ = H.conv1x1_bf16(H.pad_rows(x.to(dev)), t, H.pack_wt_bf16(w.to(dev), planes), w.shape[0], pro, b.to(dev), None,
+                              None if res is None else H.pad_rows(res.to(dev)))
+        torch.cuda.synchronize()
+    # (the tanh on load: the bound of test_conv1x1_relu_affine_tanh_prologue where it is the wider one)
+    assert rel_max(y[..., :t].cpu().double().numpy(), ref.numpy()) < (max(tol, 2e-5) if mode == "relu_tanh" else tol)
+
+
+@pytest.mark.parametrize("xb,yb", [(False, True), (True, False), (True, True)])
+@pytest.mark.parametrize("mode", ["plain", "stats", "res", "affine", "affine_stats", "affine_res"])
+def test_conv1x1_bf16_rows_every_variant_on_every_kernel(H, dev, xb, yb, mode):
+    """bf16 x / y rows (planes = 1) in all six (prologue, statistics, residual) variants on the interleaved kernel and both
+    tiles of the one-tile kernel (the large shapes of test_round2_gpu / test_round4_gpu reach five of the eighteen): bit
+    for bit the fp32-row kernel's result on the bf16-rounded data, rounded once, as there; and the fp64 product at the
+    planes = 1 bound of test_conv1x1_bf16_planes."""
+    m = 512 if mode.endswith("res") else 256
+    x, w, b, pro, keep, res, ref, t = _small_gemm_case(mode, m, dev, H, round_x=True)
+    want = mode.endswith("stats")
+    wb, xp = H.pack_wt_bf16(w.to(dev), 1), H.pad_rows(x.to(dev))
+    rp = None if res is None else H.pad_rows(res.to(dev))
+    for kernel in ("il", "narrow", "wide"):
+        with _abi.debug(_SMALL_GEMM_KERNELS[kernel]):
+            y_ref, st_ref = H.conv1x1_bf16(xp, t, wb, m, pro, b.to(dev), None, rp, want_stats=want)
+            y, st = H.conv1x1_bf16(xp.bfloat16() if xb else xp, t, wb, m, pro, b.to(dev), None,
+                                   rp.bfloat16() if rp is not None and yb else rp, want_stats=want,
+                                   out_dtype=torch.bfloat16 if yb else torch.float32)
+            torch.cuda.synchronize()
+        assert y.dtype == (torch.bfloat16 if yb else torch.float32)
+        assert torch.equal(y[..., :t], y_ref[..., :t].bfloat16() if yb else y_ref[..., :t]), kernel
+        assert rel_max(y[..., :t].float().cpu().double().numpy(), ref.numpy()) < 2e-2, kernel
+        if want:
+            np.testing.assert_allclose(st.sum(1).cpu().numpy(), st_ref.sum(1).cpu().numpy(), rtol=1e-9)
+
+
 @pytest.mark.parametrize("precision,tol", [("bf16x3", TOL), ("bf16", 3e-2)])
 def test_conv_tasnet_on_the_bf16_matrix_pipe(PA, dev, golden_dir, precision, tol):
     """Config 2 with its GEMMs on the bf16 pipe: the 3-way split stays inside the fp32 tolerance against the
