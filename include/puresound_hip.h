@@ -643,7 +643,18 @@ int ps_free_decode_step_slots_f32(const float* feats, const float* mask, int mas
  * Exact fp32 products and fp32 sums, every sum of a column in one fixed order: a stream's values are bit-identical for every
  * B, whatever the other columns hold and however the frames are split into launches.  A workgroup owns 16 columns and needs
  * (2 C + 6 H) * 64 bytes of LDS: ps_dprnn_block_step_ok(C, H, K) = 1 where that fits 64 KiB (C, H, K >= 1), else
- * PS_E_UNSUPPORTED, which ps_dprnn_block_step_f32 then returns too, writing nothing.  x != y; k * B <= ld; B <= ldb. */
+ * PS_E_UNSUPPORTED, which ps_dprnn_block_step_f32 then returns too, writing nothing.  x != y; k * B <= ld; B <= ldb.
+ *
+ * Slots: ps_dprnn_block_step_slots_f32 is ps_dprnn_block_step_f32 with span [B][2] (device int, 8-byte aligned; the
+ * (birth, death) of ps_dwconv_step_slots_f32) after `counter`.  Stream b is LIVE at frame g = *counter + f iff
+ * span[b][0] <= g < span[b][1], and a live stream has a phase of its own: its position is p_b = (g - span[b][0]) % K, so
+ * its intra (h, c) is read as 0 iff p_b == 0 and its inter state is slot p_b of its column of the banks, both stored back as
+ * above.  A stream that is not live at g: its x column is not read but taken as 0 (it may hold inf / NaN), no state element
+ * of its column is stored (neither the intra (h, c) nor any bank slot), and its y column is written with finite values
+ * nobody should read (ps_free_decode_step_slots_f32 adds nothing for that frame).  A workgroup whose 16 streams are all
+ * dead at a frame skips the frame's arithmetic and stores y = 0.  Sums in the same orders: with span = (0, INT32_MAX) for
+ * every stream, y and all states are bit-identical to ps_dprnn_block_step_f32.  The same checks and return codes; span NULL
+ * or misaligned: PS_E_INVALID.  *counter + k <= INT32_MAX. */
 typedef struct ps_dprnn_pass {
   const float* wt;
   const float* bias;
@@ -658,6 +669,9 @@ int ps_dprnn_block_step_ok(int C, int H, int K);
 int ps_dprnn_block_step_f32(const float* x, float* y, const int* counter, const ps_dprnn_pass* intra,
                             const ps_dprnn_pass* inter, float* h_intra, float* c_intra, float* h_bank, float* c_bank, int C,
                             int H, int K, int B, int k, int ld, int ldb, void* stream);
+int ps_dprnn_block_step_slots_f32(const float* x, float* y, const int* counter, const int* span, const ps_dprnn_pass* intra,
+                                  const ps_dprnn_pass* inter, float* h_intra, float* c_intra, float* h_bank, float* c_bank,
+                                  int C, int H, int K, int B, int k, int ld, int ldb, void* stream);
 
 /* One cell update per (unit, frame) from COMPLETE gate pre-activations gates [N][D*4H][ld_gates] (W_ih x + W_hh h + both
  * biases: the streaming step puts [x; h] on the K axis of one ps_conv1x1_f32):  c' = sig(f) c + sig(i) tanh(g) in

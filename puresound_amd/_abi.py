@@ -193,6 +193,8 @@ SIGNATURES = {
     "ps_dprnn_block_step_ok": (C.c_int, [C.c_int] * 3),
     "ps_dprnn_block_step_f32": (C.c_int, [_vp, _vp, _vp, C.POINTER(DprnnPass), C.POINTER(DprnnPass)] + [_vp] * 4
                                 + [C.c_int] * 7 + [_vp]),
+    "ps_dprnn_block_step_slots_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(DprnnPass), C.POINTER(DprnnPass)] + [_vp] * 4
+                                      + [C.c_int] * 7 + [_vp]),
     "ps_unfold2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp] + [C.c_int] * 14 + [_vp]),
     "ps_conv2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 16 + [_vp, _vp]),
     "ps_conv2d_stats_parts": (C.c_int, [C.c_int] * 3),

@@ -18,6 +18,16 @@
 // has one fixed order (k ascending with fmaf from the bias; the LN partials by lane, then xor 8, 4, 2, 1), so a stream's bits
 // do not depend on B, on its neighbours or on how the hops are split into chunks.  A state element is loaded and stored by
 // the same thread, so a bank slot revisited within a chunk (k > K) is read back by the thread that wrote it.
+//
+// Slots (ps_dprnn_block_step_slots_f32): the same with a per-stream span [B][2] of absolute frame indices, as tcn_step.hip.
+// Column b is live at frame g iff span[b][0] <= g < span[b][1], and a live column has a phase of its own: its position is
+// p_b = (g - span[b][0]) % K, so the intra reset (p_b == 0) and the bank slot (p_b) differ between the columns of a tile.
+// Every loop that touches state, x or y strides by 256 over an index whose column is i % 16, so a thread only ever serves
+// column tid % 16: it reads that column's span once per launch and keeps liveness and p_b in registers.  A dead column reads
+// x and its states as 0 (it may hold inf / NaN) and stores no state; its y is written, finite.  The 16 columns sit in lanes
+// 16 q .. 16 q + 15 of every wave, so a wave's vote "any column live" is the same in every wave of the workgroup: a frame at
+// which the whole tile is dead skips both passes (no barrier is passed by some waves only) and stores y = 0.  The gate is a
+// compile-time variant (template <bool SLOTS>): the kernel the entry point without a span launches is the code it was.
 #include "ps_common.h"
 
 namespace ps {
@@ -47,13 +57,17 @@ __device__ __forceinline__ float dp_sum16(float v) {
 
 // One LSTM + projection + LayerNorm + residual pass on the tile: xh rows [0, C) hold the input and receive the output,
 // rows [C, C + H) and cs are scratch for (h, c); hs / cs_g point at the state rows [H][ldb] of column b0.
+// SLOTS: hs / cs_g, from_zero and alive are this thread's column's (column tid % 16): its bank slot, its segment start,
+// whether its frame is live (a column past `cols` is never alive).
+template <bool SLOTS>
 __device__ __forceinline__ void dprnn_pass(const ps_dprnn_pass& w, float* xh, float* cs, float* gt, float* pr, float* hs,
-                                           float* cs_g, bool from_zero, int C, int H, int ldb, int cols) {
+                                           float* cs_g, bool from_zero, bool alive, int C, int H, int ldb, int cols) {
   const int tid = threadIdx.x;
   const int G = 4 * H, KK = C + H;
   for (int i = tid; i < H * DP_TB; i += DP_THREADS) {
     const int u = i / DP_TB, j = i % DP_TB;
-    const bool live = j < cols && !from_zero;
+    bool live = j < cols && !from_zero;
+    if constexpr (SLOTS) live = alive && !from_zero;
     xh[(C + u) * DP_TB + j] = live ? hs[(size_t)u * ldb + j] : 0.f;
     cs[i] = live ? cs_g[(size_t)u * ldb + j] : 0.f;
   }
@@ -91,7 +105,9 @@ __device__ __forceinline__ void dprnn_pass(const ps_dprnn_pass& w, float* xh, fl
     const float cn = gf * cs[i] + gi * gg;
     const float hn = go * tanhf(cn);
     xh[(C + u) * DP_TB + j] = hn;
-    if (j < cols) {
+    bool store = j < cols;
+    if constexpr (SLOTS) store = alive;
+    if (store) {
       hs[(size_t)u * ldb + j] = hn;
       cs_g[(size_t)u * ldb + j] = cn;
     }
@@ -140,7 +156,8 @@ __device__ __forceinline__ void dprnn_pass(const ps_dprnn_pass& w, float* xh, fl
   __syncthreads();
 }
 
-__global__ __launch_bounds__(DP_THREADS) void dprnn_block_step_kernel(DprnnStepArgs a) {
+template <bool SLOTS>
+__device__ __forceinline__ void dprnn_block_step_body(const DprnnStepArgs& a, const int* __restrict__ span) {
   extern __shared__ __align__(16) float dp_lds[];
   const int C = a.C, H = a.H;
   float* xh = dp_lds;                        // [C + H][16]
@@ -152,21 +169,60 @@ __global__ __launch_bounds__(DP_THREADS) void dprnn_block_step_kernel(DprnnStepA
   const int cols = a.B - b0 < DP_TB ? a.B - b0 : DP_TB;
   const int t0 = *a.counter;
   const size_t slab = (size_t)H * a.ldb;     // one bank slot
-  for (int f = 0; f < a.k; ++f) {
-    const int p = (t0 + f) % a.K;
-    const size_t c0 = (size_t)f * a.B + b0;
-    for (int i = tid; i < C * DP_TB; i += DP_THREADS) {
-      const int m = i / DP_TB, j = i % DP_TB;
-      xh[i] = j < cols ? a.x[(size_t)m * a.ld + c0 + j] : 0.f;
+  int lo = 0, hi = 0;                        // this thread's column's span (empty past the last stream)
+  if constexpr (SLOTS) {
+    if (tid % DP_TB < cols) {
+      const int2 sp = reinterpret_cast<const int2*>(span)[b0 + tid % DP_TB];
+      lo = sp.x;
+      hi = sp.y;
     }
-    // (the pass's first barrier also covers these stores)
-    dprnn_pass(a.intra, xh, cs, gt, pr, a.h_intra + b0, a.c_intra + b0, p == 0, C, H, a.ldb, cols);
-    dprnn_pass(a.inter, xh, cs, gt, pr, a.h_bank + p * slab + b0, a.c_bank + p * slab + b0, false, C, H, a.ldb, cols);
+  }
+  for (int f = 0; f < a.k; ++f) {
+    const size_t c0 = (size_t)f * a.B + b0;
+    if constexpr (SLOTS) {
+      const int g = t0 + f;
+      const bool alive = g >= lo && g < hi;
+      if (!__any(alive)) {                   // the whole tile is dead at this frame (the same vote in every wave)
+        for (int i = tid; i < C * DP_TB; i += DP_THREADS) {
+          const int m = i / DP_TB, j = i % DP_TB;
+          if (j < cols) a.y[(size_t)m * a.ld + c0 + j] = 0.f;
+        }
+        continue;
+      }
+      const int p = alive ? (int)(((unsigned)g - (unsigned)lo) % (unsigned)a.K) : 0;   // (g - lo < 2^32: exact)
+      for (int i = tid; i < C * DP_TB; i += DP_THREADS) {
+        const int m = i / DP_TB, j = i % DP_TB;
+        xh[i] = alive ? a.x[(size_t)m * a.ld + c0 + j] : 0.f;
+      }
+      dprnn_pass<true>(a.intra, xh, cs, gt, pr, a.h_intra + b0, a.c_intra + b0, p == 0, alive, C, H, a.ldb, cols);
+      dprnn_pass<true>(a.inter, xh, cs, gt, pr, a.h_bank + p * slab + b0, a.c_bank + p * slab + b0, false, alive, C, H,
+                       a.ldb, cols);
+    } else {
+      const int p = (t0 + f) % a.K;
+      for (int i = tid; i < C * DP_TB; i += DP_THREADS) {
+        const int m = i / DP_TB, j = i % DP_TB;
+        xh[i] = j < cols ? a.x[(size_t)m * a.ld + c0 + j] : 0.f;
+      }
+      // (the pass's first barrier also covers these stores)
+      dprnn_pass<false>(a.intra, xh, cs, gt, pr, a.h_intra + b0, a.c_intra + b0, p == 0, true, C, H, a.ldb, cols);
+      dprnn_pass<false>(a.inter, xh, cs, gt, pr, a.h_bank + p * slab + b0, a.c_bank + p * slab + b0, false, true, C, H,
+                        a.ldb, cols);
+    }
     for (int i = tid; i < C * DP_TB; i += DP_THREADS) {   // (the thread that stores xh[i] for the next frame reads it here)
       const int m = i / DP_TB, j = i % DP_TB;
       if (j < cols) a.y[(size_t)m * a.ld + c0 + j] = xh[i];
     }
   }
+}
+
+__global__ __launch_bounds__(DP_THREADS) void dprnn_block_step_kernel(DprnnStepArgs a) {
+  dprnn_block_step_body<false>(a, nullptr);
+}
+
+// (at most 4 waves per SIMD, the sibling's occupancy -- LDS allows no more at the preset's shape: with a fifth in sight the
+// scheduler keeps the slot variant under 96 VGPRs by waiting for each weight load of the projection loop in turn)
+__global__ __launch_bounds__(DP_THREADS) __attribute__((amdgpu_waves_per_eu(1, 4))) void dprnn_block_step_slots_kernel(DprnnStepArgs a, const int* __restrict__ span) {
+  dprnn_block_step_body<true>(a, span);
 }
 
 static size_t dprnn_lds_bytes(int C, int H) { return (size_t)(2 * C + 6 * H) * DP_TB * sizeof(float); }
@@ -180,14 +236,20 @@ extern "C" int ps_dprnn_block_step_ok(int C, int H, int K) {
   return dprnn_lds_bytes(C < 4096 ? C : 4096, H < 4096 ? H : 4096) <= 64 * 1024 ? 1 : PS_E_UNSUPPORTED;
 }
 
-extern "C" int ps_dprnn_block_step_f32(const float* x, float* y, const int* counter, const ps_dprnn_pass* intra,
-                                       const ps_dprnn_pass* inter, float* h_intra, float* c_intra, float* h_bank,
-                                       float* c_bank, int C, int H, int K, int B, int k, int ld, int ldb, void* stream) {
-  const char* who = "ps_dprnn_block_step_f32";
+// ps_dprnn_block_step_f32 (span = NULL, slots = false) and ps_dprnn_block_step_slots_f32 share the checks and differ in the
+// kernel.
+static int dprnn_block_step_launch(const char* who, bool slots, const float* x, float* y, const int* counter, const int* span,
+                                   const ps_dprnn_pass* intra, const ps_dprnn_pass* inter, float* h_intra, float* c_intra,
+                                   float* h_bank, float* c_bank, int C, int H, int K, int B, int k, int ld, int ldb,
+                                   void* stream) {
   if (!x || !y || x == y || !counter || !intra || !inter || !h_intra || !c_intra || !h_bank || !c_bank || C <= 0 || H <= 0 ||
       K <= 0 || B <= 0 || k <= 0 || ldb < B || (long long)k * B > ld || (long long)C * ld > (1LL << 31) ||
       (long long)K * H * ldb > (1LL << 40)) {
     set_error("%s: bad argument (C=%d H=%d K=%d B=%d k=%d ld=%d ldb=%d)", who, C, H, K, B, k, ld, ldb);
+    return PS_E_INVALID;
+  }
+  if (slots && (!span || ((uintptr_t)span & 7))) {
+    set_error("%s: span must be an 8-byte aligned device array [B][2] of int", who);
     return PS_E_INVALID;
   }
   for (const ps_dprnn_pass* w : {intra, inter})
@@ -201,8 +263,27 @@ extern "C" int ps_dprnn_block_step_f32(const float* x, float* y, const int* coun
     return PS_E_UNSUPPORTED;
   }
   DprnnStepArgs a{x, y, counter, *intra, *inter, h_intra, c_intra, h_bank, c_bank, C, H, K, B, k, ld, ldb};
-  LaunchTimer timer("dprnn_block_step", (hipStream_t)stream);
-  hipLaunchKernelGGL(dprnn_block_step_kernel, dim3((B + DP_TB - 1) / DP_TB), dim3(DP_THREADS), dprnn_lds_bytes(C, H),
-                     (hipStream_t)stream, a);
+  LaunchTimer timer(slots ? "dprnn_block_step_slots" : "dprnn_block_step", (hipStream_t)stream);
+  if (slots)
+    hipLaunchKernelGGL(dprnn_block_step_slots_kernel, dim3((B + DP_TB - 1) / DP_TB), dim3(DP_THREADS), dprnn_lds_bytes(C, H),
+                       (hipStream_t)stream, a, span);
+  else
+    hipLaunchKernelGGL(dprnn_block_step_kernel, dim3((B + DP_TB - 1) / DP_TB), dim3(DP_THREADS), dprnn_lds_bytes(C, H),
+                       (hipStream_t)stream, a);
   return launch_status(who);
+}
+
+extern "C" int ps_dprnn_block_step_f32(const float* x, float* y, const int* counter, const ps_dprnn_pass* intra,
+                                       const ps_dprnn_pass* inter, float* h_intra, float* c_intra, float* h_bank,
+                                       float* c_bank, int C, int H, int K, int B, int k, int ld, int ldb, void* stream) {
+  return dprnn_block_step_launch("ps_dprnn_block_step_f32", false, x, y, counter, nullptr, intra, inter, h_intra, c_intra,
+                                 h_bank, c_bank, C, H, K, B, k, ld, ldb, stream);
+}
+
+extern "C" int ps_dprnn_block_step_slots_f32(const float* x, float* y, const int* counter, const int* span,
+                                             const ps_dprnn_pass* intra, const ps_dprnn_pass* inter, float* h_intra,
+                                             float* c_intra, float* h_bank, float* c_bank, int C, int H, int K, int B, int k,
+                                             int ld, int ldb, void* stream) {
+  return dprnn_block_step_launch("ps_dprnn_block_step_slots_f32", true, x, y, counter, span, intra, inter, h_intra, c_intra,
+                                 h_bank, c_bank, C, H, K, B, k, ld, ldb, stream);
 }

@@ -1071,11 +1071,13 @@ def pack_dprnn_pass(lstm, proj, norm, device: torch.device) -> dict:
 
 def dprnn_block_step(x: torch.Tensor, counter: torch.Tensor, intra: dict, inter: dict, h_intra: torch.Tensor,
                      c_intra: torch.Tensor, h_bank: torch.Tensor, c_bank: torch.Tensor, streams: int, frames: int,
-                     out: torch.Tensor) -> torch.Tensor:
+                     out: torch.Tensor, span: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One causal DPRNN block on `frames` new frames of `streams` streams (ps_dprnn_block_step_f32): x [1, C, ld] (column
     f * streams + b) -> out [1, C, ld] (columns past frames * streams are not written); intra / inter from pack_dprnn_pass;
     intra state h_intra / c_intra [H, ldb] and the inter banks h_bank / c_bank [K, H, ldb] (slot p = position p of a segment),
-    updated in place; frame index of column 0 = counter[0], position = index % K."""
+    updated in place; frame index of column 0 = counter[0], position = index % K.  span int32 [streams, 2]:
+    ps_dprnn_block_step_slots_f32, stream b computes frame g iff span[b, 0] <= g < span[b, 1], at position
+    (g - span[b, 0]) % K; a frame that is not live reads x as 0 and stores no state."""
     require_device(x, "dprnn_block_step")
     _, c, ld = x.shape
     k_seg, hidden, ldb = h_bank.shape
@@ -1091,6 +1093,13 @@ def dprnn_block_step(x: torch.Tensor, counter: torch.Tensor, intra: dict, inter:
             or tuple(intra["pt"].shape) != (hidden, c) or tuple(inter["pt"].shape) != (hidden, c) \
             or intra["wt"].device != x.device or inter["wt"].device != x.device:
         raise RuntimeError(f"dprnn_block_step: passes packed for C = {c}, H = {hidden} on {x.device} expected")
+    if span is not None:
+        _check_span(span, streams, x, "dprnn_block_step")
+        check(lib().ps_dprnn_block_step_slots_f32(ptr(x), ptr(out), ptr(counter), ptr(span), C.byref(intra["struct"]),
+                                                  C.byref(inter["struct"]), ptr(h_intra), ptr(c_intra), ptr(h_bank),
+                                                  ptr(c_bank), c, hidden, k_seg, streams, frames, ld, ldb,
+                                                  stream_ptr(x.device)), "ps_dprnn_block_step_slots_f32")
+        return out
     check(lib().ps_dprnn_block_step_f32(ptr(x), ptr(out), ptr(counter), C.byref(intra["struct"]), C.byref(inter["struct"]),
                                         ptr(h_intra), ptr(c_intra), ptr(h_bank), ptr(c_bank), c, hidden, k_seg, streams,
                                         frames, ld, ldb, stream_ptr(x.device)), "ps_dprnn_block_step_f32")

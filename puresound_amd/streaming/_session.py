@@ -7,15 +7,30 @@ run advances), `_body(hops)` (the launches of `hops` hops: self._io[hops] = (inp
 windows [hops, B*window])), `_flush_into(out)`; it may set `max_hops` and override `_around_body`.  Its init_streams checks
 its own arguments, calls `_begin` and allocates what `_state` returns; `_queue` [B, window], `_tail` [B, window - hop] and
 `_counter` (int32 [1], the device frame counter) are allocated here.
+
+Slots (tcn.py, dprnn.py): a session of fixed capacity whose columns begin and end streams of their own while it runs.  The
+model-independent half lives here: the device span [B, 2] of (birth, death) frame indices and the host record per slot, the
+slot checks, open / end / close, the hops each slot was fed, the frame limit, and the rules that a slot session has no
+priming phase and no flush().  A streamer with slots calls `_begin` and then `_make_slots` in its init_slots, passes
+`self._span` to its kernels in `_body`, and provides `_enrolment_rule()` (whether open() takes an enrolment, and the words
+that say why), `_open_slot(slot, enroll)` (reset or seed the slot's model state) and a `_flush_into(out, tail)` that takes
+the tail rows to flush.
 """
 import contextlib
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 
 from .. import hip
 from ..graphs import capture
 from ..nnet._plans import tensor_signature
+
+
+#: frames per launch at most of the streamers that split a chunk into pieces (tcn.py, dprnn.py)
+K_MAX = 16
+INT32_MAX = 2 ** 31 - 1
+#: a session stops here: the device frame counter is an int32, and a launch reads up to K_MAX frames past it
+FRAME_LIMIT = INT32_MAX - K_MAX
 
 
 def check_on_device(model, name: str) -> None:
@@ -40,6 +55,7 @@ class HopSession:
         self._mask_act = model.mask_constraint.lower()
         self._out_mode = model.output_constraint.lower()
         self.streams = None
+        self._span = self._slots = None
         self._drop_weights()
 
     @property
@@ -87,6 +103,13 @@ class HopSession:
         self._tail = torch.zeros(self.streams, self.window - self.hop_length, dtype=torch.float32, device=device)
         self._counter = torch.zeros(1, dtype=torch.int32, device=device)
         self._io: Dict[int, tuple] = {}
+        self._span = None        # int32 [B, 2] (birth, death) in a slot session
+        self._slots = None       # per slot None (idle) or dict(hops fed, total hops once end() was called)
+
+    def _make_slots(self) -> None:
+        """After _begin: the session is a slot session, every slot idle."""
+        self._span = torch.zeros(self.streams, 2, dtype=torch.int32, device=self.device)
+        self._slots = [None] * self.streams
 
     def _around_body(self):
         """A context manager that encloses every run of _body (eager, warm-up and capture; never a replay)."""
@@ -109,7 +132,8 @@ class HopSession:
         self._hops += 1
 
     def _priming(self) -> bool:
-        return self._hops < self.prime_hops
+        """(a slot session has no priming phase: a slot's first prime_hops frames are dead by its span)"""
+        return self._slots is None and self._hops < self.prime_hops
 
     def _run_piece(self, piece: torch.Tensor) -> torch.Tensor:
         """Whole hops of one launch -> their output samples [B, hops*hop] (graph replay or eager)."""
@@ -129,10 +153,19 @@ class HopSession:
         return out.clone()
 
     def _run(self, chunk: torch.Tensor) -> torch.Tensor:
-        """Whole hops past the priming -> their output samples, in pieces of at most max_hops hops."""
+        """Whole hops past the priming -> their output samples, in pieces of at most max_hops hops.  In a slot session: the
+        frame limit before the chunk, the hops each slot's stream was fed after it."""
+        k = chunk.shape[1] // self.hop_length
+        if self._slots is not None and self.frames + k > FRAME_LIMIT:
+            raise RuntimeError(f"{type(self).__name__}: {self.frames} + {k} frames pass this session's limit of {FRAME_LIMIT} "
+                               f"(2**31 - 1 - K_MAX: the device frame counter is an int32); close the streams and call "
+                               f"init_slots() for a new session")
         self._ready()
         step = self.max_hops * self.hop_length if self.max_hops else chunk.shape[1]
         outs = [self._run_piece(chunk[:, i:i + step]) for i in range(0, chunk.shape[1], step)]
+        for st in self._slots or ():
+            if st is not None:
+                st["hops"] = st["hops"] + k if st["total"] is None else min(st["hops"] + k, st["total"])
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
     def _capture(self, hops: int) -> torch.cuda.CUDAGraph:
@@ -180,6 +213,8 @@ class HopSession:
     def flush(self) -> torch.Tensor:
         """The last window - hop_length samples of every stream ([B, window - hop_length]); the streams are then finished."""
         name = f"{type(self).__name__}.flush"
+        if self._slots is not None:
+            raise RuntimeError(f"{name}: a slot session ends its streams one by one: close(slot) returns a slot's last samples")
         if self.streams is None or self._finished:
             raise RuntimeError(f"{name}: no open streams")
         if self.frames == 0:
@@ -189,3 +224,110 @@ class HopSession:
         self._flush_into(out)
         self._finished = True
         return out
+
+    # -- slots --------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def slot_output_range(samples: int, win: int, hop: int) -> range:
+        """The indices of y that hold model.inference(x, e) for a stream x of `samples` = k * hop samples in a slot, y = every
+        output of the slot from open() on ‖ close(): the offline output after the latency, win - hop samples."""
+        n = HopSession.output_length(samples, win, hop)
+        return range(win - hop, win - hop + n["emitted"] + n["flushed"])
+
+    @property
+    def active(self) -> List[int]:
+        """The slots that carry a stream (opened and not yet closed)."""
+        return [] if self._slots is None else [i for i, st in enumerate(self._slots) if st is not None]
+
+    def _slot(self, slot: int, what: str, idle: bool) -> int:
+        """Check that `slot` names a slot of this slot session that is idle / carries a stream -> its index."""
+        name = f"{type(self).__name__}.{what}"
+        if not hasattr(self, "init_slots"):
+            raise NotImplementedError(f"{name}: {type(self).__name__} has no slot sessions: its streams start together in "
+                                      f"init_streams() and end together in flush()")
+        if self.streams is None or self._slots is None:
+            raise RuntimeError(f"{name}: not a slot session; call init_slots() (an init_streams() session starts and ends "
+                               f"all its streams at once, with flush())")
+        if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.streams:
+            raise IndexError(f"{name}: slot {slot!r} is out of range; this session has slots 0 .. {self.streams - 1}")
+        if idle and self._slots[slot] is not None:
+            raise RuntimeError(f"{name}: slot {slot} carries a stream; close({slot}) it first, or take one of the idle slots "
+                               f"{[i for i, st in enumerate(self._slots) if st is None]}")
+        if not idle and self._slots[slot] is None:
+            raise RuntimeError(f"{name}: slot {slot} is idle; open({slot}) starts a stream in it")
+        return slot
+
+    @torch.no_grad()
+    def open(self, slot: int, enroll: Optional[torch.Tensor] = None) -> None:
+        """Start a stream in the idle slot `slot`: its first input hop is the first hop of the next step / step_chunk call.
+        enroll [L'] or [1, L'] on the model's device, where the streamer's model takes one; what it seeds is computed here,
+        once.  No synchronisation, no captured graph is touched."""
+        name = f"{type(self).__name__}.open"
+        slot = self._slot(slot, "open", idle=True)
+        required, why = self._enrolment_rule()
+        if (enroll is not None) != required:
+            raise ValueError(f"{name}: an enrolment [L'] is required {why}")
+        if enroll is not None:
+            hip.require_device(enroll, name)
+            if enroll.device != self.device:
+                raise RuntimeError(f"{name}: the enrolment is on {enroll.device}, the session on {self.device}; move it with "
+                                   f".to({str(self.device)!r})")
+            enroll = enroll[None] if enroll.dim() == 1 else enroll
+            if enroll.dim() != 2 or enroll.shape[0] != 1:
+                raise ValueError(f"{name}: enroll must be [L'] or [1, L'] (one stream), got {tuple(enroll.shape)}")
+        if self.frames + self.prime_hops > FRAME_LIMIT:
+            raise RuntimeError(f"{name}: the session is at its limit of {FRAME_LIMIT} frames (an int32 frame counter); close "
+                               f"the streams and call init_slots() for a new session")
+        self._check_parameters()
+        self._open_slot(slot, enroll)
+        self._queue[slot].zero_()
+        self._tail[slot].zero_()
+        # frames counter .. counter + prime_hops - 1 see a partly filled window: dead.  (device-side add: no read-back)
+        self._span[slot, 0:1] = self._counter + self.prime_hops
+        self._span[slot, 1:2] = INT32_MAX
+        self._slots[slot] = dict(hops=0, total=None)
+
+    def _needs(self, st: dict, more: int, what: str, slot: int) -> None:
+        """flush()'s rule per slot: a stream that ends after fewer than window samples has no frame."""
+        need = self.window // self.hop_length
+        if st["hops"] + more < need:
+            raise RuntimeError(f"{type(self).__name__}.{what}: the stream in slot {slot} would end after "
+                               f"{(st['hops'] + more) * self.hop_length} samples, and a stream needs {self.window} (no "
+                               f"complete frame yet): step {need - st['hops'] - more} more hops of it first")
+
+    @torch.no_grad()
+    def end(self, slot: int, hops: int) -> None:
+        """The stream in `slot` has `hops` >= 0 more hops of input: frames after them are dead, whatever the caller pads the
+        rest of a chunk with, and the slot's later output hops drain its overlap-add tail."""
+        name = f"{type(self).__name__}.end"
+        slot = self._slot(slot, "end", idle=False)
+        st = self._slots[slot]
+        if not isinstance(hops, int) or hops < 0:
+            raise ValueError(f"{name}: hops = {hops!r}: the whole hops of input still to come, >= 0")
+        if st["total"] is not None:
+            raise RuntimeError(f"{name}: slot {slot} was ended already ({st['total'] - st['hops']} hops to go); close({slot}) "
+                               f"frees it")
+        self._needs(st, hops, "end", slot)
+        self._span[slot, 1:2] = self._counter + hops
+        st["total"] = st["hops"] + hops
+
+    @torch.no_grad()
+    def close(self, slot: int) -> torch.Tensor:
+        """-> [window - hop]: what is left of the slot's overlap-add tail, through the output constraint; the slot is idle
+        again.  Without an earlier end() the stream ends now.  (The slot's model state stays as it is: nothing reads or
+        writes it while the slot is idle, and open() resets it.)"""
+        slot = self._slot(slot, "close", idle=False)
+        st = self._slots[slot]
+        if st["total"] is None:
+            self._needs(st, 0, "close", slot)
+        elif st["hops"] < st["total"]:
+            raise RuntimeError(f"{type(self).__name__}.close: end({slot}, ..) announced {st['total'] - st['hops']} more hops "
+                               f"of input; step them first")
+        self._ready()
+        if st["total"] is None:
+            self.end(slot, 0)
+        out = torch.empty(1, self.window - self.hop_length, dtype=torch.float32, device=self.device)
+        self._flush_into(out, self._tail[slot:slot + 1])
+        self._tail[slot].zero_()
+        self._span[slot].zero_()
+        self._slots[slot] = None
+        return out[0]

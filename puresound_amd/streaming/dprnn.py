@@ -21,6 +21,17 @@ order (the two 1x1 convolutions always take ps_conv1x1_f32's tiled kernel: MIN_G
 packs its own weights from the parameters; the model's own setting and plans are left as they were.  The enrolment states are
 computed once per session by the model's own offline pieces, in the model's own arithmetic.  The session around the kernels
 (priming, step / step_chunk / flush, eager run or graph replay, the capture) is HopSession's: streaming/_session.py.
+
+Slots (init_slots / open / end / close; the bookkeeping is HopSession's): a session of fixed capacity B whose columns begin
+and end streams of their own while it runs.  Per slot the device holds a span (birth, death) of absolute frame indices; frame
+g of column b is live iff birth[b] <= g < death[b].  The segment position is part of the recurrence, so a stream that joins
+at an arbitrary frame has a phase of its own: ps_dprnn_block_step_slots_f32 puts frame g of column b at position
+(g - birth[b]) % K -- its frame n at n % K, whatever the session's counter says -- resets the intra state and picks the bank
+slot by it, reads a dead frame's input as 0 and stores no state for it; ps_free_decode_step_slots_f32 adds nothing for a dead
+frame.  open() zeroes the slot's queue, tail and intra states and sets all K bank slots of its column (zero, or the states
+its enrolment ends in), so nothing of the slot's predecessor is left.  What a slot returned from open to close, followed by
+close()'s samples, is `model.inference(x, enroll)` of its own stream after latency_samples samples of constrain(0), whatever
+the other slots do; every sum has one fixed order per column, so it is bit-identical to a block session of that stream.
 """
 from typing import List, Optional
 
@@ -30,13 +41,10 @@ from .. import hip
 from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
 from ..nnet.dprnn import DPRNN
 from ..nnet.lobe.encoder import FreeEncDec
-from ._session import HopSession, check_on_device
+# K_MAX: frames per launch at most, step_chunk splits longer chunks; FRAME_LIMIT: where a session stops (the device frame
+# counter is an int32, and a launch reads up to K_MAX frames past it); INT32_MAX: the death of a stream that has not ended
+from ._session import FRAME_LIMIT, INT32_MAX, K_MAX, HopSession, check_on_device  # noqa: F401
 
-#: frames per launch at most: step_chunk splits longer chunks
-K_MAX = 16
-INT32_MAX = 2 ** 31 - 1
-#: a session stops here: the device frame counter is an int32, and a launch reads up to K_MAX frames past it
-FRAME_LIMIT = INT32_MAX - K_MAX
 #: the 1x1 convolutions always run on at least this many columns (the rows are at least 128 wide; the columns past the chunk
 #: hold values nobody reads): ps_conv1x1_f32 has another kernel, with another order of summation, for 64 columns or fewer,
 #: and a stream's bits must not depend on how many columns share its launch
@@ -101,9 +109,17 @@ class StreamingDPRNN(HopSession):
 
     s = StreamingDPRNN(model); s.init_streams(B, enroll); s.step(hop [B, hop]) -> [B, hop] or None while the first window
     fills; s.step_chunk([B, k*hop]) -> what k step() calls return, concatenated; s.flush() -> the last win - hop samples.
+
+    Slots, for streams that begin and end on their own: s.init_slots(capacity); s.open(slot, enroll [L']); every
+    s.step / s.step_chunk([capacity, k*hop]) -> [capacity, k*hop] from the first hop on (idle slots: constrain(0));
+    s.end(slot, hops) when the stream has `hops` more hops of input; s.close(slot) -> the last win - hop samples, and the
+    slot is idle again.  What a slot returned from open to close, then close's samples, is model.inference(x, enroll) of its
+    own stream after latency_samples samples of constrain(0) (slot_output_range(L, win, hop)), whatever the other slots do,
+    and bit-identical to a block session of that stream.
     """
 
     max_hops = K_MAX
+    _how_to_start = "call init_streams() first (or init_slots())"
 
     def __init__(self, model: SoTaskWrapModule):
         check_streamable(model)
@@ -143,18 +159,61 @@ class StreamingDPRNN(HopSession):
             hip.require_device(enroll, "StreamingDPRNN.init_streams")
             if enroll.dim() != 2 or enroll.shape[0] != b:
                 raise ValueError(f"StreamingDPRNN.init_streams: enroll must be [{b}, L'], got {tuple(enroll.shape)}")
-            feats, te = model.encoder.encode_padded(enroll.contiguous(), m.padded_frames_needed)
-            seeds = m.hidden_states_padded(feats, te)       # per block (h, c) [B, H, ldq]: [b, :, p] = position p of stream b
+            seeds = self._seeds(enroll)
+        self._new_session(b, dev, use_graph)
+        if seeds is not None:
+            self._seed_banks(slice(0, b), seeds)
+
+    def _seeds(self, enroll: torch.Tensor) -> list:
+        """The final inter-LSTM states of the enrolment pass, by the model's own offline pieces: per block (h, c)
+        [B, H, ldq], [b, :, p] = position p of stream b."""
+        model, m = self.model, self.model.masker
+        feats, te = model.encoder.encode_padded(enroll.contiguous(), m.padded_frames_needed)
+        return m.hidden_states_padded(feats, te)
+
+    def _seed_banks(self, cols: slice, seeds: list) -> None:
+        """All K slots of the columns `cols` of every block's banks <- the seeds of as many streams."""
+        k = self.model.masker.seg_size
+        for bank, seed in zip(self._banks, seeds):
+            for dst, src in zip(bank, seed):
+                dst[:, :, cols] = src[:, :, :k].float().permute(2, 1, 0)
+
+    def _new_session(self, b: int, dev: torch.device, use_graph: bool) -> None:
+        """Zeroed state of b columns."""
+        m = self.model.masker
         self._begin(b, dev, use_graph)
         k, h, ldb = m.seg_size, m.hidden_size, hip.padded_frames(b)
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
         self._intra = [(z(h, ldb), z(h, ldb)) for _ in range(m.n_blocks)]
         self._banks = [(z(k, h, ldb), z(k, h, ldb)) for _ in range(m.n_blocks)]
-        if seeds is not None:
-            for bank, seed in zip(self._banks, seeds):
-                for dst, src in zip(bank, seed):
-                    dst[:, :, :b] = src[:, :, :k].float().permute(2, 1, 0)
         self._bufs = {}
+
+    @torch.no_grad()
+    def init_slots(self, capacity: int, use_graph: bool = True) -> None:
+        """Start a slot session of `capacity` columns, every slot idle (every state zeroed); open() starts a stream."""
+        if int(capacity) < 1:
+            raise ValueError("init_slots: capacity >= 1")
+        self._new_session(int(capacity), next(self.model.parameters()).device, use_graph)
+        self._make_slots()
+
+    def _enrolment_rule(self) -> tuple:
+        tse = bool(self.model.embedding_free_tse)
+        return tse, ("iff the model is embedding_free_tse (this one " +
+                     ("is: pass enroll)" if tse else "is not: pass no enroll)"))
+
+    def _open_slot(self, slot: int, enroll: Optional[torch.Tensor]) -> None:
+        """Nothing of the slot's predecessor stays: the intra (h, c) of every block zeroed, all K bank slots of the column
+        zeroed or, with an enrolment, set to the inter states its pass ends in (computed here, once, as init_streams does)."""
+        seeds = self._seeds(enroll) if enroll is not None else None
+        for h, c in self._intra:
+            h[:, slot].zero_()
+            c[:, slot].zero_()
+        if seeds is None:
+            for h, c in self._banks:
+                h[:, :, slot].zero_()
+                c[:, :, slot].zero_()
+        else:
+            self._seed_banks(slice(slot, slot + 1), seeds)
 
     def _state(self) -> List[torch.Tensor]:
         return [self._queue, self._tail, self._counter] + [t for pair in self._intra + self._banks for t in pair]
@@ -186,20 +245,23 @@ class StreamingDPRNN(HopSession):
         x = feats
         for i, (intra, inter) in enumerate(pk["blocks"]):
             y = bufs["x0"] if i % 2 == 0 else bufs["x1"]
-            hip.dprnn_block_step(x, self._counter, intra, inter, *self._intra[i], *self._banks[i], self.streams, hops, out=y)
+            hip.dprnn_block_step(x, self._counter, intra, inter, *self._intra[i], *self._banks[i], self.streams, hops, out=y,
+                                 span=self._span)
             x = y
         hip.conv1x1(x, cols, pk["out_wt"], c, pk["out_pro"], pk["out_b"], out=bufs["mask"])
-        hip.free_decode_step(feats, bufs["mask"], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode)
+        hip.free_decode_step(feats, bufs["mask"], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode,
+                             span=self._span, counter=self._counter if self._span is not None else None)
         hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
 
     def _run(self, chunk: torch.Tensor) -> torch.Tensor:
+        """(a block session has the frame limit too; the core checks a slot session's, with its own way out)"""
         k = chunk.shape[1] // self.hop_length
-        if self.frames + k > FRAME_LIMIT:
+        if self._slots is None and self.frames + k > FRAME_LIMIT:
             raise RuntimeError(f"StreamingDPRNN: {self.frames} + {k} frames pass this session's limit of {FRAME_LIMIT} "
                                f"(2**31 - 1 - K_MAX: the device frame counter is an int32); flush the streams and call "
                                f"init_streams() for a new session")
         return super()._run(chunk)
 
-    def _flush_into(self, out: torch.Tensor) -> None:
-        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail, out, self.hop_length, out_mode=self._out_mode,
-                             flush=True)
+    def _flush_into(self, out: torch.Tensor, tail: Optional[torch.Tensor] = None) -> None:
+        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail if tail is None else tail, out, self.hop_length,
+                             out_mode=self._out_mode, flush=True)

@@ -25,8 +25,8 @@ it runs.  Per slot the device holds a span (birth, death) of absolute frame indi
 birth[b] <= g < death[b].  ps_dwconv_step_slots_f32 reads a frame that is not live as 0 (the rule for g < 0, per column) and
 ps_free_decode_step_slots_f32 adds nothing for it; everything else in a hop is column-wise, so dead columns compute values
 nobody reads.  A slot's output is the offline output of its stream delayed by latency_samples, whatever the other slots do.
-The session around the kernels (priming, step / step_chunk / flush, eager run or graph replay, the capture) is HopSession's:
-streaming/_session.py.
+The session around the kernels (priming, step / step_chunk / flush, eager run or graph replay, the capture) and the slot
+bookkeeping (open / end / close, the spans, the frame limit) are HopSession's: streaming/_session.py.
 """
 from typing import Dict, List, Optional
 
@@ -38,13 +38,9 @@ from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
 from ..nnet.conv_tasnet import TCN, ConvTasNet
 from ..nnet.lobe.encoder import FreeEncDec
 from ..nnet.lobe.norm import ChanLN, norm_plan
-from ._session import HopSession, check_on_device
-
-#: frames per launch at most: step_chunk splits longer chunks (the rings hold (P-1)*dilation + K_MAX frames)
-K_MAX = 16
-INT32_MAX = 2 ** 31 - 1
-#: a slot session stops here: the device frame counter is an int32, and a launch reads up to K_MAX frames past it
-FRAME_LIMIT = INT32_MAX - K_MAX
+# K_MAX: frames per launch at most, step_chunk splits longer chunks (the rings hold (P-1)*dilation + K_MAX frames);
+# FRAME_LIMIT: where a slot session stops, INT32_MAX: the death of a stream that has not ended
+from ._session import FRAME_LIMIT, INT32_MAX, K_MAX, HopSession, check_on_device  # noqa: F401
 
 
 def check_streamable(model) -> None:
@@ -112,14 +108,6 @@ class StreamingConvTasNet(HopSession):
         check_streamable(model)
         super().__init__(model, model.encoder.win_length, model.encoder.hop_length)
         self.win_length = self.window
-        self._span = self._slots = None
-
-    @staticmethod
-    def slot_output_range(samples: int, win: int, hop: int) -> range:
-        """The indices of y that hold model.inference(x, e) for a stream x of `samples` = k * hop samples in a slot, y = every
-        output of the slot from open() on ‖ close(): the offline output after the latency, win - hop samples."""
-        n = HopSession.output_length(samples, win, hop)
-        return range(win - hop, win - hop + n["emitted"] + n["flushed"])
 
     # -- weights ------------------------------------------------------------------------------------------------------
     def _build_packs(self, dev: torch.device) -> None:
@@ -178,8 +166,6 @@ class StreamingConvTasNet(HopSession):
         """Zeroed state of b columns (self._emb is set by the caller)."""
         m = self.model.masker
         self._begin(b, dev, use_graph)
-        self._span = None        # int32 [B, 2] (birth, death) in a slot session
-        self._slots = None       # per slot None (idle) or dict(hops fed, total hops once end() was called)
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
         self._blocks: List[TCN] = [blk for stack in m.tcn_list for blk in stack]
         # one circular ring of activated depthwise inputs per block: (P-1)*dilation frames of history plus a chunk
@@ -198,52 +184,15 @@ class StreamingConvTasNet(HopSession):
         if model.speaker_net is not None and any(m.tcn_with_embed):
             self._emb = torch.zeros(b, m.embed_dim, dtype=torch.float32, device=dev)
         self._new_session(b, dev, use_graph)
-        self._span = torch.zeros(b, 2, dtype=torch.int32, device=dev)
-        self._slots = [None] * b
+        self._make_slots()
 
-    @property
-    def active(self) -> List[int]:
-        """The slots that carry a stream (opened and not yet closed)."""
-        return [] if self._slots is None else [i for i, st in enumerate(self._slots) if st is not None]
+    def _enrolment_rule(self) -> tuple:
+        has = self.model.speaker_net is not None
+        return has, f"iff the model has a speaker_net (this one has {'one: pass enroll' if has else 'none: pass no enroll'})"
 
-    def _slot(self, slot: int, what: str, idle: bool) -> int:
-        """Check that `slot` names a slot of this slot session that is idle / carries a stream -> its index."""
-        name = f"StreamingConvTasNet.{what}"
-        if self.streams is None or self._slots is None:
-            raise RuntimeError(f"{name}: not a slot session; call init_slots() (an init_streams() session starts and ends "
-                               f"all its streams at once, with flush())")
-        if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.streams:
-            raise IndexError(f"{name}: slot {slot!r} is out of range; this session has slots 0 .. {self.streams - 1}")
-        if idle and self._slots[slot] is not None:
-            raise RuntimeError(f"{name}: slot {slot} carries a stream; close({slot}) it first, or take one of the idle slots "
-                               f"{[i for i, st in enumerate(self._slots) if st is None]}")
-        if not idle and self._slots[slot] is None:
-            raise RuntimeError(f"{name}: slot {slot} is idle; open({slot}) starts a stream in it")
-        return slot
-
-    @torch.no_grad()
-    def open(self, slot: int, enroll: Optional[torch.Tensor] = None) -> None:
-        """Start a stream in the idle slot `slot`: its first input hop is the first hop of the next step / step_chunk call.
-        enroll [L'] or [1, L'] on the model's device, required iff the model has a speaker_net; its embedding is computed
-        here, once.  No synchronisation, no captured graph is touched."""
-        name = "StreamingConvTasNet.open"
-        slot = self._slot(slot, "open", idle=True)
+    def _open_slot(self, slot: int, enroll: Optional[torch.Tensor]) -> None:
+        """The slot's embedding, computed here, once (the rings need no reset: a dead frame's ring slot is never read)."""
         model, m = self.model, self.model.masker
-        if (enroll is not None) != (model.speaker_net is not None):
-            raise ValueError(f"{name}: an enrolment [L'] is required iff the model has a speaker_net (this one has "
-                             f"{'one: pass enroll' if model.speaker_net is not None else 'none: pass no enroll'})")
-        if enroll is not None:
-            hip.require_device(enroll, name)
-            if enroll.device != self.device:
-                raise RuntimeError(f"{name}: the enrolment is on {enroll.device}, the session on {self.device}; move it with "
-                                   f".to({str(self.device)!r})")
-            enroll = enroll[None] if enroll.dim() == 1 else enroll
-            if enroll.dim() != 2 or enroll.shape[0] != 1:
-                raise ValueError(f"{name}: enroll must be [L'] or [1, L'] (one stream), got {tuple(enroll.shape)}")
-        if self.frames + self.prime_hops > FRAME_LIMIT:
-            raise RuntimeError(f"{name}: the session is at its limit of {FRAME_LIMIT} frames (an int32 frame counter); close "
-                               f"the streams and call init_slots() for a new session")
-        self._check_parameters()
         if self._emb is not None:
             dvec = model.inference_tse_embedding(enroll)[..., 0].float().contiguous()   # [1, E]
             dvec = (hip.l2_normalize(dvec) if m.embed_norm else dvec)[0]
@@ -252,57 +201,6 @@ class StreamingConvTasNet(HopSession):
             for bufs in self._bufs.values():           # (chunk lengths created later read self._emb)
                 for r in bufs["res"]:
                     r[0, c:, slot:bufs["n"]:self.streams] = dvec[:, None]
-        self._queue[slot].zero_()
-        self._tail[slot].zero_()
-        # frames counter .. counter + prime_hops - 1 see a partly filled window: dead.  (device-side add: no read-back)
-        self._span[slot, 0:1] = self._counter + self.prime_hops
-        self._span[slot, 1:2] = INT32_MAX
-        self._slots[slot] = dict(hops=0, total=None)
-
-    def _needs(self, st: dict, more: int, what: str, slot: int) -> None:
-        """flush()'s rule per slot: a stream that ends after fewer than win samples has no frame."""
-        need = self.win_length // self.hop_length
-        if st["hops"] + more < need:
-            raise RuntimeError(f"StreamingConvTasNet.{what}: the stream in slot {slot} would end after "
-                               f"{(st['hops'] + more) * self.hop_length} samples, and a stream needs {self.win_length} (no "
-                               f"complete frame yet): step {need - st['hops'] - more} more hops of it first")
-
-    @torch.no_grad()
-    def end(self, slot: int, hops: int) -> None:
-        """The stream in `slot` has `hops` >= 0 more hops of input: frames after them are dead, whatever the caller pads the
-        rest of a chunk with, and the slot's later output hops drain its overlap-add tail."""
-        slot = self._slot(slot, "end", idle=False)
-        st = self._slots[slot]
-        if not isinstance(hops, int) or hops < 0:
-            raise ValueError(f"StreamingConvTasNet.end: hops = {hops!r}: the whole hops of input still to come, >= 0")
-        if st["total"] is not None:
-            raise RuntimeError(f"StreamingConvTasNet.end: slot {slot} was ended already ({st['total'] - st['hops']} hops to "
-                               f"go); close({slot}) frees it")
-        self._needs(st, hops, "end", slot)
-        self._span[slot, 1:2] = self._counter + hops
-        st["total"] = st["hops"] + hops
-
-    @torch.no_grad()
-    def close(self, slot: int) -> torch.Tensor:
-        """-> [win - hop]: what is left of the slot's overlap-add tail, through the output constraint; the slot is idle
-        again.  Without an earlier end() the stream ends now."""
-        slot = self._slot(slot, "close", idle=False)
-        st = self._slots[slot]
-        if st["total"] is None:
-            self._needs(st, 0, "close", slot)
-        elif st["hops"] < st["total"]:
-            raise RuntimeError(f"StreamingConvTasNet.close: end({slot}, ..) announced {st['total'] - st['hops']} more hops of "
-                               f"input; step them first")
-        self._ready()
-        if st["total"] is None:
-            self.end(slot, 0)
-        out = torch.empty(1, self.win_length - self.hop_length, dtype=torch.float32, device=self.device)
-        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail[slot:slot + 1], out, self.hop_length,
-                             out_mode=self._out_mode, flush=True)
-        self._tail[slot].zero_()
-        self._span[slot].zero_()
-        self._slots[slot] = None
-        return out[0]
 
     def _state(self) -> List[torch.Tensor]:
         return [self._queue, self._tail, self._counter] + self._rings
@@ -368,31 +266,6 @@ class StreamingConvTasNet(HopSession):
                              span=self._span, counter=self._counter if self._span is not None else None)
         hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
 
-    def _run(self, chunk: torch.Tensor) -> torch.Tensor:
-        """In a slot session: the frame limit before the chunk, the hops each slot's stream was fed after it."""
-        k = chunk.shape[1] // self.hop_length
-        if self._slots is not None and self.frames + k > FRAME_LIMIT:
-            raise RuntimeError(f"StreamingConvTasNet: {self.frames} + {k} frames pass this session's limit of {FRAME_LIMIT} "
-                               f"(2**31 - 1 - K_MAX: the device frame counter is an int32); close the streams and call "
-                               f"init_slots() for a new session")
-        out = super()._run(chunk)
-        for st in self._slots or ():
-            if st is not None:
-                st["hops"] = st["hops"] + k if st["total"] is None else min(st["hops"] + k, st["total"])
-        return out
-
-    def _priming(self) -> bool:
-        """(a slot session has no priming phase: a slot's first prime_hops frames are dead by its span)"""
-        return self._slots is None and super()._priming()
-
-    def _flush_into(self, out: torch.Tensor) -> None:
-        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail, out, self.hop_length, out_mode=self._out_mode,
-                             flush=True)
-
-    @torch.no_grad()
-    def flush(self) -> torch.Tensor:
-        """The last win - hop_length samples of every stream ([B, win - hop_length]); the streams are then finished."""
-        if self._slots is not None:
-            raise RuntimeError("StreamingConvTasNet.flush: a slot session ends its streams one by one: close(slot) returns a "
-                               "slot's last samples")
-        return super().flush()
+    def _flush_into(self, out: torch.Tensor, tail: Optional[torch.Tensor] = None) -> None:
+        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail if tail is None else tail, out, self.hop_length,
+                             out_mode=self._out_mode, flush=True)

@@ -4,8 +4,10 @@ veve_dprnn_v0_causal (tests/golden/cases.py "cfg4_tse_short", deterministic weig
 
 For each B: step() (one hop per call) and step_chunk() of --chunk hops, graph replays, a device synchronise after every call;
 p50 / p90 / p99 of the per-call wall time over --replays calls after --warmup.  Prints a plain-text report
-(profiles/streaming_dprnn.txt holds one run).  --profile-only B,K: a short run of K-hop chunks at B streams and nothing else,
-for rocprofv3."""
+(profiles/streaming_dprnn.txt holds one run).  --slots: the same calls on a slot session of capacity B (init_slots), once
+with every slot opened with its own 1 s enrolment and once with the first quarter of the slots open (the other columns idle:
+whole tiles of 16 columns are dead), none ended.  --profile-only B,K: a short run of K-hop chunks at B streams and nothing
+else, for rocprofv3."""
 import argparse
 import os
 import sys
@@ -25,10 +27,17 @@ from puresound_amd.streaming import StreamingDPRNN  # noqa: E402
 SR, SECONDS = 16000, 2
 
 
-def time_mode(s, b, chunk_hops, replays, warmup, dev):
-    """Per-call ms of `replays` calls (step() when chunk_hops == 1, else step_chunk of chunk_hops hops)."""
+def time_mode(s, b, chunk_hops, replays, warmup, dev, open_slots=None):
+    """Per-call ms of `replays` calls (step() when chunk_hops == 1, else step_chunk of chunk_hops hops).  open_slots: a slot
+    session of capacity b with slots 0 .. open_slots - 1 open (None: a block session of b streams)."""
     x = det_wave(100 + b, b, SR * SECONDS).to(dev)
-    s.init_streams(streams=b, enroll=det_wave(200 + b, b, SR).to(dev), use_graph=True)
+    enroll = det_wave(200 + b, b, SR).to(dev)
+    if open_slots is None:
+        s.init_streams(streams=b, enroll=enroll, use_graph=True)
+    else:
+        s.init_slots(b, use_graph=True)
+        for i in range(open_slots):
+            s.open(i, enroll[i])
     hop = s.hop_length
     total = x.shape[1] // hop
     pos = 0
@@ -41,7 +50,7 @@ def time_mode(s, b, chunk_hops, replays, warmup, dev):
         pos += chunk_hops
         return s.step(piece) if chunk_hops == 1 else s.step_chunk(piece)
 
-    for _ in range(s.prime_hops):
+    for _ in range(s.prime_hops if open_slots is None else 0):     # (a slot session has no priming phase)
         s.step(x[:, pos * hop:(pos + 1) * hop])
         pos += 1
     for _ in range(warmup):
@@ -63,7 +72,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=8, help="hops per step_chunk call")
     ap.add_argument("--replays", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--profile-only", default="", help="B,K: 200 calls of K-hop chunks at B streams, no report")
+    ap.add_argument("--slots", action="store_true", help="slot sessions of capacity B: every slot open, then a quarter")
+    ap.add_argument("--profile-only", default="", help="B,K: 200 calls of K-hop chunks at B streams (--slots: B open slots), no report")
     ap.add_argument("--tree", default="", help="source revision to print in the header")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -73,24 +83,33 @@ def main():
     s = StreamingDPRNN(model)
     if args.profile_only:
         b, k = (int(v) for v in args.profile_only.split(","))
-        time_mode(s, b, k, 200, 20, dev)
+        time_mode(s, b, k, 200, 20, dev, b if args.slots else None)
         return
     hop_ms = 1e3 * s.hop_length / SR
     print(f"# tools/bench_streaming_dprnn.py  tree {args.tree or '(not given)'}  device {torch.cuda.get_device_name(dev)}")
     print(f"# veve_dprnn_v0_causal (win {s.win_length}, hop {s.hop_length}, latency {s.latency_samples} samples); "
           f"per-call wall ms, graph replays, device sync per call; {args.replays} calls after {args.warmup} warm-up; "
           f"real-time budget {hop_ms:.1f} ms per hop")
-    print(f"{'B':>6} {'hops/call':>9} {'budget':>7} {'p50':>8} {'p90':>8} {'p99':>8}  real-time")
-    for k in (1, args.chunk):
-        budget = hop_ms * k
-        best = 0
-        for b in [int(v) for v in args.batches.split(",")]:
-            p = time_mode(s, b, k, args.replays, args.warmup, dev)
-            ok = p[99] < budget
-            best = b if ok and b > best else best
-            print(f"{b:>6} {k:>9} {budget:>7.1f} {p[50]:>8.3f} {p[90]:>8.3f} {p[99]:>8.3f}  {'yes' if ok else 'no'}", flush=True)
-        print(f"largest measured real-time B for {k}-hop calls (p99 < {budget:.1f} ms): {best}", flush=True)
-        torch.cuda.empty_cache()
+    batches = [int(v) for v in args.batches.split(",")]
+    # (what the header says, how many slots of a capacity-B session are open); a block session: None
+    modes = [("block session (init_streams)", lambda b: None)]
+    if args.slots:
+        modes = [("slot session (init_slots), every slot open", lambda b: b),
+                 ("slot session (init_slots), the first quarter of the slots open", lambda b: max(1, b // 4))]
+    for title, opened in modes:
+        print(f"# {title}")
+        print(f"{'B':>6} {'hops/call':>9} {'budget':>7} {'p50':>8} {'p90':>8} {'p99':>8}  real-time")
+        for k in (1, args.chunk):
+            budget = hop_ms * k
+            best = 0
+            for b in batches:
+                p = time_mode(s, b, k, args.replays, args.warmup, dev, opened(b))
+                ok = p[99] < budget
+                best = b if ok and b > best else best
+                print(f"{b:>6} {k:>9} {budget:>7.1f} {p[50]:>8.3f} {p[90]:>8.3f} {p[99]:>8.3f}  {'yes' if ok else 'no'}",
+                      flush=True)
+            print(f"largest measured real-time B for {k}-hop calls (p99 < {budget:.1f} ms): {best}", flush=True)
+            torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":
