@@ -417,7 +417,7 @@ int ps_lstm_f16x2_f32(const ps_lstm_args* args, void* stream);
  * unidirectional along time, Q = F, q_stride = ld, step_stride = 1).  hout as ps_lstm_f32 ([N][D*H][ldt]).  No initial or
  * final states (h0, c0, h_last, c_last must be NULL).  step_stride = 1 needs 16-byte-aligned rows and q_stride and, when
  * steps % 4 != 0, D = 1 and room for the padded group inside the row (those frames are written as zeros).
- * ps_lstm_fmajor_ok(args, ldm) = 1 when a launch qualifies, else PS_E_UNSUPPORTED. */
+ * ps_lstm_fmajor_ok(args, ldm) = 1 when a launch qualifies, else 0. */
 int ps_lstm_fmajor_ok(const ps_lstm_args* args, int ldm);
 /* The same for H = 256 (SkiM's segment LSTMs, /root/reference/puresound/nnet/skim.py:45-114) and H = 192 (the speaker LSTM of
  * tse_skim_v1): W_hh as two fp16 terms is 1 MiB per direction and fits no CU, so it is streamed from L2 every step in

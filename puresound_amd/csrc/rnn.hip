@@ -1,12 +1,12 @@
-// Recurrent-masker kernels (DPRNN, SkiM, StreamingSkiM of mcw519/PureSound) on the padded channel-major layout
-// [N][C][ldt] the rest of the library uses, so every Linear / 1x1 conv of these models is a ps_conv1x1_f32 call:
+// Recurrences of the recurrent maskers (DPRNN, SkiM, DPCRN / DPARN of mcw519/PureSound) over gate pre-activations that a
+// 1x1 conv already produced (W_ih x + b_ih + b_hh); hout on the library's padded channel-major layout [N][D*H][ldt]:
 //
-//   ps_lstm_f32            the recurrence of a 1-layer nn.LSTM (both directions) over gate pre-activations that a
-//                          1x1 conv already produced (W_ih x + b_ih + b_hh); dprnn.py:155-171, skim.py:215-222
-//   ps_chan_layernorm_f32  nn.LayerNorm(C) / ChanLN over the channels of each frame with the residual add, PReLU,
-//                          sigmoid and gating product that follow it in the reference; dprnn.py:157-172,
-//                          skim.py:85-98,226, lobe/trivial.py:61-126,160
-//   ps_film_apply_f32      FiLM modulation scale * x + bias; lobe/trivial.py:162-167
+//   ps_lstm_f32, ps_lstm_f16x2_f32   a 1-layer nn.LSTM (both directions), gx channel-major; dprnn.py:155-171, skim.py:215-222
+//   ps_rnn_f32                       nn.RNN (tanh) / nn.GRU the same way; lobe/rnn.py:19-35
+//   ps_lstm_fmajor_*                 gx FRAME-MAJOR: H = 128 (lstm_fm.inc; dpcrn.py:34-81), H = 256 / 192 with W_hh streamed from its
+//                                    packed image (lstm_fm256.inc) or resident in the registers of several CUs (lstm_coop.inc)
+//
+// Order: kernels, checks, dispatch, entries.
 //
 // LSTM recurrence.  One workgroup owns LS = 4 sequences and all 4H gate rows (thread g = gate row).  W_hh^T stays in
 // registers (H <= 64) or is streamed from L2 (coalesced [k][g] rows), h_{t-1} is broadcast from LDS, the four gate
@@ -857,146 +857,6 @@ __global__ __launch_bounds__(H * 4) void lstm_m4_kernel(LstmK k) {
   }
 }
 
-// ---- LayerNorm over channels ---------------------------------------------------------------------------------
-struct ClnArgs {
-  const float* x;
-  const float* gamma;
-  const float* beta;
-  const float* res;
-  const float* slope;
-  const float* mul;
-  float* y;
-  float eps;
-  int sigmoid;
-  int C, T, ldt;
-};
-
-// 64 frames x 4 channel quarters per workgroup; three passes over the (L1/L2 resident) 64 x C tile: mean,
-// centred second moment (the reference's two-pass variance), normalise + epilogue.
-template <int PARTS>
-__global__ __launch_bounds__(64 * PARTS) void chan_layernorm_kernel(ClnArgs a) {
-  __shared__ float red[PARTS][64];
-  const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
-  const int t = blockIdx.x * 64 + lane, n = blockIdx.y;
-  const bool live = t < a.T;
-  const size_t base = (size_t)n * a.C * a.ldt + (live ? t : 0);
-  float s = 0.f;
-  for (int ch = part; ch < a.C; ch += PARTS) s += live ? a.x[base + (size_t)ch * a.ldt] : 0.f;
-  red[part][lane] = s;
-  __syncthreads();
-  float tot = 0.f;
-#pragma unroll
-  for (int p = 0; p < PARTS; ++p) tot += red[p][lane];
-  const float mean = tot / (float)a.C;
-  __syncthreads();
-  float q = 0.f;
-  for (int ch = part; ch < a.C; ch += PARTS) {
-    const float dv = live ? a.x[base + (size_t)ch * a.ldt] - mean : 0.f;
-    q += dv * dv;
-  }
-  red[part][lane] = q;
-  __syncthreads();
-  tot = 0.f;
-#pragma unroll
-  for (int p = 0; p < PARTS; ++p) tot += red[p][lane];
-  const float var = tot / (float)a.C;
-  const float rstd = 1.f / sqrtf(var + a.eps);
-  if (!live) return;
-  const float slope = a.slope ? a.slope[0] : 1.f;
-  for (int ch = part; ch < a.C; ch += PARTS) {
-    const size_t off = base + (size_t)ch * a.ldt;
-    float v = (a.x[off] - mean) * rstd * a.gamma[ch] + a.beta[ch];
-    if (a.slope) v = prelu(v, slope);
-    if (a.sigmoid) v = sigmoidf_(v);
-    if (a.mul) v *= a.mul[off];
-    if (a.res) v += a.res[off];
-    a.y[off] = v;
-  }
-}
-
-// The same for C <= 4 * CPT with the thread's channels held in registers: one pass over x instead of three (on the 2-D maps
-// of DPCRN / DPARN -- 32 x 32,745 frames x 128 channels -- the three passes ran at 2 TB/s of useful traffic, 770 us).  Sums in the
-// order of chan_layernorm_kernel<4>: identical results.
-template <int CPT>
-__global__ __launch_bounds__(256) void chan_layernorm_reg_kernel(ClnArgs a) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
-  const int t = blockIdx.x * 64 + lane, n = blockIdx.y;
-  const bool live = t < a.T;
-  const size_t base = (size_t)n * a.C * a.ldt + (live ? t : 0);
-  float v[CPT];
-#pragma unroll
-  for (int i = 0; i < CPT; ++i) {
-    const int ch = part + 4 * i;
-    v[i] = (live && ch < a.C) ? a.x[base + (size_t)ch * a.ldt] : 0.f;
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < CPT; ++i) s += v[i];
-  red[part][lane] = s;
-  __syncthreads();
-  const float mean = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) / (float)a.C;
-  __syncthreads();
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < CPT; ++i) {
-    const float dv = (live && part + 4 * i < a.C) ? v[i] - mean : 0.f;
-    q += dv * dv;
-  }
-  red[part][lane] = q;
-  __syncthreads();
-  const float var = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) / (float)a.C;
-  const float rstd = 1.f / sqrtf(var + a.eps);
-  if (!live) return;
-  const float slope = a.slope ? a.slope[0] : 1.f;
-#pragma unroll
-  for (int i = 0; i < CPT; ++i) {
-    const int ch = part + 4 * i;
-    if (ch < a.C) {
-      const size_t off = base + (size_t)ch * a.ldt;
-      float o = (v[i] - mean) * rstd * a.gamma[ch] + a.beta[ch];
-      if (a.slope) o = prelu(o, slope);
-      if (a.sigmoid) o = sigmoidf_(o);
-      if (a.mul) o *= a.mul[off];
-      if (a.res) o += a.res[off];
-      a.y[off] = o;
-    }
-  }
-}
-
-// One LSTM cell update per (unit, frame) from complete gate pre-activations (the streaming step: the recurrent
-// product W_hh h is part of the gates GEMM there, its K axis being [x; h]).
-__global__ __launch_bounds__(256) void lstm_cell_kernel(const float* __restrict__ gates, float* __restrict__ c,
-                                                        float* __restrict__ h, int H, int T, int ldg, int lds_) {
-  const int t = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
-  const int nd = blockIdx.z;  // utterance * directions + direction
-  if (t >= T || j >= H) return;
-  const float* g = gates + ((size_t)nd * 4 * H + j) * ldg + t;
-  const size_t so = ((size_t)nd * H + j) * lds_ + t;
-  const float gi = sigmoidf_(g[0]);
-  const float gf = sigmoidf_(g[(size_t)H * ldg]);
-  const float gg = tanhf(g[(size_t)2 * H * ldg]);
-  const float go = sigmoidf_(g[(size_t)3 * H * ldg]);
-  const float cn = gf * c[so] + gi * gg;
-  c[so] = cn;
-  h[so] = go * tanhf(cn);
-}
-
-__global__ __launch_bounds__(256) void film_apply_kernel(const float* __restrict__ x, const float* __restrict__ sb,
-                                                         float* __restrict__ y, int C, int T, int ldt) {
-  const int t = (blockIdx.x * 256 + threadIdx.x) * 4;
-  const int ch = blockIdx.y, n = blockIdx.z;
-  if (t >= T) return;
-  const size_t xo = ((size_t)n * C + ch) * ldt + t;
-  const size_t so = ((size_t)n * 2 * C + ch) * ldt + t;
-  const size_t bo = so + (size_t)C * ldt;
-  const f32x4 xv = *reinterpret_cast<const f32x4*>(x + xo);
-  const f32x4 sv = *reinterpret_cast<const f32x4*>(sb + so);
-  const f32x4 bv = *reinterpret_cast<const f32x4*>(sb + bo);
-  *reinterpret_cast<f32x4*>(y + xo) = sv * xv + bv;
-}
-
 // ---- the 4-sequence recurrence with the product W_hh h in two fp16 terms (ps_lstm_f16x2_f32, inter-segment pass) --------
 // The step of lstm_m4_kernel is a dependent chain: 64 v_mfma_f32_4x4x1_f32 (512 cycles of issue), the cell, one LDS
 // exchange.  v_mfma_f32_4x4x4_f16 takes four k per issue: with W_hh 2^e = hi + lo once per workgroup and h 2^10 = hi +
@@ -1155,29 +1015,236 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 }  // namespace ps
 
+// the cooperative kernel's counters (a kernel, not hipMemsetAsync: inside a replayed graph a memset node does not have to go
+// through the L2 the counters' atomics work in -- the first graph replays of that launch computed with the previous replay's counts)
+__global__ __launch_bounds__(256) void zero_words_kernel(unsigned* p, int n) {
+  for (int i = threadIdx.x; i < n; i += 256) p[i] = 0u;
+}
+
 using namespace ps;
 
-static int lstm_launch(const ps_lstm_args* args, void* stream, bool f16x2);
+// ---- checks: predicates on ps_lstm_args; every entry composes them and keeps its own message and return code ------------
+// non-null gx / hout (and whh_t where the kernel reads it), D = 1 or 2, positive sizes, non-negative strides
+static bool sizes_ok(const ps_lstm_args& a, bool reads_whh_t = true) {
+  return a.gx && a.hout && (a.whh_t || !reads_whh_t) && a.N > 0 && a.H > 0 && a.D >= 1 && a.D <= 2 && a.Q > 0 && a.steps > 0 &&
+         a.q_stride >= 0 && a.step_stride >= 0 && a.ldt > 0;
+}
+static long long last_frame(const ps_lstm_args& a) { return (long long)(a.Q - 1) * a.q_stride + (long long)(a.steps - 1) * a.step_stride; }
+static bool has_states(const ps_lstm_args& a) { return a.h0 || a.c0 || a.h_last || a.c_last; }
+// all state tensors of a launch are read and written with the row stride ldq
+static bool states_ok(const ps_lstm_args& a) { return !has_states(a) || a.ldq >= a.Q; }
+static bool shift_ok(const ps_lstm_args& a, int max_shift) { return a.state_shift >= 0 && a.state_shift <= max_shift; }
+// frame-major gx [N][ldt][ldm]: 16-byte frames that hold the D*4H gate rows, 4-byte aligned hout
+static bool fmajor_ok(const ps_lstm_args& a, int ldm) {
+  return ldm >= a.D * 4 * a.H && ldm % 4 == 0 && !((uintptr_t)a.gx & 15) && !((uintptr_t)a.hout & 3);
+}
 
 // (no message: the probe of a caller choosing its path)
 static bool lstm_fmajor_fits(const ps_lstm_args& a, int ldm) {
-  if (!a.gx || !a.whh_t || !a.hout || a.h0 || a.c0 || a.h_last || a.c_last || a.H != 128 || a.D < 1 || a.D > 2 || a.N <= 0 ||
-      a.Q <= 0 || a.steps <= 0 || a.q_stride < 0 || a.step_stride < 0 || a.ldt <= 0 || a.state_shift != 0)
-    return false;
-  if ((long long)(a.Q - 1) * a.q_stride + (long long)(a.steps - 1) * a.step_stride >= a.ldt) return false;
-  if (ldm < a.D * 512 || ldm % 4 || (long long)a.ldt * ldm * 4 >= (1LL << 31) || (long long)a.ldt * 128 * 4 >= (1LL << 31)) return false;
-  if (((uintptr_t)a.gx & 15) || ((uintptr_t)a.hout & 3)) return false;
-  return (long long)a.N * ((a.Q + 15) / 16) < (1LL << 30);
+  return sizes_ok(a) && a.H == 128 && !has_states(a) && shift_ok(a, 0) && last_frame(a) < a.ldt && fmajor_ok(a, ldm) &&
+         (long long)a.ldt * ldm * 4 < (1LL << 31) && (long long)a.ldt * 128 * 4 < (1LL << 31) &&
+         (long long)a.N * ((a.Q + 15) / 16) < (1LL << 30);
 }
 
 static bool lstm_h256_fits(const ps_lstm_args& a, int ldm) {
-  if (!a.gx || !a.hout || (a.H != 256 && a.H != 192) || a.D < 1 || a.D > 2 || a.N <= 0 || a.Q <= 0 || a.steps <= 0 || a.q_stride < 0 ||
-      a.step_stride < 0 || a.ldt <= 0 || (a.state_shift != 0 && a.state_shift != 1))
-    return false;
-  if ((long long)(a.Q - 1) * a.q_stride + (long long)(a.steps - 1) * a.step_stride >= a.ldt) return false;
-  if (ldm < a.D * 4 * a.H || ldm % 4 || ((uintptr_t)a.gx & 15) || ((uintptr_t)a.hout & 3)) return false;
-  if ((a.h0 || a.c0 || a.h_last || a.c_last) && a.ldq < a.Q) return false;
-  return (long long)a.N * a.Q < (1LL << 30);
+  return sizes_ok(a, false) && (a.H == 256 || a.H == 192) && shift_ok(a, 1) && last_frame(a) < a.ldt && fmajor_ok(a, ldm) &&
+         states_ok(a) && (long long)a.N * a.Q < (1LL << 30);
+}
+
+// ---- dispatch: store widths, the cooperative launch's layout, the kernel choice ------------------------------------------
+// 8-byte h' stores of the h256 and cooperative kernels: consecutive frames in pairs that start on an 8-byte boundary
+// (PS_DBG_LSTM_4B_STORES keeps the 4-byte ones: tests run both)
+static bool store_pairs(const ps_lstm_args& a) {
+  return a.step_stride == 1 && a.q_stride % 2 == 0 && a.ldt % 2 == 0 && !((uintptr_t)a.hout & 7) &&
+         (a.D == 1 || a.steps % 2 == 0) && !dbg(PS_DBG_LSTM_4B_STORES);
+}
+
+// 16-byte step groups: steps are consecutive frames starting on a 16-byte boundary.  A forward-only pass may end
+// in a partial group: it reads / writes up to 3 frames past its last step, which must still lie inside the row
+// (pad frames; they are never read as data).  Without the groups a long pass over consecutive frames re-fetches
+// every 128-byte line of the gate pre-activations once per step (DPCRN's inter pass: 10.8 ms instead of ~3).
+// gx_too: gx is read in groups as well (channel-major gx; the frame-major entry has its gx rule in lstm_fmajor_fits).
+static bool step_groups(const ps_lstm_args& a, bool gx_too) {
+  const int steps4 = (a.steps + 3) / 4 * 4;
+  const bool tail_ok = a.steps % 4 == 0 || (a.D == 1 && (long long)(a.Q - 1) * a.q_stride + steps4 <= a.ldt);
+  return a.step_stride == 1 && tail_ok && a.q_stride % 4 == 0 && a.ldt % 4 == 0 && !(gx_too && ((uintptr_t)a.gx & 15)) &&
+         !((uintptr_t)a.hout & 15);
+}
+
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// The cooperative kernel: the streamed kernel's shapes, few enough sequence groups that every slice of every group gets a CU
+// of its own at the same time (the group barrier spins: co-residency is a correctness condition, not a tuning choice).
+// Workspace: the h exchange (hx_bytes), then sync_words counters, error word and XCD notes (hip._coop_layout mirrors it).
+struct CoopLayout {
+  int waves;           // per workgroup (= 16-unit row blocks per slice); 0: the launch does not fit
+  bool per_direction;  // both directions do not fit at once: one launch per direction
+  int groups;          // of 16 sequences
+  size_t hx_bytes, sync_words, bytes;
+};
+
+// waves: 2 when the launch then still fits the chip -- more, smaller slices measured faster per step with a handful of
+// groups (the speaker LSTM: 9.5 ms against 13.6) -- else 4, else 4 per direction if a direction fits, else 0
+static CoopLayout coop_layout(const ps_lstm_args& a, int ldm) {
+  CoopLayout l{};
+  if (!lstm_h256_fits(a, ldm) || a.steps < 2) return l;
+  const long long groups = ((long long)a.N * a.Q + 15) / 16;
+  const long long rounds = (groups * a.D + 7) / 8 * 8;
+  if (rounds * (a.H / 32) <= device_cus()) l.waves = 2;
+  else if (rounds * (a.H / 64) <= device_cus()) l.waves = 4;
+  else if (a.D == 2 && (groups + 7) / 8 * 8 * (a.H / 64) <= device_cus()) l.waves = 4, l.per_direction = true;
+  else return l;
+  l.groups = (int)groups;
+  l.hx_bytes = align_up((size_t)2 * a.D * l.groups * 2 * 16 * (a.H + 8) * sizeof(_Float16), 256);
+  l.sync_words = align_up((size_t)(a.D * l.groups * (2 + a.H / (16 * l.waves)) + 1) * sizeof(unsigned), 256) / sizeof(unsigned);
+  l.bytes = l.hx_bytes + l.sync_words * sizeof(unsigned);
+  return l;
+}
+
+// Calls f(H, WAVES, PAIRS) with the variant of an H = 256 / 192 launch as std::integral_constant values: the template
+// arguments of its kernel (the streamed kernel has no WAVES).
+template <class F>
+static void with_h256_variant(int H, int waves, bool pairs, F&& f) {
+  auto with_pairs = [&](auto HH, auto WW) {
+    if (pairs) f(HH, WW, std::integral_constant<int, 2>{});
+    else f(HH, WW, std::integral_constant<int, 1>{});
+  };
+  if (H == 256 && waves == 2) with_pairs(std::integral_constant<int, 256>{}, std::integral_constant<int, 2>{});
+  else if (H == 256) with_pairs(std::integral_constant<int, 256>{}, std::integral_constant<int, 4>{});
+  else if (waves == 2) with_pairs(std::integral_constant<int, 192>{}, std::integral_constant<int, 2>{});
+  else with_pairs(std::integral_constant<int, 192>{}, std::integral_constant<int, 4>{});
+}
+
+struct LstmPlan {
+  void (*kernel)(LstmK);
+  dim3 grid, block;
+  size_t lds;
+};
+
+// What a (valid) ps_lstm_f32 / ps_lstm_f16x2_f32 launch runs: a function of the arguments and the debug switches alone.
+static LstmPlan lstm_plan(const ps_lstm_args& a, bool f16x2) {
+  if ((a.H != 64 && a.H != 128) || dbg(PS_DBG_LSTM_SCALAR)) {  // thread = gate row, LS sequences per workgroup
+    auto rows = [&](void (*kernel)(LstmK)) {
+      return LstmPlan{kernel, dim3((a.Q + LS - 1) / LS, a.N, a.D), dim3((4 * a.H + 63) / 64 * 64), (size_t)5 * a.H * sizeof(f32x4)};
+    };
+    return a.H <= LSTM_WREG ? rows(lstm_kernel<true>) : rows(lstm_kernel<false>);
+  }
+  const long long seqs = (long long)a.N * a.Q;
+  const bool contig = step_groups(a, true), h64 = a.H == 64, stores_4b = dbg(PS_DBG_LSTM_4B_STORES);
+  // 16 sequences per workgroup when there are enough sequences to fill the chip that way (PS_DBG_LSTM_WIDE / _M4 force one)
+  const bool wide = dbg(PS_DBG_LSTM_WIDE) ? true : dbg(PS_DBG_LSTM_M4) ? false : (h64 && contig && seqs >= 16 * 256);
+  // 4 sequences per workgroup: a multiple of 8 workgroups, see the XCD-aware group order
+  const dim3 grid((unsigned)(wide ? (seqs + 15) / 16 : ((seqs + 3) / 4 + 7) / 8 * 8), 1, a.D);
+  auto run = [&](void (*kernel)(LstmK)) { return LstmPlan{kernel, grid, dim3(4 * a.H), 0}; };
+  if (wide) {
+    // whole segments of 20 consecutive frames (DPRNN's intra pass at K = 20): all steps fetched up front
+    const bool seg = h64 && contig && a.steps == 20 && !stores_4b;
+    if (seg && f16x2) return a.D == 1 ? run(lstm_seg_f16x2_kernel<64, 20, false>) : run(lstm_seg_f16x2_kernel<64, 20, true>);
+    if (seg) return a.D == 1 ? run(lstm_seg_kernel<64, 20, false>) : run(lstm_seg_kernel<64, 20, true>);
+    if (h64) return contig ? run(lstm_mfma_kernel<64, true>) : run(lstm_mfma_kernel<64, false>);
+    return run(lstm_mfma_kernel<128, false>);  // H = 128: the 16-byte group path does not fit the 256-VGPR budget of 8 waves
+  }
+  if (!h64) return contig ? run(lstm_m4_kernel<128, true>) : run(lstm_m4_kernel<128, false>);
+  if (contig) return run(lstm_m4_kernel<64, true>);
+  return f16x2 && !stores_4b ? run(lstm_m4_f16x2_kernel) : run(lstm_m4_kernel<64, false>);
+}
+
+// ---- entries -------------------------------------------------------------------------------------------------------------
+static int lstm_launch(const ps_lstm_args* args, void* stream, bool f16x2) {
+  if (!args) {
+    set_error("ps_lstm_f32: null args");
+    return PS_E_INVALID;
+  }
+  const ps_lstm_args& a = *args;
+  if (!sizes_ok(a) || a.N > 65535) {
+    set_error("ps_lstm_f32: bad argument (N=%d H=%d D=%d Q=%d steps=%d)", a.N, a.H, a.D, a.Q, a.steps);
+    return PS_E_INVALID;
+  }
+  if (4 * a.H > 1024) {
+    set_error("ps_lstm_f32: hidden size %d > 256 is not supported", a.H);
+    return PS_E_UNSUPPORTED;
+  }
+  if (last_frame(a) >= a.ldt) {
+    set_error("ps_lstm_f32: the last frame %lld lies outside the row (ldt=%d)", last_frame(a), a.ldt);
+    return PS_E_INVALID;
+  }
+  if (!states_ok(a)) {
+    set_error("ps_lstm_f32: ldq=%d < Q=%d", a.ldq, a.Q);
+    return PS_E_INVALID;
+  }
+  if (!shift_ok(a, 1)) {
+    set_error("ps_lstm_f32: state_shift must be 0 or 1");
+    return PS_E_INVALID;
+  }
+  const LstmPlan p = lstm_plan(a, f16x2);
+  {
+    LaunchTimer timer("lstm", (hipStream_t)stream);
+    hipLaunchKernelGGL(p.kernel, p.grid, p.block, p.lds, (hipStream_t)stream, LstmK{a});
+  }
+  return launch_status("ps_lstm_f32");
+}
+
+extern "C" int ps_lstm_f32(const ps_lstm_args* args, void* stream) { return lstm_launch(args, stream, false); }
+extern "C" int ps_lstm_f16x2_f32(const ps_lstm_args* args, void* stream) { return lstm_launch(args, stream, true); }
+
+extern "C" int ps_rnn_f32(const ps_lstm_args* args, int kind, const float* bhn, void* stream) {
+  if (!args || (kind != PS_RNN_TANH && kind != PS_RNN_GRU)) {
+    set_error("ps_rnn_f32: null args or unknown cell kind %d", kind);
+    return PS_E_INVALID;
+  }
+  const ps_lstm_args& a = *args;
+  const int ng = kind == PS_RNN_GRU ? 3 : 1;
+  if (!sizes_ok(a) || a.c0 || a.c_last || a.N > 65535 || !shift_ok(a, 0) || (kind == PS_RNN_GRU && !bhn)) {
+    set_error("ps_rnn_f32: bad argument (N=%d H=%d D=%d Q=%d steps=%d; no cell states, the GRU needs bhn)", a.N, a.H, a.D, a.Q, a.steps);
+    return PS_E_INVALID;
+  }
+  if (ng * a.H > 1024 || a.H * LS > 1024) {
+    set_error("ps_rnn_f32: hidden size %d is not supported (GRU: <= 256, RNN: <= 256)", a.H);
+    return PS_E_UNSUPPORTED;
+  }
+  if (last_frame(a) >= a.ldt || !states_ok(a)) {
+    set_error("ps_rnn_f32: a frame lies outside the row (ldt=%d) or ldq=%d < Q=%d", a.ldt, a.ldq, a.Q);
+    return PS_E_INVALID;
+  }
+  LstmK k{a};
+  const int rows = ng * a.H > a.H * LS ? ng * a.H : a.H * LS;
+  const int threads = (rows + 63) / 64 * 64;
+  const size_t lds = (size_t)(a.H + ng * a.H + a.H) * sizeof(f32x4);
+  dim3 grid((a.Q + LS - 1) / LS, a.N, a.D);
+  {
+    LaunchTimer timer("lstm", (hipStream_t)stream);
+    if (kind == PS_RNN_GRU)
+      hipLaunchKernelGGL((rnn_kernel<2>), grid, dim3(threads), lds, (hipStream_t)stream, k, bhn);
+    else
+      hipLaunchKernelGGL((rnn_kernel<0>), grid, dim3(threads), lds, (hipStream_t)stream, k, bhn);
+  }
+  return launch_status("ps_rnn_f32");
+}
+
+extern "C" int ps_lstm_fmajor_ok(const ps_lstm_args* args, int ldm) { return args && lstm_fmajor_fits(*args, ldm) ? 1 : 0; }
+
+extern "C" int ps_lstm_fmajor_f16x2_f32(const ps_lstm_args* args, int ldm, void* stream) {
+  if (!args || !lstm_fmajor_fits(*args, ldm)) {
+    set_error("ps_lstm_fmajor_f16x2_f32: H = 128, D = 1 or 2, no states, every frame inside the row, slabs below 2 GiB "
+              "(ps_lstm_fmajor_ok)");
+    return args ? PS_E_UNSUPPORTED : PS_E_INVALID;
+  }
+  const ps_lstm_args& a = *args;
+  LstmFm k{a, ldm, g_debug_ablate, (a.Q + 15) / 16, 0};
+  k.total = a.N * k.nblk;
+  // one workgroup per CU (148 KiB of LDS), the directions side by side; a multiple of 8 for the XCD-aware block order
+  int cap = device_cus() / a.D / 8 * 8;
+  cap = cap < 8 ? 8 : cap;
+  const int want = (k.total + 7) / 8 * 8;
+  dim3 grid((unsigned)(want < cap ? want : cap), 1, a.D);
+  {
+    LaunchTimer timer("lstm", (hipStream_t)stream);
+    // (PS_DBG_LSTM_4B_STORES: 4-byte h' stores for consecutive frames too; tests run both)
+    if (step_groups(a, false) && !dbg(PS_DBG_LSTM_4B_STORES))
+      hipLaunchKernelGGL((lstm_fm_f16x2_kernel<true>), grid, dim3(512), 0, (hipStream_t)stream, k);
+    else
+      hipLaunchKernelGGL((lstm_fm_f16x2_kernel<false>), grid, dim3(512), 0, (hipStream_t)stream, k);
+  }
+  return launch_status("ps_lstm_fmajor_f16x2_f32");
 }
 
 extern "C" int ps_lstm_fmajor_h256_ok(const ps_lstm_args* args, int ldm) { return args && lstm_h256_fits(*args, ldm) ? 1 : 0; }
@@ -1200,52 +1267,16 @@ extern "C" int ps_lstm_fmajor_h256_f16x2_f32(const ps_lstm_args* args, int ldm, 
   }
   const long long seqs = (long long)a.N * a.Q;
   dim3 grid((unsigned)((seqs + 15) / 16), 1, a.D);
-  const bool pairs = a.step_stride == 1 && a.q_stride % 2 == 0 && a.ldt % 2 == 0 && !((uintptr_t)a.hout & 7) &&
-                     (a.D == 1 || a.steps % 2 == 0) && !dbg(PS_DBG_LSTM_4B_STORES);
   {
     LaunchTimer timer("lstm", (hipStream_t)stream);
-    if (a.H == 256 && pairs)
-      hipLaunchKernelGGL((lstm_fm_h256_kernel<256, 2>), grid, dim3(512), 0, (hipStream_t)stream, k);
-    else if (a.H == 256)
-      hipLaunchKernelGGL((lstm_fm_h256_kernel<256, 1>), grid, dim3(512), 0, (hipStream_t)stream, k);
-    else if (pairs)
-      hipLaunchKernelGGL((lstm_fm_h256_kernel<192, 2>), grid, dim3(384), 0, (hipStream_t)stream, k);
-    else
-      hipLaunchKernelGGL((lstm_fm_h256_kernel<192, 1>), grid, dim3(384), 0, (hipStream_t)stream, k);
+    with_h256_variant(a.H, 0, store_pairs(a), [&](auto H, auto, auto PAIRS) {
+      hipLaunchKernelGGL((lstm_fm_h256_kernel<H(), PAIRS()>), grid, dim3(2 * H()), 0, (hipStream_t)stream, k);
+    });
   }
   return launch_status("ps_lstm_fmajor_h256_f16x2_f32");
 }
 
-// the cooperative kernel: the streamed kernel's shapes, few enough sequence groups that every slice of every group gets a CU
-// of its own at the same time (the group barrier spins: co-residency is a correctness condition, not a tuning choice)
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-__global__ __launch_bounds__(256) void zero_words_kernel(unsigned* p, int n) {
-  for (int i = threadIdx.x; i < n; i += 256) p[i] = 0u;
-}
-
-// waves per workgroup (= 16-unit row blocks per slice): 2 when the launch then still fits the chip -- more, smaller slices
-// measured faster per step with a handful of groups (the speaker LSTM: 9.5 ms against 13.6) -- else 4, else 0 (does not fit)
-static int lstm_coop_waves(const ps_lstm_args& a, int ldm, int* groups_out) {
-  if (!lstm_h256_fits(a, ldm) || a.steps < 2) return 0;
-  const long long groups = ((long long)a.N * a.Q + 15) / 16;
-  const long long rounds = (groups * a.D + 7) / 8 * 8;
-  if (groups_out) *groups_out = (int)groups;
-  if (rounds * (a.H / 32) <= device_cus()) return 2;
-  if (rounds * (a.H / 64) <= device_cus()) return 4;
-  // both directions do not fit at once: one launch per direction, if a direction does
-  if (a.D == 2 && (groups + 7) / 8 * 8 * (a.H / 64) <= device_cus()) return -4;
-  return 0;
-}
-
-extern "C" size_t ps_lstm_fmajor_coop_workspace_bytes(const ps_lstm_args* args, int ldm) {
-  int groups = 0;
-  int wv = args ? lstm_coop_waves(*args, ldm, &groups) : 0;
-  if (!wv) return 0;
-  wv = wv < 0 ? -wv : wv;
-  const size_t hx = align_up((size_t)2 * args->D * groups * 2 * 16 * (args->H + 8) * sizeof(_Float16), 256);
-  return hx + align_up((size_t)(args->D * groups * (2 + args->H / (16 * wv)) + 1) * sizeof(unsigned), 256);
-}
+extern "C" size_t ps_lstm_fmajor_coop_workspace_bytes(const ps_lstm_args* args, int ldm) { return args ? coop_layout(*args, ldm).bytes : 0; }
 
 extern "C" int ps_lstm_fmajor_coop_f16x2_f32(const ps_lstm_args* args, int ldm, const void* whh_image, const float* acc_scale,
                                              void* workspace, size_t workspace_bytes, void* stream) {
@@ -1253,466 +1284,35 @@ extern "C" int ps_lstm_fmajor_coop_f16x2_f32(const ps_lstm_args* args, int ldm, 
     set_error("ps_lstm_fmajor_coop_f16x2_f32: null argument, unaligned weight image or workspace (256 bytes)");
     return PS_E_INVALID;
   }
-  const size_t need = ps_lstm_fmajor_coop_workspace_bytes(args, ldm);
-  if (!need) {
+  const ps_lstm_args& a = *args;
+  const CoopLayout l = coop_layout(a, ldm);
+  if (!l.waves) {
     set_error("ps_lstm_fmajor_coop_f16x2_f32: ps_lstm_fmajor_h256_f16x2_f32's shapes with at most %d / (D * H / 64) groups of 16 "
               "sequences and at least two steps (ps_lstm_fmajor_coop_workspace_bytes = 0)", device_cus());
     return PS_E_UNSUPPORTED;
   }
-  if (workspace_bytes < need) {
-    set_error("ps_lstm_fmajor_coop_f16x2_f32: workspace too small (%zu < %zu)", workspace_bytes, need);
+  if (workspace_bytes < l.bytes) {
+    set_error("ps_lstm_fmajor_coop_f16x2_f32: workspace too small (%zu < %zu)", workspace_bytes, l.bytes);
     return PS_E_INVALID;
   }
-  const ps_lstm_args& a = *args;
-  int groups = 0;
-  int wv = lstm_coop_waves(a, ldm, &groups);
-  const bool per_direction = wv < 0;
-  wv = wv < 0 ? -wv : wv;
-  const size_t hx = align_up((size_t)2 * a.D * groups * 2 * 16 * (a.H + 8) * sizeof(_Float16), 256);
   LstmCoop k{a, ldm, whh_image, {acc_scale[0], a.D > 1 ? acc_scale[1] : acc_scale[0]}, (_Float16*)workspace,
-             (unsigned*)((char*)workspace + hx), groups, dbg(PS_DBG_COOP_AGENT_FENCES) ? 0 : 1, dbg(PS_DBG_COOP_SCATTER) ? 1 : 0,
-             dbg(PS_DBG_COOP_SABOTAGE) ? 1 : 0, 0, a.D, g_debug_ablate};
+             (unsigned*)((char*)workspace + l.hx_bytes), l.groups, dbg(PS_DBG_COOP_AGENT_FENCES) ? 0 : 1,
+             dbg(PS_DBG_COOP_SCATTER) ? 1 : 0, dbg(PS_DBG_COOP_SABOTAGE) ? 1 : 0, 0, a.D, g_debug_ablate};
   if (!(k.up[0] > 0.f) || !(k.up[1] > 0.f)) {
     set_error("ps_lstm_fmajor_coop_f16x2_f32: accumulator scales must be positive");
     return PS_E_INVALID;
   }
-  // (a kernel, not hipMemsetAsync: inside a replayed graph a memset node does not have to go through the L2 the counters'
-  //  atomics work in -- the first graph replays of this launch computed with the previous replay's counts)
-  hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, k.sync, (int)((need - hx) / sizeof(unsigned)));
+  hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, k.sync, (int)l.sync_words);
   {
     LaunchTimer timer("lstm", (hipStream_t)stream);
-    // clusters (direction, group) in rounds of 8, one per XCD; H / 32 slices each
-    for (int d0 = 0; d0 < (per_direction ? a.D : 1); ++d0) {
-    if (per_direction) k.d0 = d0, k.nd = 1;
-    dim3 grid((unsigned)((k.nd * groups + 7) / 8 * (a.H / (16 * wv)) * 8));
-    // (the streamed kernel's rule for 8-byte h' stores; PS_DBG_LSTM_4B_STORES keeps the 4-byte ones: tests run both)
-    const bool pairs = a.step_stride == 1 && a.q_stride % 2 == 0 && a.ldt % 2 == 0 && !((uintptr_t)a.hout & 7) &&
-                       (a.D == 1 || a.steps % 2 == 0) && !dbg(PS_DBG_LSTM_4B_STORES);
-#define PS_COOP(HH, WW)                                                                                            \
-  if (pairs)                                                                                                       \
-    hipLaunchKernelGGL((lstm_coop_kernel<HH, WW, 2>), grid, dim3(64 * WW), 0, (hipStream_t)stream, k);             \
-  else                                                                                                             \
-    hipLaunchKernelGGL((lstm_coop_kernel<HH, WW, 1>), grid, dim3(64 * WW), 0, (hipStream_t)stream, k);
-    if (a.H == 256 && wv == 2) {
-      PS_COOP(256, 2)
-    } else if (a.H == 256) {
-      PS_COOP(256, 4)
-    } else if (wv == 2) {
-      PS_COOP(192, 2)
-    } else {
-      PS_COOP(192, 4)
+    // clusters (direction, group) in rounds of 8, one per XCD; H / (16 waves) slices each
+    for (int d0 = 0; d0 < (l.per_direction ? a.D : 1); ++d0) {
+      if (l.per_direction) k.d0 = d0, k.nd = 1;
+      dim3 grid((unsigned)((k.nd * l.groups + 7) / 8 * (a.H / (16 * l.waves)) * 8));
+      with_h256_variant(a.H, l.waves, store_pairs(a), [&](auto H, auto WAVES, auto PAIRS) {
+        hipLaunchKernelGGL((lstm_coop_kernel<H(), WAVES(), PAIRS()>), grid, dim3(64 * WAVES()), 0, (hipStream_t)stream, k);
+      });
     }
-    }
-#undef PS_COOP
   }
   return launch_status("ps_lstm_fmajor_coop_f16x2_f32");
-}
-
-extern "C" int ps_lstm_fmajor_ok(const ps_lstm_args* args, int ldm) { return args && lstm_fmajor_fits(*args, ldm) ? 1 : 0; }
-
-extern "C" int ps_lstm_fmajor_f16x2_f32(const ps_lstm_args* args, int ldm, void* stream) {
-  if (!args || !lstm_fmajor_fits(*args, ldm)) {
-    set_error("ps_lstm_fmajor_f16x2_f32: H = 128, D = 1 or 2, no states, every frame inside the row, slabs below 2 GiB "
-              "(ps_lstm_fmajor_ok)");
-    return args ? PS_E_UNSUPPORTED : PS_E_INVALID;
-  }
-  const ps_lstm_args& a = *args;
-  LstmFm k{a, ldm, g_debug_ablate, (a.Q + 15) / 16, 0};
-  k.total = a.N * k.nblk;
-  // one workgroup per CU (148 KiB of LDS), the directions side by side; a multiple of 8 for the XCD-aware block order
-  int cap = device_cus() / a.D / 8 * 8;
-  cap = cap < 8 ? 8 : cap;
-  const int want = (k.total + 7) / 8 * 8;
-  dim3 grid((unsigned)(want < cap ? want : cap), 1, a.D);
-  const int sp = (a.steps + 3) / 4 * 4;
-  const bool contig = a.step_stride == 1 && a.q_stride % 4 == 0 && a.ldt % 4 == 0 && !((uintptr_t)a.hout & 15) &&
-                      (a.steps % 4 == 0 || (a.D == 1 && (long long)(a.Q - 1) * a.q_stride + sp <= a.ldt)) &&
-                      !dbg(PS_DBG_LSTM_4B_STORES);  // (PS_DBG_LSTM_4B_STORES: 4-byte h' stores for consecutive frames too; tests run both)
-  {
-    LaunchTimer timer("lstm", (hipStream_t)stream);
-    if (contig)
-      hipLaunchKernelGGL((lstm_fm_f16x2_kernel<true>), grid, dim3(512), 0, (hipStream_t)stream, k);
-    else
-      hipLaunchKernelGGL((lstm_fm_f16x2_kernel<false>), grid, dim3(512), 0, (hipStream_t)stream, k);
-  }
-  return launch_status("ps_lstm_fmajor_f16x2_f32");
-}
-
-extern "C" int ps_rnn_f32(const ps_lstm_args* args, int kind, const float* bhn, void* stream) {
-  if (!args || (kind != PS_RNN_TANH && kind != PS_RNN_GRU)) {
-    set_error("ps_rnn_f32: null args or unknown cell kind %d", kind);
-    return PS_E_INVALID;
-  }
-  const ps_lstm_args& a = *args;
-  const int ng = kind == PS_RNN_GRU ? 3 : 1;
-  if (!a.gx || !a.whh_t || !a.hout || a.c0 || a.c_last || a.N <= 0 || a.H <= 0 || a.D < 1 || a.D > 2 || a.Q <= 0 || a.steps <= 0 ||
-      a.q_stride < 0 || a.step_stride < 0 || a.ldt <= 0 || a.N > 65535 || a.state_shift != 0 || (kind == PS_RNN_GRU && !bhn)) {
-    set_error("ps_rnn_f32: bad argument (N=%d H=%d D=%d Q=%d steps=%d; no cell states, the GRU needs bhn)", a.N, a.H, a.D, a.Q, a.steps);
-    return PS_E_INVALID;
-  }
-  if (ng * a.H > 1024 || a.H * LS > 1024) {
-    set_error("ps_rnn_f32: hidden size %d is not supported (GRU: <= 256, RNN: <= 256)", a.H);
-    return PS_E_UNSUPPORTED;
-  }
-  if ((long long)(a.Q - 1) * a.q_stride + (long long)(a.steps - 1) * a.step_stride >= a.ldt ||
-      ((a.h0 || a.h_last) && a.ldq < a.Q)) {
-    set_error("ps_rnn_f32: a frame lies outside the row (ldt=%d) or ldq=%d < Q=%d", a.ldt, a.ldq, a.Q);
-    return PS_E_INVALID;
-  }
-  LstmK k{a};
-  const int rows = ng * a.H > a.H * LS ? ng * a.H : a.H * LS;
-  const int threads = (rows + 63) / 64 * 64;
-  const size_t lds = (size_t)(a.H + ng * a.H + a.H) * sizeof(f32x4);
-  dim3 grid((a.Q + LS - 1) / LS, a.N, a.D);
-  {
-    LaunchTimer timer("lstm", (hipStream_t)stream);
-    if (kind == PS_RNN_GRU)
-      hipLaunchKernelGGL((rnn_kernel<2>), grid, dim3(threads), lds, (hipStream_t)stream, k, bhn);
-    else
-      hipLaunchKernelGGL((rnn_kernel<0>), grid, dim3(threads), lds, (hipStream_t)stream, k, bhn);
-  }
-  return launch_status("ps_rnn_f32");
-}
-
-extern "C" int ps_lstm_f32(const ps_lstm_args* args, void* stream) { return lstm_launch(args, stream, false); }
-
-extern "C" int ps_lstm_f16x2_f32(const ps_lstm_args* args, void* stream) { return lstm_launch(args, stream, true); }
-
-static int lstm_launch(const ps_lstm_args* args, void* stream, bool f16x2) {
-  if (!args) {
-    set_error("ps_lstm_f32: null args");
-    return PS_E_INVALID;
-  }
-  const ps_lstm_args& a = *args;
-  if (!a.gx || !a.whh_t || !a.hout || a.N <= 0 || a.H <= 0 || a.D < 1 || a.D > 2 || a.Q <= 0 || a.steps <= 0 ||
-      a.q_stride < 0 || a.step_stride < 0 || a.ldt <= 0 || a.N > 65535) {
-    set_error("ps_lstm_f32: bad argument (N=%d H=%d D=%d Q=%d steps=%d)", a.N, a.H, a.D, a.Q, a.steps);
-    return PS_E_INVALID;
-  }
-  if (4 * a.H > 1024) {
-    set_error("ps_lstm_f32: hidden size %d > 256 is not supported", a.H);
-    return PS_E_UNSUPPORTED;
-  }
-  const long long last = (long long)(a.Q - 1) * a.q_stride + (long long)(a.steps - 1) * a.step_stride;
-  if (last >= a.ldt) {
-    set_error("ps_lstm_f32: the last frame %lld lies outside the row (ldt=%d)", last, a.ldt);
-    return PS_E_INVALID;
-  }
-  if ((a.h0 || a.c0 || a.h_last || a.c_last) && a.ldq < a.Q) {
-    set_error("ps_lstm_f32: ldq=%d < Q=%d", a.ldq, a.Q);
-    return PS_E_INVALID;
-  }
-  if (a.state_shift != 0 && a.state_shift != 1) {
-    set_error("ps_lstm_f32: state_shift must be 0 or 1");
-    return PS_E_INVALID;
-  }
-  LstmK k{a};
-  const int threads = (4 * a.H + 63) / 64 * 64;
-  const size_t lds = (size_t)5 * a.H * sizeof(f32x4);
-  dim3 grid((a.Q + LS - 1) / LS, a.N, a.D);
-  if ((a.H == 64 || a.H == 128) && !dbg(PS_DBG_LSTM_SCALAR)) {
-    const long long seqs = (long long)a.N * a.Q;
-    // 16-byte step groups: steps are consecutive frames starting on a 16-byte boundary.  A forward-only pass may end
-    // in a partial group: it reads / writes up to 3 frames past its last step, which must still lie inside the row
-    // (pad frames; they are never read as data).  Without the groups a long pass over consecutive frames re-fetches
-    // every 128-byte line of the gate pre-activations once per step (DPCRN's inter pass: 10.8 ms instead of ~3).
-    const int steps4 = (a.steps + 3) / 4 * 4;
-    const bool tail_ok = a.steps % 4 == 0 || (a.D == 1 && (long long)(a.Q - 1) * a.q_stride + steps4 <= a.ldt);
-    const bool contig = a.step_stride == 1 && tail_ok && a.q_stride % 4 == 0 && a.ldt % 4 == 0 &&
-                        !((uintptr_t)a.gx & 15) && !((uintptr_t)a.hout & 15);
-    // 16 sequences per workgroup when there are enough sequences to fill the chip that way (PS_DBG_LSTM_WIDE / _M4 force one)
-    const bool wide = dbg(PS_DBG_LSTM_WIDE) ? true : dbg(PS_DBG_LSTM_M4) ? false : (a.H == 64 && contig && seqs >= 16 * 256);
-    LaunchTimer timer("lstm", (hipStream_t)stream);
-    if (wide) {
-      dim3 mgrid((unsigned)((seqs + 15) / 16), 1, a.D);
-      // whole segments of 20 consecutive frames (DPRNN's intra pass at K = 20): all steps fetched up front
-      const bool seg = a.H == 64 && contig && a.steps == 20 && !dbg(PS_DBG_LSTM_4B_STORES);
-      if (seg && f16x2 && a.D == 1)
-        hipLaunchKernelGGL((lstm_seg_f16x2_kernel<64, 20, false>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
-      else if (seg && f16x2)
-        hipLaunchKernelGGL((lstm_seg_f16x2_kernel<64, 20, true>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
-      else if (seg && a.D == 1)
-        hipLaunchKernelGGL((lstm_seg_kernel<64, 20, false>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
-      else if (seg)
-        hipLaunchKernelGGL((lstm_seg_kernel<64, 20, true>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
-      else if (a.H == 64 && contig)
-        hipLaunchKernelGGL((lstm_mfma_kernel<64, true>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
-      else if (a.H == 64)
-        hipLaunchKernelGGL((lstm_mfma_kernel<64, false>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
-      else  // H = 128: the 16-byte group path does not fit the 256-VGPR budget of 8 waves
-        hipLaunchKernelGGL((lstm_mfma_kernel<128, false>), mgrid, dim3(512), 0, (hipStream_t)stream, k);
-    } else {
-      dim3 mgrid((unsigned)(((seqs + 3) / 4 + 7) / 8 * 8), 1, a.D);  // multiple of 8: see the XCD-aware group order
-      if (a.H == 64 && contig)
-        hipLaunchKernelGGL((lstm_m4_kernel<64, true>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
-      else if (a.H == 64 && f16x2 && !dbg(PS_DBG_LSTM_4B_STORES))
-        hipLaunchKernelGGL(lstm_m4_f16x2_kernel, mgrid, dim3(256), 0, (hipStream_t)stream, k);
-      else if (a.H == 64)
-        hipLaunchKernelGGL((lstm_m4_kernel<64, false>), mgrid, dim3(256), 0, (hipStream_t)stream, k);
-      else if (contig)
-        hipLaunchKernelGGL((lstm_m4_kernel<128, true>), mgrid, dim3(512), 0, (hipStream_t)stream, k);
-      else
-        hipLaunchKernelGGL((lstm_m4_kernel<128, false>), mgrid, dim3(512), 0, (hipStream_t)stream, k);
-    }
-    return launch_status("ps_lstm_f32");
-  }
-  {
-    LaunchTimer timer("lstm", (hipStream_t)stream);
-    if (a.H <= LSTM_WREG)
-      hipLaunchKernelGGL((lstm_kernel<true>), grid, dim3(threads), lds, (hipStream_t)stream, k);
-    else
-      hipLaunchKernelGGL((lstm_kernel<false>), grid, dim3(threads), lds, (hipStream_t)stream, k);
-  }
-  return launch_status("ps_lstm_f32");
-}
-
-extern "C" int ps_chan_layernorm_f32(const float* x, const float* gamma, const float* beta, float eps,
-                                     const float* prelu_slope, int sigmoid, const float* mul, const float* res,
-                                     float* y, int N, int C, int T, int ldt, void* stream) {
-  if (!x || !gamma || !beta || !y || N <= 0 || C <= 0 || T <= 0 || ldt < T || N > 65535) {
-    set_error("ps_chan_layernorm_f32: bad argument (N=%d C=%d T=%d ldt=%d)", N, C, T, ldt);
-    return PS_E_INVALID;
-  }
-  ClnArgs a{x, gamma, beta, res, prelu_slope, mul, y, eps, sigmoid, C, T, ldt};
-  {
-    LaunchTimer timer("chan_layernorm", (hipStream_t)stream);
-    // few frames (streaming step, state rows): split the channels 16 ways instead of 4 to shorten the serial walk
-    if ((long long)((T + 63) / 64) * N < 64)
-      hipLaunchKernelGGL((chan_layernorm_kernel<16>), dim3((T + 63) / 64, N), dim3(1024), 0, (hipStream_t)stream, a);
-    else if (C <= 64 && !dbg(PS_DBG_CHAN_LN_THREE_PASS))  // (else the three-pass kernel; tests run both)
-      hipLaunchKernelGGL((chan_layernorm_reg_kernel<16>), dim3((T + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, a);
-    else if (C <= 128 && !dbg(PS_DBG_CHAN_LN_THREE_PASS))
-      hipLaunchKernelGGL((chan_layernorm_reg_kernel<32>), dim3((T + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, a);
-    else if (C <= 256 && !dbg(PS_DBG_CHAN_LN_THREE_PASS))
-      hipLaunchKernelGGL((chan_layernorm_reg_kernel<64>), dim3((T + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, a);
-    else
-      hipLaunchKernelGGL((chan_layernorm_kernel<4>), dim3((T + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, a);
-  }
-  return launch_status("ps_chan_layernorm_f32");
-}
-
-extern "C" int ps_film_apply_f32(const float* x, const float* scale_bias, float* y, int N, int C, int T, int ldt,
-                                 void* stream) {
-  if (!x || !scale_bias || !y || N <= 0 || C <= 0 || T <= 0 || ldt < T || C > 65535 || N > 65535) {
-    set_error("ps_film_apply_f32: bad argument (N=%d C=%d T=%d ldt=%d)", N, C, T, ldt);
-    return PS_E_INVALID;
-  }
-  if (ldt % 4 || ((uintptr_t)x & 15) || ((uintptr_t)scale_bias & 15) || ((uintptr_t)y & 15)) {
-    set_error("ps_film_apply_f32: rows must be 16-byte aligned");
-    return PS_E_ALIGN;
-  }
-  {
-    LaunchTimer timer("film_apply", (hipStream_t)stream);
-    hipLaunchKernelGGL(film_apply_kernel, dim3((T + 1023) / 1024, C, N), dim3(256), 0, (hipStream_t)stream, x,
-                       scale_bias, y, C, T, ldt);
-  }
-  return launch_status("ps_film_apply_f32");
-}
-
-extern "C" int ps_lstm_cell_f32(const float* gates, float* c, float* h, int N, int H, int D, int T, int ld_gates,
-                                int ld_state, void* stream) {
-  if (!gates || !c || !h || N <= 0 || H <= 0 || D < 1 || D > 2 || T <= 0 || ld_gates < T || ld_state < T ||
-      (long long)N * D > 65535) {
-    set_error("ps_lstm_cell_f32: bad argument (N=%d H=%d D=%d T=%d)", N, H, D, T);
-    return PS_E_INVALID;
-  }
-  {
-    LaunchTimer timer("lstm_cell", (hipStream_t)stream);
-    hipLaunchKernelGGL(lstm_cell_kernel, dim3((T + 63) / 64, (H + 3) / 4, N * D), dim3(256), 0, (hipStream_t)stream,
-                       gates, c, h, H, T, ld_gates, ld_state);
-  }
-  return launch_status("ps_lstm_cell_f32");
-}
-
-// ---- GatedTCN pieces (conv_tasnet.py:129-215) -----------------------------------------------------------------
-namespace ps {
-
-// Unfold a dense dilated convolution into a 1x1 one: row (j, k) of the output is input channel k shifted by tap j
-// (zero outside [0, T)), so W[m][k][j] becomes a plain [M][P*Kc] matrix for ps_conv1x1_f32.  Optional per-(utterance,
-// channel) FiLM scale/shift applied before the zero padding, and E constant embedding rows appended per tap (the
-// reference concatenates the repeated embedding BEFORE F.conv1d pads, so its taps drop out at the edges too).
-__global__ __launch_bounds__(256) void unfold_taps_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                          const float* __restrict__ scale,
-                                                          const float* __restrict__ shift,
-                                                          const float* __restrict__ embed, int K, int E, int T, int T_out,
-                                                          int ldt, int P, int dilation, int left) {
-  // T = valid input frames, T_out >= T = output frames (the causal gated block of the reference pads both sides and
-  // trims only after its output conv: its norms see T + padding frames, conv_tasnet.py:203-211)
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int row = blockIdx.y;  // j * (K + E) + k
-  const int n = blockIdx.z;
-  const int Kc = K + E;
-  const int j = row / Kc, k = row % Kc;
-  if (t >= T_out) return;
-  const int src = t + j * dilation - left;
-  float v = 0.f;
-  if (src >= 0 && src < T) {
-    if (k < K) {
-      v = x[((size_t)n * K + k) * ldt + src];
-      if (scale) v = v * scale[(size_t)n * K + k] + shift[(size_t)n * K + k];
-    } else {
-      v = embed[(size_t)n * E + (k - K)];
-    }
-  }
-  y[((size_t)n * P * Kc + row) * ldt + t] = v;
-}
-
-struct GateArgs {
-  const float* l;
-  const float* r;
-  float* y;
-  ps_prologue pl, pr;
-  int H, T, ldt;
-};
-
-// y = PReLU(norm(l)) * sigmoid(PReLU(norm(r))): the two branch tails of the gated block, norms gLN / folded bN1d.
-__global__ __launch_bounds__(256) void gated_product_kernel(GateArgs a) {
-  __shared__ double red[8];
-  const int n = blockIdx.z, ch = blockIdx.y;
-  const NormScalars nl = load_norm_scalars(a.pl, n, red);
-  const NormScalars nr = load_norm_scalars(a.pr, n, red);
-  const int t = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (t >= a.T) return;
-  const float scl = a.pl.norm != PS_NORM_NONE ? a.pl.gamma[ch] * nl.rstd : 1.f;
-  const float shl = (a.pl.norm != PS_NORM_NONE ? a.pl.beta[ch] : 0.f) - nl.mean * scl;
-  const float scr = a.pr.norm != PS_NORM_NONE ? a.pr.gamma[ch] * nr.rstd : 1.f;
-  const float shr = (a.pr.norm != PS_NORM_NONE ? a.pr.beta[ch] : 0.f) - nr.mean * scr;
-  const float sl = a.pl.prelu ? a.pl.slope[0] : 1.f, sr = a.pr.prelu ? a.pr.slope[0] : 1.f;
-  const size_t off = ((size_t)n * a.H + ch) * a.ldt + t;
-  const f32x4 lv = *reinterpret_cast<const f32x4*>(a.l + off);
-  const f32x4 rv = *reinterpret_cast<const f32x4*>(a.r + off);
-  f32x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float lf = prelu(lv[e] * scl + shl, sl);
-    const float rf = prelu(rv[e] * scr + shr, sr);
-    o[e] = lf * sigmoidf_(rf);
-  }
-  *reinterpret_cast<f32x4*>(a.y + off) = o;
-}
-
-}  // namespace ps
-
-extern "C" int ps_unfold_taps_f32(const float* x, float* y, int N, int K, int T, int ldt, int P, int dilation, int left,
-                                  const float* scale, const float* shift, const float* embed, int E, void* stream) {
-  return ps_unfold_taps_out_f32(x, y, N, K, T, T, ldt, P, dilation, left, scale, shift, embed, E, stream);
-}
-
-extern "C" int ps_unfold_taps_out_f32(const float* x, float* y, int N, int K, int T, int T_out, int ldt, int P,
-                                      int dilation, int left, const float* scale, const float* shift,
-                                      const float* embed, int E, void* stream) {
-  if (!x || !y || N <= 0 || K <= 0 || T <= 0 || T_out < T || ldt < T_out || P <= 0 || dilation <= 0 || left < 0 || E < 0 ||
-      (E > 0 && !embed) || ((scale == nullptr) != (shift == nullptr)) || (long long)P * (K + E) > 65535 || N > 65535) {
-    set_error("ps_unfold_taps_f32: bad argument (N=%d K=%d T=%d P=%d dilation=%d left=%d E=%d)", N, K, T, P, dilation,
-              left, E);
-    return PS_E_INVALID;
-  }
-  {
-    LaunchTimer timer("unfold_taps", (hipStream_t)stream);
-    hipLaunchKernelGGL(unfold_taps_kernel, dim3((T_out + 255) / 256, P * (K + E), N), dim3(256), 0, (hipStream_t)stream,
-                       x, y, scale, shift, embed, K, E, T, T_out, ldt, P, dilation, left);
-  }
-  return launch_status("ps_unfold_taps_f32");
-}
-
-static int check_gate_prologue(const ps_prologue& p, const char* side) {
-  if (p.norm != PS_NORM_NONE && (!p.gamma || !p.beta)) {
-    set_error("ps_gated_product_f32: %s norm needs gamma/beta", side);
-    return PS_E_INVALID;
-  }
-  if (p.norm == PS_NORM_GLOBAL && (!p.stats || p.parts <= 0 || p.count <= 0)) {
-    set_error("ps_gated_product_f32: %s PS_NORM_GLOBAL needs stats/parts/count", side);
-    return PS_E_INVALID;
-  }
-  if (p.prelu && !p.slope) {
-    set_error("ps_gated_product_f32: %s prelu needs slope", side);
-    return PS_E_INVALID;
-  }
-  return 0;
-}
-
-extern "C" int ps_gated_product_f32(const float* left, const float* right, float* y, int N, int H, int T, int ldt,
-                                    const ps_prologue* pro_left, const ps_prologue* pro_right, void* stream) {
-  if (!left || !right || !y || !pro_left || !pro_right || N <= 0 || H <= 0 || T <= 0 || ldt < T || H > 65535 ||
-      N > 65535) {
-    set_error("ps_gated_product_f32: bad argument (N=%d H=%d T=%d ldt=%d)", N, H, T, ldt);
-    return PS_E_INVALID;
-  }
-  if (ldt % 4 || ((uintptr_t)left & 15) || ((uintptr_t)right & 15) || ((uintptr_t)y & 15)) {
-    set_error("ps_gated_product_f32: rows must be 16-byte aligned");
-    return PS_E_ALIGN;
-  }
-  int rc = check_gate_prologue(*pro_left, "left");
-  if (rc) return rc;
-  rc = check_gate_prologue(*pro_right, "right");
-  if (rc) return rc;
-  GateArgs a{left, right, y, *pro_left, *pro_right, H, T, ldt};
-  {
-    LaunchTimer timer("gated_product", (hipStream_t)stream);
-    hipLaunchKernelGGL(gated_product_kernel, dim3((T + 1023) / 1024, H, N), dim3(256), 0, (hipStream_t)stream, a);
-  }
-  return launch_status("ps_gated_product_f32");
-}
-
-// ---- 50 % overlapped segmentation (SplitMerge.split / merge, lobe/trivial.py:178-241; SkiM.split / merge) ------------
-namespace ps {
-
-// mode 0 (split): dst frame s*K + k <- src frame (s/2)*K + k + (s&1)*K/2 - K/2 (zero outside [0, T_src))
-// mode 1 (merge): dst frame t <- (src[even cover] + src[odd cover]) / 2
-__global__ __launch_bounds__(256) void segment_overlap_kernel(const float* __restrict__ src, float* __restrict__ dst,
-                                                              int T_src, int ld_src, int T_dst, int ld_dst, int K,
-                                                              int mode) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  const size_t row = blockIdx.y;
-  if (f >= T_dst) return;
-  const float* s = src + row * ld_src;
-  const int stride = K / 2;
-  float v;
-  if (mode == 0) {
-    const int seg = f / K, k = f % K;
-    const int t = (seg >> 1) * K + k + (seg & 1) * stride - stride;
-    v = (t >= 0 && t < T_src) ? s[t] : 0.f;
-  } else {
-    const int e = stride + f;
-    const int fa = (2 * (e / K)) * K + e % K;
-    const int fb = (2 * (f / K) + 1) * K + f % K;
-    v = (s[fa] + s[fb]) * 0.5f;
-  }
-  dst[row * ld_dst + f] = v;
-}
-
-}  // namespace ps
-
-extern "C" int ps_segment_overlap_f32(const float* src, float* dst, int64_t rows, int T_src, int ld_src, int T_dst,
-                                      int ld_dst, int K, int merge, void* stream) {
-  if (!src || !dst || rows <= 0 || rows > 65535 * 32768LL || T_src <= 0 || T_dst <= 0 || ld_src < T_src ||
-      ld_dst < T_dst || K < 2) {
-    set_error("ps_segment_overlap_f32: bad argument");
-    return PS_E_INVALID;
-  }
-  const int stride = K / 2;
-  if (!merge) {
-    // every source index the split reads is checked in the kernel; the destination must be whole segment pairs
-    if (T_dst % (2 * K)) {
-      set_error("ps_segment_overlap_f32: split destination must hold an even number of %d-frame segments", K);
-      return PS_E_INVALID;
-    }
-  } else {
-    // the last merged frame reads even-stream index stride + T_dst - 1 and odd-stream index T_dst - 1
-    const long long e = (long long)stride + T_dst - 1;
-    const long long fa = (2 * (e / K)) * K + e % K, fb = (2LL * ((T_dst - 1) / K) + 1) * K + (T_dst - 1) % K;
-    if (fa >= T_src || fb >= T_src) {
-      set_error("ps_segment_overlap_f32: merge source is too short (%d frames)", T_src);
-      return PS_E_INVALID;
-    }
-  }
-  using namespace ps;
-  LaunchTimer timer("segment_overlap", (hipStream_t)stream);
-  const int64_t chunk = 65535;
-  for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
-    const int64_t nr = rows - r0 < chunk ? rows - r0 : chunk;
-    hipLaunchKernelGGL(segment_overlap_kernel, dim3((T_dst + 255) / 256, (unsigned)nr), dim3(256), 0,
-                       (hipStream_t)stream, src + r0 * ld_src, dst + r0 * ld_dst, T_src, ld_src, T_dst, ld_dst, K, merge);
-  }
-  return launch_status("ps_segment_overlap_f32");
 }

@@ -457,12 +457,30 @@ def attn_weights(logits: torch.Tensor, t: int, lengths: Optional[torch.Tensor] =
     return out
 
 
-def _lstm_state_args(who: str, a: LstmArgs, n: int, rows: int, q: int, h0, c0, want_state: bool, state_out, device):
-    """Fills a.h0 / c0 / h_last / c_last / ldq of an LSTM launch; returns the final-state pair (h, c) or None.  All state
-    tensors of one launch share the row stride ldq (the kernels read and write every one of them with it)."""
+COOP_LSTM = os.environ.get("PS_COOP_LSTM", "1") != "0"   # 0: always the streamed-weight kernel
+_COOP_LAST = [None]
+RNN_KINDS = {"RNN": 0, "GRU": 2}
+
+
+def _require_operand(who: str, device: torch.device, dtype: torch.dtype = torch.float32, **tensors) -> None:
+    """Tensors whose pointers go into ps_lstm_args or the call: on the input's device, `dtype`, contiguous.  Anything else
+    reaches the kernel as a wild pointer: a GPU fault, not an error."""
+    for name, t in tensors.items():
+        if t is not None and (t.device != device or t.dtype != dtype or not t.is_contiguous()):
+            raise RuntimeError(f"{who}: {name} must be a contiguous {dtype} tensor on {device} "
+                               f"(got {t.dtype} on {t.device}, strides {tuple(t.stride())})")
+
+
+def _lstm_state_args(who: str, a: LstmArgs, n: int, rows: int, q: int, h0, c0, want_state: bool, state_out, device,
+                     cell: bool = True):
+    """Fills a.h0 / c0 / h_last / c_last / ldq of a launch; returns the final-state pair (h, c) or None (cell = False, the
+    RNN / GRU: no c).  All state tensors of one launch share the row stride ldq (the kernels read and write every one of
+    them with it)."""
     ldq = padded_frames(q)
-    for name, t in (("h0", h0), ("c0", c0)):
-        if t is not None and (tuple(t.shape[:2]) != (n, rows) or t.shape[2] < q or not t.is_contiguous()):
+    h_last, c_last = state_out if state_out is not None else (None, None)
+    _require_operand(who, device, h0=h0, c0=c0, state_out_h=h_last, state_out_c=c_last)
+    for name, t in (("h0", h0), ("c0", c0), ("state_out[0]", h_last), ("state_out[1]", c_last)):
+        if t is not None and (t.dim() != 3 or tuple(t.shape[:2]) != (n, rows) or t.shape[2] < q):
             raise RuntimeError(f"{who}: {name} must be a contiguous state tensor [N, D*H, ldq >= Q]")
     if h0 is not None:
         ldq = h0.shape[2]
@@ -470,18 +488,40 @@ def _lstm_state_args(who: str, a: LstmArgs, n: int, rows: int, q: int, h0, c0, w
         ldq = c0.shape[2]
     if (h0 is not None and c0 is not None) and h0.shape[2] != c0.shape[2]:
         raise RuntimeError(f"{who}: h0 and c0 must share ldq")
-    h_last = c_last = None
     if state_out is not None:
-        h_last, c_last = state_out
-        if h_last.shape[2] != ldq and (h0 is not None or c0 is not None):
+        if (h_last.shape[2] != ldq and (h0 is not None or c0 is not None)) or c_last.shape[2] != h_last.shape[2]:
             raise RuntimeError(f"{who}: state_out must share ldq with h0/c0")
         ldq = h_last.shape[2]
     elif want_state:
         h_last = torch.zeros(n, rows, ldq, dtype=torch.float32, device=device)
-        c_last = torch.zeros_like(h_last)
+        c_last = torch.zeros_like(h_last) if cell else None
     a.h0, a.c0, a.h_last, a.c_last = ptr(h0), ptr(c0), ptr(h_last), ptr(c_last)
     a.ldq = ldq
     return (h_last, c_last) if h_last is not None else None
+
+
+def _lstm_args(who: str, gx: torch.Tensor, n: int, ldt: int, whh_t, out, hidden: int, dirs: int, walk: tuple, h0=None, c0=None,
+               want_state: bool = False, state_shift: int = 0, state_out=None, cell: bool = True):
+    """The ps_lstm_args of every recurrence launch -> (args, hout, final states or None).  walk = (Q, q_stride, steps,
+    step_stride); out: where hout [N, D*H, ldt] goes (None = a new tensor)."""
+    _require_operand(who, gx.device, whh_t=whh_t, out=out)
+    hout = out if out is not None else torch.empty(n, dirs * hidden, ldt, dtype=torch.float32, device=gx.device)
+    if tuple(hout.shape) != (n, dirs * hidden, ldt):
+        raise RuntimeError(f"{who}: out must be a contiguous [N, D*H, ldt] tensor")
+    a = LstmArgs()
+    a.gx, a.whh_t, a.hout = ptr(gx), ptr(whh_t), ptr(hout)
+    a.N, a.H, a.D, a.ldt, a.state_shift = n, hidden, dirs, ldt, state_shift
+    a.Q, a.q_stride, a.steps, a.step_stride = walk
+    state = _lstm_state_args(who, a, n, dirs * hidden, walk[0], h0, c0, want_state, state_out, gx.device, cell)
+    return a, hout, state
+
+
+def _frame_rows(who: str, gx_fm: torch.Tensor) -> int:
+    """ldm of frame-major gate pre-activations [N, ldt, D*4H]: the frames may be padded rows (stride(1) >= D*4H)"""
+    ldm = gx_fm.stride(1)
+    if gx_fm.stride(2) != 1 or gx_fm.stride(0) != gx_fm.shape[1] * ldm:
+        raise RuntimeError(f"{who}: gx must be a [N, ldt, :D*4H] view of contiguous frame rows")
+    return ldm
 
 
 def lstm(gx: torch.Tensor, whh_t: torch.Tensor, hidden: int, dirs: int, q: int, q_stride: int, steps: int,
@@ -495,22 +535,14 @@ def lstm(gx: torch.Tensor, whh_t: torch.Tensor, hidden: int, dirs: int, q: int, 
     n, rows, ldt = gx.shape
     if rows != dirs * 4 * hidden or tuple(whh_t.shape) != (dirs, hidden, 4 * hidden):
         raise RuntimeError("lstm: gx must be [N, D*4H, ldt] and whh_t [D, H, 4H]")
-    hout = out if out is not None else torch.empty(n, dirs * hidden, ldt, dtype=torch.float32, device=gx.device)
-    if tuple(hout.shape) != (n, dirs * hidden, ldt) or not hout.is_contiguous():
-        raise RuntimeError("lstm: out must be a contiguous [N, D*H, ldt] tensor")
-    a = LstmArgs()
-    a.gx, a.whh_t, a.hout = ptr(gx), ptr(whh_t), ptr(hout)
-    state = _lstm_state_args("lstm", a, n, dirs * hidden, q, h0, c0, want_state, state_out, gx.device)
-    a.N, a.H, a.D, a.Q, a.q_stride, a.steps, a.step_stride = n, hidden, dirs, q, q_stride, steps, step_stride
-    a.ldt, a.state_shift = ldt, state_shift
+    _require_operand("lstm", gx.device, gx=gx)
+    a, hout, state = _lstm_args("lstm", gx, n, ldt, whh_t, out, hidden, dirs, (q, q_stride, steps, step_stride), h0, c0,
+                                want_state, state_shift, state_out)
     if f16x2:
         check(lib().ps_lstm_f16x2_f32(C.byref(a), stream_ptr(gx.device)), "ps_lstm_f16x2_f32")
     else:
         check(lib().ps_lstm_f32(C.byref(a), stream_ptr(gx.device)), "ps_lstm_f32")
     return hout, state
-
-
-RNN_KINDS = {"RNN": 0, "GRU": 2}
 
 
 def rnn(gx: torch.Tensor, whh_t: torch.Tensor, kind: str, hidden: int, dirs: int, q: int, q_stride: int, steps: int,
@@ -523,39 +555,18 @@ def rnn(gx: torch.Tensor, whh_t: torch.Tensor, kind: str, hidden: int, dirs: int
     g = (3 if kind == "GRU" else 1) * hidden
     if kind not in RNN_KINDS or rows != dirs * g or tuple(whh_t.shape) != (dirs, hidden, g):
         raise RuntimeError("rnn: kind RNN / GRU, gx [N, D*G, ldt], whh_t [D, H, G]")
-    if bhn is not None and (tuple(bhn.shape) != (dirs, hidden) or not bhn.is_contiguous()):
+    _require_operand("rnn", gx.device, gx=gx, bhn=bhn)
+    if bhn is not None and tuple(bhn.shape) != (dirs, hidden):
         raise RuntimeError("rnn: bhn must be a contiguous [D, H] tensor")
-    ldq = 0
-    if h0 is not None:
-        require_device(h0, "rnn")
-        if h0.dim() != 3 or tuple(h0.shape[:2]) != (n, dirs * hidden) or h0.shape[2] < q or not h0.is_contiguous():
-            raise RuntimeError("rnn: h0 must be a contiguous state tensor [N, D*H, ldq >= Q]")
-        ldq = h0.shape[2]
-    h_last = None
-    if want_state:
-        ldq = ldq or padded_frames(q)
-        h_last = torch.zeros(n, dirs * hidden, ldq, dtype=torch.float32, device=gx.device)
-    hout = torch.empty(n, dirs * hidden, ldt, dtype=torch.float32, device=gx.device)
-    a = LstmArgs()
-    a.gx, a.whh_t, a.hout = ptr(gx), ptr(whh_t), ptr(hout)
-    a.h0, a.h_last = ptr(h0), ptr(h_last)
-    a.N, a.H, a.D, a.Q, a.q_stride, a.steps, a.step_stride = n, hidden, dirs, q, q_stride, steps, step_stride
-    a.ldt, a.ldq, a.state_shift = ldt, ldq, 0
+    a, hout, state = _lstm_args("rnn", gx, n, ldt, whh_t, None, hidden, dirs, (q, q_stride, steps, step_stride), h0, None,
+                                want_state, cell=False)
     check(lib().ps_rnn_f32(C.byref(a), RNN_KINDS[kind], ptr(bhn), stream_ptr(gx.device)), "ps_rnn_f32")
-    return (hout, h_last) if want_state else hout
-
-
-def _lstm_fmajor_args(gx_fm: torch.Tensor, whh_t: torch.Tensor, hout, hidden, dirs, q, q_stride, steps, step_stride):
-    n, ldt, rows = gx_fm.shape
-    a = LstmArgs()
-    a.gx, a.whh_t, a.hout = ptr(gx_fm), ptr(whh_t), ptr(hout)
-    a.N, a.H, a.D, a.Q, a.q_stride, a.steps, a.step_stride = n, hidden, dirs, q, q_stride, steps, step_stride
-    a.ldt, a.ldq, a.state_shift = ldt, 0, 0
-    return a
+    return (hout, state[0]) if want_state else hout
 
 
 def lstm_fmajor_ok(n: int, ldt: int, hidden: int, dirs: int, q: int, q_stride: int, steps: int, step_stride: int) -> bool:
-    """Does ps_lstm_fmajor_f16x2_f32 take this pass?  (shape / stride conditions only: H = 128, no states, slabs < 2 GiB)"""
+    """Does ps_lstm_fmajor_f16x2_f32 take this pass?  (The shape / stride conditions of lstm_fmajor_fits in csrc/rnn.hip: H =
+    128, slabs < 2 GiB; tests/test_lstm_refusals.py holds it against ps_lstm_fmajor_ok.)"""
     if hidden != 128 or dirs not in (1, 2) or (q - 1) * q_stride + (steps - 1) * step_stride >= ldt:
         return False
     return ldt * fmajor_ld(dirs * 512) * 4 < 2 ** 31
@@ -570,13 +581,8 @@ def lstm_fmajor(gx_fm: torch.Tensor, whh_t: torch.Tensor, hidden: int, dirs: int
     n, ldt, rows = gx_fm.shape
     if rows != dirs * 4 * hidden or tuple(whh_t.shape) != (dirs, hidden, 4 * hidden):
         raise RuntimeError("lstm_fmajor: gx must be [N, ldt, D*4H] and whh_t [D, H, 4H]")
-    ldm = gx_fm.stride(1)
-    if gx_fm.stride(2) != 1 or gx_fm.stride(0) != ldt * ldm:
-        raise RuntimeError("lstm_fmajor: gx must be a [N, ldt, :D*4H] view of contiguous frame rows")
-    hout = out if out is not None else torch.empty(n, dirs * hidden, ldt, dtype=torch.float32, device=gx_fm.device)
-    if tuple(hout.shape) != (n, dirs * hidden, ldt) or not hout.is_contiguous():
-        raise RuntimeError("lstm_fmajor: out must be a contiguous [N, D*H, ldt] tensor")
-    a = _lstm_fmajor_args(gx_fm, whh_t, hout, hidden, dirs, q, q_stride, steps, step_stride)
+    ldm = _frame_rows("lstm_fmajor", gx_fm)
+    a, hout, _ = _lstm_args("lstm_fmajor", gx_fm, n, ldt, whh_t, out, hidden, dirs, (q, q_stride, steps, step_stride))
     check(lib().ps_lstm_fmajor_f16x2_f32(C.byref(a), ldm, stream_ptr(gx_fm.device)), "ps_lstm_fmajor_f16x2_f32")
     return hout
 
@@ -605,6 +611,7 @@ def pack_whh_h256(whh_t: torch.Tensor):
 
 
 def lstm_fmajor_h256_ok(n: int, ldt: int, dirs: int, q: int, q_stride: int, steps: int, step_stride: int) -> bool:
+    """The walk conditions of lstm_h256_fits in csrc/rnn.hip (the caller has H = 256 or 192 from the weight image)."""
     return dirs in (1, 2) and (q - 1) * q_stride + (steps - 1) * step_stride < ldt
 
 
@@ -617,18 +624,13 @@ def lstm_fmajor_h256(gx_fm: torch.Tensor, whh_image: torch.Tensor, acc_scale, di
     require_device(gx_fm, "lstm_fmajor_h256")
     hidden = whh_image.shape[1] * 32
     n, ldt, rows = gx_fm.shape
-    if (rows != dirs * 4 * hidden or hidden not in (256, 192) or whh_image.dtype != torch.float16
+    if (rows != dirs * 4 * hidden or hidden not in (256, 192)
             or tuple(whh_image.shape) != (dirs, hidden // 32, hidden // 32, 2, 4, 2, 64, 8)):
         raise RuntimeError("lstm_fmajor_h256: gx must be [N, ldt, D*4H] and the image pack_whh_h256's")
-    ldm = gx_fm.stride(1)
-    if gx_fm.stride(2) != 1 or gx_fm.stride(0) != ldt * ldm:
-        raise RuntimeError("lstm_fmajor_h256: gx must be a [N, ldt, :D*1024] view of contiguous frame rows")
-    hout = out if out is not None else torch.empty(n, dirs * hidden, ldt, dtype=torch.float32, device=gx_fm.device)
-    a = LstmArgs()
-    a.gx, a.whh_t, a.hout = ptr(gx_fm), None, ptr(hout)
-    state = _lstm_state_args("lstm_fmajor_h256", a, n, dirs * hidden, q, h0, c0, want_state, state_out, gx_fm.device)
-    a.N, a.H, a.D, a.Q, a.q_stride, a.steps, a.step_stride = n, hidden, dirs, q, q_stride, steps, step_stride
-    a.ldt, a.state_shift = ldt, state_shift
+    _require_operand("lstm_fmajor_h256", gx_fm.device, torch.float16, whh_image=whh_image)
+    ldm = _frame_rows("lstm_fmajor_h256", gx_fm)
+    a, hout, state = _lstm_args("lstm_fmajor_h256", gx_fm, n, ldt, None, out, hidden, dirs, (q, q_stride, steps, step_stride),
+                                h0, c0, want_state, state_shift, state_out)
     sc = (C.c_float * 2)(float(acc_scale[0]), float(acc_scale[-1]))
     # few sequence groups (a speaker LSTM over all frames, SkiM's Mem-LSTMs): the cooperative kernel -- W_hh resident in the
     # registers of H / 32 CUs per group -- instead of streaming 1 MiB of it through one CU every step
@@ -644,10 +646,6 @@ def lstm_fmajor_h256(gx_fm: torch.Tensor, whh_image: torch.Tensor, acc_scale, di
     return hout, state
 
 
-COOP_LSTM = os.environ.get("PS_COOP_LSTM", "1") != "0"   # 0: always the streamed-weight kernel
-_COOP_LAST = [None]
-
-
 def _coop_slices(dirs: int, groups: int, hidden: int) -> int:
     """slices per group the launcher picks: H / 32 (two waves each) while the launch fits the chip, else H / 64"""
     rounds = (groups * dirs + 7) // 8 * 8   # (both directions in one launch; one launch per direction beyond that: H / 64 too)
@@ -656,8 +654,8 @@ def _coop_slices(dirs: int, groups: int, hidden: int) -> int:
 
 
 def _coop_layout(dirs: int, groups: int, hidden: int) -> tuple[int, int, int]:
-    """int32 indices into the cooperative LSTM's workspace (lstm_coop.inc: the h exchange, then D * groups barrier
-    counters): (error word, first XCD id, first XCD mask)."""
+    """int32 indices into the cooperative LSTM's workspace -- the Python copy of coop_layout() in csrc/rnn.hip (the h
+    exchange, then D * groups barrier counters; lstm_coop.inc): (error word, first XCD id, first XCD mask)."""
     hx = (2 * dirs * groups * 2 * 16 * (hidden + 8) * 2 + 255) // 256 * 256
     err = hx // 4 + dirs * groups
     return err, err + 1, err + 1 + dirs * groups * _coop_slices(dirs, groups, hidden)
