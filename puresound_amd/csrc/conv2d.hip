@@ -512,65 +512,104 @@ __global__ __launch_bounds__(256) void conv2d_rows_kernel(Conv2dArgs a, int span
 
 using namespace ps;
 
-extern "C" int ps_conv2d_f16x2_f32(const float* x1, int C1, const float* x2, int C2, const void* wimg, int w_exp,
-                                   const float* bias, float* y, int N, int M, int Fin, int T_in, int T, int ld, int kf, int kt,
-                                   int stride_f, int dil_f, int dil_t, int pad_f, int pad_t, int Fout, int transposed, int act,
-                                   const float* slope, double* ostats, void* stream) {
-  if (!x1 || !wimg || !y || N <= 0 || M <= 0 || C1 <= 0 || C2 < 0 || (C2 > 0 && !x2) || Fin <= 0 || Fout <= 0 || T <= 0 ||
+// ---- checks ------------------------------------------------------------------------------------------------------------------
+// Channel tiles of the MFMA kernels: 32 * mb channels per workgroup, mtiles of them.
+struct Conv2dTiles {
+  int mb, mtiles;
+};
+
+static Conv2dTiles conv2d_tiles(int M) {
+  const int mb = M <= 32 ? 1 : M <= 64 ? 2 : 4;
+  return {mb, (M + 32 * mb - 1) / (32 * mb)};
+}
+
+// The argument rules of the three launching entries; fills `a`.  `w_ok`: the entry's own rules for its weights (wt non-null;
+// the fp16x2 entry, whose kernel reads an image instead of wt: image, exponent, alignment).  `who` names the entry.
+static int conv2d_args(const char* who, Conv2dArgs& a, const float* x1, int C1, const float* x2, int C2, const float* wt, bool w_ok,
+                       const float* bias, float* y, int N, int M, int Fin, int T_in, int T, int ld, int kf, int kt, int stride_f,
+                       int dil_f, int dil_t, int pad_f, int pad_t, int Fout, int transposed, int act, const float* slope,
+                       double* ostats) {
+  if (!x1 || !w_ok || !y || N <= 0 || M <= 0 || C1 <= 0 || C2 < 0 || (C2 > 0 && !x2) || Fin <= 0 || Fout <= 0 || T <= 0 ||
       T_in <= 0 || ld < T || ld < T_in || ld % 128 || kf <= 0 || kt <= 0 || stride_f <= 0 || dil_f <= 0 || dil_t <= 0 ||
-      Fout > 65535 || act < 0 || act > 5 || (act == 2 && !slope) || w_exp < -100 || w_exp > 100 || ((uintptr_t)wimg & 15)) {
-    set_error("ps_conv2d_f16x2_f32: bad argument (N=%d M=%d C=%d+%d F=%d->%d T=%d k=%dx%d act=%d)", N, M, C1, C2, Fin, Fout, T,
-              kf, kt, act);
+      Fout > 65535 || act < 0 || act > 5 || (act == 2 && !slope)) {
+    set_error("%s: bad argument (N=%d M=%d C=%d+%d F=%d->%d T=%d k=%dx%d act=%d)", who, N, M, C1, C2, Fin, Fout, T, kf, kt, act);
     return PS_E_INVALID;
   }
   const long long K = (long long)(C1 + C2) * kf * kt;
   const int Kp = (int)((K + 15) / 16 * 16);
-  if (Kp > C2D_MAXK || (long long)(C1 > C2 ? C1 : C2) * Fin * ld >= (1LL << 30)) {
-    set_error("ps_conv2d_f16x2_f32: Cin*kf*kt = %lld exceeds %d, or an utterance of the input exceeds 2^30 elements", K, C2D_MAXK);
+  if (Kp > C2D_MAXK) {
+    set_error("%s: Cin*kf*kt = %lld exceeds %d", who, K, C2D_MAXK);
     return PS_E_UNSUPPORTED;
   }
-  const int mb = M <= 32 ? 1 : M <= 64 ? 2 : 4;
-  const int mtiles = (M + 32 * mb - 1) / (32 * mb);
-  if ((long long)N * mtiles > 65535) {
-    set_error("ps_conv2d_f16x2_f32: N * channel tiles exceeds the grid limit");
+  if ((long long)(C1 > C2 ? C1 : C2) * Fin * ld >= (1LL << 30)) {
+    set_error("%s: one utterance of the input exceeds 2^30 elements", who);
     return PS_E_UNSUPPORTED;
   }
-  Conv2dF16Args fa{{x1, x2, nullptr, bias, slope, y, C1, C2, Fin, T, T_in, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, pad_t,
-                    Fout, M, (int)K, Kp, transposed, act, ostats},
-                   wimg, ldexpf(1.f, -w_exp)};
-  dim3 grid(ld / 128, Fout, N * mtiles);
-  const int Kq = (Kp + 31) / 32 * 32;
-  const size_t lds = (size_t)2 * Kq * sizeof(int) + (size_t)2 * 32 * mb * 128;
-  {
-    LaunchTimer timer("conv2d", (hipStream_t)stream);
-    if (mb == 1)
-      hipLaunchKernelGGL((conv2d_f16x2_kernel<1>), grid, dim3(256), lds, (hipStream_t)stream, fa);
-    else if (mb == 2)
-      hipLaunchKernelGGL((conv2d_f16x2_kernel<2>), grid, dim3(256), lds, (hipStream_t)stream, fa);
-    else
-      hipLaunchKernelGGL((conv2d_f16x2_kernel<4>), grid, dim3(256), lds, (hipStream_t)stream, fa);
+  if ((long long)N * conv2d_tiles(M).mtiles > 65535) {
+    set_error("%s: N * channel tiles exceeds the grid limit", who);
+    return PS_E_UNSUPPORTED;
   }
-  return launch_status("ps_conv2d_f16x2_f32");
+  a = Conv2dArgs{x1, x2, wt, bias, slope, y, C1, C2, Fin, T, T_in, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, pad_t,
+                 Fout, M, (int)K, Kp, transposed, act, ostats};
+  return 0;
 }
 
+// ---- plan --------------------------------------------------------------------------------------------------------------------
+// Calls f(MB) with the channel-tile width as a std::integral_constant: the template argument of an MFMA kernel.
+template <class F>
+static void with_mb(int mb, F&& f) {
+  if (mb == 1) f(std::integral_constant<int, 1>{});
+  else if (mb == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 4>{});
+}
+
+// The fp32 entries: the row-block kernel for <= 4 output channels when its table fits (span = input rows feeding 8 output
+// rows), otherwise the implicit GEMM.
+static int conv2d_launch(const Conv2dArgs& a, int N, hipStream_t stream) {
+  LaunchTimer timer("conv2d", stream);
+  const int span = a.transposed ? ((C2D_R - 1) + (a.kf - 1) * a.df) / a.sf + 2 : (C2D_R - 1) * a.sf + (a.kf - 1) * a.df + 1;
+  const long long nent = (long long)(a.C1 + a.C2) * span * a.kt;
+  const int mm = a.M <= 2 ? 2 : 4;
+  const size_t rows_lds = (size_t)((nent + 3) / 4 * 4) * 2 * sizeof(int) + (size_t)nent * C2D_R * mm * sizeof(float);
+  if (a.M <= 4 && !a.stats && N <= 65535 && rows_lds <= 150 * 1024 && (a.Fout + C2D_R - 1) / C2D_R <= 65535) {
+    static bool lds_raised = false;  // (dynamic LDS above 64 KiB has to be allowed per kernel, once)
+    if (!lds_raised) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_rows_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_rows_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      lds_raised = true;
+    }
+    hipLaunchKernelGGL(mm == 2 ? conv2d_rows_kernel<2> : conv2d_rows_kernel<4>, dim3((a.ld + 511) / 512, (a.Fout + C2D_R - 1) / C2D_R, N),
+                       dim3(256), rows_lds, stream, a, span, (int)nent);
+    return launch_status("ps_conv2d_f32");
+  }
+  const Conv2dTiles t = conv2d_tiles(a.M);
+  const int Kq = (a.Kp + 31) / 32 * 32;
+  const size_t as = 32 * t.mb + (t.mb > 1 ? 32 : 0);
+  const size_t lds = (size_t)3 * Kq * sizeof(int) + 2 * C2D_KC * as * sizeof(float);
+  with_mb(t.mb, [&](auto MB) {
+    hipLaunchKernelGGL(conv2d_lds_kernel<MB()>, dim3(a.ld / 128, a.Fout, N * t.mtiles), dim3(256), lds, stream, a);
+  });
+  return launch_status("ps_conv2d_f32");
+}
+
+// ---- entries -----------------------------------------------------------------------------------------------------------------
 extern "C" int ps_conv2d_stats_parts(int M, int Fout, int ld) {
   if (M <= 0 || Fout <= 0 || ld <= 0 || ld % 128) return 0;
-  const int mb = M <= 32 ? 1 : M <= 64 ? 2 : 4;
-  return (ld / 128) * Fout * ((M + 32 * mb - 1) / (32 * mb));
+  return (ld / 128) * Fout * conv2d_tiles(M).mtiles;
 }
-
-static int conv2d_launch(const float* x1, int C1, const float* x2, int C2, const float* wt, const float* bias, float* y, int N,
-                         int M, int Fin, int T_in, int T, int ld, int kf, int kt, int stride_f, int dil_f, int dil_t, int pad_f,
-                         int pad_t, int Fout, int transposed, int act, const float* slope, double* ostats, void* stream);
 
 extern "C" int ps_conv2d_f32(const float* x1, int C1, const float* x2, int C2, const float* wt, const float* bias,
                              float* y, int N, int M, int Fin, int T_in, int T, int ld, int kf, int kt, int stride_f,
                              int dil_f, int dil_t, int pad_f, int pad_t, int Fout, int transposed, int act,
                              const float* slope, void* stream) {
-  return conv2d_launch(x1, C1, x2, C2, wt, bias, y, N, M, Fin, T_in, T, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, pad_t, Fout,
-                       transposed, act, slope, nullptr, stream);
+  Conv2dArgs a;
+  if (const int rc = conv2d_args("ps_conv2d_f32", a, x1, C1, x2, C2, wt, wt != nullptr, bias, y, N, M, Fin, T_in, T, ld, kf, kt, stride_f,
+                                 dil_f, dil_t, pad_f, pad_t, Fout, transposed, act, slope, nullptr))
+    return rc;
+  return conv2d_launch(a, N, (hipStream_t)stream);
 }
 
+// (no activation; the shared rules report under ps_conv2d_f32's name)
 extern "C" int ps_conv2d_stats_f32(const float* x1, int C1, const float* x2, int C2, const float* wt, const float* bias,
                                    float* y, int N, int M, int Fin, int T_in, int T, int ld, int kf, int kt, int stride_f,
                                    int dil_f, int dil_t, int pad_f, int pad_t, int Fout, int transposed, double* ostats,
@@ -579,69 +618,31 @@ extern "C" int ps_conv2d_stats_f32(const float* x1, int C1, const float* x2, int
     set_error("ps_conv2d_stats_f32: ostats is NULL");
     return PS_E_INVALID;
   }
-  return conv2d_launch(x1, C1, x2, C2, wt, bias, y, N, M, Fin, T_in, T, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, pad_t, Fout,
-                       transposed, 0, nullptr, ostats, stream);
+  Conv2dArgs a;
+  if (const int rc = conv2d_args("ps_conv2d_f32", a, x1, C1, x2, C2, wt, wt != nullptr, bias, y, N, M, Fin, T_in, T, ld, kf, kt, stride_f,
+                                 dil_f, dil_t, pad_f, pad_t, Fout, transposed, 0, nullptr, ostats))
+    return rc;
+  return conv2d_launch(a, N, (hipStream_t)stream);
 }
 
-static int conv2d_launch(const float* x1, int C1, const float* x2, int C2, const float* wt, const float* bias, float* y, int N,
-                         int M, int Fin, int T_in, int T, int ld, int kf, int kt, int stride_f, int dil_f, int dil_t, int pad_f,
-                         int pad_t, int Fout, int transposed, int act, const float* slope, double* ostats, void* stream) {
-  if (!x1 || !wt || !y || N <= 0 || M <= 0 || C1 <= 0 || C2 < 0 || (C2 > 0 && !x2) || Fin <= 0 || Fout <= 0 || T <= 0 ||
-      T_in <= 0 || ld < T || ld < T_in || ld % 128 || kf <= 0 || kt <= 0 || stride_f <= 0 || dil_f <= 0 || dil_t <= 0 ||
-      Fout > 65535 || act < 0 || act > 5 || (act == 2 && !slope)) {
-    set_error("ps_conv2d_f32: bad argument (N=%d M=%d C=%d+%d F=%d->%d T=%d k=%dx%d act=%d)", N, M, C1, C2, Fin, Fout, T, kf,
-              kt, act);
-    return PS_E_INVALID;
-  }
-  const long long K = (long long)(C1 + C2) * kf * kt;
-  const int Kp = (int)((K + 15) / 16 * 16);
-  if (Kp > C2D_MAXK) {
-    set_error("ps_conv2d_f32: Cin*kf*kt = %lld exceeds %d", K, C2D_MAXK);
-    return PS_E_UNSUPPORTED;
-  }
-  if ((long long)(C1 > C2 ? C1 : C2) * Fin * ld >= (1LL << 30)) {
-    set_error("ps_conv2d_f32: one utterance of the input exceeds 2^30 elements");
-    return PS_E_UNSUPPORTED;
-  }
-  const int mb = M <= 32 ? 1 : M <= 64 ? 2 : 4;
-  const int mtiles = (M + 32 * mb - 1) / (32 * mb);
-  if ((long long)N * mtiles > 65535) {
-    set_error("ps_conv2d_f32: N * channel tiles exceeds the grid limit");
-    return PS_E_UNSUPPORTED;
-  }
-  Conv2dArgs a{x1, x2, wt, bias, slope, y, C1, C2, Fin, T, T_in, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, pad_t,
-               Fout, M, (int)K, Kp, transposed, act, ostats};
-  dim3 grid(ld / 128, Fout, N * mtiles);
+extern "C" int ps_conv2d_f16x2_f32(const float* x1, int C1, const float* x2, int C2, const void* wimg, int w_exp,
+                                   const float* bias, float* y, int N, int M, int Fin, int T_in, int T, int ld, int kf, int kt,
+                                   int stride_f, int dil_f, int dil_t, int pad_f, int pad_t, int Fout, int transposed, int act,
+                                   const float* slope, double* ostats, void* stream) {
+  Conv2dF16Args fa{{}, wimg, 0.f};
+  if (const int rc = conv2d_args("ps_conv2d_f16x2_f32", fa.g, x1, C1, x2, C2, nullptr,
+                                 wimg && w_exp >= -100 && w_exp <= 100 && !((uintptr_t)wimg & 15), bias, y, N, M, Fin, T_in, T, ld, kf, kt,
+                                 stride_f, dil_f, dil_t, pad_f, pad_t, Fout, transposed, act, slope, ostats))
+    return rc;
+  fa.winv = ldexpf(1.f, -w_exp);
+  const Conv2dTiles t = conv2d_tiles(M);
+  const int Kq = (fa.g.Kp + 31) / 32 * 32;
+  const size_t lds = (size_t)2 * Kq * sizeof(int) + (size_t)2 * 32 * t.mb * 128;
   {
     LaunchTimer timer("conv2d", (hipStream_t)stream);
-    // <= 4 output channels: the row-block kernel when its table fits (span = input rows feeding 8 output rows)
-    const int span = transposed ? ((C2D_R - 1) + (kf - 1) * dil_f) / stride_f + 2 : (C2D_R - 1) * stride_f + (kf - 1) * dil_f + 1;
-    const long long nent = (long long)(C1 + C2) * span * kt;
-    const int mm = M <= 2 ? 2 : 4;
-    const size_t rows_lds = (size_t)((nent + 3) / 4 * 4) * 2 * sizeof(int) + (size_t)nent * C2D_R * mm * sizeof(float);
-    if (M <= 4 && !ostats && N <= 65535 && rows_lds <= 150 * 1024 && (Fout + C2D_R - 1) / C2D_R <= 65535) {
-      dim3 rgrid((ld + 511) / 512, (Fout + C2D_R - 1) / C2D_R, N);
-      static bool lds_raised = false;  // (dynamic LDS above 64 KiB has to be allowed per kernel, once)
-      if (!lds_raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_rows_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_rows_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        lds_raised = true;
-      }
-      if (mm == 2)
-        hipLaunchKernelGGL((conv2d_rows_kernel<2>), rgrid, dim3(256), rows_lds, (hipStream_t)stream, a, span, (int)nent);
-      else
-        hipLaunchKernelGGL((conv2d_rows_kernel<4>), rgrid, dim3(256), rows_lds, (hipStream_t)stream, a, span, (int)nent);
-    } else {
-      const int Kq = (Kp + 31) / 32 * 32;
-      const size_t as = 32 * mb + (mb > 1 ? 32 : 0);
-      const size_t lds = (size_t)3 * Kq * sizeof(int) + 2 * C2D_KC * as * sizeof(float);
-      if (mb == 1)
-        hipLaunchKernelGGL((conv2d_lds_kernel<1>), grid, dim3(256), lds, (hipStream_t)stream, a);
-      else if (mb == 2)
-        hipLaunchKernelGGL((conv2d_lds_kernel<2>), grid, dim3(256), lds, (hipStream_t)stream, a);
-      else
-        hipLaunchKernelGGL((conv2d_lds_kernel<4>), grid, dim3(256), lds, (hipStream_t)stream, a);
-    }
+    with_mb(t.mb, [&](auto MB) {
+      hipLaunchKernelGGL(conv2d_f16x2_kernel<MB()>, dim3(ld / 128, Fout, N * t.mtiles), dim3(256), lds, (hipStream_t)stream, fa);
+    });
   }
-  return launch_status("ps_conv2d_f32");
+  return launch_status("ps_conv2d_f16x2_f32");
 }

@@ -391,49 +391,17 @@ __global__ __launch_bounds__(256, 8) void dwconv_wave_kernel(DwArgs a) {
   }
 }
 
-}  // namespace ps
-
-extern "C" int ps_dwconv_stats_parts(int H, int T) {
-  if (H <= 0 || T <= 0) return 0;
-  return ((T + ps::DW_FRAMES - 1) / ps::DW_FRAMES) * ((H + ps::DW_ROWS - 1) / ps::DW_ROWS);
-}
-
-extern "C" int ps_dwconv_f32(const float* x, const float* w, const float* b, float* y, int N, int H, int T,
-                             int ldt, int P, int dilation, int left, const ps_prologue* pro, double* ostats,
-                             void* stream) {
-  return ps_dwconv_io(x, 0, w, b, y, 0, N, H, T, ldt, P, dilation, left, pro, ostats, stream);
-}
-
-static int dwconv_any(const void* x_any, int x_bf16, const float* w, const float* b, void* y_any, int y_bf16, int N, int H, int T,
-                      int ldt, int P, int dilation, int left, const ps_prologue* pro, double* ostats, float* amax, void* stream);
-
-extern "C" int ps_dwconv_io(const void* x_any, int x_bf16, const float* w, const float* b, void* y_any, int y_bf16, int N,
-                            int H, int T, int ldt, int P, int dilation, int left, const ps_prologue* pro, double* ostats,
-                            void* stream) {
-  return dwconv_any(x_any, x_bf16, w, b, y_any, y_bf16, N, H, T, ldt, P, dilation, left, pro, ostats, nullptr, stream);
-}
-
-extern "C" int ps_dwconv_amax_ok(int P, int dilation, int left) {
+// ---- checks ------------------------------------------------------------------------------------------------------------------
+// The wave-private kernel takes this shape: P = 3, a halo of at most 256 frames that, with the frames in front of it rounded
+// to whole 16-byte pieces, fits the 64 * DWW_NV pieces of a strip.
+static bool wave_fits(int P, int dilation, int left) {
   return P == 3 && dilation > 0 && left >= 0 && left <= 2 * dilation && 2 * dilation <= 256 &&
-         ps::DW_FRAMES / 4 + ((left + 3) / 4 * 4 + 2 * dilation - left + 3) / 4 <= 64 * ps::DWW_NV;
+         DW_FRAMES / 4 + ((left + 3) / 4 * 4 + 2 * dilation - left + 3) / 4 <= 64 * DWW_NV;
 }
 
-extern "C" int ps_dwconv_amax_f32(const float* x, const float* w, const float* b, float* y, int N, int H, int T, int ldt, int P,
-                                  int dilation, int left, const ps_prologue* pro, float* y_amax, void* stream) {
-  using namespace ps;
-  if (!y_amax || !ps_dwconv_amax_ok(P, dilation, left)) {
-    set_error("ps_dwconv_amax_f32: the maxima are an output of the wave-private kernel only (P = 3, 2 * dilation <= 256; "
-              "ps_dwconv_amax_ok); got P=%d dilation=%d left=%d", P, dilation, left);
-    return PS_E_UNSUPPORTED;
-  }
-  return dwconv_any(x, 0, w, b, y, 0, N, H, T, ldt, P, dilation, left, pro, nullptr, y_amax, stream);
-}
-
-static int dwconv_any(const void* x_any, int x_bf16, const float* w, const float* b, void* y_any, int y_bf16, int N, int H, int T,
-                      int ldt, int P, int dilation, int left, const ps_prologue* pro, double* ostats, float* amax, void* stream) {
-  using namespace ps;
-  const float* x = (const float*)x_any;
-  float* y = (float*)y_any;
+// The argument rules of every entry (their messages carry ps_dwconv_f32's name, whichever entry was called).
+static int dwconv_check(const void* x, const float* w, const void* y, int N, int H, int T, int ldt, int P, int dilation, int left,
+                        const ps_prologue* pro) {
   if (!x || !w || !y || N <= 0 || H <= 0 || T <= 0 || P <= 0 || P > DW_MAXP || dilation <= 0 || left < 0) {
     set_error("ps_dwconv_f32: bad argument (N=%d H=%d T=%d P=%d dilation=%d left=%d)", N, H, T, P, dilation, left);
     return PS_E_INVALID;
@@ -451,80 +419,107 @@ static int dwconv_any(const void* x_any, int x_bf16, const float* w, const float
     set_error("ps_dwconv_f32: ldt=%d must be a multiple of %d >= T=%d and pointers 16-byte aligned", ldt, kTileT, T);
     return PS_E_ALIGN;
   }
-  DwArgs a{};
-  a.x = x;
-  a.w = w;
-  a.b = b;
-  a.y = y;
-  a.ostats = ostats;
-  a.amax = amax;
-  if (pro) {
-    a.pro = *pro;
-    if (a.pro.norm != PS_NORM_NONE && (!a.pro.gamma || !a.pro.beta)) {
-      set_error("ps_dwconv_f32: norm prologue needs gamma/beta");
-      return PS_E_INVALID;
-    }
-    if (a.pro.norm == PS_NORM_GLOBAL && (!a.pro.stats || a.pro.parts <= 0 || a.pro.count <= 0)) {
-      set_error("ps_dwconv_f32: PS_NORM_GLOBAL prologue needs stats/parts/count");
-      return PS_E_INVALID;
-    }
-    if (a.pro.prelu && !a.pro.slope) {
-      set_error("ps_dwconv_f32: prelu prologue needs slope");
-      return PS_E_INVALID;
-    }
-  } else {
-    a.pro.norm = PS_NORM_NONE;
+  if (const int rc = check_prologue("ps_dwconv_f32", pro)) return rc;
+  // (the kernels read gamma / beta under every norm but PS_NORM_NONE, a value outside the enum included)
+  if (pro && pro->norm != PS_NORM_NONE && (!pro->gamma || !pro->beta)) {
+    set_error("ps_dwconv_f32: norm prologue needs gamma/beta");
+    return PS_E_INVALID;
   }
-  a.H = H;
-  a.T = T;
-  a.ldt = ldt;
-  a.P = P;
-  a.dilation = dilation;
-  a.left = left;
-  const bool aligned = (dilation % 4 == 0) && (left % 4 == 0);
-  dim3 grid((T + DW_FRAMES - 1) / DW_FRAMES, (H + DW_ROWS - 1) / DW_ROWS, N);
+  return 0;
+}
+
+// ---- plan --------------------------------------------------------------------------------------------------------------------
+// What a (valid) launch runs: a function of the arguments and the debug switches alone.  bf16 rows outside their build
+// (P = 3 within the small halo) have no kernel, nor have maxima of bf16 rows.
+struct DwPlan {
+  bool supported, wave, aligned, small, xb, yb, amax;
+};
+
+static DwPlan dwconv_plan(int P, int dilation, int left, bool xb, bool yb, bool amax) {
+  DwPlan p{true, false, dilation % 4 == 0 && left % 4 == 0, (P - 1) * dilation + 8 <= DW_SMALLHALO, xb, yb, amax};
+  // (PS_DBG_DWCONV_WG keeps the workgroup-synchronised kernel: tests run both; the maxima come from the wave kernel only)
+  p.wave = amax || (wave_fits(P, dilation, left) && !dbg(PS_DBG_DWCONV_WG) && xb == yb);
+  if (xb || yb) p.supported = p.wave ? !amax : P == 3 && p.small;
+  return p;
+}
+
+// Calls f(A, B, C) with three switches as std::bool_constant values: the template arguments of a kernel.
+template <class F>
+static void with_bools(bool a, bool b, bool c, F&& f) {
+  auto with_c = [&](auto A, auto B) {
+    if (c) f(A, B, std::true_type{});
+    else f(A, B, std::false_type{});
+  };
+  auto with_b = [&](auto A) {
+    if (b) with_c(A, std::true_type{});
+    else with_c(A, std::false_type{});
+  };
+  if (a) with_b(std::true_type{});
+  else with_b(std::false_type{});
+}
+
+static void dwconv_launch(const DwPlan& p, int P, const DwArgs& a, dim3 grid, hipStream_t st) {
+  if (p.wave)
+    with_bools(p.aligned, p.xb, p.amax, [&](auto AL, auto B16, auto AMAX) {
+      if constexpr (!(B16() && AMAX()))  // (the maxima are built for fp32 rows)
+        hipLaunchKernelGGL((dwconv_wave_kernel<AL(), B16(), AMAX()>), grid, dim3(256), 0, st, a);
+    });
+  else if (p.xb || p.yb)
+    with_bools(p.aligned, p.xb, p.yb, [&](auto AL, auto XB, auto YB) {
+      if constexpr (XB() || YB()) hipLaunchKernelGGL((dwconv_kernel<3, AL(), DW_SMALLHALO, XB(), YB()>), grid, dim3(256), 0, st, a);
+    });
+  else if (P != 3)
+    hipLaunchKernelGGL((dwconv_kernel<0, false>), grid, dim3(256), 0, st, a);
+  else
+    with_bools(p.aligned, p.small, false, [&](auto AL, auto SMALL, auto) {
+      hipLaunchKernelGGL((dwconv_kernel<3, AL(), SMALL() ? DW_SMALLHALO : DW_MAXHALO>), grid, dim3(256), 0, st, a);
+    });
+}
+
+static int dwconv_any(const void* x, int x_bf16, const float* w, const float* b, void* y, int y_bf16, int N, int H, int T, int ldt,
+                      int P, int dilation, int left, const ps_prologue* pro, double* ostats, float* amax, void* stream) {
+  if (const int rc = dwconv_check(x, w, y, N, H, T, ldt, P, dilation, left, pro)) return rc;
+  const DwPlan plan = dwconv_plan(P, dilation, left, x_bf16 != 0, y_bf16 != 0, amax != nullptr);
+  if (!plan.supported) {
+    set_error("ps_dwconv_io: bf16 rows are built for P = 3 with (P-1)*dilation <= %d", DW_SMALLHALO - 8);
+    return PS_E_UNSUPPORTED;
+  }
+  DwArgs a{(const float*)x, w, b, (float*)y, ostats, pro ? *pro : ps_prologue{}, H, T, ldt, P, dilation, left, amax};
   {
     LaunchTimer timer("dwconv", (hipStream_t)stream);
-    hipStream_t st = (hipStream_t)stream;
-    const bool small = (P - 1) * dilation + 8 <= DW_SMALLHALO;
-    const bool wave_ok = P == 3 && 2 * dilation <= 256 &&
-                         DW_FRAMES / 4 + ((left + 3) / 4 * 4 + 2 * dilation - left + 3) / 4 <= 64 * DWW_NV && !dbg(PS_DBG_DWCONV_WG);
-    if (amax) {  // (ps_dwconv_amax_f32: fp32 rows, the wave-private kernel's shapes)
-      if (aligned) hipLaunchKernelGGL((dwconv_wave_kernel<true, false, true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((dwconv_wave_kernel<false, false, true>), grid, dim3(256), 0, st, a);
-    } else if (x_bf16 && y_bf16 && wave_ok) {  // (PS_DBG_DWCONV_WG keeps the workgroup-synchronised kernel)
-      if (aligned) hipLaunchKernelGGL((dwconv_wave_kernel<true, true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((dwconv_wave_kernel<false, true>), grid, dim3(256), 0, st, a);
-    } else if (x_bf16 || y_bf16) {
-      if (P != 3 || !small) {
-        set_error("ps_dwconv_io: bf16 rows are built for P = 3 with (P-1)*dilation <= %d", DW_SMALLHALO - 8);
-        return PS_E_UNSUPPORTED;
-      }
-#define PS_DW(AL, XBV, YBV) hipLaunchKernelGGL((dwconv_kernel<3, AL, DW_SMALLHALO, XBV, YBV>), grid, dim3(256), 0, st, a)
-      if (aligned) {
-        if (x_bf16 && y_bf16) PS_DW(true, true, true);
-        else if (x_bf16) PS_DW(true, true, false);
-        else PS_DW(true, false, true);
-      } else {
-        if (x_bf16 && y_bf16) PS_DW(false, true, true);
-        else if (x_bf16) PS_DW(false, true, false);
-        else PS_DW(false, false, true);
-      }
-#undef PS_DW
-    } else if (P == 3 && 2 * dilation <= 256 && DW_FRAMES / 4 + ((left + 3) / 4 * 4 + 2 * dilation - left + 3) / 4 <= 64 * DWW_NV &&
-               !dbg(PS_DBG_DWCONV_WG)) {  // (PS_DBG_DWCONV_WG keeps the workgroup-synchronised kernel: tests run both)
-      if (aligned) hipLaunchKernelGGL((dwconv_wave_kernel<true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((dwconv_wave_kernel<false>), grid, dim3(256), 0, st, a);
-    } else if (P == 3 && aligned && small)
-      hipLaunchKernelGGL((dwconv_kernel<3, true, DW_SMALLHALO>), grid, dim3(256), 0, st, a);
-    else if (P == 3 && small)
-      hipLaunchKernelGGL((dwconv_kernel<3, false, DW_SMALLHALO>), grid, dim3(256), 0, st, a);
-    else if (P == 3 && aligned)
-      hipLaunchKernelGGL((dwconv_kernel<3, true>), grid, dim3(256), 0, st, a);
-    else if (P == 3)
-      hipLaunchKernelGGL((dwconv_kernel<3, false>), grid, dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((dwconv_kernel<0, false>), grid, dim3(256), 0, st, a);
+    dwconv_launch(plan, P, a, dim3((T + DW_FRAMES - 1) / DW_FRAMES, (H + DW_ROWS - 1) / DW_ROWS, N), (hipStream_t)stream);
   }
   return launch_status("ps_dwconv_f32");
+}
+
+}  // namespace ps
+
+// ---- entries -----------------------------------------------------------------------------------------------------------------
+extern "C" int ps_dwconv_stats_parts(int H, int T) {
+  if (H <= 0 || T <= 0) return 0;
+  return ((T + ps::DW_FRAMES - 1) / ps::DW_FRAMES) * ((H + ps::DW_ROWS - 1) / ps::DW_ROWS);
+}
+
+extern "C" int ps_dwconv_io(const void* x_any, int x_bf16, const float* w, const float* b, void* y_any, int y_bf16, int N,
+                            int H, int T, int ldt, int P, int dilation, int left, const ps_prologue* pro, double* ostats,
+                            void* stream) {
+  return ps::dwconv_any(x_any, x_bf16, w, b, y_any, y_bf16, N, H, T, ldt, P, dilation, left, pro, ostats, nullptr, stream);
+}
+
+extern "C" int ps_dwconv_f32(const float* x, const float* w, const float* b, float* y, int N, int H, int T,
+                             int ldt, int P, int dilation, int left, const ps_prologue* pro, double* ostats,
+                             void* stream) {
+  return ps::dwconv_any(x, 0, w, b, y, 0, N, H, T, ldt, P, dilation, left, pro, ostats, nullptr, stream);
+}
+
+extern "C" int ps_dwconv_amax_ok(int P, int dilation, int left) { return ps::wave_fits(P, dilation, left); }
+
+extern "C" int ps_dwconv_amax_f32(const float* x, const float* w, const float* b, float* y, int N, int H, int T, int ldt, int P,
+                                  int dilation, int left, const ps_prologue* pro, float* y_amax, void* stream) {
+  if (!y_amax || !ps::wave_fits(P, dilation, left)) {
+    ps::set_error("ps_dwconv_amax_f32: the maxima are an output of the wave-private kernel only (P = 3, 2 * dilation <= 256; "
+                  "ps_dwconv_amax_ok); got P=%d dilation=%d left=%d", P, dilation, left);
+    return PS_E_UNSUPPORTED;
+  }
+  return ps::dwconv_any(x, 0, w, b, y, 0, N, H, T, ldt, P, dilation, left, pro, nullptr, y_amax, stream);
 }

@@ -552,35 +552,68 @@ __global__ __launch_bounds__(256) void embed_bias_kernel(const float* __restrict
 
 using namespace ps;
 
-extern "C" int ps_pad_rows_f32(const float* src, float* dst, int64_t rows, int T, int ldt, void* stream) {
+// ---- checks ------------------------------------------------------------------------------------------------------------------
+static int decode_args_check(const char* who, const float* feats, const float* w, const float* out, int N, int C, int T, int ldt,
+                             int win, int hop) {
+  if (feats && w && out && N > 0 && C > 0 && T > 0 && win > 0 && hop > 0 && ldt >= T) return 0;
+  set_error("%s: bad argument (N=%d C=%d T=%d win=%d hop=%d)", who, N, C, T, win, hop);
+  return PS_E_INVALID;
+}
+
+static int decode_modes_check(const char* who, int mask_act, int out_mode) {
+  if (mask_act >= PS_ACT_LINEAR && mask_act <= PS_ACT_SIGMOID && out_mode >= PS_OUT_CLAMP && out_mode <= PS_OUT_NONE) return 0;
+  set_error("%s: unknown mask_act=%d or out_mode=%d", who, mask_act, out_mode);
+  return PS_E_INVALID;
+}
+
+// ---- plan --------------------------------------------------------------------------------------------------------------------
+// The shapes the matrix-pipe decoder takes: the benchmark's filterbank on long rows, whole groups of k pairs, 32-bit offsets
+// within an utterance.  (Each caller adds what else it needs: a workspace, or rows that hold their frames.)
+static bool decode_mfma_fits(int N, int C, int T, int ldt, int win, int hop) {
+  return N > 0 && N <= 65535 && T >= 64 && win == 32 && hop == 16 && C % (2 * DM_UC) == 0 &&
+         (long long)C * ldt * 4 < (1ll << 31);
+}
+
+static int decode_tiles(int T) { return T / 32 + 1; }  // 32-frame tiles of the matrix-pipe decoder, the last one partial
+
+// The decoder, then the boundary fix-up that adds the tile tails left in the workspace.  (The fix-up grids differ: the
+// scoring build needs the utterance as a grid dimension for its partial slots.)
+template <bool MOM>
+static void launch_decode_mfma(const float* feats, const float* mask, int mask_act, const float* w, float* out, void* workspace,
+                               int N, int C, int T, int ldt, int out_mode, const DecodeScore& sc, hipStream_t s) {
+  const int ntiles = decode_tiles(T);
+  hipLaunchKernelGGL(free_decode_mfma_kernel<MOM>, dim3((ntiles + 3) / 4, N), dim3(256), 0, s, feats, mask, mask_act, w, out,
+                     (float*)workspace, C, T, ldt, ntiles, out_mode, sc);
+  const dim3 fix = MOM ? dim3(((ntiles - 1) * 16 + 255) / 256, N)
+                       : dim3((unsigned)(((long long)N * (ntiles - 1) * 16 + 255) / 256));
+  hipLaunchKernelGGL(free_decode_fixup_kernel<MOM>, fix, dim3(256), 0, s, out, (const float*)workspace, T, ntiles, N, out_mode,
+                     sc);
+}
+
+// A row-copy entry: rows of src_ld frames to rows of dst_ld, in folds because grid.y is limited to 65535.
+static int copy_rows(const char* who, const char* label, void (*kernel)(const float*, float*, int64_t, int, int), const float* src,
+                     float* dst, int64_t rows, int T, int ldt, int src_ld, int dst_ld, void* stream) {
   if (!src || !dst || rows <= 0 || T <= 0 || ldt < T || rows > 0x7fffffff) {
-    set_error("ps_pad_rows_f32: bad argument");
+    set_error("%s: bad argument", who);
     return PS_E_INVALID;
   }
-  // grid.y is limited to 65535: fold rows
   const int64_t chunk = 65535;
-  LaunchTimer timer("pad_rows", (hipStream_t)stream);
+  LaunchTimer timer(label, (hipStream_t)stream);
   for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
     const int64_t nr = rows - r0 < chunk ? rows - r0 : chunk;
-    hipLaunchKernelGGL(pad_rows_kernel, dim3((ldt + 255) / 256, (unsigned)nr), dim3(256), 0, (hipStream_t)stream,
-                       src + r0 * T, dst + r0 * ldt, nr, T, ldt);
+    hipLaunchKernelGGL(kernel, dim3((dst_ld + 255) / 256, (unsigned)nr), dim3(256), 0, (hipStream_t)stream, src + r0 * src_ld,
+                       dst + r0 * dst_ld, nr, T, ldt);
   }
-  return launch_status("ps_pad_rows_f32");
+  return launch_status(who);
+}
+
+// ---- entries -----------------------------------------------------------------------------------------------------------------
+extern "C" int ps_pad_rows_f32(const float* src, float* dst, int64_t rows, int T, int ldt, void* stream) {
+  return copy_rows("ps_pad_rows_f32", "pad_rows", pad_rows_kernel, src, dst, rows, T, ldt, T, ldt, stream);
 }
 
 extern "C" int ps_unpad_rows_f32(const float* src, float* dst, int64_t rows, int T, int ldt, void* stream) {
-  if (!src || !dst || rows <= 0 || T <= 0 || ldt < T || rows > 0x7fffffff) {
-    set_error("ps_unpad_rows_f32: bad argument");
-    return PS_E_INVALID;
-  }
-  const int64_t chunk = 65535;
-  LaunchTimer timer("unpad_rows", (hipStream_t)stream);
-  for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
-    const int64_t nr = rows - r0 < chunk ? rows - r0 : chunk;
-    hipLaunchKernelGGL(unpad_rows_kernel, dim3((T + 255) / 256, (unsigned)nr), dim3(256), 0, (hipStream_t)stream,
-                       src + r0 * ldt, dst + r0 * T, nr, T, ldt);
-  }
-  return launch_status("ps_unpad_rows_f32");
+  return copy_rows("ps_unpad_rows_f32", "unpad_rows", unpad_rows_kernel, src, dst, rows, T, ldt, ldt, T, stream);
 }
 
 extern "C" int ps_free_encode_f32(const float* wav, const float* w, float* feats, int N, int L, int C, int win,
@@ -594,9 +627,6 @@ extern "C" int ps_free_encode_f32(const float* wav, const float* w, float* feats
               (L - win) / hop + 1, ldt, kTileT);
     return PS_E_INVALID;
   }
-  // few frames (streaming: one frame per stream): spread the channels over more workgroups
-  const int cchunk = ((long long)N * ((T + 255) / 256) * ((C + ENC_CCHUNK - 1) / ENC_CCHUNK) < 64) ? 4 : ENC_CCHUNK;
-  dim3 grid((T + 255) / 256, (C + cchunk - 1) / cchunk, N);
   hipStream_t s = (hipStream_t)stream;
   LaunchTimer timer("free_encode", s);
   // long rows of the benchmark's filterbank: the matrix-pipe kernel (PS_DBG_ENCDEC_VALU keeps the VALU kernels of rounds
@@ -606,38 +636,23 @@ extern "C" int ps_free_encode_f32(const float* wav, const float* w, float* feats
     hipLaunchKernelGGL(free_encode_mfma_kernel, g, dim3(256), 0, s, wav, w, feats, L, C, T, ldt, relu);
     return launch_status("ps_free_encode_f32");
   }
-  if (win == 32)
-    hipLaunchKernelGGL(free_encode_kernel<32>, grid, dim3(256), 0, s, wav, w, feats, L, C, win, hop, T, ldt, relu,
-                       cchunk);
-  else if (win == 16)
-    hipLaunchKernelGGL(free_encode_kernel<16>, grid, dim3(256), 0, s, wav, w, feats, L, C, win, hop, T, ldt, relu,
-                       cchunk);
-  else
-    hipLaunchKernelGGL(free_encode_kernel<0>, grid, dim3(256), 0, s, wav, w, feats, L, C, win, hop, T, ldt, relu,
-                       cchunk);
+  // few frames (streaming: one frame per stream): spread the channels over more workgroups
+  const int cchunk = ((long long)N * ((T + 255) / 256) * ((C + ENC_CCHUNK - 1) / ENC_CCHUNK) < 64) ? 4 : ENC_CCHUNK;
+  const auto kernel = win == 32 ? free_encode_kernel<32> : win == 16 ? free_encode_kernel<16> : free_encode_kernel<0>;
+  hipLaunchKernelGGL(kernel, dim3((T + 255) / 256, (C + cchunk - 1) / cchunk, N), dim3(256), 0, s, wav, w, feats, L, C, win, hop,
+                     T, ldt, relu, cchunk);
   return launch_status("ps_free_encode_f32");
 }
 
 extern "C" int ps_free_decode_f32(const float* feats, const float* mask, int mask_act, const float* w, float* out,
                                   int N, int C, int T, int ldt, int win, int hop, int out_mode, void* stream) {
-  if (!feats || !w || !out || N <= 0 || C <= 0 || T <= 0 || win <= 0 || hop <= 0 || ldt < T) {
-    set_error("ps_free_decode_f32: bad argument (N=%d C=%d T=%d win=%d hop=%d)", N, C, T, win, hop);
-    return PS_E_INVALID;
-  }
-  if (mask_act < PS_ACT_LINEAR || mask_act > PS_ACT_SIGMOID || out_mode < PS_OUT_CLAMP || out_mode > PS_OUT_NONE) {
-    set_error("ps_free_decode_f32: unknown mask_act=%d or out_mode=%d", mask_act, out_mode);
-    return PS_E_INVALID;
-  }
+  if (const int rc = decode_args_check("ps_free_decode_f32", feats, w, out, N, C, T, ldt, win, hop)) return rc;
+  if (const int rc = decode_modes_check("ps_free_decode_f32", mask_act, out_mode)) return rc;
   hipStream_t s = (hipStream_t)stream;
   LaunchTimer timer("free_decode", s);
-  if (win == 32 && hop == 16) {
-    constexpr int BTF = 255;
-    hipLaunchKernelGGL((free_decode_kernel<32, 16>), dim3((T + BTF - 1) / BTF, N), dim3(256), 0, s, feats, mask,
-                       mask_act, w, out, C, T, ldt, out_mode);
-  } else if (win == 16 && hop == 8) {
-    constexpr int BTF = 255;
-    hipLaunchKernelGGL((free_decode_kernel<16, 8>), dim3((T + BTF - 1) / BTF, N), dim3(256), 0, s, feats, mask,
-                       mask_act, w, out, C, T, ldt, out_mode);
+  if ((win == 32 && hop == 16) || (win == 16 && hop == 8)) {  // (a workgroup owns 256 frames less its one halo frame)
+    hipLaunchKernelGGL((win == 32 ? free_decode_kernel<32, 16> : free_decode_kernel<16, 8>), dim3((T + 254) / 255, N), dim3(256),
+                       0, s, feats, mask, mask_act, w, out, C, T, ldt, out_mode);
   } else if (hop == win && win <= 256 && 256 % win == 0 && T <= 65535) {
     hipLaunchKernelGGL(free_decode_frame_kernel, dim3(T, N), dim3(256), 0, s, feats, mask, mask_act, w, out, C, T, ldt,
                        win, out_mode);
@@ -649,44 +664,30 @@ extern "C" int ps_free_decode_f32(const float* feats, const float* mask, int mas
   return launch_status("ps_free_decode_f32");
 }
 
+// One 16-sample tail per tile (sized for every row of the filterbank, whether or not the matrix-pipe decoder then takes it).
 extern "C" size_t ps_free_decode_workspace_bytes(int N, int T, int win, int hop) {
   if (N <= 0 || T <= 0 || win != 32 || hop != 16) return 0;
-  return (size_t)N * (T / 32 + 1) * 16 * sizeof(float);  // one 16-sample tail per 32-frame tile
+  return (size_t)N * decode_tiles(T) * 16 * sizeof(float);
 }
 
 extern "C" int ps_free_decode_ws_f32(const float* feats, const float* mask, int mask_act, const float* w, float* out,
                                      int N, int C, int T, int ldt, int win, int hop, int out_mode, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-  const size_t need = ps_free_decode_workspace_bytes(N, T, win, hop);
-  // the matrix-pipe kernel: the benchmark's filterbank on long rows, with the side buffer it needs (PS_DBG_ENCDEC_VALU
-  // keeps the VALU kernel; so does a missing or short workspace)
-  if (need == 0 || !workspace || workspace_bytes < need || T < 64 || N > 65535 || ((uintptr_t)out & 15) ||
-      ((uintptr_t)workspace & 15) || C % (2 * ps::DM_UC) || (long long)C * ldt * 4 >= (1ll << 31) || dbg(PS_DBG_ENCDEC_VALU))
+  // the matrix-pipe kernel, with the side buffer it needs (PS_DBG_ENCDEC_VALU keeps the VALU kernel; so does a missing,
+  // short or misaligned workspace)
+  if (!decode_mfma_fits(N, C, T, ldt, win, hop) || !workspace || workspace_bytes < ps_free_decode_workspace_bytes(N, T, win, hop) ||
+      ((uintptr_t)out & 15) || ((uintptr_t)workspace & 15) || dbg(PS_DBG_ENCDEC_VALU))
     return ps_free_decode_f32(feats, mask, mask_act, w, out, N, C, T, ldt, win, hop, out_mode, stream);
-  if (!feats || !w || !out || C <= 0 || ldt < T) {
-    set_error("ps_free_decode_ws_f32: bad argument (N=%d C=%d T=%d)", N, C, T);
-    return PS_E_INVALID;
-  }
-  if (mask_act < PS_ACT_LINEAR || mask_act > PS_ACT_SIGMOID || out_mode < PS_OUT_CLAMP || out_mode > PS_OUT_NONE) {
-    set_error("ps_free_decode_ws_f32: unknown mask_act=%d or out_mode=%d", mask_act, out_mode);
-    return PS_E_INVALID;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  LaunchTimer timer("free_decode", s);
-  const int ntiles = T / 32 + 1;
-  hipLaunchKernelGGL(free_decode_mfma_kernel<false>, dim3((ntiles + 3) / 4, N), dim3(256), 0, s, feats, mask, mask_act, w,
-                     out, (float*)workspace, C, T, ldt, ntiles, out_mode, ps::DecodeScore{});
-  const long long fix = (long long)N * (ntiles - 1) * 16;
-  hipLaunchKernelGGL(free_decode_fixup_kernel<false>, dim3((unsigned)((fix + 255) / 256)), dim3(256), 0, s, out,
-                     (const float*)workspace, T, ntiles, N, out_mode, ps::DecodeScore{});
+  if (const int rc = decode_args_check("ps_free_decode_ws_f32", feats, w, out, N, C, T, ldt, win, hop)) return rc;
+  if (const int rc = decode_modes_check("ps_free_decode_ws_f32", mask_act, out_mode)) return rc;
+  LaunchTimer timer("free_decode", (hipStream_t)stream);
+  launch_decode_mfma<false>(feats, mask, mask_act, w, out, workspace, N, C, T, ldt, out_mode, DecodeScore{}, (hipStream_t)stream);
   return launch_status("ps_free_decode_ws_f32");
 }
 
 extern "C" int ps_free_decode_moments_parts(int N, int C, int T, int ldt, int win, int hop) {
-  if (N <= 0 || N > 65535 || C <= 0 || T < 64 || ldt < T || win != 32 || hop != 16 || C % (2 * ps::DM_UC) ||
-      (long long)C * ldt * 4 >= (1ll << 31))
-    return 0;
-  const int ntiles = T / 32 + 1;
+  if (!decode_mfma_fits(N, C, T, ldt, win, hop) || C <= 0 || ldt < T) return 0;
+  const int ntiles = decode_tiles(T);
   return ntiles + ((ntiles - 1) * 16 + 255) / 256;
 }
 
@@ -707,18 +708,10 @@ extern "C" int ps_free_decode_moments_f32(const float* feats, const float* mask,
               "ldr=%d)", ref_len, ldr);
     return PS_E_INVALID;
   }
-  if (mask_act < PS_ACT_LINEAR || mask_act > PS_ACT_SIGMOID || out_mode < PS_OUT_CLAMP || out_mode > PS_OUT_NONE) {
-    set_error("ps_free_decode_moments_f32: unknown mask_act=%d or out_mode=%d", mask_act, out_mode);
-    return PS_E_INVALID;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  LaunchTimer timer("free_decode_moments", s);
-  const int ntiles = T / 32 + 1;
-  const ps::DecodeScore sc{ref, partials, ldr, ref_len, nparts};
-  hipLaunchKernelGGL(free_decode_mfma_kernel<true>, dim3((ntiles + 3) / 4, N), dim3(256), 0, s, feats, mask, mask_act, w,
-                     out, (float*)workspace, C, T, ldt, ntiles, out_mode, sc);
-  hipLaunchKernelGGL(free_decode_fixup_kernel<true>, dim3(((ntiles - 1) * 16 + 255) / 256, N), dim3(256), 0, s, out,
-                     (const float*)workspace, T, ntiles, N, out_mode, sc);
+  if (const int rc = decode_modes_check("ps_free_decode_moments_f32", mask_act, out_mode)) return rc;
+  LaunchTimer timer("free_decode_moments", (hipStream_t)stream);
+  launch_decode_mfma<true>(feats, mask, mask_act, w, out, workspace, N, C, T, ldt, out_mode,
+                           DecodeScore{ref, partials, ldr, ref_len, nparts}, (hipStream_t)stream);
   return launch_status("ps_free_decode_moments_f32");
 }
 

@@ -31,6 +31,20 @@ def pack_wt(w: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _require_operand(who: str, device: torch.device, dtype: torch.dtype = torch.float32, **tensors) -> None:
+    """Tensors whose pointers go into the call or its argument struct: on the input's device, `dtype`, contiguous.  Anything
+    else reaches the kernel as a wild pointer: a GPU fault, not an error."""
+    for name, t in tensors.items():
+        if t is not None and not (t.dtype is dtype and t.is_contiguous() and t.device == device):
+            raise RuntimeError(f"{who}: {name} must be a contiguous {dtype} tensor on {device} "
+                               f"(got {t.dtype} on {t.device}, strides {tuple(t.stride())})")
+
+
+def _stats_buffer(n: int, parts: int, device: torch.device, zeroed: bool = False) -> torch.Tensor:
+    """[N, parts, 2] fp64: the partial (sum, sum of squares) slots a producer leaves for the next global norm."""
+    return (torch.zeros if zeroed else torch.empty)(n, parts, 2, dtype=torch.float64, device=device)
+
+
 def pad_rows(x: torch.Tensor, min_frames: int = 0) -> torch.Tensor:
     """compact [..., T] -> padded [..., ldt] (zeros in the pad); ldt also covers `min_frames`."""
     require_device(x, "pad_rows")
@@ -76,20 +90,28 @@ def free_encode(wav: torch.Tensor, w: torch.Tensor, hop: int, relu: bool = False
     return feats, t
 
 
+def _decode_buffers(who: str, feats: torch.Tensor, t: int, win: int, hop: int, out: Optional[torch.Tensor]):
+    """-> (out [N, (T-1)*hop+win], workspace or None, its bytes): the matrix-pipe decoder (win = 32, hop = 16, long rows)
+    completes tile boundaries through a small side buffer."""
+    n = feats.shape[0]
+    if out is None:
+        out = torch.empty(n, (t - 1) * hop + win, dtype=torch.float32, device=feats.device)
+    elif tuple(out.shape) != (n, (t - 1) * hop + win) or not out.is_contiguous():
+        raise RuntimeError(f"{who}: `out` must be a contiguous [N, (T-1)*hop+win] tensor")
+    ws_bytes = lib().ps_free_decode_workspace_bytes(n, t, win, hop)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=feats.device) if ws_bytes else None
+    return out, ws, ws_bytes
+
+
 def free_decode(feats: torch.Tensor, t: int, w: torch.Tensor, hop: int, mask: Optional[torch.Tensor] = None,
                 mask_act: str = "linear", out_mode: str = "none", out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """feats/mask padded [N,C,ldt] -> waveform [N,(T-1)*hop+win] (into `out` if given: contiguous rows)."""
     require_device(feats, "free_decode")
     require_weight(w, feats, "free_decode")
+    _require_operand("free_decode", feats.device, mask=mask)
     n, c, ldt = feats.shape
     win = w.shape[-1]
-    if out is None:
-        out = torch.empty(n, (t - 1) * hop + win, dtype=torch.float32, device=feats.device)
-    elif tuple(out.shape) != (n, (t - 1) * hop + win) or not out.is_contiguous():
-        raise RuntimeError("free_decode: `out` must be a contiguous [N, (T-1)*hop+win] tensor")
-    # the matrix-pipe decoder (win = 32, hop = 16, long rows) completes tile boundaries through a small side buffer
-    ws_bytes = lib().ps_free_decode_workspace_bytes(n, t, win, hop)
-    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=feats.device) if ws_bytes else None
+    out, ws, ws_bytes = _decode_buffers("free_decode", feats, t, win, hop, out)
     check(lib().ps_free_decode_ws_f32(ptr(feats), ptr(mask), _abi.PS_ACT[mask_act], ptr(w), ptr(out), n, c, t, ldt,
                                       win, hop, _abi.PS_OUT[out_mode], ptr(ws), ws_bytes, stream_ptr(feats.device)),
           "ps_free_decode_ws_f32")
@@ -115,6 +137,9 @@ def free_decode_moments(feats: torch.Tensor, t: int, w: torch.Tensor, hop: int, 
     require_device(feats, "free_decode_moments")
     require_device(ref, "free_decode_moments")
     require_weight(w, feats, "free_decode_moments")
+    _require_operand("free_decode_moments", feats.device, mask=mask)
+    if ref.device != feats.device:   # (its rows may be strided: ldr goes with the pointer)
+        raise RuntimeError(f"free_decode_moments: ref must be on {feats.device} (got {ref.device})")
     n, c, ldt = feats.shape
     win = w.shape[-1]
     lout = (t - 1) * hop + win
@@ -124,14 +149,9 @@ def free_decode_moments(feats: torch.Tensor, t: int, w: torch.Tensor, hop: int, 
     if parts == 0:
         out = free_decode(feats, t, w, hop, mask, mask_act, out_mode, out)
         return out, wave_moments(out, align_reference(ref, lout))
-    if out is None:
-        out = torch.empty(n, lout, dtype=torch.float32, device=feats.device)
-    elif tuple(out.shape) != (n, lout) or not out.is_contiguous():
-        raise RuntimeError("free_decode_moments: `out` must be a contiguous [N, (T-1)*hop+win] tensor")
+    out, ws, ws_bytes = _decode_buffers("free_decode_moments", feats, t, win, hop, out)
     if ref.stride(1) != 1:
         ref = ref.contiguous()
-    ws_bytes = lib().ps_free_decode_workspace_bytes(n, t, win, hop)
-    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=feats.device)
     part = torch.empty(n, parts, 5, dtype=torch.float64, device=feats.device)
     check(lib().ps_free_decode_moments_f32(ptr(feats), ptr(mask), _abi.PS_ACT[mask_act], ptr(w), ptr(out), n, c, t, ldt,
                                            win, hop, _abi.PS_OUT[out_mode], ptr(ref), ref.stride(0), ref.shape[1],
@@ -191,6 +211,7 @@ def magphase(spec: torch.Tensor, take_sqrt: bool) -> torch.Tensor:
 def istft_ola(frames: torch.Tensor, t: int, window: torch.Tensor, hop: int, out_mode: str = "none") -> torch.Tensor:
     """synthesis frames padded [N,n_fft,ldt] -> waveform [N,(T-1)*hop+n_fft] (window, /n_fft, OLA, /window-sum)."""
     require_device(frames, "istft_ola")
+    _require_operand("istft_ola", frames.device, window=window)
     n, n_fft, ldt = frames.shape
     out = torch.empty(n, (t - 1) * hop + n_fft, dtype=torch.float32, device=frames.device)
     check(lib().ps_istft_ola_f32(ptr(frames), ptr(window), ptr(out), n, n_fft, hop, t, ldt, _abi.PS_OUT[out_mode],
@@ -219,10 +240,7 @@ def conv1x1(x: torch.Tensor, t: int, wt: torch.Tensor, m: int, pro: Optional[Pro
     require_device(x, "conv1x1")
     n, k, ldt = x.shape
     y = out if out is not None else torch.zeros(n, m, ldt, dtype=torch.float32, device=x.device)
-    stats = None
-    if want_stats:
-        parts = lib().ps_conv1x1_stats_parts(m, t)
-        stats = torch.zeros(n, parts, 2, dtype=torch.float64, device=x.device)
+    stats = _stats_buffer(n, lib().ps_conv1x1_stats_parts(m, t), x.device, zeroed=True) if want_stats else None
     check(lib().ps_conv1x1_f32(ptr(x), ptr(wt), ptr(y), n, k, m, t, ldt, C.byref(pro) if pro is not None else None,
                                ptr(bias), ptr(bias_n), ptr(res), ptr(stats), stream_ptr(x.device)), "ps_conv1x1_f32")
     return y, stats
@@ -296,10 +314,8 @@ def conv1x1_f16x2(x: torch.Tensor, t: int, wt_planes: torch.Tensor, w_exp: int, 
     require_device(x, "conv1x1_f16x2")
     n, k, ldt = x.shape
     y = out if out is not None else torch.empty(n, m, ldt, dtype=torch.float32, device=x.device)
-    stats = amax = None
-    if want_stats:
-        parts = lib().ps_conv1x1_stats_parts(m, t)
-        stats = torch.zeros(n, parts, 2, dtype=torch.float64, device=x.device)
+    stats = _stats_buffer(n, lib().ps_conv1x1_stats_parts(m, t), x.device, zeroed=True) if want_stats else None
+    amax = None
     if want_amax:
         amax = torch.zeros(n, lib().ps_conv1x1_stats_parts(m, t), dtype=torch.float32, device=x.device)
     if x_amax is not None:
@@ -389,10 +405,7 @@ def conv1x1_bf16(x: torch.Tensor, t: int, wt_planes: torch.Tensor, m: int, pro: 
     y = out if out is not None else torch.empty(n, m, ldt, dtype=out_dtype, device=x.device)
     if res is not None and res.dtype != y.dtype:
         raise ValueError(f"conv1x1_bf16: the residual rows must have the output's dtype ({y.dtype}), got {res.dtype}")
-    stats = None
-    if want_stats:
-        parts = lib().ps_conv1x1_stats_parts(m, t)
-        stats = torch.zeros(n, parts, 2, dtype=torch.float64, device=x.device)
+    stats = _stats_buffer(n, lib().ps_conv1x1_stats_parts(m, t), x.device, zeroed=True) if want_stats else None
     check(lib().ps_conv1x1_bf16_io(ptr(x), int(x.dtype == torch.bfloat16), ptr(wt_planes), ptr(y),
                                    int(y.dtype == torch.bfloat16), n, k, m, t, ldt, planes,
                                    C.byref(pro) if pro is not None else None, ptr(bias), ptr(bias_n), ptr(res),
@@ -406,6 +419,7 @@ def dwconv(x: torch.Tensor, t: int, w: torch.Tensor, b: Optional[torch.Tensor], 
     """x padded [N,H,ldt] (fp32 or bf16 rows), w [H,1,P] -> y padded [N,H,ldt] (+ partial stats; with want_amax the
     partial maxima of |y| [N, parts] instead: ps_dwconv_amax_f32, fp32 rows, P = 3, 2 * dilation <= 256)."""
     require_device(x, "dwconv", allow_bf16=True)
+    _require_operand("dwconv", x.device, w=w, b=b)
     n, h, ldt = x.shape
     p = w.shape[-1]
     y = torch.zeros(n, h, ldt, dtype=out_dtype or x.dtype, device=x.device)
@@ -415,10 +429,7 @@ def dwconv(x: torch.Tensor, t: int, w: torch.Tensor, b: Optional[torch.Tensor], 
                                        C.byref(pro) if pro is not None else None, ptr(amax), stream_ptr(x.device)),
               "ps_dwconv_amax_f32")
         return y, amax
-    stats = None
-    if want_stats:
-        parts = lib().ps_dwconv_stats_parts(h, t)
-        stats = torch.zeros(n, parts, 2, dtype=torch.float64, device=x.device)
+    stats = _stats_buffer(n, lib().ps_dwconv_stats_parts(h, t), x.device, zeroed=True) if want_stats else None
     check(lib().ps_dwconv_io(ptr(x), int(x.dtype == torch.bfloat16), ptr(w), ptr(b), ptr(y),
                              int(y.dtype == torch.bfloat16), n, h, t, ldt, p, dilation, left,
                              C.byref(pro) if pro is not None else None, ptr(stats), stream_ptr(x.device)),
@@ -460,15 +471,6 @@ def attn_weights(logits: torch.Tensor, t: int, lengths: Optional[torch.Tensor] =
 COOP_LSTM = os.environ.get("PS_COOP_LSTM", "1") != "0"   # 0: always the streamed-weight kernel
 _COOP_LAST = [None]
 RNN_KINDS = {"RNN": 0, "GRU": 2}
-
-
-def _require_operand(who: str, device: torch.device, dtype: torch.dtype = torch.float32, **tensors) -> None:
-    """Tensors whose pointers go into ps_lstm_args or the call: on the input's device, `dtype`, contiguous.  Anything else
-    reaches the kernel as a wild pointer: a GPU fault, not an error."""
-    for name, t in tensors.items():
-        if t is not None and (t.device != device or t.dtype != dtype or not t.is_contiguous()):
-            raise RuntimeError(f"{who}: {name} must be a contiguous {dtype} tensor on {device} "
-                               f"(got {t.dtype} on {t.device}, strides {tuple(t.stride())})")
 
 
 def _lstm_state_args(who: str, a: LstmArgs, n: int, rows: int, q: int, h0, c0, want_state: bool, state_out, device,
@@ -1104,14 +1106,22 @@ def dprnn_block_step(x: torch.Tensor, counter: torch.Tensor, intra: dict, inter:
     return out
 
 
+def _conv2d_sources(who: str, x1: torch.Tensor, x2: Optional[torch.Tensor]) -> tuple[int, int, int, int, int]:
+    """x1 [N,C1,F,ld] (+ x2 [N,C2,F,ld], the skip connection a decoder layer concatenates) -> (N, C1, C2, F, ld)."""
+    require_device(x1, who)
+    n, c1, f_in, ld = x1.shape
+    if x2 is None:
+        return n, c1, 0, f_in, ld
+    _require_operand(who, x1.device, x2=x2)
+    if (x2.shape[0], x2.shape[2], x2.shape[3]) != (n, f_in, ld):
+        raise RuntimeError(f"{who}: the two sources must agree in N, F and ld")
+    return n, c1, x2.shape[1], f_in, ld
+
+
 def unfold2d(x1: torch.Tensor, x2: Optional[torch.Tensor], t: int, f_out: int, kf: int, kt: int, stride_f: int,
              dil_f: int, dil_t: int, pad_f: int, pad_t: int, transposed: bool, t_in: Optional[int] = None) -> torch.Tensor:
     """x1 [N,C1,F,ld] (+ x2 [N,C2,F,ld]) -> tap rows [N, (C1+C2)*kf*kt, f_out*ld] for the Conv2d / ConvTranspose2d GEMM."""
-    require_device(x1, "unfold2d")
-    n, c1, f_in, ld = x1.shape
-    c2 = 0 if x2 is None else x2.shape[1]
-    if x2 is not None and (x2.shape[0], x2.shape[2], x2.shape[3]) != (n, f_in, ld):
-        raise RuntimeError("unfold2d: the two sources must agree in N, F and ld")
+    n, c1, c2, f_in, ld = _conv2d_sources("unfold2d", x1, x2)
     y = torch.empty(n, (c1 + c2) * kf * kt, f_out * ld, dtype=torch.float32, device=x1.device)
     check(lib().ps_unfold2d_f32(ptr(x1), c1, ptr(x2), c2, ptr(y), n, f_in, t if t_in is None else t_in, t, ld, kf, kt, stride_f, dil_f, dil_t, pad_f,
                                 pad_t, f_out, int(transposed), stream_ptr(x1.device)), "ps_unfold2d_f32")
@@ -1122,11 +1132,8 @@ def conv2d(x1: torch.Tensor, x2: Optional[torch.Tensor], wt: torch.Tensor, bias:
            f_out: int, kf: int, kt: int, stride_f: int, dil_f: int, dil_t: int, pad_f: int, pad_t: int, transposed: bool,
            act: str = "none", slope: Optional[torch.Tensor] = None, t_in: Optional[int] = None) -> torch.Tensor:
     """Implicit-GEMM Conv2d / ConvTranspose2d on [N,C,F,ld] rows -> [N,M,f_out,ld] with bias + activation."""
-    require_device(x1, "conv2d")
-    n, c1, f_in, ld = x1.shape
-    c2 = 0 if x2 is None else x2.shape[1]
-    if x2 is not None and (x2.shape[0], x2.shape[2], x2.shape[3]) != (n, f_in, ld):
-        raise RuntimeError("conv2d: the two sources must agree in N, F and ld")
+    n, c1, c2, f_in, ld = _conv2d_sources("conv2d", x1, x2)
+    _require_operand("conv2d", x1.device, wt=wt, bias=bias, slope=slope)
     y = torch.empty(n, m, f_out, ld, dtype=torch.float32, device=x1.device)
     check(lib().ps_conv2d_f32(ptr(x1), c1, ptr(x2), c2, ptr(wt), ptr(bias), ptr(y), n, m, f_in,
                               t if t_in is None else t_in, t, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, pad_t, f_out,
@@ -1155,15 +1162,11 @@ def conv2d_f16x2(x1: torch.Tensor, x2: Optional[torch.Tensor], wimg: torch.Tenso
                  want_stats: bool = False):
     """conv2d / conv2d_stats in the fp16x2 arithmetic (ps_conv2d_f16x2_f32; weights from pack_conv2d_f16x2).  Returns y, or
     (y, stats) with want_stats (the activation should then be "none": a gLN follows)."""
-    require_device(x1, "conv2d_f16x2")
-    n, c1, f_in, ld = x1.shape
-    c2 = 0 if x2 is None else x2.shape[1]
-    if x2 is not None and (x2.shape[0], x2.shape[2], x2.shape[3]) != (n, f_in, ld):
-        raise RuntimeError("conv2d_f16x2: the two sources must agree in N, F and ld")
+    n, c1, c2, f_in, ld = _conv2d_sources("conv2d_f16x2", x1, x2)
+    _require_operand("conv2d_f16x2", x1.device, torch.float16, wimg=wimg)
+    _require_operand("conv2d_f16x2", x1.device, bias=bias, slope=slope)
     y = torch.empty(n, m, f_out, ld, dtype=torch.float32, device=x1.device)
-    stats = None
-    if want_stats:
-        stats = torch.empty(n, lib().ps_conv2d_stats_parts(m, f_out, ld), 2, dtype=torch.float64, device=x1.device)
+    stats = _stats_buffer(n, lib().ps_conv2d_stats_parts(m, f_out, ld), x1.device) if want_stats else None
     check(lib().ps_conv2d_f16x2_f32(ptr(x1), c1, ptr(x2), c2, ptr(wimg), int(w_exp), ptr(bias), ptr(y), n, m, f_in,
                                     t if t_in is None else t_in, t, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, pad_t, f_out,
                                     int(transposed), ACT_KINDS[act], ptr(slope), ptr(stats), stream_ptr(x1.device)),
@@ -1176,13 +1179,10 @@ def conv2d_stats(x1: torch.Tensor, x2: Optional[torch.Tensor], wt: torch.Tensor,
                  t_in: Optional[int] = None):
     """conv2d without activation + the partial (sum, sum of squares) of its outputs over the t valid frames ->
     (y [N,M,f_out,ld], stats [N, parts, 2] fp64): the convolution in front of a gLN (ps_conv2d_stats_f32)."""
-    require_device(x1, "conv2d_stats")
-    n, c1, f_in, ld = x1.shape
-    c2 = 0 if x2 is None else x2.shape[1]
-    if x2 is not None and (x2.shape[0], x2.shape[2], x2.shape[3]) != (n, f_in, ld):
-        raise RuntimeError("conv2d_stats: the two sources must agree in N, F and ld")
+    n, c1, c2, f_in, ld = _conv2d_sources("conv2d_stats", x1, x2)
+    _require_operand("conv2d_stats", x1.device, wt=wt, bias=bias)
     y = torch.empty(n, m, f_out, ld, dtype=torch.float32, device=x1.device)
-    stats = torch.empty(n, lib().ps_conv2d_stats_parts(m, f_out, ld), 2, dtype=torch.float64, device=x1.device)
+    stats = _stats_buffer(n, lib().ps_conv2d_stats_parts(m, f_out, ld), x1.device)
     check(lib().ps_conv2d_stats_f32(ptr(x1), c1, ptr(x2), c2, ptr(wt), ptr(bias), ptr(y), n, m, f_in,
                                     t if t_in is None else t_in, t, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, pad_t, f_out,
                                     int(transposed), ptr(stats), stream_ptr(x1.device)), "ps_conv2d_stats_f32")
@@ -1202,7 +1202,7 @@ def row_stats(x: torch.Tensor, t: int) -> torch.Tensor:
     """padded rows [N, rows, ld] -> [N, parts, 2] fp64 partial (sum, sum of squares) over the t valid frames."""
     require_device(x, "row_stats")
     n, rows, ld = x.shape
-    out = torch.empty(n, lib().ps_row_stats_parts(), 2, dtype=torch.float64, device=x.device)
+    out = _stats_buffer(n, lib().ps_row_stats_parts(), x.device)
     check(lib().ps_row_stats_f64(ptr(x), ptr(out), n, rows, t, ld, stream_ptr(x.device)), "ps_row_stats_f64")
     return out
 
