@@ -716,7 +716,8 @@ typedef struct ps_tcn_block {
   int hidden_bf16;
   /* gemm_planes = 2 ("fp16x2", ps_conv1x1_f16x2_f32): in_wb / pw_wb / out_wb hold the two-plane fp16 images of
    * 2^w_exp[i] * W (i = 0 / 1 / 2: in, pointwise, out); dw_* / pw_* = max |gamma|, max |beta| of the norms in front of
-   * the pointwise and output convs (both PS_NORM_GLOBAL: the bound on the normalised values gives the activation scale);
+   * the pointwise and output convs (PS_NORM_GLOBAL: the bound on the normalised values gives the activation scale; or
+   * PS_NORM_AFFINE: the producer's measured maxima, mapped through the largest scale and shift, give it);
    * the residual stream's range travels from out_conv to the next in_conv as partial maxima inside the workspace */
   int w_exp[3];
   float dw_gmax, dw_bmax, pw_gmax, pw_bmax;
@@ -818,7 +819,8 @@ int ps_absmax_f32(const float* x, float* amax, int N, int C, int T, int ldt, voi
 size_t ps_conv_tasnet_workspace_bytes(int N, int C, int H, int T);
 
 /* x_in [N][C][ldt] is read only; x_out [N][C][ldt] receives the mask logits (pre-constraint).
- * dvec [N][E] may be NULL; blocks_host is a HOST array (it only carries launch arguments). */
+ * dvec [N][E] may be NULL; blocks_host is a HOST array (it only carries launch arguments).  A refused call launches
+ * nothing: every argument and every block is checked before the first launch. */
 int ps_conv_tasnet_f32(const ps_tcn_block* blocks_host, int n_blocks, const float* x_in, float* x_out,
                        const float* dvec, int embed_norm, int N, int T, int ldt, void* workspace,
                        size_t workspace_bytes, void* stream);

@@ -19,10 +19,12 @@ int g_debug_grid_cap = 0;
 int g_debug_ablate = 0;
 void* g_debug_buffer = nullptr;
 
+static void vset_error(const char* fmt, va_list ap) { vsnprintf(g_err, sizeof(g_err), fmt, ap); }
+
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  vset_error(fmt, ap);
   va_end(ap);
 }
 
@@ -214,247 +216,229 @@ extern "C" size_t ps_conv_tasnet_workspace_bytes(int N, int C, int H, int T) {
   return carve(nullptr, N, C, H, T).bytes;
 }
 
-// x_amax / x_amax_parts: partial maxima of |x_in| (gemm_planes = 2); y_amax: where out_conv leaves those of x_out
-// sb: the residual stream (x_in, x_out) is bf16 rows too (ps_conv_tasnet_bf16_rows; needs gemm_planes = 1 with hidden_bf16)
-static int run_block(const ps_tcn_block& b, const float* x_in, float* x_out, const float* dvec, int embed_norm,
-                     int N, int T, int ldt, const TasnetWs& w, const float* x_amax, int x_amax_parts, float* y_amax,
-                     void* stream, int sb = 0) {
-  int rc;
-  const float eps = 1e-8f;  // GlobLN.eps and gGN's eps (lobe/norm.py:10,96); folded BN carries its own
+// The driver: helpers, the checks, the per-block plan, the launch path, the three entries.
+static int dw_left(int P, int dilation, int causal) { return causal ? (P - 1) * dilation : ((P - 1) / 2) * dilation; }
+
+// gemm_planes = 2 behind a folded BatchNorm (bN1d blocks: no bound on the normalised values exists): the producer leaves the
+// maxima of its output behind -- in the statistics slots such a norm has no use for -- and the consumer maps them through the
+// norm's largest scale and shift
+static bool measured_behind(const ps_tcn_block& b, int norm) { return b.gemm_planes == 2 && norm == PS_NORM_AFFINE; }
+
+// the maxima of the depthwise output come from the kernel that measures while it writes, or from one ps_absmax_f32 pass
+// into a statistics slot of ws_parts (sum, sum of squares) pairs
+static bool dw_maxima_have_room(int P, int dilation, int causal, int ws_parts) {
+  return ps_dwconv_amax_ok(P, dilation, dw_left(P, dilation, causal)) ||
+         (size_t)ps_absmax_parts() * sizeof(float) <= (size_t)ws_parts * 2 * sizeof(double);
+}
+
+// bf16 rows (sb): launches the register-B kernel takes run with ONE fp16 product per multiply-add (ps_conv1x1_f16_rows)
+// whenever the block carries the fp16 weight image and the input's range is known; behind a norm that is a global one
+static bool out_conv_on_f16_rows(const ps_tcn_block& b, int sb, int N, int T) {
+  return sb && b.out_wf && b.pw_norm == PS_NORM_GLOBAL && ps_conv1x1_f16_rows_ok(N, b.H, b.C, T);
+}
+
+// THE rule for the range chain: this block's out_conv leaves the partial maxima of the stream for the next in_conv, and its
+// own in_conv reads those the block before left -- fp16x2 blocks, and bf16-rows blocks on the f16-rows kernel at both ends
+static bool leaves_maxima(const ps_tcn_block& b, int sb, int N, int T) {
+  return b.gemm_planes == 2 || (out_conv_on_f16_rows(b, sb, N, T) && b.in_wf);
+}
+
+// norm + PReLU in front of a consumer: GlobLN.eps and gGN's eps (lobe/norm.py:10,96); a folded BN carries its own
+static ps_prologue norm_prelu(int norm, const double* stats, int parts, double count, const float* gamma, const float* beta,
+                              const float* slope) {
+  return ps_prologue{norm, /*prelu*/ 1, stats, parts, count, /*eps*/ 1e-8f, gamma, beta, slope, /*pre_relu*/ 0, /*post_tanh*/ 0};
+}
+
+// The range descriptor of GEMM `which` (0 / 1 / 2: in_conv, pointwise, out_conv) in the fp16x2 and the f16-rows arithmetic.
+// in_conv: the maxima of the stream (x_amax).  Behind a norm (gmax / bmax: its largest scale and shift, times
+// max(1, |slope|), from the planner): the producer's measured maxima when there are any, else the bound of a global norm.
+static ps_f16x2_range gemm_range(const ps_tcn_block& b, int which, double count, const float* x_amax, int x_amax_parts,
+                                 float* y_amax) {
+  ps_f16x2_range rng{};
+  rng.w_exp = b.w_exp[which], rng.y_amax = y_amax;
+  const float gmax = which == 1 ? b.dw_gmax : b.pw_gmax, bmax = which == 1 ? b.dw_bmax : b.pw_bmax;
+  if (which == 0 || (x_amax && gmax > 0.f)) {
+    rng.x_amax = x_amax;
+    rng.x_amax_parts = x_amax_parts;
+    // behind a per-channel affine map: |scale_c v + shift_c| <= max|scale| max|v| + max|shift|
+    rng.amax_mul = which == 0 ? 0.f : gmax;
+    rng.amax_add = which == 0 ? 0.f : bmax;
+  } else if (x_amax) {
+    rng.x_bound = bmax > 0.f ? bmax : 1.f;  // (scale = 0: the map is the constant shift)
+  } else {
+    // behind a global norm |z| <= sqrt(count - 1), so |gamma z + beta| <= max|gamma| sqrt(count) + max|beta|
+    rng.x_bound = gmax * (float)sqrt(count) + bmax;
+    if (!(rng.x_bound > 0.f)) rng.x_bound = 1.f;  // (gamma = beta = 0: every value is 0)
+  }
+  return rng;
+}
+
+// sets the message and hands back the code
+static int refuse(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vset_error(fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+// Everything a call can be refused for, before the first launch: the arguments, then block by block
+static int check_call(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out, const float* dvec,
+                      int embed_norm, int N, int T, int ldt, void* workspace, size_t workspace_bytes, const float* x_amax,
+                      int x_amax_parts, void* stream, int sb) {
+  if (x_amax && x_amax_parts <= 0) return refuse(PS_E_INVALID, "ps_conv_tasnet_ranged_f32: x_amax needs x_amax_parts > 0");
+  if (!blocks || n_blocks <= 0 || !x_in || !x_out || !workspace || N <= 0 || T <= 0)
+    return refuse(PS_E_INVALID, "ps_conv_tasnet_f32: null pointer or non-positive size");
+  if (x_in == x_out)
+    return refuse(PS_E_INVALID, "ps_conv_tasnet_f32: x_in must not alias x_out (the input is never modified)");
+  if (ldt != ps_padded_frames(T))
+    return refuse(PS_E_ALIGN, "ps_conv_tasnet_f32: ldt=%d must be ps_padded_frames(T=%d)=%d", ldt, T, ps_padded_frames(T));
+  const int C = blocks[0].C, H = blocks[0].H;
+  for (int i = 0; i < n_blocks; ++i) {
+    const ps_tcn_block& b = blocks[i];
+    if (b.C != C || b.H != H || b.P <= 0 || b.dilation <= 0)
+      return refuse(PS_E_INVALID, "ps_conv_tasnet_f32: block %d has inconsistent sizes (C=%d H=%d P=%d dilation=%d)", i, b.C,
+                    b.H, b.P, b.dilation);
+    // reference: AssertionError in DepthwiseSeparableConv1d (lobe/cnn.py:40-44)
+    if (b.causal && (b.in_norm == PS_NORM_GLOBAL || b.dw_norm == PS_NORM_GLOBAL || b.pw_norm == PS_NORM_GLOBAL))
+      return refuse(PS_E_INVALID, "ps_conv_tasnet_f32: block %d: global norms conflict with causal=1", i);
+  }
+  const size_t need = ps_conv_tasnet_workspace_bytes(N, C, H, T);
+  if (workspace_bytes < need)
+    return refuse(PS_E_INVALID, "ps_conv_tasnet_f32: workspace too small (%zu < %zu)", workspace_bytes, need);
+  if ((uintptr_t)workspace & 255) return refuse(PS_E_ALIGN, "ps_conv_tasnet_f32: workspace must be 256-byte aligned");
+  const int ws_parts = ps_stats_parts(H, T);
+  const auto ranged = [](int norm) { return norm == PS_NORM_GLOBAL || norm == PS_NORM_AFFINE; };
+  for (int i = 0; i < n_blocks; ++i) {
+    const ps_tcn_block& b = blocks[i];
+    if (sb && (b.gemm_planes != 1 || !b.hidden_bf16))
+      return refuse(PS_E_UNSUPPORTED,
+                    "ps_conv_tasnet_bf16_rows: block %d is not in the bf16 arithmetic (gemm_planes = 1, hidden_bf16)", i);
+    if (b.in_embed_w && !dvec)
+      return refuse(PS_E_INVALID, "ps_conv_tasnet_f32: block expects an embedding (E=%d) but dvec is NULL", b.E);
+    // (the range of the block's input is never missing: the caller's, the block before's, or one ps_absmax_f32 pass, whose
+    // ps_absmax_parts() is a positive constant)
+    if (b.gemm_planes == 2 && (!ranged(b.dw_norm) || !ranged(b.pw_norm)))
+      return refuse(PS_E_UNSUPPORTED,
+                    "ps_conv_tasnet_f32: gemm_planes=2 (fp16x2) needs a global norm (a bound on the normalised values) or a "
+                    "per-channel affine norm (the producer's measured maxima) in front of the pointwise and output convs, and "
+                    "the range of the block's input");
+    if (b.gemm_planes != 0 && (!b.in_wb || !b.pw_wb || !b.out_wb))
+      return refuse(PS_E_INVALID, "ps_conv_tasnet_f32: gemm_planes=%d needs the plane-packed weights in_wb / pw_wb / out_wb",
+                    b.gemm_planes);
+    if (b.gemm_planes < 0 || b.gemm_planes > 3)  // (what ps_conv1x1_bf16_io would answer at the block's first GEMM)
+      return refuse(PS_E_INVALID, "ps_conv1x1_bf16_f32: planes must be 1 (bf16 products) or 3 (fp32-accurate 3-way split), got %d",
+                    b.gemm_planes);
+    if (measured_behind(b, b.dw_norm) && !dw_maxima_have_room(b.P, b.dilation, b.causal, ws_parts))
+      return refuse(PS_E_UNSUPPORTED, "ps_conv_tasnet_f32: no room for the maxima of the depthwise output (T=%d)", T);
+  }
+  return 0;
+}
+
+// What one block enqueues, decided without launching.  The three GEMMs (0 / 1 / 2: in_conv, pointwise, out_conv) each run
+// on one of five entries: exact fp32 MFMA; fp16x2; bf16 rows with one fp16 product; the bf16 pipe with 1 / 3 operand planes.
+// hidden_bf16 (with gemm_planes = 1): y1, y2, y3 -- which never leave the workspace -- are bf16 rows.
+enum GemmEntry { GEMM_F32, GEMM_F16X2, GEMM_F16_ROWS, GEMM_BF16_PLANES_1, GEMM_BF16_PLANES_3 };
+enum DwEntry { DW_MEASURING, DW_IO, DW_IO_THEN_ABSMAX };  // (the last: a shape outside the kernel that measures while it writes)
+struct BlockPlan {
+  GemmEntry gemm[3];
+  ps_f16x2_range rng[3];  // GEMM_F16X2 and GEMM_F16_ROWS
+  DwEntry dw;
+  int hb;        // the hidden maps are bf16 rows
+  float *a2, *a3;  // where the maxima of y2 / y3 go (fp16x2 behind a folded BatchNorm), else NULL
+};
+
+// x_amax / x_amax_parts: partial maxima of the block's input, or NULL; y_amax: where out_conv leaves those of x_out, or NULL
+static BlockPlan plan_block(const ps_tcn_block& b, int N, int T, const TasnetWs& w, int sb, const float* x_amax,
+                            int x_amax_parts, float* y_amax) {
+  BlockPlan p{};
   const double count = (double)b.H * (double)T;
-  const int gemm_parts_h = ps_conv1x1_stats_parts(b.H, T);
-  const int dw_parts = ps_dwconv_stats_parts(b.H, T);
+  p.hb = (b.hidden_bf16 && b.gemm_planes == 1) ? 1 : 0;
+  p.a2 = measured_behind(b, b.dw_norm) ? reinterpret_cast<float*>(w.s2) : nullptr;
+  p.a3 = measured_behind(b, b.pw_norm) ? reinterpret_cast<float*>(w.s3) : nullptr;
+  p.dw = !p.a2 ? DW_IO : ps_dwconv_amax_ok(b.P, b.dilation, dw_left(b.P, b.dilation, b.causal)) ? DW_MEASURING : DW_IO_THEN_ABSMAX;
+  const int a2_parts = p.dw == DW_MEASURING ? ps_dwconv_stats_parts(b.H, T) : ps_absmax_parts();
+  const GemmEntry plain = b.gemm_planes == 0 ? GEMM_F32 : b.gemm_planes == 2 ? GEMM_F16X2  // (check_call: 0 .. 3)
+                          : b.gemm_planes == 1 ? GEMM_BF16_PLANES_1 : GEMM_BF16_PLANES_3;
+  p.gemm[0] = p.gemm[1] = p.gemm[2] = plain;
+  if (sb) {
+    if (b.in_wf && x_amax && ps_conv1x1_f16_rows_ok(N, b.C, b.H, T)) p.gemm[0] = GEMM_F16_ROWS;
+    if (b.pw_wf && b.dw_norm == PS_NORM_GLOBAL && ps_conv1x1_f16_rows_ok(N, b.H, b.H, T)) p.gemm[1] = GEMM_F16_ROWS;
+    if (out_conv_on_f16_rows(b, sb, N, T)) p.gemm[2] = GEMM_F16_ROWS;
+  }
+  p.rng[0] = gemm_range(b, 0, count, x_amax, x_amax_parts, nullptr);
+  p.rng[1] = gemm_range(b, 1, count, p.a2, a2_parts, p.a3);
+  p.rng[2] = gemm_range(b, 2, count, p.a3, ps_conv1x1_stats_parts(b.H, T), y_amax);
+  return p;
+}
+
+// wt / wb / wf: the weight in kernel layout, plane-packed, and as the fp16 image of the f16-rows kernel
+static int launch_gemm(GemmEntry entry, const ps_f16x2_range& rng, const float* x, int xb, const float* wt, const void* wb,
+                       const void* wf, float* y, int yb, int N, int K, int M, int T, int ldt, const ps_prologue* pro,
+                       const float* bias, const float* bn, const float* res, double* st, void* stream) {
+  switch (entry) {
+    case GEMM_F32: return ps_conv1x1_f32(x, wt, y, N, K, M, T, ldt, pro, bias, bn, res, st, stream);
+    case GEMM_F16X2: return ps_conv1x1_f16x2_f32(x, wb, &rng, y, N, K, M, T, ldt, pro, bias, bn, res, st, stream);
+    case GEMM_F16_ROWS: return ps_conv1x1_f16_rows(x, wf, &rng, y, N, K, M, T, ldt, pro, bias, bn, res, st, stream);
+    case GEMM_BF16_PLANES_1: return ps_conv1x1_bf16_io(x, xb, wb, y, yb, N, K, M, T, ldt, 1, pro, bias, bn, res, st, stream);
+    case GEMM_BF16_PLANES_3: return ps_conv1x1_bf16_io(x, xb, wb, y, yb, N, K, M, T, ldt, 3, pro, bias, bn, res, st, stream);
+  }
+  return PS_E_INVALID;
+}
+
+// sb: the residual stream (x_in, x_out) is bf16 rows too
+static int launch_block(const ps_tcn_block& b, const BlockPlan& p, const float* x_in, float* x_out, const float* dvec,
+                        int embed_norm, int N, int T, int ldt, const TasnetWs& w, void* stream, int sb) {
+  int rc;
+  const double count = (double)b.H * (double)T;
+  const int gemm_parts_h = ps_conv1x1_stats_parts(b.H, T), dw_parts = ps_dwconv_stats_parts(b.H, T), hb = p.hb;
 
   // 1) in_conv (no bias) [+ per-utterance embedding bias]; stats of y1
-  const float* bias_n = nullptr;
-  if (b.in_embed_w) {
-    if (!dvec) {
-      set_error("ps_conv_tasnet_f32: block expects an embedding (E=%d) but dvec is NULL", b.E);
-      return PS_E_INVALID;
-    }
-    rc = ps_embed_bias_f32(dvec, b.in_embed_w, w.bias_n, N, b.E, b.H, embed_norm, stream);
-    if (rc) return rc;
-    bias_n = w.bias_n;
-  }
-  // the three GEMMs: exact fp32 MFMA, or the bf16 pipe with 1 / 3 operand planes
-  // hidden_bf16 (with gemm_planes = 1): y1, y2, y3 -- which never leave this workspace -- are bf16 rows; the block's
-  // input and output (the residual stream) stay fp32
-  const int hb = (b.hidden_bf16 && b.gemm_planes == 1) ? 1 : 0;
-  // gemm_planes = 2 behind a folded BatchNorm (bN1d blocks: no bound on the normalised values exists): the producers leave
-  // the maxima of |y2| / |y3| behind -- in the statistics slots such a norm has no use for -- and the consumer maps them
-  // through the norm's largest scale and shift
-  float* const a2 = (b.gemm_planes == 2 && b.dw_norm == PS_NORM_AFFINE) ? reinterpret_cast<float*>(w.s2) : nullptr;
-  float* const a3 = (b.gemm_planes == 2 && b.pw_norm == PS_NORM_AFFINE) ? reinterpret_cast<float*>(w.s3) : nullptr;
-  int a2_parts = 0;
-  // `which` = 0 / 1 / 2: in_conv, pointwise, out_conv (gemm_planes = 2: each has its own range descriptor)
-  auto gemm = [&](int which, const float* x, int xb, const float* wt, const void* wb, float* y, int yb, int K, int M,
-                  const ps_prologue* pro, const float* bias, const float* bn, const float* res, double* st) {
-    if (b.gemm_planes == 0) return ps_conv1x1_f32(x, wt, y, N, K, M, T, ldt, pro, bias, bn, res, st, stream);
-    if (b.gemm_planes == 2) {
-      ps_f16x2_range rng{};
-      rng.w_exp = b.w_exp[which];
-      const float gmax = which == 1 ? b.dw_gmax : b.pw_gmax, bmax = which == 1 ? b.dw_bmax : b.pw_bmax;
-      const float* measured = which == 1 ? a2 : a3;  // maxima of the producer's output in front of a folded BatchNorm
-      if (which == 0) {
-        rng.x_amax = x_amax;
-        rng.x_amax_parts = x_amax_parts;
-      } else if (measured && gmax > 0.f) {
-        // behind a per-channel affine map: |scale_c v + shift_c| <= max|scale| max|v| + max|shift| (times max(1, |slope|),
-        // folded into gmax / bmax by the planner)
-        rng.x_amax = measured;
-        rng.x_amax_parts = which == 1 ? a2_parts : gemm_parts_h;
-        rng.amax_mul = gmax;
-        rng.amax_add = bmax;
-      } else if (measured) {
-        rng.x_bound = bmax > 0.f ? bmax : 1.f;  // (scale = 0: the map is the constant shift)
-      } else {
-        // behind a global norm |z| <= sqrt(count - 1), so |gamma z + beta| <= max|gamma| sqrt(count) + max|beta|
-        rng.x_bound = gmax * (float)sqrt(count) + bmax;
-        if (!(rng.x_bound > 0.f)) rng.x_bound = 1.f;  // (gamma = beta = 0: every value is 0)
-      }
-      if (which == 1) rng.y_amax = a3;
-      if (which == 2) rng.y_amax = y_amax;
-      return ps_conv1x1_f16x2_f32(x, wb, &rng, y, N, K, M, T, ldt, pro, bias, bn, res, st, stream);
-    }
-    // bf16 residual stream: launches the register-B kernel takes run with bf16 rows and ONE fp16 product per multiply-add
-    // (ps_conv1x1_f16_rows) whenever the block carries the fp16 weight images and the input's range is known
-    const void* wf = which == 0 ? b.in_wf : which == 1 ? b.pw_wf : b.out_wf;
-    if (sb && wf && xb && yb && ps_conv1x1_f16_rows_ok(N, K, M, T)) {
-      ps_f16x2_range rng{};
-      rng.w_exp = b.w_exp[which];
-      bool have = true;
-      if (which == 0) {
-        rng.x_amax = x_amax;
-        rng.x_amax_parts = x_amax_parts;
-        have = x_amax != nullptr;
-      } else {
-        const float gmax = which == 1 ? b.dw_gmax : b.pw_gmax, bmax = which == 1 ? b.dw_bmax : b.pw_bmax;
-        rng.x_bound = gmax * (float)sqrt(count) + bmax;
-        if (!(rng.x_bound > 0.f)) rng.x_bound = 1.f;
-        have = (which == 1 ? b.dw_norm : b.pw_norm) == PS_NORM_GLOBAL;
-      }
-      if (which == 2) rng.y_amax = y_amax;
-      if (have) return ps_conv1x1_f16_rows(x, wf, &rng, y, N, K, M, T, ldt, pro, bias, bn, res, st, stream);
-    }
-    return ps_conv1x1_bf16_io(x, xb, wb, y, yb, N, K, M, T, ldt, b.gemm_planes, pro, bias, bn, res, st, stream);
-  };
-  auto ranged = [](int norm) { return norm == PS_NORM_GLOBAL || norm == PS_NORM_AFFINE; };
-  if (b.gemm_planes == 2 && (!ranged(b.dw_norm) || !ranged(b.pw_norm) || !x_amax)) {
-    set_error("ps_conv_tasnet_f32: gemm_planes=2 (fp16x2) needs a global norm (a bound on the normalised values) or a "
-              "per-channel affine norm (the producer's measured maxima) in front of the pointwise and output convs, and the "
-              "range of the block's input");
-    return PS_E_UNSUPPORTED;
-  }
-  if (b.gemm_planes != 0 && (!b.in_wb || !b.pw_wb || !b.out_wb)) {
-    set_error("ps_conv_tasnet_f32: gemm_planes=%d needs the plane-packed weights in_wb / pw_wb / out_wb", b.gemm_planes);
-    return PS_E_INVALID;
-  }
-  if (sb && !hb) {
-    set_error("ps_conv_tasnet_bf16_rows: block needs gemm_planes = 1 with hidden_bf16 (got planes=%d hidden_bf16=%d)",
-              b.gemm_planes, b.hidden_bf16);
-    return PS_E_UNSUPPORTED;
-  }
-  rc = gemm(0, x_in, sb, b.in_wt, b.in_wb, w.y1, hb, b.C, b.H, nullptr, nullptr, bias_n, nullptr,
-            b.in_norm == PS_NORM_GLOBAL ? w.s1 : nullptr);
+  const float* bias_n = b.in_embed_w ? w.bias_n : nullptr;
+  if (bias_n && (rc = ps_embed_bias_f32(dvec, b.in_embed_w, w.bias_n, N, b.E, b.H, embed_norm, stream))) return rc;
+  rc = launch_gemm(p.gemm[0], p.rng[0], x_in, sb, b.in_wt, b.in_wb, b.in_wf, w.y1, hb, N, b.C, b.H, T, ldt, nullptr, nullptr,
+                   bias_n, nullptr, b.in_norm == PS_NORM_GLOBAL ? w.s1 : nullptr, stream);
   if (rc) return rc;
 
-  // 2) depthwise: prologue = in_conv's norm + PReLU; stats of y2
-  ps_prologue p1{};
-  p1.norm = b.in_norm;
-  p1.prelu = 1;
-  p1.stats = w.s1;
-  p1.parts = gemm_parts_h;
-  p1.count = count;
-  p1.eps = eps;
-  p1.gamma = b.in_gamma;
-  p1.beta = b.in_beta;
-  p1.slope = b.in_slope;
-  const int left = b.causal ? (b.P - 1) * b.dilation : ((b.P - 1) / 2) * b.dilation;
-  if (a2 && ps_dwconv_amax_ok(b.P, b.dilation, left)) {
-    rc = ps_dwconv_amax_f32(w.y1, b.dw_w, b.dw_b, w.y2, N, b.H, T, ldt, b.P, b.dilation, left, &p1, a2, stream);
-    a2_parts = dw_parts;
+  // 2) depthwise: prologue = in_conv's norm + PReLU; stats (or maxima) of y2
+  const ps_prologue p1 = norm_prelu(b.in_norm, w.s1, gemm_parts_h, count, b.in_gamma, b.in_beta, b.in_slope);
+  const int left = dw_left(b.P, b.dilation, b.causal);
+  if (p.dw == DW_MEASURING) {
+    rc = ps_dwconv_amax_f32(w.y1, b.dw_w, b.dw_b, w.y2, N, b.H, T, ldt, b.P, b.dilation, left, &p1, p.a2, stream);
   } else {
     rc = ps_dwconv_io(w.y1, hb, b.dw_w, b.dw_b, w.y2, hb, N, b.H, T, ldt, b.P, b.dilation, left, &p1,
                       b.dw_norm == PS_NORM_GLOBAL ? w.s2 : nullptr, stream);
-    if (!rc && a2) {  // (a shape outside the kernel that measures while it writes: one more pass over y2)
-      if ((size_t)ps_absmax_parts() * sizeof(float) > (size_t)w.parts * 2 * sizeof(double)) {
-        set_error("ps_conv_tasnet_f32: no room for the maxima of the depthwise output (T=%d)", T);
-        return PS_E_UNSUPPORTED;
-      }
-      rc = ps_absmax_f32(w.y2, a2, N, b.H, T, ldt, stream);
-      a2_parts = ps_absmax_parts();
-    }
+    if (!rc && p.dw == DW_IO_THEN_ABSMAX) rc = ps_absmax_f32(w.y2, p.a2, N, b.H, T, ldt, stream);
   }
   if (rc) return rc;
 
   // 3) pointwise: prologue = depthwise norm + PReLU; stats of y3
-  ps_prologue p2{};
-  p2.norm = b.dw_norm;
-  p2.prelu = 1;
-  p2.stats = w.s2;
-  p2.parts = dw_parts;
-  p2.count = count;
-  p2.eps = eps;
-  p2.gamma = b.dw_gamma;
-  p2.beta = b.dw_beta;
-  p2.slope = b.dw_slope;
-  rc = gemm(1, w.y2, hb, b.pw_wt, b.pw_wb, w.y3, hb, b.H, b.H, &p2, b.pw_b, nullptr, nullptr,
-            b.pw_norm == PS_NORM_GLOBAL ? w.s3 : nullptr);
+  const ps_prologue p2 = norm_prelu(b.dw_norm, w.s2, dw_parts, count, b.dw_gamma, b.dw_beta, b.dw_slope);
+  rc = launch_gemm(p.gemm[1], p.rng[1], w.y2, hb, b.pw_wt, b.pw_wb, b.pw_wf, w.y3, hb, N, b.H, b.H, T, ldt, &p2, b.pw_b,
+                   nullptr, nullptr, b.pw_norm == PS_NORM_GLOBAL ? w.s3 : nullptr, stream);
   if (rc) return rc;
 
   // 4) out_conv + bias + residual: prologue = pointwise norm + PReLU
-  ps_prologue p3{};
-  p3.norm = b.pw_norm;
-  p3.prelu = 1;
-  p3.stats = w.s3;
-  p3.parts = gemm_parts_h;
-  p3.count = count;
-  p3.eps = eps;
-  p3.gamma = b.pw_gamma;
-  p3.beta = b.pw_beta;
-  p3.slope = b.pw_slope;
-  return gemm(2, w.y3, hb, b.out_wt, b.out_wb, x_out, sb, b.H, b.C, &p3, b.out_b, nullptr, x_in, nullptr);
-}
-
-extern "C" int ps_conv_tasnet_f32(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out,
-                                  const float* dvec, int embed_norm, int N, int T, int ldt, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-  return ps_conv_tasnet_ranged_f32(blocks, n_blocks, x_in, x_out, dvec, embed_norm, N, T, ldt, workspace, workspace_bytes,
-                                   nullptr, 0, stream);
-}
-
-static int conv_tasnet_rows(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out, const float* dvec,
-                            int embed_norm, int N, int T, int ldt, void* workspace, size_t workspace_bytes,
-                            const float* x_amax, int x_amax_parts, void* stream, int sb);
-
-extern "C" int ps_conv_tasnet_ranged_f32(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out,
-                                         const float* dvec, int embed_norm, int N, int T, int ldt, void* workspace,
-                                         size_t workspace_bytes, const float* x_amax, int x_amax_parts, void* stream) {
-  return conv_tasnet_rows(blocks, n_blocks, x_in, x_out, dvec, embed_norm, N, T, ldt, workspace, workspace_bytes, x_amax,
-                          x_amax_parts, stream, 0);
-}
-
-// BASELINE config 3's arithmetic ("bf16 storage / fp32 accumulate"): the residual stream is bf16 rows as well
-extern "C" int ps_conv_tasnet_bf16_rows(const ps_tcn_block* blocks, int n_blocks, const void* x_in, void* x_out,
-                                        const float* dvec, int embed_norm, int N, int T, int ldt, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-  return conv_tasnet_rows(blocks, n_blocks, (const float*)x_in, (float*)x_out, dvec, embed_norm, N, T, ldt, workspace,
-                          workspace_bytes, nullptr, 0, stream, 1);
+  const ps_prologue p3 = norm_prelu(b.pw_norm, w.s3, gemm_parts_h, count, b.pw_gamma, b.pw_beta, b.pw_slope);
+  return launch_gemm(p.gemm[2], p.rng[2], w.y3, hb, b.out_wt, b.out_wb, b.out_wf, x_out, sb, N, b.H, b.C, T, ldt, &p3, b.out_b,
+                     nullptr, x_in, nullptr, stream);
 }
 
 static int conv_tasnet_rows(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out, const float* dvec,
                             int embed_norm, int N, int T, int ldt, void* workspace, size_t workspace_bytes,
                             const float* x_amax, int x_amax_parts, void* stream, int sb) {
-  if (x_amax && x_amax_parts <= 0) {
-    set_error("ps_conv_tasnet_ranged_f32: x_amax needs x_amax_parts > 0");
-    return PS_E_INVALID;
-  }
-  if (!blocks || n_blocks <= 0 || !x_in || !x_out || !workspace || N <= 0 || T <= 0) {
-    set_error("ps_conv_tasnet_f32: null pointer or non-positive size");
-    return PS_E_INVALID;
-  }
-  if (x_in == x_out) {
-    set_error("ps_conv_tasnet_f32: x_in must not alias x_out (the input is never modified)");
-    return PS_E_INVALID;
-  }
-  if (ldt != ps_padded_frames(T)) {
-    set_error("ps_conv_tasnet_f32: ldt=%d must be ps_padded_frames(T=%d)=%d", ldt, T, ps_padded_frames(T));
-    return PS_E_ALIGN;
-  }
+  if (const int rc = check_call(blocks, n_blocks, x_in, x_out, dvec, embed_norm, N, T, ldt, workspace, workspace_bytes, x_amax,
+                                x_amax_parts, stream, sb))
+    return rc;
   const int C = blocks[0].C, H = blocks[0].H;
-  for (int i = 0; i < n_blocks; ++i) {
-    const ps_tcn_block& b = blocks[i];
-    if (b.C != C || b.H != H || b.P <= 0 || b.dilation <= 0) {
-      set_error("ps_conv_tasnet_f32: block %d has inconsistent sizes (C=%d H=%d P=%d dilation=%d)", i, b.C, b.H, b.P,
-                b.dilation);
-      return PS_E_INVALID;
-    }
-    if (b.causal && (b.in_norm == PS_NORM_GLOBAL || b.dw_norm == PS_NORM_GLOBAL || b.pw_norm == PS_NORM_GLOBAL)) {
-      // reference: AssertionError in DepthwiseSeparableConv1d (lobe/cnn.py:40-44)
-      set_error("ps_conv_tasnet_f32: block %d: global norms conflict with causal=1", i);
-      return PS_E_INVALID;
-    }
-  }
-  if (workspace_bytes < ps_conv_tasnet_workspace_bytes(N, C, H, T)) {
-    set_error("ps_conv_tasnet_f32: workspace too small (%zu < %zu)", workspace_bytes,
-              ps_conv_tasnet_workspace_bytes(N, C, H, T));
-    return PS_E_INVALID;
-  }
-  if ((uintptr_t)workspace & 255) {
-    set_error("ps_conv_tasnet_f32: workspace must be 256-byte aligned");
-    return PS_E_ALIGN;
-  }
   const TasnetWs w = carve(workspace, N, C, H, T);
   // block 0 reads the caller's input and writes x_out; later blocks update x_out in place (each
   // workgroup reads exactly the residual elements it overwrites).
-  int have_parts = 0;  // partial maxima of the current residual stream in w.amax[i & 1] (fp16x2 blocks only)
+  int have_parts = 0;  // partial maxima of the current residual stream in w.amax[i & 1] (blocks that leave_maxima only)
   const int out_parts = ps_conv1x1_stats_parts(C, T);
   for (int i = 0; i < n_blocks; ++i) {
     const float* xi = i == 0 ? x_in : x_out;
-    // (bf16 rows: out_conv leaves the maxima of the stream for the next in_conv when it runs on the register-B kernel)
-    const bool rows16 = sb && blocks[i].out_wf && blocks[i].in_wf && ps_conv1x1_f16_rows_ok(N, H, C, T) &&
-                        blocks[i].pw_norm == PS_NORM_GLOBAL;
-    const bool f16 = blocks[i].gemm_planes == 2 || rows16;
+    const bool f16 = leaves_maxima(blocks[i], sb, N, T);
     const float* range = w.amax[i & 1];
     if (f16 && i == 0 && x_amax) {  // the caller knows the range of x_in (maxima, or any upper bound per utterance)
       range = x_amax;
@@ -466,14 +450,33 @@ static int conv_tasnet_rows(const ps_tcn_block* blocks, int n_blocks, const floa
       if (rc) return rc;
       have_parts = ps_absmax_parts();
     }
-    if (sb && (blocks[i].gemm_planes != 1 || !blocks[i].hidden_bf16)) {
-      set_error("ps_conv_tasnet_bf16_rows: block %d is not in the bf16 arithmetic (gemm_planes = 1, hidden_bf16)", i);
-      return PS_E_UNSUPPORTED;
-    }
-    const int rc = run_block(blocks[i], xi, x_out, dvec, embed_norm, N, T, ldt, w, (f16 && have_parts) ? range : nullptr,
-                             have_parts, f16 ? w.amax[(i + 1) & 1] : nullptr, stream, sb);
+    const BlockPlan plan = plan_block(blocks[i], N, T, w, sb, (f16 && have_parts) ? range : nullptr, have_parts,
+                                      f16 ? w.amax[(i + 1) & 1] : nullptr);
+    const int rc = launch_block(blocks[i], plan, xi, x_out, dvec, embed_norm, N, T, ldt, w, stream, sb);
     if (rc) return rc;
     have_parts = f16 ? out_parts : 0;
   }
   return 0;
+}
+
+extern "C" int ps_conv_tasnet_ranged_f32(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out,
+                                         const float* dvec, int embed_norm, int N, int T, int ldt, void* workspace,
+                                         size_t workspace_bytes, const float* x_amax, int x_amax_parts, void* stream) {
+  return conv_tasnet_rows(blocks, n_blocks, x_in, x_out, dvec, embed_norm, N, T, ldt, workspace, workspace_bytes, x_amax,
+                          x_amax_parts, stream, 0);
+}
+
+extern "C" int ps_conv_tasnet_f32(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out,
+                                  const float* dvec, int embed_norm, int N, int T, int ldt, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  return ps_conv_tasnet_ranged_f32(blocks, n_blocks, x_in, x_out, dvec, embed_norm, N, T, ldt, workspace, workspace_bytes,
+                                   nullptr, 0, stream);
+}
+
+// BASELINE config 3's arithmetic ("bf16 storage / fp32 accumulate"): the residual stream is bf16 rows as well
+extern "C" int ps_conv_tasnet_bf16_rows(const ps_tcn_block* blocks, int n_blocks, const void* x_in, void* x_out,
+                                        const float* dvec, int embed_norm, int N, int T, int ldt, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  return conv_tasnet_rows(blocks, n_blocks, (const float*)x_in, (float*)x_out, dvec, embed_norm, N, T, ldt, workspace,
+                          workspace_bytes, nullptr, 0, stream, 1);
 }

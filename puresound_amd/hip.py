@@ -1354,39 +1354,57 @@ def l2_normalize(dvec: torch.Tensor) -> torch.Tensor:
     return embed_bias(dvec.float(), _EYE[key], True)
 
 
+def conv_tasnet_workspace(n: int, c: int, h: int, t: int, device: torch.device,
+                          have: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The scratch conv_tasnet needs for (n, c, h, t) on `device`: `have` when it is large enough and lives there, else a new,
+    zero-filled one (three hidden maps: 415 MB at 32 x 4 s -- a caller that runs more than once keeps what this returns)."""
+    need = lib().ps_conv_tasnet_workspace_bytes(n, c, h, t)
+    if have is not None and have.numel() >= need and have.device == device:
+        return have
+    return torch.zeros(need, dtype=torch.uint8, device=device)
+
+
+def _embed_sizes(blocks: "C.Array[TcnBlock]", n_blocks: int) -> frozenset:
+    """The E of the blocks that take an embedding.  Kept on the array: callers hold it as long as their plans."""
+    kept = getattr(blocks, "_embed_sizes", None)
+    if kept is None or kept[0] != n_blocks:
+        kept = blocks._embed_sizes = (n_blocks, frozenset(blocks[i].E for i in range(n_blocks) if blocks[i].in_embed_w))
+    return kept[1]
+
+
 def conv_tasnet(blocks: "C.Array[TcnBlock]", n_blocks: int, x_pad: torch.Tensor, t: int, c: int, h: int,
                 dvec: Optional[torch.Tensor], embed_norm: bool,
                 workspace: Optional[torch.Tensor] = None, x_amax: Optional[torch.Tensor] = None,
                 bf16_rows: bool = False) -> torch.Tensor:
     """Run the whole masker on padded input [N,C,ldt]; returns padded mask logits [N,C,ldt] (the frames beyond T are
     not written).  x_amax [N, parts]: per utterance, values whose maximum bounds |x_pad[n]| -- the range blocks in the
-    fp16x2 arithmetic scale their input by (without it they measure it with one pass over x_pad)."""
+    fp16x2 arithmetic scale their input by (without it they measure it with one pass over x_pad).  bf16 rows in (or
+    bf16_rows): the residual stream as bf16 rows (BASELINE config 3's arithmetic), every block in the bf16 arithmetic."""
     require_device(x_pad, "conv_tasnet", allow_bf16=True)
+    if x_pad.dim() != 3 or x_pad.shape[1] != c or not x_pad.is_contiguous():
+        raise RuntimeError(f"conv_tasnet: x_pad must be contiguous [N, C={c}, ldt] (got {tuple(x_pad.shape)}, "
+                           f"strides {x_pad.stride()})")
     n, _, ldt = x_pad.shape
+    dev = x_pad.device
+    if x_amax is not None and (x_amax.dim() != 2 or x_amax.shape[0] != n or not x_amax.is_contiguous()):
+        raise ValueError(f"conv_tasnet: x_amax must be a contiguous [N={n}, parts] tensor, got {tuple(x_amax.shape)}")
+    _require_operand("conv_tasnet", dev, dvec=dvec, x_amax=x_amax)
+    if dvec is not None:
+        sizes = _embed_sizes(blocks, n_blocks)
+        if dvec.dim() != 2 or dvec.shape[0] != n or sizes - {dvec.shape[1]}:
+            raise RuntimeError(f"conv_tasnet: dvec must be [N={n}, E], the blocks' E={sorted(sizes)} (got {tuple(dvec.shape)})")
     if bf16_rows and x_pad.dtype == torch.float32:
         # fp32 rows in, fp32 rows out, the residual stream in between as bf16 rows (two dtype casts around the stack)
         return conv_tasnet(blocks, n_blocks, x_pad.to(torch.bfloat16), t, c, h, dvec, embed_norm, workspace).float()
-    if x_pad.dtype == torch.bfloat16:
-        # the residual stream as bf16 rows (BASELINE config 3's arithmetic): every block in the bf16 arithmetic
-        need = lib().ps_conv_tasnet_workspace_bytes(n, c, h, t)
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.zeros(need, dtype=torch.uint8, device=x_pad.device)
-        out = torch.empty_like(x_pad)
-        check(lib().ps_conv_tasnet_bf16_rows(blocks, n_blocks, ptr(x_pad), ptr(out), ptr(dvec), int(embed_norm), n, t, ldt,
-                                             ptr(workspace), workspace.numel(), stream_ptr(x_pad.device)),
-              "ps_conv_tasnet_bf16_rows")
-        return out
-    need = lib().ps_conv_tasnet_workspace_bytes(n, c, h, t)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.zeros(need, dtype=torch.uint8, device=x_pad.device)
+    workspace = conv_tasnet_workspace(n, c, h, t, dev, workspace)
+    _require_operand("conv_tasnet", dev, torch.uint8, workspace=workspace)
     out = torch.empty_like(x_pad)
-    parts = 0
-    if x_amax is not None:
-        require_device(x_amax, "conv_tasnet (x_amax)")
-        if x_amax.dim() != 2 or x_amax.shape[0] != n or not x_amax.is_contiguous():
-            raise ValueError(f"conv_tasnet: x_amax must be a contiguous [N={n}, parts] tensor, got {tuple(x_amax.shape)}")
-        parts = x_amax.shape[1]
-    check(lib().ps_conv_tasnet_ranged_f32(blocks, n_blocks, ptr(x_pad), ptr(out), ptr(dvec), int(embed_norm), n, t, ldt,
-                                          ptr(workspace), workspace.numel(), ptr(x_amax), parts,
-                                          stream_ptr(x_pad.device)), "ps_conv_tasnet_ranged_f32")
+    if x_pad.dtype == torch.bfloat16:
+        check(lib().ps_conv_tasnet_bf16_rows(blocks, n_blocks, ptr(x_pad), ptr(out), ptr(dvec), int(embed_norm), n, t, ldt,
+                                             ptr(workspace), workspace.numel(), stream_ptr(dev)), "ps_conv_tasnet_bf16_rows")
+    else:
+        parts = 0 if x_amax is None else x_amax.shape[1]
+        check(lib().ps_conv_tasnet_ranged_f32(blocks, n_blocks, ptr(x_pad), ptr(out), ptr(dvec), int(embed_norm), n, t, ldt,
+                                              ptr(workspace), workspace.numel(), ptr(x_amax), parts, stream_ptr(dev)),
+              "ps_conv_tasnet_ranged_f32")
     return out

@@ -427,11 +427,9 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
                     # (x_amax: a bound on the features for fp16x2 blocks -- without one the driver measures them: 93 us)
                     # the driver's scratch (three hidden maps: 415 MB at 32 x 4 s) is kept, not re-allocated and
                     # zero-filled per call as hip.conv_tasnet does for callers without one
-                    need = hip.lib().ps_conv_tasnet_workspace_bytes(x.shape[0], run[0].in_channels, run[0].hid_channels, t)
-                    ws = self.__dict__.get("_spk_workspace")
-                    if ws is None or ws.numel() < need or ws.device != x.device:
-                        ws = torch.zeros(need, dtype=torch.uint8, device=x.device)
-                        object.__setattr__(self, "_spk_workspace", ws)
+                    ws = hip.conv_tasnet_workspace(x.shape[0], run[0].in_channels, run[0].hid_channels, t, x.device,
+                                                   self.__dict__.get("_spk_workspace"))
+                    object.__setattr__(self, "_spk_workspace", ws)
                     x = hip.conv_tasnet(blocks, len(plans), x, t, run[0].in_channels, run[0].hid_channels, None, False,
                                         workspace=ws, x_amax=x_amax, bf16_rows=all(p["rows_bf16"] for p in plans))
                 else:

@@ -143,11 +143,12 @@ class TCN(_PlanCache, nn.Module):
         b.gemm_planes = planes
         b.hidden_bf16 = int(hb)
         rows_bf16 = bool(hb and self.stream_bf16)
-        if planes == 2:
-            assert fused and kinds["dw"] in (PS_NORM_GLOBAL, PS_NORM_AFFINE) and kinds["pw"] in (PS_NORM_GLOBAL, PS_NORM_AFFINE)
-            for i, (key, wsrc) in enumerate((("in_wb", w_in[:, :c, 0]),
-                                             ("pw_wb", dsc.pointwise[0].weight.detach().to(**f32)),
-                                             ("out_wb", self.out_conv.weight.detach().to(**f32)))):
+        weights = (w_in[:, :c, 0], dsc.pointwise[0].weight.detach().to(**f32), self.out_conv.weight.detach().to(**f32))
+
+        def f16_images(keys):
+            """the fp16x2 images of the three weights under `keys`, with their exponents, and the bounds on the activations
+            in front of the pointwise and output convs"""
+            for i, (key, wsrc) in enumerate(zip(keys, weights)):
                 t[key], b.w_exp[i] = hip.pack_wt_f16x2(wsrc)
             # bound on |PReLU(gamma z + beta)| for the fp16 range: the PReLU runs before the split, and a slope beyond 1
             # in magnitude makes a negative value LARGER -- the factor max(1, |slope|) covers it
@@ -155,21 +156,17 @@ class TCN(_PlanCache, nn.Module):
             fp = max(1.0, abs(float(t["pw_slope"][0])))
             b.dw_gmax, b.dw_bmax = float(t["dw_gamma"].abs().max()) * fd, float(t["dw_beta"].abs().max()) * fd
             b.pw_gmax, b.pw_bmax = float(t["pw_gamma"].abs().max()) * fp, float(t["pw_beta"].abs().max()) * fp
+
+        if planes == 2:
+            assert fused and kinds["dw"] in (PS_NORM_GLOBAL, PS_NORM_AFFINE) and kinds["pw"] in (PS_NORM_GLOBAL, PS_NORM_AFFINE)
+            f16_images(("in_wb", "pw_wb", "out_wb"))
         elif planes:
-            t["in_wb"] = hip.pack_wt_bf16(w_in[:, :c, 0], planes)
-            t["pw_wb"] = hip.pack_wt_bf16(dsc.pointwise[0].weight.detach().to(**f32), planes)
-            t["out_wb"] = hip.pack_wt_bf16(self.out_conv.weight.detach().to(**f32), planes)
+            for key, wsrc in zip(("in_wb", "pw_wb", "out_wb"), weights):
+                t[key] = hip.pack_wt_bf16(wsrc, planes)
             if rows_bf16 and fused and kinds["dw"] == PS_NORM_GLOBAL and kinds["pw"] == PS_NORM_GLOBAL:
                 # bf16 residual stream: large launches run ps_conv1x1_f16_rows (bf16 rows, one fp16 product) -- the fp16
                 # images of the weights and the bounds of the normalised activations, as for "fp16x2"
-                for i, (key, wsrc) in enumerate((("in_wf", w_in[:, :c, 0]),
-                                                 ("pw_wf", dsc.pointwise[0].weight.detach().to(**f32)),
-                                                 ("out_wf", self.out_conv.weight.detach().to(**f32)))):
-                    t[key], b.w_exp[i] = hip.pack_wt_f16x2(wsrc)
-                fd = max(1.0, abs(float(t["dw_slope"][0])))
-                fp = max(1.0, abs(float(t["pw_slope"][0])))
-                b.dw_gmax, b.dw_bmax = float(t["dw_gamma"].abs().max()) * fd, float(t["dw_beta"].abs().max()) * fd
-                b.pw_gmax, b.pw_bmax = float(t["pw_gamma"].abs().max()) * fp, float(t["pw_beta"].abs().max()) * fp
+                f16_images(("in_wf", "pw_wf", "out_wf"))
         for k, v in t.items():
             setattr(b, k, ptr(v))
         _PLAN_SERIAL[0] += 1
@@ -448,13 +445,10 @@ class ConvTasNet(_PlanCache, nn.Module):
             raise RuntimeError("ConvTasNet.forward: tcn_with_embed is set but no dvec was given")
         if not need_embed:
             dvec = None  # reference ignores dvec when no block takes it (conv_tasnet.py:354-357)
-        n = x_pad.shape[0]
-        need = hip.lib().ps_conv_tasnet_workspace_bytes(n, self.input_dim, self.tcn_dim, t)
         if self._workspace is None:
             self._workspace = {}
-        ws = self._workspace.get(lane)
-        if ws is None or ws.numel() < need or ws.device != x_pad.device:
-            ws = self._workspace[lane] = torch.zeros(need, dtype=torch.uint8, device=x_pad.device)
+        ws = self._workspace[lane] = hip.conv_tasnet_workspace(x_pad.shape[0], self.input_dim, self.tcn_dim, t, x_pad.device,
+                                                               self._workspace.get(lane))
         rows_bf16 = all(m.plan(x_pad.device)["rows_bf16"] for stack in self.tcn_list for m in stack)
         return hip.conv_tasnet(blocks, n_blocks, x_pad, t, self.input_dim, self.tcn_dim,
                                None if dvec is None else dvec.contiguous().float(),

@@ -22,9 +22,7 @@ def run(nsplit, reps=10):
             s.wait_stream(cur)
             with torch.cuda.stream(s):
                 feats, t = model.encoder.encode_padded(c)
-                need = hip.lib().ps_conv_tasnet_workspace_bytes(c.shape[0], 512, 256, t)
-                if ws[i] is None:
-                    ws[i] = torch.zeros(need, dtype=torch.uint8, device=dev)
+                ws[i] = hip.conv_tasnet_workspace(c.shape[0], 512, 256, t, dev, ws[i])
                 mask = hip.conv_tasnet(blocks, nb, feats, t, 512, 256, None, False, ws[i])
                 outs.append(model.encoder.decode_padded(feats, t, mask, "relu", "linear"))
         for s in streams:
