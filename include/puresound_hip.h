@@ -673,6 +673,59 @@ int ps_dprnn_block_step_slots_f32(const float* x, float* y, const int* counter, 
                                   const ps_dprnn_pass* inter, float* h_intra, float* c_intra, float* h_bank, float* c_bank,
                                   int C, int H, int K, int B, int k, int ld, int ldb, void* stream);
 
+/* k causal frames of ONE block of the causal skipping-memory LSTM (SkiM with causal = True, seg_overlap = False;
+ * skim.py:251-469) for B streams in one launch (puresound_amd/streaming/skim.py).  Columns as above: x, y [C][ld], column
+ * f * B + b; `counter` (device int, read and never written) = the absolute index of the chunk's first frame.  Frame
+ * g = *counter + f is position p = g % K of segment s = g / K.  Per frame and stream:
+ *   state:    p != 0: (h, c) = (seg_h, seg_c)[.][b], the running state [H][ldb];  p == 0: (h, c) = 0 when init_h is NULL (the
+ *             first block), else slot s % NS of init_h / init_c [NS][H][ldb];
+ *   FiLM:     with film_wt: u = LN(x) (film_gamma, film_beta, film_eps), x' = (Ws u + rs[.][b]) * u + (Wb u + rb[.][b]) with
+ *             film_wt [C][2C] = the feature columns of (cond_scale ; cond_bias) transposed (k-major, the C scale rows first)
+ *             and rs, rb [C][ldb] what the stream's embedding adds (lobe/trivial.py:157-165); without: x' = x;
+ *   SegLSTM:  gates = W [x' ; h] + b, LSTM cell (gates i, f, g, o), (h', c') -> (seg_h, seg_c) in place,
+ *             y = x' + LN(P h' + b_p)  (skim.py:198-229; the residual is the FiLM output);
+ *   MemLSTM:  when p == K - 1 and mem_h.wt is given (every block but the last): z_h = one step of h_net on the input h' from
+ *             (mh_h, mc_h) [H][ldb], updated in place, out_h = h' + LN(Ph z_h + b); the same with c_net on c' from
+ *             (mh_c, mc_c); (out_h, out_c) -> slot (s + 1) % NS of out_h / out_c [NS][H][ldb], the NEXT block's init_h /
+ *             init_c (skim.py:45-114 with its causal shift by one segment).  No other slot is touched.
+ * ps_skim_block (a HOST struct, copied into the kernel arguments): seg as ps_dprnn_pass; mem_h / mem_c the same with C := H
+ * (wt [2H][4H], pt [H][H], pbias, gamma, beta [H]), mem_h.wt NULL = no MemLSTM; film_wt NULL = no FiLM.  ps_skim_state (a
+ * HOST struct too) names the per-stream tensors.  A launch that crosses segment ends visits several slots:
+ * NS >= (k - 1) / K + 3 is required wherever a bank is given (block i + 1 has read every slot block i can overwrite).
+ * Exact fp32 products and fp32 sums, every sum of a column in one fixed order: a stream's values are bit-identical for every
+ * B, whatever the other columns hold and however the frames are split into launches.  A workgroup owns 16 columns and needs
+ * (2 max(C, H) + 2 H + max(4 H, 2 C)) * 64 bytes of LDS: ps_skim_block_step_ok(C, H, K) = 1 where that fits 160 KiB
+ * (C, H, K >= 1), else PS_E_UNSUPPORTED, which ps_skim_block_step_f32 then returns too, writing nothing.  x != y;
+ * 1 <= k <= 16; k * B <= ld; B <= ldb; x, y, counter 4-byte aligned; *counter + k <= INT32_MAX.  Everything is checked
+ * before the launch: PS_E_INVALID with a ps_last_error() text otherwise. */
+typedef struct ps_skim_block {
+  ps_dprnn_pass seg;
+  ps_dprnn_pass mem_h;
+  ps_dprnn_pass mem_c;
+  const float* film_wt;
+  const float* film_gamma;
+  const float* film_beta;
+  float film_eps;
+  int reserved;
+} ps_skim_block;
+typedef struct ps_skim_state {
+  const float* rs;
+  const float* rb;
+  float* seg_h;
+  float* seg_c;
+  const float* init_h;
+  const float* init_c;
+  float* mh_h;
+  float* mc_h;
+  float* mh_c;
+  float* mc_c;
+  float* out_h;
+  float* out_c;
+} ps_skim_state;
+int ps_skim_block_step_ok(int C, int H, int K);
+int ps_skim_block_step_f32(const float* x, float* y, const int* counter, const ps_skim_block* blk, const ps_skim_state* st,
+                           int C, int H, int K, int NS, int B, int k, int ld, int ldb, void* stream);
+
 /* One cell update per (unit, frame) from COMPLETE gate pre-activations gates [N][D*4H][ld_gates] (W_ih x + W_hh h + both
  * biases: the streaming step puts [x; h] on the K axis of one ps_conv1x1_f32):  c' = sig(f) c + sig(i) tanh(g) in
  * place in c [N][D*H][ld_state], h' = sig(o) tanh(c') into h [N][D*H][ld_state].  (SegLSTM with a one-frame

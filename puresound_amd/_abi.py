@@ -87,6 +87,16 @@ class DprnnPass(C.Structure):
     _fields_ = [(k, _vp) for k in ("wt", "bias", "pt", "pbias", "gamma", "beta")] + [("eps", C.c_float), ("reserved", C.c_int)]
 
 
+class SkimBlock(C.Structure):
+    _fields_ = [("seg", DprnnPass), ("mem_h", DprnnPass), ("mem_c", DprnnPass)] + [
+        (k, _vp) for k in ("film_wt", "film_gamma", "film_beta")] + [("film_eps", C.c_float), ("reserved", C.c_int)]
+
+
+class SkimState(C.Structure):
+    _fields_ = [(k, _vp) for k in ("rs", "rb", "seg_h", "seg_c", "init_h", "init_c", "mh_h", "mc_h", "mh_c", "mc_c", "out_h",
+                                   "out_c")]
+
+
 class LstmArgs(C.Structure):
     _fields_ = [("gx", _vp), ("whh_t", _vp), ("h0", _vp), ("c0", _vp), ("hout", _vp), ("h_last", _vp),
                 ("c_last", _vp)] + [(k, C.c_int) for k in ("N", "H", "D", "Q", "q_stride", "steps", "step_stride",
@@ -195,6 +205,8 @@ SIGNATURES = {
                                 + [C.c_int] * 7 + [_vp]),
     "ps_dprnn_block_step_slots_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(DprnnPass), C.POINTER(DprnnPass)] + [_vp] * 4
                                       + [C.c_int] * 7 + [_vp]),
+    "ps_skim_block_step_ok": (C.c_int, [C.c_int] * 3),
+    "ps_skim_block_step_f32": (C.c_int, [_vp, _vp, _vp, C.POINTER(SkimBlock), C.POINTER(SkimState)] + [C.c_int] * 8 + [_vp]),
     "ps_unfold2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp] + [C.c_int] * 14 + [_vp]),
     "ps_conv2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 16 + [_vp, _vp]),
     "ps_conv2d_stats_parts": (C.c_int, [C.c_int] * 3),

@@ -1,0 +1,356 @@
+// k causal frames of ONE block of the causal skipping-memory LSTM (SkiM, causal=True, seg_overlap=False) for B concurrent
+// streams in one launch (puresound_amd/streaming/skim.py).  Layout as dprnn_step.hip: the k frames of a chunk for the B
+// streams are the columns f * B + b of a [1][C][ld] tensor, and `counter` is the device frame counter (absolute index of the
+// chunk's first frame), which the kernel reads and never writes, so no launch argument depends on the frame index.
+//
+// Frame g = *counter + f sits at position p = g % K of segment s = g / K.  Per frame and column:
+//   state:  p != 0: the running (seg_h, seg_c) [H][ldb];  p == 0: zero without incoming banks (block 0), else slot s % NS of
+//           init_h / init_c [NS][H][ldb] (what the previous block's MemLSTM made of ITS state at the end of segment s - 1)
+//   FiLM:   u = LN(x); x' = (Ws u + rs) * u + (Wb u + rb)  (rs, rb [C][ldb]: the embedding's share, per stream); none: x' = x
+//   SegLSTM gates = W [x' ; h] + b, LSTM cell (gates i, f, g, o), (h', c') -> (seg_h, seg_c), y = x' + LN(P h' + b_p)
+//   hand-over, when p == K - 1 and the block has a MemLSTM: z_h = one step of h_net on h' from (mh_h, mc_h), updated in place,
+//           out_h = h' + LN(Ph z_h + b); the same with c_net on c' from (mh_c, mc_c); (out_h, out_c) -> slot (s + 1) % NS of
+//           the NEXT block's banks.
+// Every dependency is per stream, so a workgroup owns SK_TB stream columns, walks the chunk's frames in order and never reads
+// another workgroup's columns or state.
+//
+// Slots.  Block i writes, while it runs a chunk [g0, g0 + k), the slots of the segments s_lo + 1 .. s_hi + 1 (s_lo = g0 / K,
+// s_hi = (g0 + k - 1) / K), and block i + 1, which has finished every frame before g0, still has to read those of
+// s_lo .. s_hi + 1 at most: s_hi - s_lo + 2 <= (k - 1) / K + 3 different segments, so NS >= (k - 1) / K + 3 slots never hand
+// a slot to a new segment before its old one was read.
+//
+// Work inside a workgroup (256 threads, 16 columns) as dprnn_step.hip: a matrix-vector product gives a thread up to four
+// output rows for 16 columns (or one for 8), the weight stored k-major and read coalesced over the rows from L2, the inputs of
+// a k a broadcast read of LDS shared by the thread's rows; the cell runs on (unit, column) pairs; LayerNorm gives a column to
+// 16 lanes.  Every sum of a column has one fixed order (k ascending with fmaf from the bias, the input rows before the state
+// rows; the LN partials by lane, then xor 8, 4, 2, 1), so a stream's bits do not depend on B, on its neighbours or on how the
+// hops are split into launches.  A state element is loaded and stored by the same thread: the hand-over reads the (h', c')
+// its own thread has just stored.
+#include "ps_common.h"
+
+namespace ps {
+
+constexpr int SK_TB = 16;        // stream columns per workgroup
+constexpr int SK_THREADS = 256;
+constexpr size_t SK_LDS_MAX = 160 * 1024;
+
+struct SkimStepArgs {
+  const float* x;
+  float* y;
+  const int* counter;
+  ps_skim_block w;
+  ps_skim_state s;
+  int C, H, K, NS, B, k, ld, ldb;
+};
+
+__device__ __forceinline__ float sk_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
+
+// Sum over the 16 lanes that share a column (lanes 16 q .. 16 q + 15 of a wave), the same order in every lane.
+__device__ __forceinline__ float sk_sum16(float v) {
+  v += __shfl_xor(v, 8, 16);
+  v += __shfl_xor(v, 4, 16);
+  v += __shfl_xor(v, 2, 16);
+  v += __shfl_xor(v, 1, 16);
+  return v;
+}
+
+typedef float sk_f2 __attribute__((ext_vector_type(2)));
+
+// out[r][.] = bias[r] + sum_k wt[k][r] in[k][.] for `rows` rows over kk inputs (wt k-major [kk][rows], bias NULL = 0), all 16
+// columns of a row in one thread.  A thread takes R rows (r0, r0 + 256, ..) at once: the 16 inputs of a k are read from LDS
+// once for R rows (at R = 1 the LDS reads, not the arithmetic, bound the product), R weight loads per k are in flight, and
+// the 16 sums of a row advance as 8 packed pairs.  The sum of a column is the same fmaf chain for every R.
+template <int R>
+__device__ __forceinline__ void sk_rows16(const float* __restrict__ wt, const float* __restrict__ bias, int rows, int kk,
+                                          const float* in, float* out) {
+  for (int r0 = threadIdx.x; r0 < rows; r0 += SK_THREADS * R) {
+    sk_f2 acc[R][8];
+    int rr[R];                                            // (a row past the end repeats r0: computed, not stored)
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      rr[q] = r0 + q * SK_THREADS < rows ? r0 + q * SK_THREADS : r0;
+      const float b = bias ? bias[rr[q]] : 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[q][j] = sk_f2{b, b};
+    }
+#pragma unroll 4
+    for (int k = 0; k < kk; ++k) {
+      float w[R];
+#pragma unroll
+      for (int q = 0; q < R; ++q) w[q] = wt[(size_t)k * rows + rr[q]];
+      const float4* xv = reinterpret_cast<const float4*>(in + k * SK_TB);
+      sk_f2 x[8];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float4 v = xv[j];
+        x[2 * j] = sk_f2{v.x, v.y};
+        x[2 * j + 1] = sk_f2{v.z, v.w};
+      }
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        const sk_f2 wq = sk_f2{w[q], w[q]};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[q][j] = __builtin_elementwise_fma(wq, x[j], acc[q][j]);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q)
+      if (r0 + q * SK_THREADS < rows) {
+        float4* o = reinterpret_cast<float4*>(out + (r0 + q * SK_THREADS) * SK_TB);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          o[j] = make_float4(acc[q][2 * j].x, acc[q][2 * j].y, acc[q][2 * j + 1].x, acc[q][2 * j + 1].y);
+      }
+  }
+}
+
+// (R by the number of rows alone: 4 rows per thread where 256 threads then still all have work)
+__device__ __forceinline__ void sk_rows_all(const float* __restrict__ wt, const float* __restrict__ bias, int rows, int kk,
+                                            const float* in, float* out) {
+  if (rows >= 4 * SK_THREADS)
+    sk_rows16<4>(wt, bias, rows, kk, in, out);
+  else if (rows >= 2 * SK_THREADS)
+    sk_rows16<2>(wt, bias, rows, kk, in, out);
+  else
+    sk_rows16<1>(wt, bias, rows, kk, in, out);
+}
+
+// The same product with a row's 16 columns split over two threads (the projections: C or H rows, fewer than threads).
+__device__ __forceinline__ void sk_rows_halves(const float* __restrict__ wt, const float* __restrict__ bias, int rows, int kk,
+                                               const float* in, float* out) {
+  for (int i = threadIdx.x; i < rows * 2; i += SK_THREADS) {
+    const int r = i % rows, half = i / rows;
+    sk_f2 acc[4];
+    const float b = bias[r];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = sk_f2{b, b};
+    const float* wr = wt + r;
+    const float* xv = in + half * 8;
+#pragma unroll 8
+    for (int k = 0; k < kk; ++k) {
+      const float wk = wr[(size_t)k * rows];
+      const float4 v0 = *reinterpret_cast<const float4*>(xv + k * SK_TB);
+      const float4 v1 = *reinterpret_cast<const float4*>(xv + k * SK_TB + 4);
+      const sk_f2 w2 = sk_f2{wk, wk};
+      acc[0] = __builtin_elementwise_fma(w2, sk_f2{v0.x, v0.y}, acc[0]);
+      acc[1] = __builtin_elementwise_fma(w2, sk_f2{v0.z, v0.w}, acc[1]);
+      acc[2] = __builtin_elementwise_fma(w2, sk_f2{v1.x, v1.y}, acc[2]);
+      acc[3] = __builtin_elementwise_fma(w2, sk_f2{v1.z, v1.w}, acc[3]);
+    }
+    float4* o = reinterpret_cast<float4*>(out + r * SK_TB + half * 8);
+    o[0] = make_float4(acc[0].x, acc[0].y, acc[1].x, acc[1].y);
+    o[1] = make_float4(acc[2].x, acc[2].y, acc[3].x, acc[3].y);
+  }
+}
+
+// Mean and 1 / sqrt(var + eps) of column tid / 16 of v [rows][16] (biased two-pass variance), the same in its 16 lanes.
+__device__ __forceinline__ void sk_ln_stats(const float* v, int rows, float eps, float& mean, float& rstd) {
+  const int col = threadIdx.x / 16, l = threadIdx.x % 16;
+  float s = 0.f;
+  for (int m = l; m < rows; m += 16) s += v[m * SK_TB + col];
+  mean = sk_sum16(s) / (float)rows;
+  float q = 0.f;
+  for (int m = l; m < rows; m += 16) {
+    const float d = v[m * SK_TB + col] - mean;
+    q = fmaf(d, d, q);
+  }
+  rstd = 1.f / sqrtf(sk_sum16(q) / (float)rows + eps);
+}
+
+// The LSTM cell on gt [4H][16] and cs [H][16]: h' -> hrow [H][16] and hg, c' -> cs and cg (hg / cg: the state rows [H][ldb]
+// of column b0).
+__device__ __forceinline__ void sk_cell(const float* gt, float* cs, float* hrow, float* hg, float* cg, int H, int ldb, int cols) {
+  for (int i = threadIdx.x; i < H * SK_TB; i += SK_THREADS) {
+    const int u = i / SK_TB, j = i % SK_TB;
+    const float gi = sk_sigmoid(gt[u * SK_TB + j]);
+    const float gf = sk_sigmoid(gt[(H + u) * SK_TB + j]);
+    const float gg = tanhf(gt[(2 * H + u) * SK_TB + j]);
+    const float go = sk_sigmoid(gt[(3 * H + u) * SK_TB + j]);
+    const float cn = gf * cs[i] + gi * gg;
+    const float hn = go * tanhf(cn);
+    hrow[i] = hn;
+    cs[i] = cn;
+    if (j < cols) {
+      hg[(size_t)u * ldb + j] = hn;
+      cg[(size_t)u * ldb + j] = cn;
+    }
+  }
+}
+
+__global__ __launch_bounds__(SK_THREADS) void skim_block_step_kernel(SkimStepArgs a) {
+  extern __shared__ __align__(16) float sk_lds[];
+  const int C = a.C, H = a.H;
+  const int CH = C > H ? C : H;
+  float* xh = sk_lds;                                   // [max(C, H) + H][16]: the input rows, then the state rows
+  float* cs = xh + (CH + H) * SK_TB;                    // [H][16]
+  float* gt = cs + H * SK_TB;                           // [max(4H, 2C)][16]
+  float* pr = gt + (4 * H > 2 * C ? 4 * H : 2 * C) * SK_TB;   // [max(C, H)][16]
+  const int tid = threadIdx.x;
+  const int b0 = blockIdx.x * SK_TB;
+  const int cols = a.B - b0 < SK_TB ? a.B - b0 : SK_TB;
+  const int t0 = *a.counter;
+  const size_t slab = (size_t)H * a.ldb;                // one bank slot
+  const bool film = a.w.film_wt != nullptr, mem = a.w.mem_h.wt != nullptr;
+  const int col = tid / 16, l = tid % 16;               // LayerNorm: 256 threads = 16 columns x 16 lanes
+  for (int f = 0; f < a.k; ++f) {
+    const size_t c0 = (size_t)f * a.B + b0;
+    const int g = t0 + f, p = g % a.K, s = g / a.K;
+    for (int i = tid; i < C * SK_TB; i += SK_THREADS) {
+      const int m = i / SK_TB, j = i % SK_TB;
+      xh[i] = j < cols ? a.x[(size_t)m * a.ld + c0 + j] : 0.f;
+    }
+    {
+      const float* hs = a.s.seg_h + b0;
+      const float* cg = a.s.seg_c + b0;
+      bool zero = false;
+      if (p == 0) {
+        zero = a.s.init_h == nullptr;
+        if (!zero) {
+          hs = a.s.init_h + (size_t)(s % a.NS) * slab + b0;
+          cg = a.s.init_c + (size_t)(s % a.NS) * slab + b0;
+        }
+      }
+      for (int i = tid; i < H * SK_TB; i += SK_THREADS) {
+        const int u = i / SK_TB, j = i % SK_TB;
+        const bool live = j < cols && !zero;
+        xh[C * SK_TB + i] = live ? hs[(size_t)u * a.ldb + j] : 0.f;
+        cs[i] = live ? cg[(size_t)u * a.ldb + j] : 0.f;
+      }
+    }
+    __syncthreads();
+    if (film) {
+      float mean, rstd;
+      sk_ln_stats(xh, C, a.w.film_eps, mean, rstd);
+      for (int m = l; m < C; m += 16)
+        xh[m * SK_TB + col] = (xh[m * SK_TB + col] - mean) * rstd * a.w.film_gamma[m] + a.w.film_beta[m];
+      __syncthreads();
+      sk_rows_all(a.w.film_wt, nullptr, 2 * C, C, xh, gt);
+      __syncthreads();
+      for (int i = tid; i < C * SK_TB; i += SK_THREADS) {
+        const int m = i / SK_TB, j = i % SK_TB;
+        const float sc = gt[i] + (j < cols ? a.s.rs[(size_t)m * a.ldb + b0 + j] : 0.f);
+        const float bi = gt[C * SK_TB + i] + (j < cols ? a.s.rb[(size_t)m * a.ldb + b0 + j] : 0.f);
+        xh[i] = fmaf(sc, xh[i], bi);
+      }
+      __syncthreads();
+    }
+    sk_rows_all(a.w.seg.wt, a.w.seg.bias, 4 * H, C + H, xh, gt);
+    __syncthreads();
+    sk_cell(gt, cs, xh + C * SK_TB, a.s.seg_h + b0, a.s.seg_c + b0, H, a.ldb, cols);
+    __syncthreads();
+    sk_rows_halves(a.w.seg.pt, a.w.seg.pbias, C, H, xh + C * SK_TB, pr);
+    __syncthreads();
+    {
+      float mean, rstd;
+      sk_ln_stats(pr, C, a.w.seg.eps, mean, rstd);
+      for (int m = l; m < C; m += 16)
+        xh[m * SK_TB + col] += (pr[m * SK_TB + col] - mean) * rstd * a.w.seg.gamma[m] + a.w.seg.beta[m];
+    }
+    __syncthreads();
+    for (int i = tid; i < C * SK_TB; i += SK_THREADS) {   // (the thread that stores xh[i] for the next frame reads it here)
+      const int m = i / SK_TB, j = i % SK_TB;
+      if (j < cols) a.y[(size_t)m * a.ld + c0 + j] = xh[i];
+    }
+    if (p == a.K - 1 && mem) {                            // (the same decision in every thread of the launch)
+      __syncthreads();
+      const size_t slot = (size_t)((s + 1) % a.NS) * slab + b0;
+      for (int net = 0; net < 2; ++net) {
+        const ps_dprnn_pass& w = net == 0 ? a.w.mem_h : a.w.mem_c;
+        const float* v = (net == 0 ? a.s.seg_h : a.s.seg_c) + b0;   // (h', c'): element i was stored by this thread
+        float* mh = (net == 0 ? a.s.mh_h : a.s.mh_c) + b0;
+        float* mc = (net == 0 ? a.s.mc_h : a.s.mc_c) + b0;
+        float* out = (net == 0 ? a.s.out_h : a.s.out_c) + slot;
+        for (int i = tid; i < H * SK_TB; i += SK_THREADS) {
+          const int u = i / SK_TB, j = i % SK_TB;
+          const bool live = j < cols;
+          xh[i] = live ? v[(size_t)u * a.ldb + j] : 0.f;
+          xh[H * SK_TB + i] = live ? mh[(size_t)u * a.ldb + j] : 0.f;
+          cs[i] = live ? mc[(size_t)u * a.ldb + j] : 0.f;
+        }
+        __syncthreads();
+        sk_rows_all(w.wt, w.bias, 4 * H, 2 * H, xh, gt);
+        __syncthreads();
+        sk_cell(gt, cs, xh + H * SK_TB, mh, mc, H, a.ldb, cols);
+        __syncthreads();
+        sk_rows_halves(w.pt, w.pbias, H, H, xh + H * SK_TB, pr);
+        __syncthreads();
+        float mean, rstd;
+        sk_ln_stats(pr, H, w.eps, mean, rstd);
+        if (col < cols)
+          for (int m = l; m < H; m += 16)
+            out[(size_t)m * a.ldb + col] = xh[m * SK_TB + col] + ((pr[m * SK_TB + col] - mean) * rstd * w.gamma[m] + w.beta[m]);
+        __syncthreads();
+      }
+    }
+  }
+}
+
+static size_t skim_lds_rows(long long C, long long H) {
+  const long long ch = C > H ? C : H;
+  return (size_t)((ch + H) + H + (4 * H > 2 * C ? 4 * H : 2 * C) + ch);
+}
+
+}  // namespace ps
+
+using namespace ps;
+
+extern "C" int ps_skim_block_step_ok(int C, int H, int K) {
+  if (C < 1 || H < 1 || K < 1) return PS_E_UNSUPPORTED;
+  return skim_lds_rows(C < 65536 ? C : 65536, H < 65536 ? H : 65536) * SK_TB * sizeof(float) <= SK_LDS_MAX ? 1 : PS_E_UNSUPPORTED;
+}
+
+static bool pass_complete(const ps_dprnn_pass& w) { return w.wt && w.bias && w.pt && w.pbias && w.gamma && w.beta; }
+
+extern "C" int ps_skim_block_step_f32(const float* x, float* y, const int* counter, const ps_skim_block* blk,
+                                      const ps_skim_state* st, int C, int H, int K, int NS, int B, int k, int ld, int ldb,
+                                      void* stream) {
+  const char* who = "ps_skim_block_step_f32";
+  if (!x || !y || x == y || !counter || !blk || !st || C <= 0 || H <= 0 || K <= 0 || B <= 0 || k <= 0 || k > 16 || ldb < B ||
+      (long long)k * B > ld || (long long)C * ld > (1LL << 31) || (long long)(C > H ? C : H) * ldb > (1LL << 31)) {
+    set_error("%s: bad argument (C=%d H=%d K=%d NS=%d B=%d k=%d ld=%d ldb=%d; 1 <= k <= 16)", who, C, H, K, NS, B, k, ld, ldb);
+    return PS_E_INVALID;
+  }
+  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)counter) & 3) {
+    set_error("%s: x, y and counter must be 4-byte aligned", who);
+    return PS_E_INVALID;
+  }
+  if (!pass_complete(blk->seg) || !st->seg_h || !st->seg_c) {
+    set_error("%s: the SegLSTM needs wt, bias, pt, pbias, gamma, beta and the states seg_h, seg_c", who);
+    return PS_E_INVALID;
+  }
+  if (blk->film_wt && (!blk->film_gamma || !blk->film_beta || !st->rs || !st->rb)) {
+    set_error("%s: FiLM needs film_gamma, film_beta and the per-stream terms rs, rb", who);
+    return PS_E_INVALID;
+  }
+  if ((st->init_h == nullptr) != (st->init_c == nullptr)) {
+    set_error("%s: init_h and init_c go together", who);
+    return PS_E_INVALID;
+  }
+  const bool mem = blk->mem_h.wt != nullptr;
+  if (mem && (!pass_complete(blk->mem_h) || !pass_complete(blk->mem_c) || !st->mh_h || !st->mc_h || !st->mh_c || !st->mc_c ||
+              !st->out_h || !st->out_c)) {
+    set_error("%s: the MemLSTM needs both nets complete, the states mh_h, mc_h, mh_c, mc_c and the banks out_h, out_c", who);
+    return PS_E_INVALID;
+  }
+  if ((mem || st->init_h) && (NS < (k - 1) / K + 3 || (long long)NS * H * ldb > (1LL << 40))) {
+    set_error("%s: NS = %d bank slots; k = %d frames over segments of K = %d need (k - 1) / K + 3 = %d", who, NS, k, K,
+              (k - 1) / K + 3);
+    return PS_E_INVALID;
+  }
+  if (ps_skim_block_step_ok(C, H, K) != 1) {
+    set_error("%s: (C, H, K) = (%d, %d, %d): the tile of 16 columns needs (2 max(C, H) + 2 H + max(4 H, 2 C)) * 64 bytes of "
+              "LDS, 160 KiB at most", who, C, H, K);
+    return PS_E_UNSUPPORTED;
+  }
+  const size_t lds = skim_lds_rows(C, H) * SK_TB * sizeof(float);
+  static const bool big_lds = hipFuncSetAttribute(reinterpret_cast<const void*>(&skim_block_step_kernel),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_LDS_MAX) == hipSuccess;
+  if (!big_lds && lds > 64 * 1024) {   // (dynamic LDS beyond 64 KiB has to be asked for, once per kernel)
+    set_error("%s: %zu bytes of LDS refused by the runtime", who, lds);
+    return PS_E_UNSUPPORTED;
+  }
+  SkimStepArgs a{x, y, counter, *blk, *st, C, H, K, mem || st->init_h ? NS : 1, B, k, ld, ldb};
+  LaunchTimer timer("skim_block_step", (hipStream_t)stream);
+  hipLaunchKernelGGL(skim_block_step_kernel, dim3((B + SK_TB - 1) / SK_TB), dim3(SK_THREADS), lds, (hipStream_t)stream, a);
+  return launch_status(who);
+}

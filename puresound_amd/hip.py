@@ -1106,6 +1106,90 @@ def dprnn_block_step(x: torch.Tensor, counter: torch.Tensor, intra: dict, inter:
     return out
 
 
+def skim_block_step_ok(c: int, hidden: int, seg: int) -> bool:
+    """Whether ps_skim_block_step_f32 has a kernel for (C, H, K)."""
+    return lib().ps_skim_block_step_ok(int(c), int(hidden), int(seg)) == 1
+
+
+def skim_bank_slots(frames: int, seg: int) -> int:
+    """The hand-over bank slots ps_skim_block_step_f32 asks for when a launch runs up to `frames` frames."""
+    return (int(frames) - 1) // int(seg) + 3
+
+
+def pack_skim_block(masker, i: int, device: torch.device) -> dict:
+    """Block i of a causal SkiM -> the fp32 tensors of a ps_skim_block and the struct pointing at them (keep the dict alive
+    while launches read it): the feature columns of its FiLM with the input norm (a block without fusion has none), the
+    SegLSTM with projection and norm, MemLSTM i when there is one (every block but the last).  `embed_wt` [2C, E]: the
+    embedding columns of (cond_scale ; cond_bias), for the per-stream terms rs / rb."""
+    f32 = lambda t: t.detach().to(dtype=torch.float32, device=device)  # noqa: E731
+    c = masker.input_size
+    seg = masker.seg_lstm[i]
+    p = dict(seg=pack_dprnn_pass(seg.lstm, seg.proj, seg.norm, device), C=c, H=masker.hidden_size, film=None, mem=None)
+    s = _abi.SkimBlock()
+    s.seg = p["seg"]["struct"]
+    if masker.embed_dim > 0 and masker.block_with_embed[i]:
+        film = masker.seg_input_fusion[i]
+        ws, wb = f32(film.cond_scale.weight)[:, :, 0], f32(film.cond_bias.weight)[:, :, 0]
+        p["film"] = dict(wt=torch.cat([ws[:, :c], wb[:, :c]], 0).t().contiguous(),                       # [C, 2C]
+                         gamma=f32(film.norm.weight).contiguous(), beta=f32(film.norm.bias).contiguous(),
+                         embed_wt=torch.cat([ws[:, c:], wb[:, c:]], 0).contiguous())
+        s.film_wt, s.film_gamma, s.film_beta = (ptr(p["film"][k]) for k in ("wt", "gamma", "beta"))
+        s.film_eps = float(film.norm.eps)
+    if i < masker.n_blocks - 1:
+        m = masker.mem_lstm[i]
+        p["mem"] = (pack_dprnn_pass(m.h_net, m.h_proj, m.h_norm, device), pack_dprnn_pass(m.c_net, m.c_proj, m.c_norm, device))
+        s.mem_h, s.mem_c = p["mem"][0]["struct"], p["mem"][1]["struct"]
+    p["struct"] = s
+    return p
+
+
+def skim_block_step(x: torch.Tensor, counter: torch.Tensor, block: dict, seg_state: tuple, seg: int, streams: int, frames: int,
+                    out: torch.Tensor, terms: Optional[tuple] = None, bank_in: Optional[tuple] = None,
+                    mem_state: Optional[tuple] = None, bank_out: Optional[tuple] = None) -> torch.Tensor:
+    """One causal SkiM block on `frames` new frames of `streams` streams (ps_skim_block_step_f32): x [1, C, ld] (column
+    f * streams + b) -> out [1, C, ld] (columns past frames * streams are not written); block from pack_skim_block;
+    seg_state = (seg_h, seg_c) [H, ldb]; terms = (rs, rb) [C, ldb] iff the block has FiLM; bank_in = (init_h, init_c)
+    [NS, H, ldb], None for the first block; mem_state = (mh_h, mc_h, mh_c, mc_c) [H, ldb] and bank_out = the next block's
+    banks iff the block has a MemLSTM.  States and bank_out are updated in place; frame index of column 0 = counter[0],
+    position = index % seg."""
+    who = "skim_block_step"
+    require_device(x, who)
+    _, c, ld = x.shape
+    hidden, ldb = seg_state[0].shape
+    if not (x.is_contiguous() and out.is_contiguous()) or out.shape != x.shape or out.dtype != torch.float32 \
+            or counter.dtype != torch.int32 or counter.device != x.device:
+        raise RuntimeError(f"{who}: contiguous fp32 x and out [1, C, ld], an int32 counter on their device expected")
+    if (c, hidden) != (block["C"], block["H"]) or block["seg"]["wt"].device != x.device:
+        raise RuntimeError(f"{who}: a block packed for C = {c}, H = {hidden} on {x.device} expected")
+    if (terms is not None) != (block["film"] is not None) or (mem_state is not None) != (block["mem"] is not None) \
+            or (bank_out is not None) != (block["mem"] is not None):
+        raise RuntimeError(f"{who}: terms go with a FiLM block, mem_state and bank_out with a MemLSTM, and only with them")
+    st = _abi.SkimState()
+    ns = 0
+    groups = (("seg_state", seg_state, ("seg_h", "seg_c"), (hidden, ldb)), ("terms", terms, ("rs", "rb"), (c, ldb)),
+              ("mem_state", mem_state, ("mh_h", "mc_h", "mh_c", "mc_c"), (hidden, ldb)),
+              ("bank_in", bank_in, ("init_h", "init_c"), None), ("bank_out", bank_out, ("out_h", "out_c"), None))
+    for what, tensors, names, shape in groups:
+        if tensors is None:
+            continue
+        if len(tensors) != len(names):
+            raise RuntimeError(f"{who}: {what} must be {names}")
+        for name, t in zip(names, tensors):
+            require_weight(t, x, who)
+            if shape is None:
+                ns = ns or t.shape[0]
+                shape_ok = t.dim() == 3 and tuple(t.shape) == (ns, hidden, ldb)
+            else:
+                shape_ok = tuple(t.shape) == shape
+            if not shape_ok:
+                raise RuntimeError(f"{who}: {what}: states [H, ldb], terms [C, ldb] and banks [NS, H, ldb] of one H, ldb and NS "
+                                   f"expected (got {tuple(t.shape)} for {name})")
+            setattr(st, name, ptr(t))
+    check(lib().ps_skim_block_step_f32(ptr(x), ptr(out), ptr(counter), C.byref(block["struct"]), C.byref(st), c, hidden,
+                                       int(seg), ns, streams, frames, ld, ldb, stream_ptr(x.device)), "ps_skim_block_step_f32")
+    return out
+
+
 def _conv2d_sources(who: str, x1: torch.Tensor, x2: Optional[torch.Tensor]) -> tuple[int, int, int, int, int]:
     """x1 [N,C1,F,ld] (+ x2 [N,C2,F,ld], the skip connection a decoder layer concatenates) -> (N, C1, C2, F, ld)."""
     require_device(x1, who)

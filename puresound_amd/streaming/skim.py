@@ -1,0 +1,255 @@
+"""Streaming the causal time-domain SkiM speaker extractors (FreeEncDec + SkiM(causal=True) with FiLM conditioning: egs/tse
+tse_skim_v0_causal, tse_skim_v1_causal, tse_skim_v2_causal, tse_skim_v0_causal_vad) on the HIP path, one hop at a time for B
+concurrent streams.
+
+The model is exactly causal in time.  A segment is K = seg_size consecutive frames (seg_overlap=False).  With causal=True every
+SegLSTM runs forward only; block 0 starts every segment from zero, and block i + 1 starts segment s from what MemLSTM i made of
+block i's final state of segment s - 1 (the shift in MemLSTM.forward; segment 0 starts from zero).  LayerNorm and FiLM act on
+one frame, and the zero padding to whole segments lies after the last frame.  So frame g needs frames <= g only, and the
+samples a stream returns, followed by flush(), equal `model.inference(noisy[b:b+1], enroll[b:b+1])` of that stream, win - hop
+samples late.
+
+Of that stream ALONE: on a batch the offline model is not a function of one utterance.  The reference shifts the MemLSTM's
+result along the flattened (utterance, segment) axis (skim.py:102-109), so utterance n > 0 of a batch starts its first
+segment, in every block but the first, from the state utterance n - 1 reached at the end of its LAST (zero padded) segment;
+the offline path here reproduces that.  A stream cannot depend on its neighbour's future, and does not here: row 0 of
+`model.inference(batch)` is what stream 0 returns, every other stream returns what the model gives for it as a batch of one.
+
+Layout as dprnn.py: the k frames of a chunk for the B streams are the N = k*B columns of the library's channel-major rows
+(column f*B + b = frame f, stream b).  Every dependency of a block is per stream, so one launch of ps_skim_block_step_f32
+(csrc/skim_step.hip) runs a whole block on a whole chunk: a workgroup owns 16 stream columns and walks their frames in order.
+Per block the device holds the running SegLSTM state (h, c) [H, ldB], the carried states of its MemLSTM's two nets, the
+embedding's share of FiLM's scale and bias [C, ldB] (computed once per session) and, for every block but the first, two banks
+[NS, H, ldB] of incoming hand-overs: block i writes slot (s + 1) % NS at the end of segment s, block i + 1 reads slot s % NS at
+the start of segment s.  A chunk is: stream_windows, frame, the encoder's conv1x1 (+ ReLU), n_blocks block launches, output_fc
+(a conv1x1 with a PReLU prologue), free_decode_step (two launches) and stream_commit_frames -- n_blocks + 7 or 8 launches
+whatever its length.  No launch argument depends on the frame index, so one captured graph per chunk length replays every
+chunk.
+
+Arithmetic: exact fp32 products throughout, whatever the model's gemm_precision; every sum of a stream's column has one fixed
+order (the 1x1 convolutions always take ps_conv1x1_f32's tiled kernel: MIN_GEMM_COLUMNS), so a stream's output does not depend
+on B, on its neighbours or on how its hops are split into calls.  The streamer packs its own weights from the parameters; the
+model's own setting and plans are left as they were.  The session around the kernels (priming, step / step_chunk / flush,
+eager run or graph replay, the capture) is HopSession's: streaming/_session.py.  There are no slot sessions yet.
+"""
+from typing import List, Optional
+
+import torch
+
+from .. import hip
+from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
+from ..nnet.lobe.encoder import FreeEncDec
+from ..nnet.lobe.trivial import FiLM, Gate
+from ..nnet.skim import SkiM
+from ._session import FRAME_LIMIT, K_MAX, HopSession, check_on_device
+from .dprnn import MIN_GEMM_COLUMNS
+
+
+def check_streamable(model) -> None:
+    """Raise NotImplementedError naming the reason when `model` is not a configuration this streamer computes exactly."""
+    name = "StreamingSkiMExtractor"
+    if not isinstance(model, SoTaskWrapModule):
+        raise NotImplementedError(f"{name}: a SoTaskWrapModule (got {type(model).__name__})")
+    if not isinstance(model.encoder, FreeEncDec):
+        raise NotImplementedError(f"{name}: encoder {type(model.encoder).__name__}: only the free encoder (FreeEncDec) streams "
+                                  f"here; conv-STFT models stream through StreamingSeparator")
+    win, hop = model.encoder.win_length, model.encoder.hop_length
+    if win % hop:
+        raise NotImplementedError(f"{name}: win = {win} is not a multiple of hop = {hop}")
+    if win % 4 or win > 256:
+        raise NotImplementedError(f"{name}: win = {win}: a multiple of 4 up to 256 (the window queue moves in float4 "
+                                  f"columns, the decoder keeps a window per stream in LDS)")
+    m = model.masker
+    if not isinstance(m, SkiM):
+        raise NotImplementedError(f"{name}: masker {type(m).__name__}: SkiM only (DPRNN streams through StreamingDPRNN, "
+                                  f"ConvTasNet through StreamingConvTasNet)")
+    fusions = list(m.seg_input_fusion) if m.embed_dim > 0 else []
+    if any(isinstance(f, Gate) for f in fusions):
+        raise NotImplementedError(f"{name}: Gate fusion is out of scope; FiLM-conditioned blocks stream here")
+    if not m.causal:
+        raise NotImplementedError(f"{name}: the SkiM is not causal (causal=False: bidirectional LSTMs read future frames)")
+    if m.seg_overlap:
+        raise NotImplementedError(f"{name}: seg_overlap=True (half-overlapped segments) does not stream here")
+    if model.embedding_free_tse:
+        raise NotImplementedError(f"{name}: embedding_free_tse is the DPRNN's way of enrolment (StreamingDPRNN); a SkiM takes "
+                                  f"an embedding")
+    if m.embed_dim > 0 and model.speaker_net is None:
+        raise NotImplementedError(f"{name}: embed_dim = {m.embed_dim} but the model has no speaker_net: model.inference can "
+                                  f"hand this masker no embedding, so there is no output to reproduce")
+    if m.seg_size < 1:
+        raise NotImplementedError(f"{name}: seg_size = {m.seg_size}")
+    for i, f in enumerate(fusions):
+        if f is not None and not (isinstance(f, FiLM) and f.inp_norm):
+            raise NotImplementedError(f"{name}: block {i}: fusion {type(f).__name__}: FiLM with its input norm, or none")
+    if m.output_fc[0].weight.numel() != 1:
+        raise NotImplementedError(f"{name}: PReLU with per-channel slopes is not on the HIP path")
+    pair = (model.mask_type.lower(), model.f_type.lower())
+    if pair != ("real", "real"):
+        raise NotImplementedError(f"{name}: mask pairing {pair}: the free encoder uses (real, real) only")
+    if model.mask_constraint.lower() not in _MASK_ACTS:
+        raise NotImplementedError(f"{name}: mask_constraint {model.mask_constraint!r}")
+    if model.output_constraint.lower() not in ("linear", "sigmoid"):
+        raise NotImplementedError(f"{name}: output_constraint {model.output_constraint!r}: linear or sigmoid")
+    c = model.encoder.encoder.weight.shape[0]
+    if m.input_size != c or m.output_fc[1].out_channels != c:
+        raise NotImplementedError(f"{name}: shapes: the encoder has {c} channels, the SkiM takes {m.input_size} and returns "
+                                  f"{m.output_fc[1].out_channels}; a mask per encoder channel is needed")
+    if not hip.skim_block_step_ok(m.input_size, m.hidden_size, m.seg_size):
+        raise NotImplementedError(f"{name}: shapes: ps_skim_block_step_f32 has no kernel for (C, H, K) = ({m.input_size}, "
+                                  f"{m.hidden_size}, {m.seg_size}): a tile of 16 streams needs (2 max(C, H) + 2 H + "
+                                  f"max(4 H, 2 C)) * 64 bytes of LDS, 160 KiB at most")
+    if model.training:
+        raise NotImplementedError(f"{name}: the model is in training mode -- call .eval()")
+    check_on_device(model, name)
+
+
+class StreamingSkiMExtractor(HopSession):
+    """Hop-by-hop inference of a causal SkiM speaker extractor (or plain SkiM separator) for B streams (see the module
+    docstring).
+
+    s = StreamingSkiMExtractor(model); s.init_streams(B, enroll=e) or s.init_streams(B, embed=d);
+    s.step(hop [B, hop]) -> [B, hop] or None while the first window fills; s.step_chunk([B, k*hop]) -> what k step() calls
+    return, concatenated; s.flush() -> the last win - hop samples.
+    """
+
+    max_hops = K_MAX
+
+    def __init__(self, model: SoTaskWrapModule):
+        check_streamable(model)
+        super().__init__(model, model.encoder.win_length, model.encoder.hop_length)
+        self.win_length = self.window
+
+    # -- weights ------------------------------------------------------------------------------------------------------
+    def _build_packs(self, dev: torch.device) -> None:
+        """fp32 weights packed for the kernels, held by the streamer: a captured graph keeps reading these tensors."""
+        f32 = dict(dtype=torch.float32, device=dev)
+        enc, m = self.model.encoder, self.model.masker
+        slope = m.output_fc[0].weight.detach().to(**f32).contiguous()
+        self._packs = dict(enc_wt=hip.pack_wt(enc.encoder.weight.detach().to(**f32)[:, 0, :]),
+                           dec_w=enc.decoder.weight.detach().to(**f32).contiguous(),
+                           blocks=[hip.pack_skim_block(m, i, dev) for i in range(m.n_blocks)],
+                           out_wt=hip.pack_wt(m.output_fc[1].weight.detach().to(**f32)),
+                           out_b=m.output_fc[1].bias.detach().to(**f32).contiguous(), out_slope=slope,
+                           out_pro=hip.make_prologue(0, True, None, 0.0, 0.0, None, None, slope))
+        if self.streams is not None:                               # (changed weights in a session: FiLM's terms follow them)
+            self._terms = self._film_terms()
+
+    # -- session ------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def init_streams(self, streams: int = 1, enroll: Optional[torch.Tensor] = None, embed: Optional[torch.Tensor] = None,
+                     use_graph: bool = True) -> None:
+        """Start `streams` new streams.  A masker with embed_dim > 0 takes exactly one of enroll [streams, L'] (through
+        model.inference_tse_embedding, once) and embed [streams, E] (what that call returns; a deployment caches it), on the
+        model's device; a masker without takes neither.  The masker's own L2 normalisation is applied here, and what the
+        embedding adds to every FiLM's scale and bias is computed here, once.  Every other state is zeroed."""
+        name = "StreamingSkiMExtractor.init_streams"
+        if int(streams) < 1:
+            raise ValueError("init_streams: streams >= 1")
+        model, m = self.model, self.model.masker
+        b = int(streams)
+        if m.embed_dim > 0 and (enroll is None) == (embed is None):
+            raise ValueError(f"{name}: the masker takes an embedding (embed_dim = {m.embed_dim}): pass exactly one of enroll "
+                             f"[streams, L'] and embed [streams, {m.embed_dim}]")
+        if m.embed_dim == 0 and (enroll is not None or embed is not None):
+            raise ValueError(f"{name}: the masker takes no embedding (embed_dim = 0): pass neither enroll nor embed")
+        dev = next(model.parameters()).device
+        if enroll is not None:
+            hip.require_device(enroll, name)
+            if enroll.dim() != 2 or enroll.shape[0] != b:
+                raise ValueError(f"{name}: enroll must be [{b}, L'], got {tuple(enroll.shape)}")
+            embed = model.inference_tse_embedding(enroll)
+        if embed is not None:
+            hip.require_device(embed, name)
+            if embed.dim() == 3 and embed.shape[2] == 1:           # (as inference_tse_embedding returns it)
+                embed = embed[:, :, 0]
+            if tuple(embed.shape) != (b, m.embed_dim) or embed.device != dev:
+                raise ValueError(f"{name}: embed must be [{b}, {m.embed_dim}] on {dev}, got {tuple(embed.shape)} on "
+                                 f"{embed.device}")
+        self._begin(b, dev, use_graph)
+        h, ldb = m.hidden_size, hip.padded_frames(max(b, MIN_GEMM_COLUMNS))
+        self._embed, self._ldb = embed, ldb
+        self._packs = None                                         # (rebuilt with this session's terms on first use)
+        ns = hip.skim_bank_slots(K_MAX, m.seg_size)
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        self._seg = [(z(h, ldb), z(h, ldb)) for _ in range(m.n_blocks)]
+        self._mem = [tuple(z(h, ldb) for _ in range(4)) for _ in range(m.n_blocks - 1)]
+        self._banks = [(z(ns, h, ldb), z(ns, h, ldb)) for _ in range(m.n_blocks - 1)]
+        self._bufs = {}
+        self._ready()
+
+    def _film_terms(self) -> list:
+        """Per block with FiLM (rs, rb) [C, ldb]: the embedding columns of cond_scale / cond_bias applied to the (normalised)
+        embedding of every stream.  Both sums run as ps_conv1x1_f32 over the streams as columns, at least MIN_GEMM_COLUMNS of
+        them, so a stream's terms do not depend on B."""
+        m = self.model.masker
+        embed, ldb = self._embed, self._ldb
+        if embed is None:
+            return [None] * m.n_blocks
+        b, e = embed.shape
+        c, cols = m.input_size, max(b, MIN_GEMM_COLUMNS)
+        rows = torch.zeros(1, e, ldb, dtype=torch.float32, device=self.device)
+        rows[0, :, :b] = embed.t()
+        if m.embed_norm:                                           # F.normalize: e / max(|e|, 1e-12)
+            ones = hip.pack_wt(torch.ones(1, e, dtype=torch.float32, device=self.device))
+            sq, _ = hip.conv1x1(rows * rows, cols, ones, 1)
+            rows = rows / sq.sqrt().clamp_min(1e-12)
+        terms = []
+        for pk in self._packs["blocks"]:
+            if pk["film"] is None:
+                terms.append(None)
+                continue
+            both, _ = hip.conv1x1(rows, cols, hip.pack_wt(pk["film"]["embed_wt"]), 2 * c)
+            terms.append((both[0, :c], both[0, c:]))
+        return terms
+
+    def _state(self) -> List[torch.Tensor]:
+        return [self._queue, self._tail, self._counter] + [t for group in self._seg + self._mem + self._banks for t in group]
+
+    # -- one chunk ----------------------------------------------------------------------------------------------------
+    def _buffers(self, hops: int) -> dict:
+        """Activation buffers of a `hops`-frame chunk: [1, C, ld] over N = hops * B columns."""
+        if hops not in self._bufs:
+            n = hops * self.streams
+            ld = hip.padded_frames(max(n, MIN_GEMM_COLUMNS))
+            c = self.model.masker.input_size
+            z = lambda: torch.zeros(1, c, ld, dtype=torch.float32, device=self.device)  # noqa: E731
+            self._bufs[hops] = dict(n=n, feats=z(), x0=z(), x1=z(), mask=z())
+        return self._bufs[hops]
+
+    def _body(self, hops: int) -> None:
+        """`hops` frames of every stream: input _io[hops][0] [B, hops*hop] -> output _io[hops][1] [B, hops*hop]."""
+        chunk, out, wins = self._io[hops]
+        hop, win, pk = self.hop_length, self.win_length, self._packs
+        m = self.model.masker
+        bufs = self._buffers(hops)
+        c, n = m.input_size, bufs["n"]
+        feats = bufs["feats"]
+        hip.stream_windows(self._queue, chunk, wins, hop)
+        frames, _ = hip.frame(wins.view(1, -1), win, win)               # [1, win, ld]: column f*B + b
+        cols = max(n, MIN_GEMM_COLUMNS)
+        hip.conv1x1(frames, cols, pk["enc_wt"], c, out=feats)
+        if self.model.encoder.output_active:
+            hip.activation_(feats, "relu", None, n)
+        x = feats
+        last = m.n_blocks - 1
+        for i, block in enumerate(pk["blocks"]):
+            y = bufs["x0"] if i % 2 == 0 else bufs["x1"]
+            hip.skim_block_step(x, self._counter, block, self._seg[i], m.seg_size, self.streams, hops, y, terms=self._terms[i],
+                                bank_in=self._banks[i - 1] if i > 0 else None, mem_state=self._mem[i] if i < last else None,
+                                bank_out=self._banks[i] if i < last else None)
+            x = y
+        hip.conv1x1(x, cols, pk["out_wt"], c, pk["out_pro"], pk["out_b"], out=bufs["mask"])
+        hip.free_decode_step(feats, bufs["mask"], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode)
+        hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
+
+    def _run(self, chunk: torch.Tensor) -> torch.Tensor:
+        k = chunk.shape[1] // self.hop_length
+        if self.frames + k > FRAME_LIMIT:
+            raise RuntimeError(f"StreamingSkiMExtractor: {self.frames} + {k} frames pass this session's limit of {FRAME_LIMIT} "
+                               f"(2**31 - 1 - K_MAX: the device frame counter is an int32); flush the streams and call "
+                               f"init_streams() for a new session")
+        return super()._run(chunk)
+
+    def _flush_into(self, out: torch.Tensor, tail: Optional[torch.Tensor] = None) -> None:
+        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail if tail is None else tail, out, self.hop_length,
+                             out_mode=self._out_mode, flush=True)
