@@ -697,7 +697,18 @@ int ps_dprnn_block_step_slots_f32(const float* x, float* y, const int* counter, 
  * (2 max(C, H) + 2 H + max(4 H, 2 C)) * 64 bytes of LDS: ps_skim_block_step_ok(C, H, K) = 1 where that fits 160 KiB
  * (C, H, K >= 1), else PS_E_UNSUPPORTED, which ps_skim_block_step_f32 then returns too, writing nothing.  x != y;
  * 1 <= k <= 16; k * B <= ld; B <= ldb; x, y, counter 4-byte aligned; *counter + k <= INT32_MAX.  Everything is checked
- * before the launch: PS_E_INVALID with a ps_last_error() text otherwise. */
+ * before the launch: PS_E_INVALID with a ps_last_error() text otherwise.
+ *
+ * Slots: ps_skim_block_step_slots_f32 is ps_skim_block_step_f32 with span [B][2] (device int, 8-byte aligned; the
+ * (birth, death) of ps_dprnn_block_step_slots_f32) after `counter`.  Stream b is LIVE at frame g iff
+ * span[b][0] <= g < span[b][1], and a live stream counts its segments from its own birth: frame n = g - span[b][0] is
+ * position p_b = n % K of segment s_b = n / K.  Its state at p_b == 0 is zero (init_h NULL) or slot s_b % NS of its column of
+ * the incoming banks; the hand-over runs for the streams that are live with p_b == K - 1 and writes slot (s_b + 1) % NS of
+ * their columns of the outgoing banks, and only those streams advance (mh, mc).  A frame that is not live reads x as 0 (it may
+ * hold anything), stores no state, MemLSTM state or bank slot, and gets y = 0.  Both neighbouring blocks count a stream's
+ * segments from the same birth, so the bound on NS is the same.  The sums are those of ps_skim_block_step_f32 in the same
+ * order: a live stream's values are bit-identical to a launch sequence of its own that began at its birth with counter 0.
+ * A null or misaligned span is PS_E_INVALID before any launch. */
 typedef struct ps_skim_block {
   ps_dprnn_pass seg;
   ps_dprnn_pass mem_h;
@@ -725,6 +736,9 @@ typedef struct ps_skim_state {
 int ps_skim_block_step_ok(int C, int H, int K);
 int ps_skim_block_step_f32(const float* x, float* y, const int* counter, const ps_skim_block* blk, const ps_skim_state* st,
                            int C, int H, int K, int NS, int B, int k, int ld, int ldb, void* stream);
+int ps_skim_block_step_slots_f32(const float* x, float* y, const int* counter, const int* span, const ps_skim_block* blk,
+                                 const ps_skim_state* st, int C, int H, int K, int NS, int B, int k, int ld, int ldb,
+                                 void* stream);
 
 /* One cell update per (unit, frame) from COMPLETE gate pre-activations gates [N][D*4H][ld_gates] (W_ih x + W_hh h + both
  * biases: the streaming step puts [x; h] on the K axis of one ps_conv1x1_f32):  c' = sig(f) c + sig(i) tanh(g) in

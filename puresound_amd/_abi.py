@@ -207,6 +207,8 @@ SIGNATURES = {
                                       + [C.c_int] * 7 + [_vp]),
     "ps_skim_block_step_ok": (C.c_int, [C.c_int] * 3),
     "ps_skim_block_step_f32": (C.c_int, [_vp, _vp, _vp, C.POINTER(SkimBlock), C.POINTER(SkimState)] + [C.c_int] * 8 + [_vp]),
+    "ps_skim_block_step_slots_f32": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(SkimBlock), C.POINTER(SkimState)] + [C.c_int] * 8
+                                     + [_vp]),
     "ps_unfold2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp] + [C.c_int] * 14 + [_vp]),
     "ps_conv2d_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 16 + [_vp, _vp]),
     "ps_conv2d_stats_parts": (C.c_int, [C.c_int] * 3),

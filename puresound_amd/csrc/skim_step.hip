@@ -26,6 +26,17 @@
 // rows; the LN partials by lane, then xor 8, 4, 2, 1), so a stream's bits do not depend on B, on its neighbours or on how the
 // hops are split into launches.  A state element is loaded and stored by the same thread: the hand-over reads the (h', c')
 // its own thread has just stored.
+//
+// Slot sessions (ps_skim_block_step_slots_f32): the same with a per-stream span [B][2] of absolute frame indices, as
+// dprnn_step.hip.  Column b is live at frame g iff span[b][0] <= g < span[b][1], and a live column counts its segments from
+// its own birth: its frame n = g - span[b][0] is position n % K of segment n / K, so the segment start (zero, or bank slot
+// (n / K) % NS of its column) and the hand-over (n % K == K - 1, into slot (n / K + 1) % NS of its column) differ between the
+// columns of a tile.  A dead column reads x and its states as 0 (they may hold inf / NaN), stores no state, MemLSTM state or
+// bank slot, and gets y = 0.  A frame at which the whole tile is dead skips all work; the hand-over runs at a frame iff some
+// column of the tile ends a segment there, and inside it only those columns load their (h', c'), advance (mh, mc) and store
+// their slot: the others keep every bit.  Both neighbouring blocks count a column's segments from the same birth, so the
+// bound on NS above holds per column.  The variant is a compile-time one (template <bool SLOTS>): the kernel the entry point
+// without a span launches is the code it was.
 #include "ps_common.h"
 
 namespace ps {
@@ -177,7 +188,16 @@ __device__ __forceinline__ void sk_cell(const float* gt, float* cs, float* hrow,
   }
 }
 
-__global__ __launch_bounds__(SK_THREADS) void skim_block_step_kernel(SkimStepArgs a) {
+// SLOTS: column b is live at frame g iff span[b][0] <= g < span[b][1] and sits at frame n = g - span[b][0] of its own stream:
+// position n % K of its segment n / K.  The loops over (row, column) pairs stride by 256 over an index whose column is
+// i % 16, so there a thread only ever serves column tid % 16; the LayerNorm passes and the bank store of the hand-over serve
+// column tid / 16.  A thread keeps the span of both columns in registers and derives liveness and position per frame for
+// both.  Votes are taken over tid % 16: every wave holds all 16 columns, so every wave of the workgroup decides alike.
+// The variant is the kernel's own template parameter: a body inlined into two kernels compiles the block kernel to other
+// code than it was (another register allocation); this way skim_block_step_kernel<false>, which never reads `span`,
+// compiles to the kernel without slots -- the frame loop instruction for instruction, 255 + 18 registers, no scratch.
+template <bool SLOTS>
+__global__ __launch_bounds__(SK_THREADS) void skim_block_step_kernel(SkimStepArgs a, const int* __restrict__ span) {
   extern __shared__ __align__(16) float sk_lds[];
   const int C = a.C, H = a.H;
   const int CH = C > H ? C : H;
@@ -192,12 +212,40 @@ __global__ __launch_bounds__(SK_THREADS) void skim_block_step_kernel(SkimStepArg
   const size_t slab = (size_t)H * a.ldb;                // one bank slot
   const bool film = a.w.film_wt != nullptr, mem = a.w.mem_h.wt != nullptr;
   const int col = tid / 16, l = tid % 16;               // LayerNorm: 256 threads = 16 columns x 16 lanes
+  int lo_j = 0, hi_j = 0, lo_c = 0, hi_c = 0;           // the spans of columns tid % 16 and tid / 16 (empty past the last stream)
+  if constexpr (SLOTS) {
+    if (l < cols) {
+      const int2 sp = reinterpret_cast<const int2*>(span)[b0 + l];
+      lo_j = sp.x;
+      hi_j = sp.y;
+    }
+    if (col < cols) {
+      const int2 sp = reinterpret_cast<const int2*>(span)[b0 + col];
+      lo_c = sp.x;
+      hi_c = sp.y;
+    }
+  }
   for (int f = 0; f < a.k; ++f) {
     const size_t c0 = (size_t)f * a.B + b0;
-    const int g = t0 + f, p = g % a.K, s = g / a.K;
+    const int g = t0 + f;
+    int p = g % a.K, s = g / a.K;
+    bool alive = true;                                  // SLOTS: of column tid % 16 (alive implies tid % 16 < cols)
+    if constexpr (SLOTS) {
+      alive = g >= lo_j && g < hi_j;
+      if (!__any(alive)) {                              // the whole tile is dead at this frame
+        for (int i = tid; i < C * SK_TB; i += SK_THREADS) {
+          const int m = i / SK_TB, j = i % SK_TB;
+          if (j < cols) a.y[(size_t)m * a.ld + c0 + j] = 0.f;
+        }
+        continue;
+      }
+      const unsigned n = (unsigned)g - (unsigned)lo_j;  // (g - lo < 2^32: exact)
+      p = (int)(n % (unsigned)a.K);
+      s = (int)(n / (unsigned)a.K);
+    }
     for (int i = tid; i < C * SK_TB; i += SK_THREADS) {
       const int m = i / SK_TB, j = i % SK_TB;
-      xh[i] = j < cols ? a.x[(size_t)m * a.ld + c0 + j] : 0.f;
+      xh[i] = (SLOTS ? alive : j < cols) ? a.x[(size_t)m * a.ld + c0 + j] : 0.f;
     }
     {
       const float* hs = a.s.seg_h + b0;
@@ -212,7 +260,7 @@ __global__ __launch_bounds__(SK_THREADS) void skim_block_step_kernel(SkimStepArg
       }
       for (int i = tid; i < H * SK_TB; i += SK_THREADS) {
         const int u = i / SK_TB, j = i % SK_TB;
-        const bool live = j < cols && !zero;
+        const bool live = (SLOTS ? alive : j < cols) && !zero;
         xh[C * SK_TB + i] = live ? hs[(size_t)u * a.ldb + j] : 0.f;
         cs[i] = live ? cg[(size_t)u * a.ldb + j] : 0.f;
       }
@@ -228,15 +276,17 @@ __global__ __launch_bounds__(SK_THREADS) void skim_block_step_kernel(SkimStepArg
       __syncthreads();
       for (int i = tid; i < C * SK_TB; i += SK_THREADS) {
         const int m = i / SK_TB, j = i % SK_TB;
-        const float sc = gt[i] + (j < cols ? a.s.rs[(size_t)m * a.ldb + b0 + j] : 0.f);
-        const float bi = gt[C * SK_TB + i] + (j < cols ? a.s.rb[(size_t)m * a.ldb + b0 + j] : 0.f);
+        const bool live = SLOTS ? alive : j < cols;
+        const float sc = gt[i] + (live ? a.s.rs[(size_t)m * a.ldb + b0 + j] : 0.f);
+        const float bi = gt[C * SK_TB + i] + (live ? a.s.rb[(size_t)m * a.ldb + b0 + j] : 0.f);
         xh[i] = fmaf(sc, xh[i], bi);
       }
       __syncthreads();
     }
     sk_rows_all(a.w.seg.wt, a.w.seg.bias, 4 * H, C + H, xh, gt);
     __syncthreads();
-    sk_cell(gt, cs, xh + C * SK_TB, a.s.seg_h + b0, a.s.seg_c + b0, H, a.ldb, cols);
+    // (SLOTS: the cell's `cols` is this thread's column's alone: all 16 or none -- a dead column stores no state)
+    sk_cell(gt, cs, xh + C * SK_TB, a.s.seg_h + b0, a.s.seg_c + b0, H, a.ldb, SLOTS ? (alive ? SK_TB : 0) : cols);
     __syncthreads();
     sk_rows_halves(a.w.seg.pt, a.w.seg.pbias, C, H, xh + C * SK_TB, pr);
     __syncthreads();
@@ -249,11 +299,28 @@ __global__ __launch_bounds__(SK_THREADS) void skim_block_step_kernel(SkimStepArg
     __syncthreads();
     for (int i = tid; i < C * SK_TB; i += SK_THREADS) {   // (the thread that stores xh[i] for the next frame reads it here)
       const int m = i / SK_TB, j = i % SK_TB;
-      if (j < cols) a.y[(size_t)m * a.ld + c0 + j] = xh[i];
+      if constexpr (SLOTS) {
+        if (j < cols) a.y[(size_t)m * a.ld + c0 + j] = alive ? xh[i] : 0.f;
+      } else {
+        if (j < cols) a.y[(size_t)m * a.ld + c0 + j] = xh[i];
+      }
     }
-    if (p == a.K - 1 && mem) {                            // (the same decision in every thread of the launch)
+    // (block kernel: the same decision in every thread of the launch; SLOTS: in every thread of the workgroup, and inside
+    // only the columns that end a segment here load, advance the MemLSTM and store their slot)
+    bool ends = p == a.K - 1, hand_over = ends;         // (of column tid % 16; of the workgroup)
+    if constexpr (SLOTS) {
+      ends = alive && ends;
+      hand_over = __any(ends);
+    }
+    if (hand_over && mem) {
       __syncthreads();
-      const size_t slot = (size_t)((s + 1) % a.NS) * slab + b0;
+      size_t slot = (size_t)((s + 1) % a.NS) * slab + b0;
+      bool ends_c = col < cols;                           // of column tid / 16, whose bank slot this thread stores
+      if constexpr (SLOTS) {
+        const unsigned n = (unsigned)g - (unsigned)lo_c;
+        ends_c = g >= lo_c && g < hi_c && (int)(n % (unsigned)a.K) == a.K - 1;
+        slot = (size_t)((n / (unsigned)a.K + 1) % (unsigned)a.NS) * slab + b0;
+      }
       for (int net = 0; net < 2; ++net) {
         const ps_dprnn_pass& w = net == 0 ? a.w.mem_h : a.w.mem_c;
         const float* v = (net == 0 ? a.s.seg_h : a.s.seg_c) + b0;   // (h', c'): element i was stored by this thread
@@ -262,7 +329,7 @@ __global__ __launch_bounds__(SK_THREADS) void skim_block_step_kernel(SkimStepArg
         float* out = (net == 0 ? a.s.out_h : a.s.out_c) + slot;
         for (int i = tid; i < H * SK_TB; i += SK_THREADS) {
           const int u = i / SK_TB, j = i % SK_TB;
-          const bool live = j < cols;
+          const bool live = SLOTS ? ends : j < cols;
           xh[i] = live ? v[(size_t)u * a.ldb + j] : 0.f;
           xh[H * SK_TB + i] = live ? mh[(size_t)u * a.ldb + j] : 0.f;
           cs[i] = live ? mc[(size_t)u * a.ldb + j] : 0.f;
@@ -270,13 +337,13 @@ __global__ __launch_bounds__(SK_THREADS) void skim_block_step_kernel(SkimStepArg
         __syncthreads();
         sk_rows_all(w.wt, w.bias, 4 * H, 2 * H, xh, gt);
         __syncthreads();
-        sk_cell(gt, cs, xh + H * SK_TB, mh, mc, H, a.ldb, cols);
+        sk_cell(gt, cs, xh + H * SK_TB, mh, mc, H, a.ldb, SLOTS ? (ends ? SK_TB : 0) : cols);
         __syncthreads();
         sk_rows_halves(w.pt, w.pbias, H, H, xh + H * SK_TB, pr);
         __syncthreads();
         float mean, rstd;
         sk_ln_stats(pr, H, w.eps, mean, rstd);
-        if (col < cols)
+        if (ends_c)
           for (int m = l; m < H; m += 16)
             out[(size_t)m * a.ldb + col] = xh[m * SK_TB + col] + ((pr[m * SK_TB + col] - mean) * rstd * w.gamma[m] + w.beta[m]);
         __syncthreads();
@@ -301,10 +368,11 @@ extern "C" int ps_skim_block_step_ok(int C, int H, int K) {
 
 static bool pass_complete(const ps_dprnn_pass& w) { return w.wt && w.bias && w.pt && w.pbias && w.gamma && w.beta; }
 
-extern "C" int ps_skim_block_step_f32(const float* x, float* y, const int* counter, const ps_skim_block* blk,
-                                      const ps_skim_state* st, int C, int H, int K, int NS, int B, int k, int ld, int ldb,
-                                      void* stream) {
-  const char* who = "ps_skim_block_step_f32";
+// ps_skim_block_step_f32 (span = NULL, slots = false) and ps_skim_block_step_slots_f32 share the checks and differ in the
+// kernel.
+static int skim_block_step_launch(const char* who, bool slots, const float* x, float* y, const int* counter, const int* span,
+                                  const ps_skim_block* blk, const ps_skim_state* st, int C, int H, int K, int NS, int B, int k,
+                                  int ld, int ldb, void* stream) {
   if (!x || !y || x == y || !counter || !blk || !st || C <= 0 || H <= 0 || K <= 0 || B <= 0 || k <= 0 || k > 16 || ldb < B ||
       (long long)k * B > ld || (long long)C * ld > (1LL << 31) || (long long)(C > H ? C : H) * ldb > (1LL << 31)) {
     set_error("%s: bad argument (C=%d H=%d K=%d NS=%d B=%d k=%d ld=%d ldb=%d; 1 <= k <= 16)", who, C, H, K, NS, B, k, ld, ldb);
@@ -312,6 +380,10 @@ extern "C" int ps_skim_block_step_f32(const float* x, float* y, const int* count
   }
   if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)counter) & 3) {
     set_error("%s: x, y and counter must be 4-byte aligned", who);
+    return PS_E_INVALID;
+  }
+  if (slots && (!span || ((uintptr_t)span & 7))) {
+    set_error("%s: span must be an 8-byte aligned device array [B][2] of int", who);
     return PS_E_INVALID;
   }
   if (!pass_complete(blk->seg) || !st->seg_h || !st->seg_c) {
@@ -343,14 +415,35 @@ extern "C" int ps_skim_block_step_f32(const float* x, float* y, const int* count
     return PS_E_UNSUPPORTED;
   }
   const size_t lds = skim_lds_rows(C, H) * SK_TB * sizeof(float);
-  static const bool big_lds = hipFuncSetAttribute(reinterpret_cast<const void*>(&skim_block_step_kernel),
+  // (dynamic LDS beyond 64 KiB has to be asked for, once per kernel)
+  static const bool big_lds = hipFuncSetAttribute(reinterpret_cast<const void*>(&skim_block_step_kernel<false>),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_LDS_MAX) == hipSuccess;
-  if (!big_lds && lds > 64 * 1024) {   // (dynamic LDS beyond 64 KiB has to be asked for, once per kernel)
+  static const bool big_lds_slots = hipFuncSetAttribute(reinterpret_cast<const void*>(&skim_block_step_kernel<true>),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_LDS_MAX) == hipSuccess;
+  if (!(slots ? big_lds_slots : big_lds) && lds > 64 * 1024) {
     set_error("%s: %zu bytes of LDS refused by the runtime", who, lds);
     return PS_E_UNSUPPORTED;
   }
   SkimStepArgs a{x, y, counter, *blk, *st, C, H, K, mem || st->init_h ? NS : 1, B, k, ld, ldb};
-  LaunchTimer timer("skim_block_step", (hipStream_t)stream);
-  hipLaunchKernelGGL(skim_block_step_kernel, dim3((B + SK_TB - 1) / SK_TB), dim3(SK_THREADS), lds, (hipStream_t)stream, a);
+  LaunchTimer timer(slots ? "skim_block_step_slots" : "skim_block_step", (hipStream_t)stream);
+  const dim3 grid((B + SK_TB - 1) / SK_TB);
+  if (slots)
+    hipLaunchKernelGGL(skim_block_step_kernel<true>, grid, dim3(SK_THREADS), lds, (hipStream_t)stream, a, span);
+  else
+    hipLaunchKernelGGL(skim_block_step_kernel<false>, grid, dim3(SK_THREADS), lds, (hipStream_t)stream, a, span);
   return launch_status(who);
+}
+
+extern "C" int ps_skim_block_step_f32(const float* x, float* y, const int* counter, const ps_skim_block* blk,
+                                      const ps_skim_state* st, int C, int H, int K, int NS, int B, int k, int ld, int ldb,
+                                      void* stream) {
+  return skim_block_step_launch("ps_skim_block_step_f32", false, x, y, counter, nullptr, blk, st, C, H, K, NS, B, k, ld, ldb,
+                                stream);
+}
+
+extern "C" int ps_skim_block_step_slots_f32(const float* x, float* y, const int* counter, const int* span,
+                                            const ps_skim_block* blk, const ps_skim_state* st, int C, int H, int K, int NS,
+                                            int B, int k, int ld, int ldb, void* stream) {
+  return skim_block_step_launch("ps_skim_block_step_slots_f32", true, x, y, counter, span, blk, st, C, H, K, NS, B, k, ld, ldb,
+                                stream);
 }

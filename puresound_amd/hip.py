@@ -1145,13 +1145,16 @@ def pack_skim_block(masker, i: int, device: torch.device) -> dict:
 
 def skim_block_step(x: torch.Tensor, counter: torch.Tensor, block: dict, seg_state: tuple, seg: int, streams: int, frames: int,
                     out: torch.Tensor, terms: Optional[tuple] = None, bank_in: Optional[tuple] = None,
-                    mem_state: Optional[tuple] = None, bank_out: Optional[tuple] = None) -> torch.Tensor:
+                    mem_state: Optional[tuple] = None, bank_out: Optional[tuple] = None,
+                    span: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One causal SkiM block on `frames` new frames of `streams` streams (ps_skim_block_step_f32): x [1, C, ld] (column
     f * streams + b) -> out [1, C, ld] (columns past frames * streams are not written); block from pack_skim_block;
     seg_state = (seg_h, seg_c) [H, ldb]; terms = (rs, rb) [C, ldb] iff the block has FiLM; bank_in = (init_h, init_c)
     [NS, H, ldb], None for the first block; mem_state = (mh_h, mc_h, mh_c, mc_c) [H, ldb] and bank_out = the next block's
     banks iff the block has a MemLSTM.  States and bank_out are updated in place; frame index of column 0 = counter[0],
-    position = index % seg."""
+    position = index % seg.  span int32 [streams, 2]: ps_skim_block_step_slots_f32, stream b computes frame g iff
+    span[b, 0] <= g < span[b, 1], as frame n = g - span[b, 0] of its own segments (position n % seg, bank slots by n // seg);
+    a frame that is not live reads x as 0, stores no state and no bank slot, and returns 0."""
     who = "skim_block_step"
     require_device(x, who)
     _, c, ld = x.shape
@@ -1185,6 +1188,12 @@ def skim_block_step(x: torch.Tensor, counter: torch.Tensor, block: dict, seg_sta
                 raise RuntimeError(f"{who}: {what}: states [H, ldb], terms [C, ldb] and banks [NS, H, ldb] of one H, ldb and NS "
                                    f"expected (got {tuple(t.shape)} for {name})")
             setattr(st, name, ptr(t))
+    if span is not None:
+        _check_span(span, streams, x, who)
+        check(lib().ps_skim_block_step_slots_f32(ptr(x), ptr(out), ptr(counter), ptr(span), C.byref(block["struct"]),
+                                                 C.byref(st), c, hidden, int(seg), ns, streams, frames, ld, ldb,
+                                                 stream_ptr(x.device)), "ps_skim_block_step_slots_f32")
+        return out
     check(lib().ps_skim_block_step_f32(ptr(x), ptr(out), ptr(counter), C.byref(block["struct"]), C.byref(st), c, hidden,
                                        int(seg), ns, streams, frames, ld, ldb, stream_ptr(x.device)), "ps_skim_block_step_f32")
     return out

@@ -8,13 +8,14 @@ windows [hops, B*window])), `_flush_into(out)`; it may set `max_hops` and overri
 its own arguments, calls `_begin` and allocates what `_state` returns; `_queue` [B, window], `_tail` [B, window - hop] and
 `_counter` (int32 [1], the device frame counter) are allocated here.
 
-Slots (tcn.py, dprnn.py): a session of fixed capacity whose columns begin and end streams of their own while it runs.  The
+Slots (tcn.py, dprnn.py, skim.py): a session of fixed capacity whose columns begin and end streams of their own while it runs.  The
 model-independent half lives here: the device span [B, 2] of (birth, death) frame indices and the host record per slot, the
 slot checks, open / end / close, the hops each slot was fed, the frame limit, and the rules that a slot session has no
 priming phase and no flush().  A streamer with slots calls `_begin` and then `_make_slots` in its init_slots, passes
 `self._span` to its kernels in `_body`, and provides `_enrolment_rule()` (whether open() takes an enrolment, and the words
 that say why), `_open_slot(slot, enroll)` (reset or seed the slot's model state) and a `_flush_into(out, tail)` that takes
-the tail rows to flush.
+the tail rows to flush.  A streamer whose open() takes other arguments (skim.py: an enrolment or its embedding) overrides
+open(), checks them and ends in `_start_slot`.
 """
 import contextlib
 from typing import Dict, List, Optional
@@ -267,18 +268,27 @@ class HopSession:
         if (enroll is not None) != required:
             raise ValueError(f"{name}: an enrolment [L'] is required {why}")
         if enroll is not None:
-            hip.require_device(enroll, name)
-            if enroll.device != self.device:
-                raise RuntimeError(f"{name}: the enrolment is on {enroll.device}, the session on {self.device}; move it with "
-                                   f".to({str(self.device)!r})")
-            enroll = enroll[None] if enroll.dim() == 1 else enroll
-            if enroll.dim() != 2 or enroll.shape[0] != 1:
-                raise ValueError(f"{name}: enroll must be [L'] or [1, L'] (one stream), got {tuple(enroll.shape)}")
+            enroll = self._one_enrolment(enroll, name)
+        self._start_slot(slot, enroll, name)
+
+    def _one_enrolment(self, enroll: torch.Tensor, name: str) -> torch.Tensor:
+        """open()'s checks of an enrolment -> [1, L']."""
+        hip.require_device(enroll, name)
+        if enroll.device != self.device:
+            raise RuntimeError(f"{name}: the enrolment is on {enroll.device}, the session on {self.device}; move it with "
+                               f".to({str(self.device)!r})")
+        enroll = enroll[None] if enroll.dim() == 1 else enroll
+        if enroll.dim() != 2 or enroll.shape[0] != 1:
+            raise ValueError(f"{name}: enroll must be [L'] or [1, L'] (one stream), got {tuple(enroll.shape)}")
+        return enroll
+
+    def _start_slot(self, slot: int, seed, name: str) -> None:
+        """The rest of open() once its arguments are checked; `seed` is what the streamer's _open_slot takes."""
         if self.frames + self.prime_hops > FRAME_LIMIT:
             raise RuntimeError(f"{name}: the session is at its limit of {FRAME_LIMIT} frames (an int32 frame counter); close "
                                f"the streams and call init_slots() for a new session")
         self._check_parameters()
-        self._open_slot(slot, enroll)
+        self._open_slot(slot, seed)
         self._queue[slot].zero_()
         self._tail[slot].zero_()
         # frames counter .. counter + prime_hops - 1 see a partly filled window: dead.  (device-side add: no read-back)

@@ -30,7 +30,21 @@ Arithmetic: exact fp32 products throughout, whatever the model's gemm_precision;
 order (the 1x1 convolutions always take ps_conv1x1_f32's tiled kernel: MIN_GEMM_COLUMNS), so a stream's output does not depend
 on B, on its neighbours or on how its hops are split into calls.  The streamer packs its own weights from the parameters; the
 model's own setting and plans are left as they were.  The session around the kernels (priming, step / step_chunk / flush,
-eager run or graph replay, the capture) is HopSession's: streaming/_session.py.  There are no slot sessions yet.
+eager run or graph replay, the capture) is HopSession's: streaming/_session.py.
+
+Slots (init_slots / open / end / close; the bookkeeping is HopSession's): a session of fixed capacity B whose columns begin
+and end streams of their own while it runs.  Per slot the device holds a span (birth, death) of absolute frame indices; frame
+g of column b is live iff birth[b] <= g < death[b].  The segment grid is part of the recurrence, so a stream that joins at an
+arbitrary frame counts its segments from its own birth: ps_skim_block_step_slots_f32 puts frame g of column b at position
+(g - birth[b]) % K of segment (g - birth[b]) // K -- its frame n where a session of its own would have it -- and takes the
+segment start (zero, or the bank slot) and the MemLSTM hand-over per column by that; a dead frame reads its input as 0 and
+stores no state and no bank slot; ps_free_decode_step_slots_f32 adds nothing for a dead frame.  open() zeroes the slot's
+queue, tail, SegLSTM and MemLSTM states and all NS slots of its column of every bank, and writes the FiLM terms of the new
+stream's embedding into its column (computed as a session of one stream computes them), so nothing of the slot's predecessor
+is left.  What a slot returned from open to close, followed by close()'s samples, is `model.inference(x[None], enroll[None])`
+of its own stream after latency_samples samples of constrain(0), whatever the other slots do; every sum has one fixed order
+per column, so it is bit-identical to an init_streams(1, ...) session of that stream.  A tile of 16 slots pays the hand-over
+at every frame at which any of its slots ends a segment: DESIGN 4.11 has what staggered births cost, measured.
 """
 from typing import List, Optional
 
@@ -41,7 +55,7 @@ from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
 from ..nnet.lobe.encoder import FreeEncDec
 from ..nnet.lobe.trivial import FiLM, Gate
 from ..nnet.skim import SkiM
-from ._session import FRAME_LIMIT, K_MAX, HopSession, check_on_device
+from ._session import FRAME_LIMIT, INT32_MAX, K_MAX, HopSession, check_on_device  # noqa: F401
 from .dprnn import MIN_GEMM_COLUMNS
 
 
@@ -110,9 +124,18 @@ class StreamingSkiMExtractor(HopSession):
     s = StreamingSkiMExtractor(model); s.init_streams(B, enroll=e) or s.init_streams(B, embed=d);
     s.step(hop [B, hop]) -> [B, hop] or None while the first window fills; s.step_chunk([B, k*hop]) -> what k step() calls
     return, concatenated; s.flush() -> the last win - hop samples.
+
+    Slots, for streams that begin and end on their own: s.init_slots(capacity); s.open(slot, enroll=e [L']) or
+    s.open(slot, embed=d [E]); every s.step / s.step_chunk([capacity, k*hop]) -> [capacity, k*hop] from the first hop on
+    (idle slots: constrain(0)); s.end(slot, hops) when the stream has `hops` more hops of input; s.close(slot) -> the last
+    win - hop samples, and the slot is idle again.  What a slot returned from open to close, then close's samples, is
+    model.inference(x[None], enroll[None]) of its own stream after latency_samples samples of constrain(0)
+    (slot_output_range(L, win, hop)), whatever the other slots do, and bit-identical to an init_streams(1, ...) session of
+    that stream.
     """
 
     max_hops = K_MAX
+    _how_to_start = "call init_streams() first (or init_slots())"
 
     def __init__(self, model: SoTaskWrapModule):
         check_streamable(model)
@@ -131,7 +154,11 @@ class StreamingSkiMExtractor(HopSession):
                            out_wt=hip.pack_wt(m.output_fc[1].weight.detach().to(**f32)),
                            out_b=m.output_fc[1].bias.detach().to(**f32).contiguous(), out_slope=slope,
                            out_pro=hip.make_prologue(0, True, None, 0.0, 0.0, None, None, slope))
-        if self.streams is not None:                               # (changed weights in a session: FiLM's terms follow them)
+        if self._slots is not None:                                # (changed weights in a session: FiLM's terms follow them;
+            for slot, embed in enumerate(self._slot_embeds):       # a slot session's, in place, for the slots that are open)
+                if embed is not None and self._slots[slot] is not None:
+                    self._write_terms(slot, embed)
+        elif self.streams is not None:
             self._terms = self._film_terms()
 
     # -- session ------------------------------------------------------------------------------------------------------
@@ -177,14 +204,105 @@ class StreamingSkiMExtractor(HopSession):
         self._bufs = {}
         self._ready()
 
+    @torch.no_grad()
+    def init_slots(self, capacity: int, use_graph: bool = True) -> None:
+        """Start a slot session of `capacity` columns, every slot idle (every state and every FiLM term zeroed); open() starts
+        a stream."""
+        if int(capacity) < 1:
+            raise ValueError("init_slots: capacity >= 1")
+        m = self.model.masker
+        b, dev = int(capacity), next(self.model.parameters()).device
+        self._begin(b, dev, use_graph)
+        self._make_slots()
+        h, c, ldb = m.hidden_size, m.input_size, hip.padded_frames(max(b, MIN_GEMM_COLUMNS))
+        self._embed, self._ldb = None, ldb
+        self._slot_embeds = [None] * b                             # per slot the embedding [1, E] its stream was opened with
+        ns = hip.skim_bank_slots(K_MAX, m.seg_size)
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        self._seg = [(z(h, ldb), z(h, ldb)) for _ in range(m.n_blocks)]
+        self._mem = [tuple(z(h, ldb) for _ in range(4)) for _ in range(m.n_blocks - 1)]
+        self._banks = [(z(ns, h, ldb), z(ns, h, ldb)) for _ in range(m.n_blocks - 1)]
+        # (the launches read these tensors for as long as the session lasts: open() writes a column of them)
+        self._terms = [(z(c, ldb), z(c, ldb)) if m.embed_dim > 0 and m.block_with_embed[i] else None for i in range(m.n_blocks)]
+        self._bufs = {}
+
+    def _enrolment_rule(self) -> tuple:
+        e = self.model.masker.embed_dim
+        if e > 0:
+            return True, (f"the masker takes an embedding (embed_dim = {e}): pass exactly one of enroll [L'] and embed [{e}]")
+        return False, "the masker takes no embedding (embed_dim = 0): pass neither enroll nor embed"
+
+    def _slot(self, slot: int, what: str, idle: bool) -> int:
+        """(a block session answers the slot calls with the NotImplementedError -- a RuntimeError, as the siblings raise --
+        and the words it has always had for them: its streams are not slots)"""
+        if self.streams is not None and self._slots is None:
+            raise NotImplementedError(f"{type(self).__name__}.{what}: an init_streams() session has no slot sessions: its "
+                                      f"streams start together and end together in flush(); call init_slots() for slots that "
+                                      f"open and close on their own")
+        return super()._slot(slot, what, idle)
+
+    @torch.no_grad()
+    def open(self, slot: int, enroll: Optional[torch.Tensor] = None, embed: Optional[torch.Tensor] = None) -> None:
+        """Start a stream in the idle slot `slot`: its first input hop is the first hop of the next step / step_chunk call.
+        A masker with embed_dim > 0 takes exactly one of enroll [L'] or [1, L'] (through model.inference_tse_embedding, here,
+        once) and embed [E], [1, E] or [1, E, 1] (what that call returns; a deployment caches it), on the session's device; a
+        masker without takes neither.  No synchronisation, no captured graph is touched."""
+        name = f"{type(self).__name__}.open"
+        slot = self._slot(slot, "open", idle=True)
+        required, why = self._enrolment_rule()
+        given = (enroll is not None) + (embed is not None)
+        if given != int(required):
+            raise ValueError(f"{name}: {why}")
+        if enroll is not None:
+            enroll = self._one_enrolment(enroll, name)
+        if embed is not None:
+            e = self.model.masker.embed_dim
+            hip.require_device(embed, name)
+            if embed.device != self.device:
+                raise RuntimeError(f"{name}: the embedding is on {embed.device}, the session on {self.device}; move it with "
+                                   f".to({str(self.device)!r})")
+            if tuple(embed.shape) not in ((e,), (1, e), (1, e, 1)):
+                raise ValueError(f"{name}: embed must be [{e}], [1, {e}] or [1, {e}, 1] (one stream), got {tuple(embed.shape)}")
+            embed = embed.reshape(1, e)
+        self._start_slot(slot, (enroll, embed), name)
+
+    def _open_slot(self, slot: int, seed: tuple) -> None:
+        """Nothing of the slot's predecessor stays: the column zeroed in every block's (seg_h, seg_c), MemLSTM states and all
+        NS slots of both banks, and the new stream's FiLM terms written into it (computed here, once, as init_streams does
+        for one stream)."""
+        enroll, embed = seed
+        if enroll is not None:
+            embed = self.model.inference_tse_embedding(enroll)[:, :, 0]
+        self._ready()
+        for group in self._seg + self._mem:
+            for t in group:
+                t[:, slot].zero_()
+        for bank in self._banks:
+            for t in bank:
+                t[:, :, slot].zero_()
+        self._slot_embeds[slot] = None if embed is None else embed.detach().to(torch.float32).clone()
+        if embed is not None:
+            self._write_terms(slot, self._slot_embeds[slot])
+
+    def _write_terms(self, slot: int, embed: torch.Tensor) -> None:
+        """Column `slot` of every block's (rs, rb) <- the terms of embed [1, E], the bits of a session of that one stream."""
+        one = self._terms_of(embed, hip.padded_frames(MIN_GEMM_COLUMNS))
+        for dst, src in zip(self._terms, one):
+            if dst is not None:
+                dst[0][:, slot] = src[0][:, 0]
+                dst[1][:, slot] = src[1][:, 0]
+
     def _film_terms(self) -> list:
         """Per block with FiLM (rs, rb) [C, ldb]: the embedding columns of cond_scale / cond_bias applied to the (normalised)
         embedding of every stream.  Both sums run as ps_conv1x1_f32 over the streams as columns, at least MIN_GEMM_COLUMNS of
         them, so a stream's terms do not depend on B."""
+        if self._embed is None:
+            return [None] * self.model.masker.n_blocks
+        return self._terms_of(self._embed, self._ldb)
+
+    def _terms_of(self, embed: torch.Tensor, ldb: int) -> list:
+        """_film_terms for embed [b, E] in rows of ldb columns."""
         m = self.model.masker
-        embed, ldb = self._embed, self._ldb
-        if embed is None:
-            return [None] * m.n_blocks
         b, e = embed.shape
         c, cols = m.input_size, max(b, MIN_GEMM_COLUMNS)
         rows = torch.zeros(1, e, ldb, dtype=torch.float32, device=self.device)
@@ -236,15 +354,17 @@ class StreamingSkiMExtractor(HopSession):
             y = bufs["x0"] if i % 2 == 0 else bufs["x1"]
             hip.skim_block_step(x, self._counter, block, self._seg[i], m.seg_size, self.streams, hops, y, terms=self._terms[i],
                                 bank_in=self._banks[i - 1] if i > 0 else None, mem_state=self._mem[i] if i < last else None,
-                                bank_out=self._banks[i] if i < last else None)
+                                bank_out=self._banks[i] if i < last else None, span=self._span)
             x = y
         hip.conv1x1(x, cols, pk["out_wt"], c, pk["out_pro"], pk["out_b"], out=bufs["mask"])
-        hip.free_decode_step(feats, bufs["mask"], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode)
+        hip.free_decode_step(feats, bufs["mask"], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode,
+                             span=self._span, counter=self._counter if self._span is not None else None)
         hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
 
     def _run(self, chunk: torch.Tensor) -> torch.Tensor:
+        """(a block session has the frame limit too; the core checks a slot session's, with its own way out)"""
         k = chunk.shape[1] // self.hop_length
-        if self.frames + k > FRAME_LIMIT:
+        if self._slots is None and self.frames + k > FRAME_LIMIT:
             raise RuntimeError(f"StreamingSkiMExtractor: {self.frames} + {k} frames pass this session's limit of {FRAME_LIMIT} "
                                f"(2**31 - 1 - K_MAX: the device frame counter is an int32); flush the streams and call "
                                f"init_streams() for a new session")

@@ -7,7 +7,13 @@ call; p50 / p99 of the per-call wall time over --replays calls after --warmup.  
 segment run the MemLSTM hand-over on top (one in 150 step() calls): they are reported on a line of their own (n of them, p50
 and the slowest).  For context the demo harness (DemoTseNet.streaming_inference_chunk) at --demo-streams streams on chunks
 of the same lengths, in the same run.  Prints a plain-text report (profiles/streaming_skim.txt holds one run).
---profile-only B,K: a short run of K-hop chunks at B streams and nothing else, for rocprofv3."""
+--profile-only B,K: a short run of K-hop chunks at B streams and nothing else, for rocprofv3.
+--slots: the slot sessions instead (init_slots / open; profiles/streaming_skim_slots.txt holds one run).  Per B and call size,
+in one run: the block session (init_streams: the yardstick), a slot session with every slot opened at frame 0, one with the
+births spread uniformly over the K frames of a segment, and the worst case, every tile's 16 slots born at 16 consecutive
+frames (a chunk of k hops then meets min(k, 16) hand-over frames per tile).  In a staggered session most calls hold a segment
+end of some slot, so every call counts: p50 / p99 / max over all of them.  Then the cost of open() with a 1 s enrolment and
+with a cached embedding."""
 import argparse
 import contextlib
 import io
@@ -64,6 +70,99 @@ def time_mode(s, b, chunk_hops, replays, warmup, dev):
     return np.asarray(plain), np.asarray(ends)
 
 
+SLOT_CASES = ("block", "slots@0", "uniform", "worst")
+
+
+def births(case, b, seg):
+    """Per slot the frame at which it is opened."""
+    if case == "uniform":
+        return [(i * seg) // b for i in range(b)]
+    if case == "worst":
+        return [i % 16 for i in range(b)]
+    return [0] * b
+
+
+def time_slots(s, b, chunk_hops, case, replays, warmup, dev):
+    """Per-call ms of `replays` calls in a slot session of b slots opened by `case` (or the block session), every call."""
+    x = det_wave(100 + b, b, SR * SECONDS).to(dev)
+    embed = det_wave(200 + b, b, s.model.masker.embed_dim).to(dev)
+    hop = s.hop_length
+    total = x.shape[1] // hop
+    pos = 0
+
+    def call(k):
+        nonlocal pos
+        if pos + k > total:
+            pos = 0
+        piece = x[:, pos * hop:(pos + k) * hop]
+        pos += k
+        s.step(piece) if k == 1 else s.step_chunk(piece)
+
+    if case == "block":
+        s.init_streams(streams=b, embed=embed, use_graph=True)
+        for _ in range(s.prime_hops):
+            call(1)
+    else:
+        s.init_slots(b, use_graph=True)
+        at = births(case, b, s.model.masker.seg_size)
+        for f in range(max(at) + 1):
+            for i in (i for i, v in enumerate(at) if v == f):
+                s.open(i, embed=embed[i])
+            call(1)
+    for _ in range(warmup):
+        call(chunk_hops)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(replays):
+        t0 = time.perf_counter()
+        call(chunk_hops)
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return np.asarray(ms)
+
+
+def time_open(s, b, dev, n=200):
+    """ms of open() in a running slot session of b slots: with a 1 s enrolment, with its cached embedding (a device
+    synchronise after every call; close() between them is not timed)."""
+    s.init_slots(b, use_graph=True)
+    hop = s.hop_length
+    x = det_wave(100, b, 2 * hop).to(dev)
+    e = det_wave(400, 1, SR)[0].to(dev)
+    d = s.model.inference_tse_embedding(e[None])
+    out = {}
+    for what, how in (("enroll 1 s", dict(enroll=e)), ("cached embed", dict(embed=d))):
+        ms = []
+        for i in range(n + 10):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            s.open(0, **how)
+            torch.cuda.synchronize()
+            if i >= 10:
+                ms.append((time.perf_counter() - t0) * 1e3)
+            s.step_chunk(x)
+            s.close(0)
+        out[what] = np.asarray(ms)
+    return out
+
+
+def report_slots(s, args, dev, hop_ms):
+    print("# slot sessions; cases: block = init_streams (the yardstick); slots@0 = every slot opened at frame 0; uniform = births "
+          "spread over the K frames of a segment; worst = every tile's 16 slots born at 16 consecutive frames")
+    print(f"{'B':>6} {'hops/call':>9} {'budget':>7} {'case':>8} {'p50':>8} {'p99':>8} {'max':>8}  p99 in budget  max in budget")
+    for k in (int(v) for v in args.chunks.split(",")):
+        budget = hop_ms * k
+        for b in (int(v) for v in args.batches.split(",")):
+            for case in SLOT_CASES:
+                ms = time_slots(s, b, k, case, args.replays, args.warmup, dev)
+                p50, p99 = np.percentile(ms, 50), np.percentile(ms, 99)
+                print(f"{b:>6} {k:>9} {budget:>7.1f} {case:>8} {p50:>8.3f} {p99:>8.3f} {ms.max():>8.3f}  "
+                      f"{'yes' if p99 < budget else 'no':>13}  {'yes' if ms.max() < budget else 'no':>13}", flush=True)
+        torch.cuda.empty_cache()
+    print("# open() in a running session of 64 slots, ms per call with a device synchronise")
+    for what, ms in time_open(s, 64, dev).items():
+        print(f"{what:>14}  p50 {np.percentile(ms, 50):>8.3f}  p99 {np.percentile(ms, 99):>8.3f}", flush=True)
+
+
 def time_demo(streams, chunk_hops, replays, warmup, dev):
     """Per-call ms of DemoTseNet.streaming_inference_chunk on chunks of chunk_hops hops (tools/bench_configs.py cfg5)."""
     from puresound_amd.streaming.demo import DemoTseNet
@@ -97,6 +196,7 @@ def main():
     ap.add_argument("--demo-streams", type=int, default=64)
     ap.add_argument("--profile-only", default="", help="B,K: 200 calls of K-hop chunks at B streams, no report")
     ap.add_argument("--tree", default="", help="source revision to print in the header")
+    ap.add_argument("--slots", action="store_true", help="measure the slot sessions against the block session")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     model = cases.build(PA.NS, "tse_skim_causal_short").eval()
@@ -113,6 +213,9 @@ def main():
     print(f"# tse_skim_v0_causal (C {m.input_size}, H {m.hidden_size}, K {m.seg_size}, {m.n_blocks} blocks; win {s.win_length}, "
           f"hop {s.hop_length}, latency {s.latency_samples} samples); per-call wall ms, graph replays, device sync per call; "
           f"{args.replays} calls after {args.warmup} warm-up; real-time budget {hop_ms:.1f} ms per hop")
+    if args.slots:
+        report_slots(s, args, dev, hop_ms)
+        return
     print("# 'segment end': the calls whose frames hold the last frame of a segment (the MemLSTM hand-over runs on top)")
     print(f"{'B':>6} {'hops/call':>9} {'budget':>7} {'p50':>8} {'p99':>8}  real-time | segment end: {'n':>4} {'p50':>8} {'max':>8}  "
           f"real-time")
