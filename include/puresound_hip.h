@@ -629,6 +629,29 @@ int ps_free_decode_step_slots_f32(const float* feats, const float* mask, int mas
                                   float* out, int ld_out, const int* span, const int* counter, int B, int k, int C, int win,
                                   int hop, int out_mode, float* ws, size_t ws_bytes, void* stream);
 
+/* k causal frames of the middle of ONE gated TCN block (GatedTCN, conv_tasnet.py:129-215, causal = True, eval BatchNorm1d)
+ * for B streams in one launch (puresound_amd/streaming/unet_tcn.py).  Columns, `counter` and the ring as ps_dwconv_step_f32:
+ * y, g [H][ld], column f * B + b = frame f < k of the chunk, stream b; t0 = *counter; one circular ring [R][H][B] per block,
+ * R >= (P-1)*dilation + k.  y is the output of the block's in_conv (ps_conv1x1_f32); out_conv with its residual is
+ * ps_conv1x1_f32 on g.
+ *   g[h][n] = PReLU(aff_l(L[h][n])) * sigmoid(PReLU(aff_r(Rt[h][n])))
+ *   L[h][n]  = sum_j sum_c Wl[h][c][j] y_c(t0 + f - (P-1-j)*dilation)
+ *   Rt[h][n] = the same with Wr, + sum over the taps j whose frame t0 + f - (P-1-j)*dilation is >= 0 of emb_taps[j][h][b]
+ * y_c(frame): the chunk's own column of y when the frame is >= t0, ring slot frame % R when 0 <= frame < t0, an exact 0 when
+ * frame < 0.  Every frame of the chunk is stored to its slot (t0 + f) % R; read and written slots are disjoint by the bound
+ * on R.  wl, wr: the [H][P*H] weights with column j*H + c (the row order of ps_unfold_taps_f32) in the layout of
+ * ps_conv1x1_f32's wt; the right convolution's embedding columns are NOT part of wr: the embedding e_b is constant over the
+ * frames and zero-padded with the other channels (use_film = False, conv_tasnet.py:192-196), so tap j adds the constant
+ * emb_taps[j][h][b] = Wr[h][H:, j] . e_b iff its frame exists; emb_taps [P][H][B] is computed once per session, NULL = no
+ * embedding.  pro_left / pro_right: the folded eval BatchNorm1d of each side (PS_NORM_AFFINE: gamma = scale, beta = shift, or
+ * PS_NORM_NONE) and its PReLU with one shared slope; NULL = identity.  A global norm returns PS_E_UNSUPPORTED and nothing is
+ * written.  Exact fp32 products; every output sums its P*H products in increasing (j, c) in one chain, then the embedding
+ * constants in increasing j, so a column's value does not depend on k or on how its stream's frames are split into launches.
+ * Writes g[h][n] for n < k*B only; g must not be y. */
+int ps_gated_tcn_step_f32(const float* y, float* ring, int R, const int* counter, const float* wl, const float* wr,
+                          const float* emb_taps, const ps_prologue* pro_left, const ps_prologue* pro_right, float* g, int H,
+                          int B, int k, int ld, int P, int dilation, void* stream);
+
 /* k causal frames of ONE block of the causal dual-path RNN (DPRNN with causal = True, seg_overlap = False; dprnn.py:10-191)
  * for B streams in one launch (puresound_amd/streaming/dprnn.py).  Columns as above: x, y [C][ld], column f * B + b; `counter`
  * (device int, read and never written) = the absolute index of the chunk's first frame.  Frame g = *counter + f is position

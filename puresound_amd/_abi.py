@@ -200,6 +200,8 @@ SIGNATURES = {
                                  + [C.POINTER(Prologue), _vp]),
     "ps_free_decode_step_slots_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp]
                                       + [C.c_int] * 6 + [_vp, C.c_size_t, _vp]),
+    "ps_gated_tcn_step_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.POINTER(Prologue), C.POINTER(Prologue), _vp]
+                              + [C.c_int] * 6 + [_vp]),
     "ps_dprnn_block_step_ok": (C.c_int, [C.c_int] * 3),
     "ps_dprnn_block_step_f32": (C.c_int, [_vp, _vp, _vp, C.POINTER(DprnnPass), C.POINTER(DprnnPass)] + [_vp] * 4
                                 + [C.c_int] * 7 + [_vp]),

@@ -1005,6 +1005,36 @@ def dwconv_step(x: torch.Tensor, ring: torch.Tensor, counter: torch.Tensor, w: t
     return y
 
 
+def gated_tcn_step(y: torch.Tensor, ring: torch.Tensor, counter: torch.Tensor, wl: torch.Tensor, wr: torch.Tensor,
+                   taps: int, dilation: int, streams: int, frames: int, pro_left: Optional[Prologue] = None,
+                   pro_right: Optional[Prologue] = None, emb_taps: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The two dense dilated convolutions, norms and gate of a causal GatedTCN block for `frames` new frames of `streams`
+    streams (ps_gated_tcn_step_f32): y [1, H, ld] (column f * streams + b, the output of in_conv); wl, wr = pack_wt of the
+    [H, taps * H] weights with column j * H + c; earlier frames of y from ring [R, H, streams] (slot g % R = frame g; the
+    chunk's frames are stored there too), frame index of column 0 = counter[0]; emb_taps [taps, H, streams]: what the
+    embedding adds to the right side per tap whose frame is >= 0 -> g [1, H, ld] (columns past frames * streams are not
+    written)."""
+    require_device(y, "gated_tcn_step")
+    _, h, ld = y.shape
+    kp = (taps * h + 15) // 16 * 16
+    _require_operand("gated_tcn_step", y.device, y=y, ring=ring, wl=wl, wr=wr, emb_taps=emb_taps, out=out)
+    if ring.dim() != 3 or tuple(ring.shape[1:]) != (h, streams) or counter.dtype != torch.int32 or counter.device != y.device:
+        raise RuntimeError("gated_tcn_step: ring [R, H, streams] and an int32 counter on y's device expected")
+    if tuple(wl.shape) != ((h + 255) // 256, kp, 256) or wl.shape != wr.shape:
+        raise RuntimeError(f"gated_tcn_step: wl, wr must be pack_wt of [H, taps * H] weights: {((h + 255) // 256, kp, 256)}")
+    if emb_taps is not None and tuple(emb_taps.shape) != (taps, h, streams):
+        raise RuntimeError(f"gated_tcn_step: emb_taps must be [{taps}, {h}, {streams}]")
+    g = out if out is not None else torch.zeros_like(y)
+    if g.shape != y.shape:
+        raise RuntimeError("gated_tcn_step: out must be a contiguous tensor of y's shape")
+    check(lib().ps_gated_tcn_step_f32(ptr(y), ptr(ring), ring.shape[0], ptr(counter), ptr(wl), ptr(wr), ptr(emb_taps),
+                                      C.byref(pro_left) if pro_left is not None else None,
+                                      C.byref(pro_right) if pro_right is not None else None, ptr(g), h, streams, frames, ld,
+                                      taps, dilation, stream_ptr(y.device)), "ps_gated_tcn_step_f32")
+    return g
+
+
 def free_decode_step(feats: Optional[torch.Tensor], mask: Optional[torch.Tensor], w: torch.Tensor, tail: torch.Tensor,
                      out: torch.Tensor, hop: int, frames: int = 0, mask_act: str = "linear", out_mode: str = "linear",
                      flush: bool = False, span: Optional[torch.Tensor] = None,

@@ -8,6 +8,12 @@ windows [hops, B*window])), `_flush_into(out)`; it may set `max_hops` and overri
 its own arguments, calls `_begin` and allocates what `_state` returns; `_queue` [B, window], `_tail` [B, window - hop] and
 `_counter` (int32 [1], the device frame counter) are allocated here.
 
+A model delay (unet_tcn.py): a streamer whose model looks `delay_frames` = D frames ahead passes D to the constructor.  Its
+first D computed frames run the body with `self._mute` set -- always eagerly -- and emit nothing: the body advances the model
+state and leaves the overlap-add tail, the window sum and its synthesis counter as they were.  So prime_hops and
+latency_samples grow by D hops, and flush() first lets the streamer run the hops that are still inside the model (the
+streamer's `_flush_into(out)` fills min(frames, D) * hop + window - hop samples).  D = 0: nothing of this happens.
+
 Slots (tcn.py, dprnn.py, skim.py): a session of fixed capacity whose columns begin and end streams of their own while it runs.  The
 model-independent half lives here: the device span [B, 2] of (birth, death) frame indices and the host record per slot, the
 slot checks, open / end / close, the hops each slot was fed, the frame limit, and the rules that a slot session has no
@@ -47,12 +53,15 @@ class HopSession:
     max_hops: Optional[int] = None
     _how_to_start = "call init_streams() first"
 
-    def __init__(self, model, window: int, hop: int):
+    def __init__(self, model, window: int, hop: int, delay_frames: int = 0):
         if model.training:
             raise RuntimeError(f"{type(self).__name__}: the model is in training mode -- call .eval()")
         self.model = model
         self.window, self.hop_length = int(window), int(hop)
-        self.prime_hops = self.window // self.hop_length - 1
+        self.delay_frames = int(delay_frames)
+        self._fill_hops = self.window // self.hop_length - 1      # hops that only fill the first analysis window
+        self.prime_hops = self._fill_hops + self.delay_frames     # hops for which step() returns None
+        self._mute = False
         self._mask_act = model.mask_constraint.lower()
         self._out_mode = model.output_constraint.lower()
         self.streams = None
@@ -61,18 +70,22 @@ class HopSession:
 
     @property
     def latency_samples(self) -> int:
-        """Samples between a sample entering and its value leaving: the analysis window minus one hop."""
-        return self.window - self.hop_length
+        """Samples between a sample entering and its value leaving: the analysis window minus one hop, plus the model's
+        delay_frames hops."""
+        return self.window - self.hop_length + self.delay_frames * self.hop_length
 
     @staticmethod
-    def output_length(samples: int, n_fft: int, hop: int) -> Dict[str, int]:
-        """Length bookkeeping of a stream of `samples` = k * hop input samples: priming hops, samples the steps emit, samples
-        flush() returns (their sum is the offline output length (T - 1) * hop + n_fft, T = (samples - n_fft) // hop + 1)."""
-        if samples % hop or n_fft % hop or samples < n_fft:
-            raise ValueError("output_length: whole hops, n_fft a multiple of hop, at least one window")
-        prime = n_fft // hop - 1
-        frames = samples // hop - prime
-        return dict(prime_hops=prime, frames=frames, emitted=frames * hop, flushed=n_fft - hop)
+    def output_length(samples: int, n_fft: int, hop: int, delay_frames: int = 0) -> Dict[str, int]:
+        """Length bookkeeping of a stream of `samples` = k * hop input samples: priming hops, the T frames computed, samples
+        the steps emit, samples flush() returns (their sum is the offline output length (T - 1) * hop + n_fft,
+        T = (samples - n_fft) // hop + 1).  delay_frames = D: the first D frames emit nothing, and flush() returns them."""
+        if samples % hop or n_fft % hop or samples < n_fft or delay_frames < 0:
+            raise ValueError("output_length: whole hops, n_fft a multiple of hop, at least one window, delay_frames >= 0")
+        fill = n_fft // hop - 1
+        frames = samples // hop - fill
+        held = min(frames, delay_frames)
+        return dict(prime_hops=fill + delay_frames, frames=frames, emitted=(frames - held) * hop,
+                    flushed=n_fft - hop + held * hop)
 
     # -- weights ------------------------------------------------------------------------------------------------------
     def _drop_weights(self) -> None:
@@ -134,16 +147,21 @@ class HopSession:
 
     def _priming(self) -> bool:
         """(a slot session has no priming phase: a slot's first prime_hops frames are dead by its span)"""
-        return self._slots is None and self._hops < self.prime_hops
+        return self._slots is None and self._hops < self._fill_hops
 
-    def _run_piece(self, piece: torch.Tensor) -> torch.Tensor:
-        """Whole hops of one launch -> their output samples [B, hops*hop] (graph replay or eager)."""
+    def _run_piece(self, piece: torch.Tensor, mute: bool = False) -> Optional[torch.Tensor]:
+        """Whole hops of one launch -> their output samples [B, hops*hop] (graph replay or eager); mute: frames inside the
+        model's delay, run eagerly with self._mute set -> None."""
         hops = piece.shape[1] // self.hop_length
         chunk, out, _ = self._io_for(hops)
         chunk.copy_(piece)
-        if not self._use_graph:
-            with self._around_body():
-                self._body(hops)
+        if mute or not self._use_graph:
+            self._mute = mute
+            try:
+                with self._around_body():
+                    self._body(hops)
+            finally:
+                self._mute = False
         else:
             g = self._graphs.get(hops)
             if g is None:
@@ -151,7 +169,7 @@ class HopSession:
             g.replay()
         self._hops += hops
         self.frames += hops
-        return out.clone()
+        return None if mute else out.clone()
 
     def _run(self, chunk: torch.Tensor) -> torch.Tensor:
         """Whole hops past the priming -> their output samples, in pieces of at most max_hops hops.  In a slot session: the
@@ -163,7 +181,12 @@ class HopSession:
                                f"init_slots() for a new session")
         self._ready()
         step = self.max_hops * self.hop_length if self.max_hops else chunk.shape[1]
-        outs = [self._run_piece(chunk[:, i:i + step]) for i in range(0, chunk.shape[1], step)]
+        quiet = min(k, max(self.delay_frames - self.frames, 0)) * self.hop_length   # frames inside the model's delay
+        for i in range(0, quiet, step):
+            self._run_piece(chunk[:, i:min(i + step, quiet)], mute=True)
+        outs = [self._run_piece(chunk[:, i:i + step]) for i in range(quiet, chunk.shape[1], step)]
+        if not outs:
+            return chunk.new_zeros(self.streams, 0)
         for st in self._slots or ():
             if st is not None:
                 st["hops"] = st["hops"] + k if st["total"] is None else min(st["hops"] + k, st["total"])
@@ -190,13 +213,14 @@ class HopSession:
     @torch.no_grad()
     def step(self, hop: torch.Tensor) -> Optional[torch.Tensor]:
         """hop [B, hop_length] new samples per stream -> [B, hop_length] output samples, or None while the first analysis
-        window fills (the first window / hop - 1 hops)."""
+        window fills and the model's delay passes (the first prime_hops = window / hop - 1 + delay_frames hops)."""
         if self._check_input(hop, "step") != 1:
             raise ValueError(f"{type(self).__name__}.step: one hop of {self.hop_length} samples per stream")
         if self._priming():
             self._prime(hop)
             return None
-        return self._run(hop)
+        out = self._run(hop)
+        return out if out.shape[1] else None
 
     @torch.no_grad()
     def step_chunk(self, chunk: torch.Tensor) -> torch.Tensor:
@@ -212,7 +236,8 @@ class HopSession:
 
     @torch.no_grad()
     def flush(self) -> torch.Tensor:
-        """The last window - hop_length samples of every stream ([B, window - hop_length]); the streams are then finished."""
+        """The last latency_samples samples of every stream ([B, window - hop_length + delay_frames * hop_length]; a stream of
+        T < delay_frames frames has T hops in place of the delay's); the streams are then finished."""
         name = f"{type(self).__name__}.flush"
         if self._slots is not None:
             raise RuntimeError(f"{name}: a slot session ends its streams one by one: close(slot) returns a slot's last samples")
@@ -221,7 +246,8 @@ class HopSession:
         if self.frames == 0:
             raise RuntimeError(f"{name}: no complete frame yet (a stream needs {self.window} samples)")
         self._ready()
-        out = torch.empty(self.streams, self.window - self.hop_length, dtype=torch.float32, device=self.device)
+        held = min(self.frames, self.delay_frames) * self.hop_length
+        out = torch.empty(self.streams, held + self.window - self.hop_length, dtype=torch.float32, device=self.device)
         self._flush_into(out)
         self._finished = True
         return out
