@@ -905,7 +905,9 @@ int ps_conv1x1_f16x2_ln_f32(const float* x, const void* wt_planes, const ps_f16x
 int ps_absmax_parts(void);
 int ps_absmax_f32(const float* x, float* amax, int N, int C, int T, int ldt, void* stream);
 
-/* bytes of scratch ps_conv_tasnet_f32 needs for a batch (3 hidden maps + stats + embed bias) */
+/* bytes of scratch ps_conv_tasnet_f32 needs for a batch (3 hidden maps + stats + embed bias + range maxima).  The
+ * workspace need not be initialised, and it may have been used at any other shape before: every word a launch reads, a
+ * launch of the same call has written.  It may be larger than this; it must not be shared by calls on two streams at once. */
 size_t ps_conv_tasnet_workspace_bytes(int N, int C, int H, int T);
 
 /* x_in [N][C][ldt] is read only; x_out [N][C][ldt] receives the mask logits (pre-constraint).

@@ -188,29 +188,38 @@ def _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip=True):
     return hip.chan_layernorm(p, t, norm["gamma"], norm["beta"], norm["eps"], res=res)
 
 
-def _h_rows(rnn: dict, x: torch.Tensor, t: int, q: int, steps: int):
+def _h_rows(rnn: dict, x: torch.Tensor, t: int, q: int, q_stride: int, steps: int, step_stride: int, lane: int = 0):
     """Output rows of a recurrence.  When the sequences do not cover the span of t frames (the 2-D maps of DPCRN / DPARN:
     F rows of ld frames, pad frames between them) the recurrence never writes the pad frames, and what follows it --
     projection, LayerNorm, the next GEMM's range maximum -- runs over the whole span: the rows then come from a zeroed
-    buffer kept with the plan (pads stay zero from call to call), so stale memory (a NaN, an Inf) cannot reach the maximum.
-    None = let the kernel wrapper allocate (every frame is written)."""
+    buffer kept with the plan, so stale memory (a NaN, an Inf) cannot reach the maximum.  One buffer per `lane` (the
+    caller's concurrent HIP streams must not write the same rows).  The pads stay zero from call to call as long as the
+    recurrence writes the same frames: when the sequence geometry changes (another utterance length inside one row
+    length: frames the longer call wrote are pad frames of the shorter one) the kept buffer is cleared on the current
+    stream, and only a change of its shape allocates a new one.  None = let the kernel wrapper allocate (every frame is
+    written)."""
     if q * steps >= t:
         return None
     n, _, ldt = x.shape
-    key = (n, ldt, x.device)
+    shape = (n, rnn["D"] * rnn["H"], ldt)
+    geometry = (t, q, q_stride, steps, step_stride)
     bufs = rnn.setdefault("h_rows", {})
-    if key not in bufs:
-        bufs.clear()
-        bufs[key] = torch.zeros(n, rnn["D"] * rnn["H"], ldt, dtype=torch.float32, device=x.device)
-    return bufs[key]
+    kept = bufs.get(lane)
+    if kept is None or tuple(kept[1].shape) != shape or kept[1].device != x.device:
+        bufs[lane] = kept = (geometry, torch.zeros(shape, dtype=torch.float32, device=x.device))
+    elif kept[0] != geometry:
+        kept[1].zero_()
+        bufs[lane] = kept = (geometry, kept[1])
+    return kept[1]
 
 
 def lstm_path(x: torch.Tensor, t: int, rnn: dict, proj: dict, norm: dict, q: int, q_stride: int, steps: int,
               step_stride: int, h0=None, c0=None, want_state: bool = False, state_shift: int = 0, state_out=None,
-              amax: Optional[list] = None, skip: bool = True):
+              amax: Optional[list] = None, skip: bool = True, lane: int = 0):
     """x + LN(proj(LSTM(x))) on padded [N,C,ldt] (dprnn.py:154-172, skim.py:215-227) -> (x', final states).
     `amax`: a one-element list carried from recurrence to recurrence in the fp16x2 arithmetic -- on entry the partial maxima
-    of |x| per utterance (or None: measured here), on return those of x' (None when the kernel that made x' has none)."""
+    of |x| per utterance (or None: measured here), on return those of x' (None when the kernel that made x' has none).
+    `lane`: which of the caller's concurrent HIP streams this is (selects the kept output rows, see _h_rows)."""
     n, _, ldt = x.shape
     dev = x.device
     planes = rnn["planes"]
@@ -229,7 +238,7 @@ def lstm_path(x: torch.Tensor, t: int, rnn: dict, proj: dict, norm: dict, q: int
             gx_fm = hip.conv1x1_f16x2_fmajor(x, t, wf, we, rnn["rows"], rnn["bias"],
                                              x_amax=x_amax if x_amax is not None else hip.absmax(x, t))
             hseq = hip.lstm_fmajor(gx_fm, rnn["whh_t"], rnn["H"], rnn["D"], q, q_stride, steps, step_stride,
-                                   out=_h_rows(rnn, x, t, q, steps))
+                                   out=_h_rows(rnn, x, t, q, q_stride, steps, step_stride, lane))
             return _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip), None
         # H = 256 (SkiM's segment LSTMs): W_hh streamed from L2 in fragment order, states carried (ps_lstm_fmajor_h256_f16x2_f32)
         if (FMAJOR_LSTM and rnn["H"] in (256, 192) and hip.lstm_fmajor_h256_ok(n, ldt, rnn["D"], q, q_stride, steps, step_stride)
@@ -240,7 +249,7 @@ def lstm_path(x: torch.Tensor, t: int, rnn: dict, proj: dict, norm: dict, q: int
                                              x_amax=x_amax if x_amax is not None else hip.absmax(x, t))
             hseq, state = hip.lstm_fmajor_h256(gx_fm, rnn["whh_h256"][0], rnn["whh_h256"][1], rnn["D"], q, q_stride, steps,
                                                step_stride, h0, c0, want_state, state_shift, state_out,
-                                               out=_h_rows(rnn, x, t, q, steps))
+                                               out=_h_rows(rnn, x, t, q, q_stride, steps, step_stride, lane))
             return _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip), state
         gx = torch.empty(n, rnn["rows"], ldt, dtype=torch.float32, device=dev)
         hip.conv1x1_f16x2(x, t, wf, we, rnn["rows"], None, rnn["bias"], out=gx,
@@ -255,5 +264,6 @@ def lstm_path(x: torch.Tensor, t: int, rnn: dict, proj: dict, norm: dict, q: int
         gx = torch.empty(n, rnn["rows"], ldt, dtype=torch.float32, device=dev)
         hip.conv1x1(x, t, rnn["wih"], rnn["rows"], None, rnn["bias"], out=gx)
     hseq, state = hip.lstm(gx, rnn["whh_t"], rnn["H"], rnn["D"], q, q_stride, steps, step_stride, h0, c0, want_state,
-                           state_shift, state_out, f16x2=rnn["planes"] == 2, out=_h_rows(rnn, x, t, q, steps))
+                           state_shift, state_out, f16x2=rnn["planes"] == 2,
+                           out=_h_rows(rnn, x, t, q, q_stride, steps, step_stride, lane))
     return _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip), state

@@ -391,10 +391,12 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         return enh_wav, hip.align_reference(ref_wav, enh_wav.shape[-1])
 
     # -- speaker branch (base_nn.py:697-705, 724-738) ---------------------------------------------------
-    def _speaker_embedding_from_feats(self, x: torch.Tensor, t: int, x_amax: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _speaker_embedding_from_feats(self, x: torch.Tensor, t: int, x_amax: Optional[torch.Tensor] = None,
+                                      lane: int = 0) -> torch.Tensor:
         """speaker_net layer by layer on padded enrolment features (base_nn.py:697-705): Magnitude, TCN (consecutive
         plain blocks go through the fused driver together), GatedTCN, AttentiveStatisticsPooling, then the k=1
-        projection conv(s) on the pooled vector -> dvec [N, E]."""
+        projection conv(s) on the pooled vector -> dvec [N, E].  `lane` selects the fused driver's kept scratch: one
+        buffer per concurrent HIP stream of inference(), as ConvTasNet._workspace."""
         layers = list(self.speaker_net) if isinstance(self.speaker_net, (nn.ModuleList, nn.Sequential)) else None
         if layers is None:
             raise NotImplementedError("HIP speaker branch: speaker_net must be a ModuleList / Sequential")
@@ -427,9 +429,12 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
                     # (x_amax: a bound on the features for fp16x2 blocks -- without one the driver measures them: 93 us)
                     # the driver's scratch (three hidden maps: 415 MB at 32 x 4 s) is kept, not re-allocated and
                     # zero-filled per call as hip.conv_tasnet does for callers without one
-                    ws = hip.conv_tasnet_workspace(x.shape[0], run[0].in_channels, run[0].hid_channels, t, x.device,
-                                                   self.__dict__.get("_spk_workspace"))
-                    object.__setattr__(self, "_spk_workspace", ws)
+                    kept = self.__dict__.get("_spk_workspace")
+                    if kept is None:
+                        kept = {}
+                        object.__setattr__(self, "_spk_workspace", kept)
+                    ws = kept[lane] = hip.conv_tasnet_workspace(x.shape[0], run[0].in_channels, run[0].hid_channels, t,
+                                                                x.device, kept.get(lane))
                     x = hip.conv_tasnet(blocks, len(plans), x, t, run[0].in_channels, run[0].hid_channels, None, False,
                                         workspace=ws, x_amax=x_amax, bf16_rows=all(p["rows_bf16"] for p in plans))
                 else:
@@ -452,7 +457,7 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
 
     def _speaker_embedding(self, enroll: torch.Tensor, lane: int = 0) -> torch.Tensor:
         """enroll [N,L'] -> dvec [N,E]; the enrolment goes through encoder_spk when there is one, else through the
-        shared encoder (base_nn.py:347-375)."""
+        shared encoder (base_nn.py:347-375).  `lane`: the HIP stream lane of inference() this call runs in."""
         enc = self.encoder_spk if self.encoder_spk is not None else self.encoder
         if isinstance(enc, ConvEncDec):
             x, t = enc.encoder.encode_padded(enroll, self.drop_first_bin)
@@ -461,7 +466,7 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         else:
             raise NotImplementedError(f"HIP speaker branch: no kernel path for a {type(enc).__name__} enrolment encoder")
         bound = enc.feature_bound(enroll) if isinstance(enc, FreeEncDec) else None
-        return self._speaker_embedding_from_feats(x, t, bound)
+        return self._speaker_embedding_from_feats(x, t, bound, lane)
 
     @torch.no_grad()
     def inference_tse_embedding(self, enroll: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -35,7 +35,8 @@ class DPARNblock2D(PlanCache, nn.Module):
                     inter=(lstm_plan(self.inter_rnn.rnn, device, self.gemm_precision), linear_plan(self.inter_rnn.proj, device),
                            layernorm_plan(self.inter_norm, device)))
 
-    def forward_padded(self, x: torch.Tensor, t: int, amax=None, intra_skip: bool = True, inter_skip: bool = True) -> torch.Tensor:
+    def forward_padded(self, x: torch.Tensor, t: int, amax=None, intra_skip: bool = True, inter_skip: bool = True,
+                       lane: int = 0) -> torch.Tensor:
         """[N, CH, F, ld] -> [N, CH, F, ld].  amax: lstm_path's one-element list (fp16x2 arithmetic: the maxima of |x| travel
         from block to block)."""
         p = self._plan_get(x.device, self._build)
@@ -59,7 +60,7 @@ class DPARNblock2D(PlanCache, nn.Module):
         else:
             y, _ = hip.proj_layernorm(a, frames, p["fc"]["wt"], p["fc"]["bias"], ch, fn["gamma"], fn["beta"], fn["eps"],
                                       y if intra_skip else None)
-        y, _ = lstm_path(y, frames, *p["inter"], q=f, q_stride=ld, steps=t, step_stride=1, amax=amax, skip=inter_skip)
+        y, _ = lstm_path(y, frames, *p["inter"], q=f, q_stride=ld, steps=t, step_stride=1, amax=amax, skip=inter_skip, lane=lane)
         return y.view(n, ch, f, ld)
 
     def forward_step(self, x: torch.Tensor, b: int, h0: torch.Tensor, c0: torch.Tensor, state_out: tuple) -> torch.Tensor:
@@ -106,14 +107,14 @@ class DPARN(Unet):
         self.dprnn_block1 = DPARNblock2D(input_size=channels[-1], hidden_size=rnn_hidden, nhead=nhead, dropout=dropout)
         self.dprnn_block2 = DPARNblock2D(input_size=channels[-1], hidden_size=rnn_hidden, nhead=nhead, dropout=dropout)
 
-    def forward_padded4(self, x4: torch.Tensor, t: int, dvec=None) -> torch.Tensor:
+    def forward_padded4(self, x4: torch.Tensor, t: int, dvec=None, lane: int = 0) -> torch.Tensor:
         if self.spectral_compress:
             raise NotImplementedError("DPARN on HIP: spectral_compress (it returns a complex tensor in the reference)")
         p = self._plan_get(x4.device, self._build_unet)
         skip = self._down(x4, t, p)
         amax = [None]
-        y = self.dprnn_block1.forward_padded(skip[-1], t, amax)
-        y = self.dprnn_block2.forward_padded(y, t, amax)
+        y = self.dprnn_block1.forward_padded(skip[-1], t, amax, lane=lane)
+        y = self.dprnn_block2.forward_padded(y, t, amax, lane=lane)
         return self._up(y, skip, t, p, self.transpose_delay)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -34,7 +34,8 @@ class DPRNNblock2D(PlanCache, nn.Module):
                     inter=(lstm_plan(self.inter_rnn.rnn, device, self.gemm_precision), linear_plan(self.inter_rnn.proj, device),
                            layernorm_plan(self.inter_norm, device)))
 
-    def forward_padded(self, x: torch.Tensor, t: int, amax=None, intra_skip: bool = True, inter_skip: bool = True) -> torch.Tensor:
+    def forward_padded(self, x: torch.Tensor, t: int, amax=None, intra_skip: bool = True, inter_skip: bool = True,
+                       lane: int = 0) -> torch.Tensor:
         """[N, CH, F, ld] -> [N, CH, F, ld].  amax: the one-element list of lstm_path (fp16x2 arithmetic: the maxima of |x|
         travel from recurrence to recurrence and from block to block instead of being measured before every GEMM)."""
         p = self._plan_get(x.device, self._build)
@@ -42,8 +43,8 @@ class DPRNNblock2D(PlanCache, nn.Module):
         y = x.view(n, ch, f * ld)
         frames = (f - 1) * ld + t                      # frames of the flattened (f, t) axis that hold data
         amax = [None] if amax is None else amax
-        y, _ = lstm_path(y, frames, *p["intra"], q=t, q_stride=1, steps=f, step_stride=ld, amax=amax, skip=intra_skip)
-        y, _ = lstm_path(y, frames, *p["inter"], q=f, q_stride=ld, steps=t, step_stride=1, amax=amax, skip=inter_skip)
+        y, _ = lstm_path(y, frames, *p["intra"], q=t, q_stride=1, steps=f, step_stride=ld, amax=amax, skip=intra_skip, lane=lane)
+        y, _ = lstm_path(y, frames, *p["inter"], q=f, q_stride=ld, steps=t, step_stride=1, amax=amax, skip=inter_skip, lane=lane)
         return y.view(n, ch, f, ld)
 
     def forward_step(self, x: torch.Tensor, b: int, h0: torch.Tensor, c0: torch.Tensor, state_out: tuple) -> torch.Tensor:
@@ -87,15 +88,15 @@ class DPCRN(Unet):
         self.dprnn_block1 = DPRNNblock2D(input_size=channels[-1], hidden_size=rnn_hidden, dropout=dropout)
         self.dprnn_block2 = DPRNNblock2D(input_size=channels[-1], hidden_size=rnn_hidden, dropout=dropout)
 
-    def forward_padded4(self, x4: torch.Tensor, t: int, dvec=None) -> torch.Tensor:
+    def forward_padded4(self, x4: torch.Tensor, t: int, dvec=None, lane: int = 0) -> torch.Tensor:
         """[N, CH0, F, ld] -> [N, CH0, F, ld]."""
         if self.spectral_compress:
             raise NotImplementedError("DPCRN on HIP: spectral_compress (it returns a complex tensor in the reference)")
         p = self._plan_get(x4.device, self._build_unet)
         skip = self._down(x4, t, p)
         amax = [None]
-        y = self.dprnn_block1.forward_padded(skip[-1], t, amax)
-        y = self.dprnn_block2.forward_padded(y, t, amax)
+        y = self.dprnn_block1.forward_padded(skip[-1], t, amax, lane=lane)
+        y = self.dprnn_block2.forward_padded(y, t, amax, lane=lane)
         return self._up(y, skip, t, p, self.transpose_delay)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -305,7 +305,7 @@ class Unet(PlanCache, nn.Module):
         ch0 = 2 if self.input_type.lower() == "ri" else 1
         return x_pad.view(n, ch0, c // ch0, ld)
 
-    def forward_padded4(self, x4: torch.Tensor, t: int, dvec: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward_padded4(self, x4: torch.Tensor, t: int, dvec: Optional[torch.Tensor] = None, lane: int = 0) -> torch.Tensor:
         p = self._plan_get(x4.device, self._build_unet)
         skip = self._down(x4, t, p)
         return self._up(skip[-1], skip, t, p, False)
@@ -315,7 +315,7 @@ class Unet(PlanCache, nn.Module):
         """Wrapper entry: padded [N, C, ld] -> padded [N, C, ld] (RI halves are the two CH0 planes: no data moves)."""
         if self.multi_output != 1:
             raise NotImplementedError("multi_output U-Net behind the single-output wrapper")
-        y = self.forward_padded4(self._rows4(x_pad), t, dvec)
+        y = self.forward_padded4(self._rows4(x_pad), t, dvec, lane)   # (lane: the recurrent bottlenecks keep rows per lane)
         return y.reshape(y.shape[0], -1, y.shape[3])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -406,7 +406,7 @@ class UnetTcn(Unet):
             y = m.forward_padded(y, t, e) if isinstance(m, GatedTCN) else m.forward_padded_staged(y, t, e)
         return y
 
-    def forward_padded4(self, x4: torch.Tensor, t: int, dvec: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward_padded4(self, x4: torch.Tensor, t: int, dvec: Optional[torch.Tensor] = None, lane: int = 0) -> torch.Tensor:
         p = self._plan_get(x4.device, self._build_unet)
         skip = self._down(x4, t, p)
         n, ch, f, ld = skip[-1].shape

@@ -378,7 +378,8 @@ def test_tse_wrapper_matches_reference_golden(PA, dev, golden_dir):
     mask = model.masker.forward_padded(feats, t, dvec[..., 0])
     pre = model.encoder.decode_padded(feats, t, mask, "relu", "none")
     assert rel_max(pre.cpu().numpy(), g["wav_preclamp"]) < TOL
-    # enrolment of a different length than the mixture, and a 4-utterance batch over two streams
+    # enrolment of a different length than the mixture, and a 4-utterance batch: one lane whatever hip_streams says (the
+    # split starts at 16 utterances; tests/test_scratch_state_gpu.py runs two lanes)
     n4 = det_wave(5, 4, 4000)
     e4 = det_wave(6, 4, 2500)
     ref4 = O.inference(n4, sd, cases.oracle_cfg(name), e4)

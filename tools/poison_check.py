@@ -1,7 +1,12 @@
 """Uninitialised-memory check at the benchmark's batch (GPU box): the caching allocator is filled with NaN blocks of the sizes
-a 32 x 4 s forward allocates (maps, workspaces, partial-statistics slots), released, and the forward must return the bits
-of a clean run.  tests/test_hip_parity.py::test_results_do_not_depend_on_uninitialised_memory does this at the fixtures'
-batch of 2, where other kernel variants run.   python tools/poison_check.py [preset ...]"""
+a 32 x 4 s forward allocates (maps, partial-statistics slots, outputs), released, and the forward must return the bits of a
+clean run.  NaN in the allocator reaches `torch.empty` memory only.  The scratch a model KEEPS from call to call -- the fused
+masker driver's workspaces, ConvTasNet._workspace[lane] and the wrapper's _spk_workspace[lane] -- is zero-filled when it
+is created, and the clean reference call creates it before anything is poisoned: so every kept workspace is overwritten
+with 0xFF bytes (NaN as fp32 and as fp64) as well.  (The zeroed LSTM output rows of DPCRN / DPARN are left alone: their
+pad frames are zero by contract, _plans._h_rows.)  tests/test_hip_parity.py::
+test_results_do_not_depend_on_uninitialised_memory and tests/test_scratch_state_gpu.py do this at the fixtures' batch of 2,
+where other kernel variants run.   python tools/poison_check.py [preset ...]"""
 import json
 import os
 import sys
@@ -29,6 +34,15 @@ def poison(dev):
     del junk
 
 
+def kept_workspaces(model):
+    """every fused-driver workspace the model holds on to (uint8 tensors)"""
+    kept = list((model.__dict__.get("_spk_workspace") or {}).values())
+    for m in model.modules():
+        if isinstance(m, PA.ConvTasNet) and m._workspace:
+            kept += list(m._workspace.values())
+    return kept
+
+
 def main():
     dev = "cuda:0"
     g = torch.Generator().manual_seed(1234)
@@ -48,11 +62,15 @@ def main():
             res = []
             for _ in range(3):
                 poison(dev)
+                dirtied = kept_workspaces(model)
+                for ws in dirtied:
+                    ws.fill_(0xFF)
                 y = model.inference(*args)
                 res.append((bool(torch.isfinite(y).all()), bool(torch.equal(y, ref))))
             ok = all(f and e for f, e in res)
             bad += not ok
-            print(json.dumps({"preset": name, "arithmetic": prec, "finite_and_equal_after_poison": res, "ok": ok}), flush=True)
+            print(json.dumps({"preset": name, "arithmetic": prec, "kept_workspaces_dirtied": len(dirtied),
+                              "finite_and_equal_after_poison": res, "ok": ok}), flush=True)
         del model
         torch.cuda.empty_cache()
     sys.exit(1 if bad else 0)
