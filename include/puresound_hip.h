@@ -586,6 +586,33 @@ int ps_istft_step_f32(const float* frames, int ldf, const float* window, float* 
                       const int* counter, int B, int n_fft, int hop, int out_mode, int flush, void* stream);
 int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs, int* counter, void* stream);
 
+/* Slots for the conv-STFT streamers (puresound_amd/streaming/unet_tcn.py): streams that begin and end on their own while the
+ * session runs.  span [B][2] (device int, 8-byte aligned) is the (birth, death) of ps_dwconv_step_slots_f32 below: frame g of
+ * stream b is LIVE iff span[b][0] <= g < span[b][1], an idle column has an empty span, and a column may hold anything while
+ * it is not live (inf / NaN included): every gate is a select, never a product.  A NULL or misaligned span, a NULL counter
+ * or shift < 0 is PS_E_INVALID before any launch.  A tensor whose layer runs `shift` frames behind the hop (up layer j of a
+ * U-Net with transpose_delay: shift = j) is read with that shift, so liveness needs no state of its own.
+ * ps_conv2d_step_slots_f32: ps_conv2d_step_f32 with t = *counter, where the "current" tensors x1 / x2 are frame t - shift of
+ *   their sources and the tap d frames back (ring slot R - d) is frame g = t - shift - d.  A tap contributes iff g is live
+ *   in its stream and an exact 0 otherwise -- both sources, the current tensors and the rings.  Bias, activation, the store
+ *   and the order of every sum are ps_conv2d_step_f32's: with span = (0, INT32_MAX) and zeroed rings the result is
+ *   bit-identical to it.  The rings need no clearing when a stream begins.
+ * ps_istft_step_slots_f32: ps_istft_step_f32 where stream b synthesises its own frame u_b = *counter - shift - span[b][0] of
+ *   T_b = span[b][1] - span[b][0] (no int overflow).  flush = 0: the frame adds frames * window / n_fft iff 0 <= u_b < T_b;
+ *   in every case out[b][j] = constrain( acc[j] / S ) for j < hop and the tail shifts, with S(u_b*hop + j) over the frames
+ *   0 <= u <= min(g/hop, T_b - 1) in the same order (none for u_b < 0, where out = constrain(tail)): a stream drains its tail
+ *   after its death with the normalisation its flush would use, an idle column emits constrain(0).  flush = 1: n_fft - hop
+ *   samples from the tail at base u_b*hop, frames up to T_b - 1, the tail left as it is; a session flushes one stream with
+ *   B = 1 on that stream's tail row and span row.  With span = (0, INT32_MAX) and shift = 0, step and flush are
+ *   bit-identical to ps_istft_step_f32. */
+int ps_conv2d_step_slots_f32(const float* x1, const float* ring1, int C1, int R1, const float* x2, const float* ring2, int C2,
+                             int R2, const float* wt, const float* bias, float* y, int M, int Fin, int B, int ld, int kf, int kt,
+                             int stride_f, int dil_f, int dil_t, int pad_f, int Fout, int transposed, int act,
+                             const float* slope, const int* counter, const int* span, int shift, void* stream);
+int ps_istft_step_slots_f32(const float* frames, int ldf, const float* window, float* tail, float* out, int ld_out,
+                            const int* counter, const int* span, int shift, int B, int n_fft, int hop, int out_mode, int flush,
+                            void* stream);
+
 /* k causal frames of the time-domain Conv-TasNet (FreeEncDec + causal ConvTasNet) for B streams at once
  * (puresound_amd/streaming/tcn.py).  Column n = f * B + b of a [C][ld] row tensor is frame f < k of the chunk, stream b < B;
  * `counter` is a device int = the absolute index t0 of the chunk's first frame, advanced by ps_stream_commit_frames_f32, so
@@ -647,10 +674,23 @@ int ps_free_decode_step_slots_f32(const float* feats, const float* mask, int mas
  * PS_NORM_NONE) and its PReLU with one shared slope; NULL = identity.  A global norm returns PS_E_UNSUPPORTED and nothing is
  * written.  Exact fp32 products; every output sums its P*H products in increasing (j, c) in one chain, then the embedding
  * constants in increasing j, so a column's value does not depend on k or on how its stream's frames are split into launches.
- * Writes g[h][n] for n < k*B only; g must not be y. */
+ * Writes g[h][n] for n < k*B only; g must not be y.
+ *
+ * Slots: ps_gated_tcn_step_slots_f32 is ps_gated_tcn_step_f32 with span [B][2] (device int, 8-byte aligned; the (birth, death)
+ * of ps_dwconv_step_slots_f32) after `counter`.  y_c(frame) is read, from the chunk or from ring slot frame % R, iff the frame
+ * is live in its stream (span[b][0] <= frame < span[b][1]) and is an exact 0 otherwise -- a select, the column may hold
+ * inf / NaN while it is not live -- and emb_taps[j][h][b] is added iff tap j's frame is live (in place of "frame >= 0").
+ * Every frame of the chunk is still stored to its ring slot and ring slots of dead frames are never read, so the ring needs
+ * no clearing when a stream begins.  Sums in the same orders: bit-identical for k = 1 / 3 / 16, and with span =
+ * (0, INT32_MAX) for every stream bit-identical to ps_gated_tcn_step_f32.  The same checks and return codes; a NULL or
+ * misaligned span is PS_E_INVALID before any launch. */
 int ps_gated_tcn_step_f32(const float* y, float* ring, int R, const int* counter, const float* wl, const float* wr,
                           const float* emb_taps, const ps_prologue* pro_left, const ps_prologue* pro_right, float* g, int H,
                           int B, int k, int ld, int P, int dilation, void* stream);
+int ps_gated_tcn_step_slots_f32(const float* y, float* ring, int R, const int* counter, const int* span, const float* wl,
+                                const float* wr, const float* emb_taps, const ps_prologue* pro_left,
+                                const ps_prologue* pro_right, float* g, int H, int B, int k, int ld, int P, int dilation,
+                                void* stream);
 
 /* k causal frames of ONE block of the causal dual-path RNN (DPRNN with causal = True, seg_overlap = False; dprnn.py:10-191)
  * for B streams in one launch (puresound_amd/streaming/dprnn.py).  Columns as above: x, y [C][ld], column f * B + b; `counter`

@@ -192,6 +192,9 @@ SIGNATURES = {
                            + [_vp, _vp]),
     "ps_istft_step_f32": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp] + [C.c_int] * 5 + [_vp]),
     "ps_stream_commit_f32": (C.c_int, [C.POINTER(RingPair), C.c_int, _vp, _vp]),
+    "ps_conv2d_step_slots_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]
+                                 + [C.c_int] * 13 + [_vp, _vp, _vp, C.c_int, _vp]),
+    "ps_istft_step_slots_f32": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp] + [C.c_int] * 6 + [_vp]),
     "ps_dwconv_step_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp] + [C.c_int] * 6 + [C.POINTER(Prologue), _vp]),
     "ps_free_decode_step_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "ps_free_decode_step_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp] + [C.c_int] * 8 + [_vp, C.c_size_t, _vp]),
@@ -202,6 +205,8 @@ SIGNATURES = {
                                       + [C.c_int] * 6 + [_vp, C.c_size_t, _vp]),
     "ps_gated_tcn_step_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.POINTER(Prologue), C.POINTER(Prologue), _vp]
                               + [C.c_int] * 6 + [_vp]),
+    "ps_gated_tcn_step_slots_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.POINTER(Prologue),
+                                              C.POINTER(Prologue), _vp] + [C.c_int] * 6 + [_vp]),
     "ps_dprnn_block_step_ok": (C.c_int, [C.c_int] * 3),
     "ps_dprnn_block_step_f32": (C.c_int, [_vp, _vp, _vp, C.POINTER(DprnnPass), C.POINTER(DprnnPass)] + [_vp] * 4
                                 + [C.c_int] * 7 + [_vp]),

@@ -45,8 +45,21 @@ __device__ __forceinline__ float gated_step_act(float v, const float* sc, const 
 constexpr int GT_TN = 64;   // columns per workgroup
 constexpr int GT_KC = 64;   // K slice staged in LDS: 12 slices at K = 768, each one round of global loads and two barriers
 
-template <int TM>
-__global__ __launch_bounds__(256) void gated_tcn_step_kernel(GatedStepArgs a) {
+// SLOTS (ps_gated_tcn_step_slots_f32): "frame g exists" is span[b][0] <= g < span[b][1] instead of g >= 0, for the chunk's
+// own columns as for the ring and for the embedding's tap constants.  A ring slot that a dead frame owns may hold anything
+// (every frame of the chunk is stored, and nothing clears the ring when a stream begins): every read is gated, and the gate
+// selects an exact 0.  The gate is a compile-time variant of the kernel (template <bool SLOTS>): the kernels the entry without
+// a span launches are the code they were.
+// Extra: nothing, or (const int* span) when SLOTS -- a trailing pack, so that the instantiation without a span has the kernel
+// arguments it always had.
+template <int TM, bool SLOTS, typename... Extra>
+__global__ __launch_bounds__(256) void gated_tcn_step_kernel(GatedStepArgs a, Extra... extra) {
+  static_assert(sizeof...(Extra) == (SLOTS ? 1 : 0), "SLOTS: span");
+  const int* span = nullptr;
+  if constexpr (SLOTS) {
+    const int* const ex[] = {extra...};
+    span = ex[0];
+  }
   constexpr int RM = TM / 16;   // output channels per thread and side
   __shared__ float Wl[GT_KC][TM];
   __shared__ float Wr[GT_KC][TM];
@@ -62,6 +75,14 @@ __global__ __launch_bounds__(256) void gated_tcn_step_kernel(GatedStepArgs a) {
   const int ng = n0 + gn;
   const bool nvalid = ng < N;
   const int gf = nvalid ? ng / a.B : 0, gb = nvalid ? ng - gf * a.B : 0;
+  int lo = 0, hi = 0;   // SLOTS: the span of the stream this thread gathers
+  if constexpr (SLOTS) {
+    if (nvalid) {
+      const int2 sp = reinterpret_cast<const int2*>(span)[gb];
+      lo = sp.x > 0 ? sp.x : 0;   // (a ring slot index is never taken from a negative frame)
+      hi = sp.y;
+    }
+  }
 
   // weights: a packed tile holds 256 output channels; TM divides 256, so a tile never straddles two of them
   const size_t woff = (size_t)(m0 / 256) * a.Kp * 256 + (m0 % 256);
@@ -95,7 +116,10 @@ __global__ __launch_bounds__(256) void gated_tcn_step_kernel(GatedStepArgs a) {
       const int fs = gf - (a.P - 1 - j) * a.dilation;
       const int gfr = t0 + fs;
       const bool own = fs >= 0;
-      yok[u] = nvalid && kx < a.K && (own || gfr >= 0);
+      if constexpr (SLOTS)
+        yok[u] = nvalid && kx < a.K && gfr >= lo && gfr < hi;
+      else
+        yok[u] = nvalid && kx < a.K && (own || gfr >= 0);
       const float* src = own ? a.y : a.ring;
       size_t off = own ? (size_t)c * a.ld + (size_t)fs * a.B + gb : (size_t)(gfr % a.R) * slab + (size_t)c * a.B + gb;
       if (!yok[u]) src = a.y, off = 0;
@@ -140,9 +164,20 @@ __global__ __launch_bounds__(256) void gated_tcn_step_kernel(GatedStepArgs a) {
       if (n >= N) continue;
       const int f = n / a.B, b = n - f * a.B;
       float r = accr[i][j];
-      if (a.emb)
-        for (int q = 0; q < a.P; ++q)
-          if (t0 + f - (a.P - 1 - q) * a.dilation >= 0) r += a.emb[((size_t)q * a.H + h) * a.B + b];
+      if constexpr (SLOTS) {
+        if (a.emb) {
+          const int2 sp = reinterpret_cast<const int2*>(span)[b];
+          const int elo = sp.x > 0 ? sp.x : 0;   // (the gather's gate: no frame below 0 exists, whatever the birth)
+          for (int q = 0; q < a.P; ++q) {
+            const int fr = t0 + f - (a.P - 1 - q) * a.dilation;
+            if (fr >= elo && fr < sp.y) r += a.emb[((size_t)q * a.H + h) * a.B + b];
+          }
+        }
+      } else {
+        if (a.emb)
+          for (int q = 0; q < a.P; ++q)
+            if (t0 + f - (a.P - 1 - q) * a.dilation >= 0) r += a.emb[((size_t)q * a.H + h) * a.B + b];
+      }
       const float lv = gated_step_act(accl[i][j], a.sc_l, a.sh_l, a.slope_l, h);
       const float rv = gated_step_act(r, a.sc_r, a.sh_r, a.slope_r, h);
       a.g[(size_t)h * a.ld + n] = lv * (1.f / (1.f + expf(-rv)));
@@ -182,14 +217,19 @@ static int gated_side(const char* who, const char* side, const ps_prologue* pro,
   return 0;
 }
 
-extern "C" int ps_gated_tcn_step_f32(const float* y, float* ring, int R, const int* counter, const float* wl, const float* wr,
-                                     const float* emb_taps, const ps_prologue* pro_left, const ps_prologue* pro_right,
-                                     float* g, int H, int B, int k, int ld, int P, int dilation, void* stream) {
-  const char* who = "ps_gated_tcn_step_f32";
+// ps_gated_tcn_step_f32 (span = NULL, slots = false) and ps_gated_tcn_step_slots_f32 share the checks and differ in the kernel.
+static int gated_tcn_step_launch(const char* who, bool slots, const float* y, float* ring, int R, const int* counter,
+                                 const int* span, const float* wl, const float* wr, const float* emb_taps,
+                                 const ps_prologue* pro_left, const ps_prologue* pro_right, float* g, int H, int B, int k, int ld,
+                                 int P, int dilation, void* stream) {
   if (!y || !ring || !counter || !wl || !wr || !g || y == g || H <= 0 || B <= 0 || k <= 0 || P <= 0 || dilation <= 0 ||
       (long long)k * B > ld || (long long)H * ld > (1LL << 31) || (long long)P * H > (1 << 24) ||
       (long long)R * H * B > (1LL << 40) || (long long)P * H * B > (1LL << 31)) {
     set_error("%s: bad argument (H=%d B=%d k=%d ld=%d P=%d dilation=%d R=%d)", who, H, B, k, ld, P, dilation, R);
+    return PS_E_INVALID;
+  }
+  if (slots && (!span || ((uintptr_t)span & 7))) {
+    set_error("%s: span must be an 8-byte aligned device array [B][2] of int", who);
     return PS_E_INVALID;
   }
   if ((long long)R < (long long)(P - 1) * dilation + k) {
@@ -208,11 +248,32 @@ extern "C" int ps_gated_tcn_step_f32(const float* y, float* ring, int R, const i
   a.H = H, a.B = B, a.k = k, a.ld = ld, a.P = P, a.dilation = dilation, a.R = R;
   a.K = P * H;
   a.Kp = (a.K + 15) / 16 * 16;
-  LaunchTimer timer("gated_tcn_step", (hipStream_t)stream);
+  hipStream_t s = (hipStream_t)stream;
+  LaunchTimer timer(slots ? "gated_tcn_step_slots" : "gated_tcn_step", s);
   const unsigned gx = (unsigned)((N + GT_TN - 1) / GT_TN);
-  if (N <= 1024)
-    hipLaunchKernelGGL((gated_tcn_step_kernel<16>), dim3(gx, (H + 15) / 16), dim3(256), 0, (hipStream_t)stream, a);
+  if (slots) {
+    if (N <= 1024)
+      hipLaunchKernelGGL((gated_tcn_step_kernel<16, true, const int*>), dim3(gx, (H + 15) / 16), dim3(256), 0, s, a, span);
+    else
+      hipLaunchKernelGGL((gated_tcn_step_kernel<32, true, const int*>), dim3(gx, (H + 31) / 32), dim3(256), 0, s, a, span);
+  } else if (N <= 1024)
+    hipLaunchKernelGGL((gated_tcn_step_kernel<16, false>), dim3(gx, (H + 15) / 16), dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((gated_tcn_step_kernel<32>), dim3(gx, (H + 31) / 32), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((gated_tcn_step_kernel<32, false>), dim3(gx, (H + 31) / 32), dim3(256), 0, s, a);
   return launch_status(who);
+}
+
+extern "C" int ps_gated_tcn_step_f32(const float* y, float* ring, int R, const int* counter, const float* wl, const float* wr,
+                                     const float* emb_taps, const ps_prologue* pro_left, const ps_prologue* pro_right,
+                                     float* g, int H, int B, int k, int ld, int P, int dilation, void* stream) {
+  return gated_tcn_step_launch("ps_gated_tcn_step_f32", false, y, ring, R, counter, nullptr, wl, wr, emb_taps, pro_left,
+                               pro_right, g, H, B, k, ld, P, dilation, stream);
+}
+
+extern "C" int ps_gated_tcn_step_slots_f32(const float* y, float* ring, int R, const int* counter, const int* span,
+                                           const float* wl, const float* wr, const float* emb_taps, const ps_prologue* pro_left,
+                                           const ps_prologue* pro_right, float* g, int H, int B, int k, int ld, int P,
+                                           int dilation, void* stream) {
+  return gated_tcn_step_launch("ps_gated_tcn_step_slots_f32", true, y, ring, R, counter, span, wl, wr, emb_taps, pro_left,
+                               pro_right, g, H, B, k, ld, P, dilation, stream);
 }

@@ -45,9 +45,26 @@ __device__ __forceinline__ float step_act(float u, int kind, float s) {
   return u;
 }
 
-template <int TM, int TN>
-__global__ __launch_bounds__(256) void conv2d_step_kernel(Conv2dStepArgs a) {
+// SLOTS (ps_conv2d_step_slots_f32): the "current" tensors are frame t - shift of their sources, t = *counter, and the tap d
+// frames back is frame g = t - shift - d of stream b; it is read iff span[b][0] <= g < span[b][1] and is an exact 0
+// otherwise -- a select, the column may hold inf / NaN while it is not live.  A thread gathers one column, so it reads its
+// stream's span once.  The gate is a compile-time variant of the kernel (template <bool SLOTS>): the kernels the entry without
+// a span launches are the code they were.
+struct Conv2dStepSlots {
+  const int* counter;
+  const int* span;   // [B][2], 8-byte aligned
+  int shift;
+};
+
+template <typename T>
+__device__ __forceinline__ const T& only(const T& v) { return v; }
+
+// Extra: nothing, or (Conv2dStepSlots) when SLOTS -- a trailing pack, so that the instantiation without a span has the
+// kernel arguments it always had.
+template <int TM, int TN, bool SLOTS, typename... Extra>
+__global__ __launch_bounds__(256) void conv2d_step_kernel(Conv2dStepArgs a, Extra... extra) {
   static_assert((TM / 4) * (TN / 4) == 256, "one 4 x 4 block per thread");
+  static_assert(sizeof...(Extra) == (SLOTS ? 1 : 0), "SLOTS: Conv2dStepSlots");
   constexpr int KC = 16;            // K slice staged in LDS
   constexpr int GR = 256 / TN;      // gather rows per pass
   __shared__ f32x4 As[KC][TM / 4];
@@ -63,6 +80,16 @@ __global__ __launch_bounds__(256) void conv2d_step_kernel(Conv2dStepArgs a) {
   const bool nvalid = ng < N;
   const int gfo = nvalid ? ng / a.B : 0, gb = nvalid ? ng - gfo * a.B : 0;
   const size_t frame1 = (size_t)a.C1 * a.Fin * a.ld, frame2 = (size_t)a.C2 * a.Fin * a.ld;
+  long long g0 = 0;      // SLOTS: the frame index of the current tensors, and this column's span
+  int lo = 0, hi = 0;
+  if constexpr (SLOTS) {
+    const Conv2dStepSlots& sl = only(extra...);
+    g0 = (long long)*sl.counter - sl.shift;
+    if (nvalid) {
+      const int2 sp = reinterpret_cast<const int2*>(sl.span)[gb];
+      lo = sp.x, hi = sp.y;
+    }
+  }
 
   // weights: the packed tile holds 256 output channels; TM divides 256, so a tile never straddles two of them
   const float* wbase = a.wt + (size_t)(m0 / 256) * a.Kp * 256 + (m0 % 256);
@@ -93,6 +120,10 @@ __global__ __launch_bounds__(256) void conv2d_step_kernel(Conv2dStepArgs a) {
           const int num = gfo + a.pf - jf * a.df;
           fi = num >= 0 ? num / a.sf : -1;
           ok = num >= 0 && fi * a.sf == num && fi < a.Fin;
+        }
+        if constexpr (SLOTS) {
+          const long long g = g0 - (a.transposed ? jt * a.dt : (a.kt - 1 - jt) * a.dt);
+          ok = ok && g >= lo && g < hi;
         }
         if (ok) {
           const int d = a.transposed ? jt * a.dt : (a.kt - 1 - jt) * a.dt;
@@ -143,20 +174,48 @@ __global__ __launch_bounds__(256) void conv2d_step_kernel(Conv2dStepArgs a) {
 // skipped where wsum <= 1e-10; the contributions enter the tail in increasing t' too (the same order as the offline sum; the
 // compiler's contraction choices may still differ between the two kernels in the last bit).
 // ---------------------------------------------------------------------------------------------------------------------
+//
+// SLOTS (ps_istft_step_slots_f32): stream b counts its frames from its own birth, u = *counter - shift - span[b][0], and has
+// T = span[b][1] - span[b][0] of them.  Step: the frame is added iff 0 <= u < T (a select: a column that is not live may hold
+// inf / NaN), the hop is emitted and the tail shifted in every case, and wsum covers the frames 0 <= u' <= min(g / hop, T - 1)
+// of sample g = u * hop + j -- none for u < 0.  So a stream drains its tail after its death with the normalisation its flush
+// would use, and an idle column emits constrain(0).  Flush: the samples from u * hop on, frames up to T - 1.  The sample
+// index is a long long: u is not bounded by the stream's length (an idle column, a slot closed late).
+struct IstftStepSlots {
+  const int* span;   // [B][2], 8-byte aligned
+  int shift;
+};
+
+// Extra: nothing, or (IstftStepSlots) when SLOTS, as conv2d_step_kernel.
+template <bool SLOTS, typename... Extra>
 __global__ __launch_bounds__(256) void istft_step_kernel(const float* __restrict__ frames, int ldf,
                                                          const float* __restrict__ window, float* __restrict__ tail,
                                                          float* __restrict__ out, int ld_out, const int* __restrict__ counter,
-                                                         int n_fft, int hop, int out_mode, int flush) {
+                                                         int n_fft, int hop, int out_mode, int flush, Extra... extra) {
+  static_assert(sizeof...(Extra) == (SLOTS ? 1 : 0), "SLOTS: IstftStepSlots");
   extern __shared__ float ola[];  // n_fft floats
   const int b = blockIdx.x, tid = threadIdx.x;
   const int keep = n_fft - hop;
   const int t = *counter;
   float* tb = tail + (size_t)b * keep;
   const float inv = (float)n_fft;
+  long long ub = 0, tcount = 0;   // SLOTS: the stream's own frame index and frame count
+  bool live = true;
+  if constexpr (SLOTS) {
+    const IstftStepSlots& sl = only(extra...);
+    const int2 sp = reinterpret_cast<const int2*>(sl.span)[b];
+    ub = (long long)t - sl.shift - sp.x;
+    tcount = (long long)sp.y - sp.x;
+    live = ub >= 0 && ub < tcount;
+  }
   if (!flush) {
     for (int j = tid; j < n_fft; j += 256) {
       const float w = window[j];
-      const float v = frames[(size_t)j * ldf + b] * w / inv;
+      float v;
+      if constexpr (SLOTS)
+        v = live ? frames[(size_t)j * ldf + b] * w / inv : 0.f;
+      else
+        v = frames[(size_t)j * ldf + b] * w / inv;
       ola[j] = j < keep ? tb[j] + v : v;
     }
   } else {
@@ -164,23 +223,46 @@ __global__ __launch_bounds__(256) void istft_step_kernel(const float* __restrict
   }
   __syncthreads();
   const int emit = flush ? keep : hop;
-  const int base = t * hop;  // first sample emitted: frame t's first (step), or the first one past the last frame's hop (flush)
-  const int t_last = flush ? t - 1 : t;
-  for (int j = tid; j < emit; j += 256) {
-    const int g = base + j;
-    int t_hi = g / hop;
-    if (t_hi > t_last) t_hi = t_last;
-    const int t_lo = (g - n_fft + 1 <= 0) ? 0 : (g - n_fft + 1 + hop - 1) / hop;
-    float wsum = 0.f;
-    for (int u = t_lo; u <= t_hi; ++u) {
-      const float w = window[g - u * hop];
-      wsum += w * w;
+  if constexpr (SLOTS) {
+    long long u_last = flush ? ub - 1 : ub;
+    if (u_last > tcount - 1) u_last = tcount - 1;
+    for (int j = tid; j < emit; j += 256) {
+      float wsum = 0.f;
+      if (ub >= 0) {
+        const long long g = ub * hop + j;
+        long long u_hi = g / hop;
+        if (u_hi > u_last) u_hi = u_last;
+        const long long u_lo = (g - n_fft + 1 <= 0) ? 0 : (g - n_fft + 1 + hop - 1) / hop;
+        for (long long u = u_lo; u <= u_hi; ++u) {
+          const float w = window[g - u * hop];
+          wsum += w * w;
+        }
+      }
+      float acc = ola[j];
+      if (wsum > 1e-10f) acc = acc / wsum;
+      if (out_mode == PS_OUT_CLAMP) acc = clamp1_keep_nan(acc);
+      if (out_mode == PS_OUT_SIGMOID) acc = 1.f / (1.f + expf(-acc));
+      out[(size_t)b * ld_out + j] = acc;
     }
-    float acc = ola[j];
-    if (wsum > 1e-10f) acc = acc / wsum;
-    if (out_mode == PS_OUT_CLAMP) acc = clamp1_keep_nan(acc);
-    if (out_mode == PS_OUT_SIGMOID) acc = 1.f / (1.f + expf(-acc));
-    out[(size_t)b * ld_out + j] = acc;
+  } else {
+    const int base = t * hop;  // first sample emitted: frame t's first (step), or the first one past the last frame's hop (flush)
+    const int t_last = flush ? t - 1 : t;
+    for (int j = tid; j < emit; j += 256) {
+      const int g = base + j;
+      int t_hi = g / hop;
+      if (t_hi > t_last) t_hi = t_last;
+      const int t_lo = (g - n_fft + 1 <= 0) ? 0 : (g - n_fft + 1 + hop - 1) / hop;
+      float wsum = 0.f;
+      for (int u = t_lo; u <= t_hi; ++u) {
+        const float w = window[g - u * hop];
+        wsum += w * w;
+      }
+      float acc = ola[j];
+      if (wsum > 1e-10f) acc = acc / wsum;
+      if (out_mode == PS_OUT_CLAMP) acc = clamp1_keep_nan(acc);
+      if (out_mode == PS_OUT_SIGMOID) acc = 1.f / (1.f + expf(-acc));
+      out[(size_t)b * ld_out + j] = acc;
+    }
   }
   if (!flush)
     for (int j = tid; j < keep; j += 256) tb[j] = ola[hop + j];
@@ -211,55 +293,123 @@ __global__ __launch_bounds__(256) void stream_commit_kernel(CommitTable tab, int
 
 using namespace ps;
 
-extern "C" int ps_conv2d_step_f32(const float* x1, const float* ring1, int C1, int R1, const float* x2, const float* ring2,
-                                  int C2, int R2, const float* wt, const float* bias, float* y, int M, int Fin, int B, int ld,
-                                  int kf, int kt, int stride_f, int dil_f, int dil_t, int pad_f, int Fout, int transposed,
-                                  int act, const float* slope, void* stream) {
+static bool span_ok(const char* who, const int* span) {
+  if (span && !((uintptr_t)span & 7)) return true;
+  set_error("%s: span must be an 8-byte aligned device array [B][2] of int", who);
+  return false;
+}
+
+// ps_conv2d_step_f32 (slots = false) and ps_conv2d_step_slots_f32 share the checks and differ in the kernel.
+static int conv2d_step_launch(const char* who, bool slots, const float* x1, const float* ring1, int C1, int R1,
+                              const float* x2, const float* ring2, int C2, int R2, const float* wt, const float* bias, float* y,
+                              int M, int Fin, int B, int ld, int kf, int kt, int stride_f, int dil_f, int dil_t, int pad_f,
+                              int Fout, int transposed, int act, const float* slope, const int* counter, const int* span,
+                              int shift, void* stream) {
   const int hist = (kt - 1) * dil_t;  // previous frames the convolution reads
   if (!x1 || !wt || !y || C1 <= 0 || C2 < 0 || (C2 > 0 && !x2) || M <= 0 || Fin <= 0 || Fout <= 0 || B <= 0 || ld < B ||
       ld % kTileT || kf <= 0 || kt <= 0 || stride_f <= 0 || dil_f <= 0 || dil_t <= 0 || pad_f < 0 ||
       (transposed != 0 && transposed != 1) || act < 0 || act > 2 || (act == 2 && !slope) || Fout * B > (1 << 30) ||
       (long long)(C1 + C2) * kf * kt > (1 << 24)) {
-    set_error("ps_conv2d_step_f32: bad argument (C1=%d C2=%d M=%d Fin=%d Fout=%d B=%d ld=%d kf=%d kt=%d act=%d)", C1, C2, M,
-              Fin, Fout, B, ld, kf, kt, act);
+    set_error("%s: bad argument (C1=%d C2=%d M=%d Fin=%d Fout=%d B=%d ld=%d kf=%d kt=%d act=%d)", who, C1, C2, M, Fin, Fout, B,
+              ld, kf, kt, act);
     return PS_E_INVALID;
   }
   if (hist > 0 && (!ring1 || R1 < hist || (C2 > 0 && (!ring2 || R2 < hist)))) {
-    set_error("ps_conv2d_step_f32: the convolution reads %d previous frames; ring slots R1=%d R2=%d", hist, R1, R2);
+    set_error("%s: the convolution reads %d previous frames; ring slots R1=%d R2=%d", who, hist, R1, R2);
     return PS_E_INVALID;
+  }
+  if (slots) {
+    if (!span_ok(who, span)) return PS_E_INVALID;
+    if (!counter || shift < 0) {
+      set_error("%s: counter (device int) is required and shift >= 0 (got %d)", who, shift);
+      return PS_E_INVALID;
+    }
   }
   Conv2dStepArgs a{x1, ring1, x2, ring2, wt, bias, slope, y, C1, C2, R1, R2, M, Fin, B, ld, kf, kt, stride_f, dil_f, dil_t,
                    pad_f, Fout, transposed, act, 0, 0};
   a.K = (C1 + C2) * kf * kt;
   a.Kp = (a.K + 15) / 16 * 16;
   const int N = Fout * B;
-  LaunchTimer timer("conv2d_step", (hipStream_t)stream);
-  if (M <= 16)
-    hipLaunchKernelGGL((conv2d_step_kernel<16, 256>), dim3((N + 255) / 256, (M + 15) / 16), dim3(256), 0,
-                       (hipStream_t)stream, a);
+  hipStream_t s = (hipStream_t)stream;
+  LaunchTimer timer(slots ? "conv2d_step_slots" : "conv2d_step", s);
+  if (slots) {
+    const Conv2dStepSlots sl{counter, span, shift};
+    if (M <= 16)
+      hipLaunchKernelGGL((conv2d_step_kernel<16, 256, true, Conv2dStepSlots>), dim3((N + 255) / 256, (M + 15) / 16), dim3(256),
+                         0, s, a, sl);
+    else if (M <= 32)
+      hipLaunchKernelGGL((conv2d_step_kernel<32, 128, true, Conv2dStepSlots>), dim3((N + 127) / 128, (M + 31) / 32), dim3(256),
+                         0, s, a, sl);
+    else
+      hipLaunchKernelGGL((conv2d_step_kernel<64, 64, true, Conv2dStepSlots>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0,
+                         s, a, sl);
+  } else if (M <= 16)
+    hipLaunchKernelGGL((conv2d_step_kernel<16, 256, false>), dim3((N + 255) / 256, (M + 15) / 16), dim3(256), 0, s, a);
   else if (M <= 32)
-    hipLaunchKernelGGL((conv2d_step_kernel<32, 128>), dim3((N + 127) / 128, (M + 31) / 32), dim3(256), 0,
-                       (hipStream_t)stream, a);
+    hipLaunchKernelGGL((conv2d_step_kernel<32, 128, false>), dim3((N + 127) / 128, (M + 31) / 32), dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((conv2d_step_kernel<64, 64>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, (hipStream_t)stream,
-                       a);
-  return launch_status("ps_conv2d_step_f32");
+    hipLaunchKernelGGL((conv2d_step_kernel<64, 64, false>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, s, a);
+  return launch_status(who);
+}
+
+extern "C" int ps_conv2d_step_f32(const float* x1, const float* ring1, int C1, int R1, const float* x2, const float* ring2,
+                                  int C2, int R2, const float* wt, const float* bias, float* y, int M, int Fin, int B, int ld,
+                                  int kf, int kt, int stride_f, int dil_f, int dil_t, int pad_f, int Fout, int transposed,
+                                  int act, const float* slope, void* stream) {
+  return conv2d_step_launch("ps_conv2d_step_f32", false, x1, ring1, C1, R1, x2, ring2, C2, R2, wt, bias, y, M, Fin, B, ld, kf,
+                            kt, stride_f, dil_f, dil_t, pad_f, Fout, transposed, act, slope, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int ps_conv2d_step_slots_f32(const float* x1, const float* ring1, int C1, int R1, const float* x2,
+                                        const float* ring2, int C2, int R2, const float* wt, const float* bias, float* y, int M,
+                                        int Fin, int B, int ld, int kf, int kt, int stride_f, int dil_f, int dil_t, int pad_f,
+                                        int Fout, int transposed, int act, const float* slope, const int* counter,
+                                        const int* span, int shift, void* stream) {
+  return conv2d_step_launch("ps_conv2d_step_slots_f32", true, x1, ring1, C1, R1, x2, ring2, C2, R2, wt, bias, y, M, Fin, B, ld,
+                            kf, kt, stride_f, dil_f, dil_t, pad_f, Fout, transposed, act, slope, counter, span, shift, stream);
+}
+
+// ps_istft_step_f32 (slots = false) and ps_istft_step_slots_f32 share the checks and differ in the kernel.
+static int istft_step_launch(const char* who, bool slots, const float* frames, int ldf, const float* window, float* tail,
+                             float* out, int ld_out, const int* counter, const int* span, int shift, int B, int n_fft, int hop,
+                             int out_mode, int flush, void* stream) {
+  if (!window || (!tail && n_fft > hop) || !out || !counter || (!flush && !frames) || B <= 0 || B > 65535 || hop <= 0 || n_fft < hop ||
+      n_fft % hop || n_fft > 8192 || (!flush && ldf < B) || ld_out < (flush ? n_fft - hop : hop) || out_mode < PS_OUT_CLAMP ||
+      out_mode > PS_OUT_NONE || (flush != 0 && flush != 1)) {
+    set_error("%s: bad argument (B=%d n_fft=%d hop=%d ldf=%d ld_out=%d out_mode=%d flush=%d)", who, B, n_fft, hop, ldf, ld_out,
+              out_mode, flush);
+    return PS_E_INVALID;
+  }
+  if (slots) {
+    if (!span_ok(who, span)) return PS_E_INVALID;
+    if (shift < 0) {
+      set_error("%s: shift >= 0 (got %d)", who, shift);
+      return PS_E_INVALID;
+    }
+  }
+  if (flush && n_fft == hop) return 0;  // nothing overlaps: no samples after the last frame
+  LaunchTimer timer(slots ? "istft_step_slots" : "istft_step", (hipStream_t)stream);
+  if (slots)
+    hipLaunchKernelGGL((istft_step_kernel<true, IstftStepSlots>), dim3(B), dim3(256), (size_t)n_fft * sizeof(float),
+                       (hipStream_t)stream, frames, ldf, window, tail, out, ld_out, counter, n_fft, hop, out_mode, flush,
+                       IstftStepSlots{span, shift});
+  else
+    hipLaunchKernelGGL(istft_step_kernel<false>, dim3(B), dim3(256), (size_t)n_fft * sizeof(float), (hipStream_t)stream, frames, ldf,
+                       window, tail, out, ld_out, counter, n_fft, hop, out_mode, flush);
+  return launch_status(who);
 }
 
 extern "C" int ps_istft_step_f32(const float* frames, int ldf, const float* window, float* tail, float* out, int ld_out,
                                  const int* counter, int B, int n_fft, int hop, int out_mode, int flush, void* stream) {
-  if (!window || (!tail && n_fft > hop) || !out || !counter || (!flush && !frames) || B <= 0 || B > 65535 || hop <= 0 || n_fft < hop ||
-      n_fft % hop || n_fft > 8192 || (!flush && ldf < B) || ld_out < (flush ? n_fft - hop : hop) || out_mode < PS_OUT_CLAMP ||
-      out_mode > PS_OUT_NONE || (flush != 0 && flush != 1)) {
-    set_error("ps_istft_step_f32: bad argument (B=%d n_fft=%d hop=%d ldf=%d ld_out=%d out_mode=%d flush=%d)", B, n_fft, hop,
-              ldf, ld_out, out_mode, flush);
-    return PS_E_INVALID;
-  }
-  if (flush && n_fft == hop) return 0;  // nothing overlaps: no samples after the last frame
-  LaunchTimer timer("istft_step", (hipStream_t)stream);
-  hipLaunchKernelGGL(istft_step_kernel, dim3(B), dim3(256), (size_t)n_fft * sizeof(float), (hipStream_t)stream, frames, ldf,
-                     window, tail, out, ld_out, counter, n_fft, hop, out_mode, flush);
-  return launch_status("ps_istft_step_f32");
+  return istft_step_launch("ps_istft_step_f32", false, frames, ldf, window, tail, out, ld_out, counter, nullptr, 0, B, n_fft,
+                           hop, out_mode, flush, stream);
+}
+
+extern "C" int ps_istft_step_slots_f32(const float* frames, int ldf, const float* window, float* tail, float* out, int ld_out,
+                                       const int* counter, const int* span, int shift, int B, int n_fft, int hop, int out_mode,
+                                       int flush, void* stream) {
+  return istft_step_launch("ps_istft_step_slots_f32", true, frames, ldf, window, tail, out, ld_out, counter, span, shift, B,
+                           n_fft, hop, out_mode, flush, stream);
 }
 
 static int stream_commit(const char* who, const ps_ring_pair* pairs_host, int n_pairs, int* counter, int advance,

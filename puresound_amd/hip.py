@@ -898,10 +898,12 @@ ACT_KINDS = {"none": 0, "relu": 1, "prelu": 2, "mish": 3, "sigmoid": 4, "tanh": 
 def conv2d_step(x1: torch.Tensor, ring1: Optional[torch.Tensor], x2: Optional[torch.Tensor], ring2: Optional[torch.Tensor],
                 wt: torch.Tensor, bias: Optional[torch.Tensor], m: int, b: int, f_out: int, kf: int, kt: int, stride_f: int,
                 dil_f: int, dil_t: int, pad_f: int, transposed: bool, act: str = "none", slope: Optional[torch.Tensor] = None,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None, counter: Optional[torch.Tensor] = None,
+                span: Optional[torch.Tensor] = None, shift: int = 0) -> torch.Tensor:
     """One causal frame of a Conv2d / ConvTranspose2d for b streams (ps_conv2d_step_f32): current frames x1 [1, C1, F, ld]
     (+ x2 [1, C2, F, ld]), previous frames from the rings [R, C, F, ld] (slot R - d = frame t - d) -> [1, m, f_out, ld]
-    (columns b..ld of `out` are not written)."""
+    (columns b..ld of `out` are not written).  span int32 [b, 2] with the int32 frame counter: ps_conv2d_step_slots_f32, the
+    current frames are frame counter[0] - shift and a tap reads frame g of stream b iff span[b, 0] <= g < span[b, 1]."""
     require_device(x1, "conv2d_step")
     _, c1, f_in, ld = x1.shape
     c2 = 0 if x2 is None else x2.shape[1]
@@ -917,6 +919,17 @@ def conv2d_step(x1: torch.Tensor, ring1: Optional[torch.Tensor], x2: Optional[to
         raise RuntimeError(f"conv2d_step: out must be a contiguous {(1, m, f_out, ld)} tensor")
     r1 = 0 if ring1 is None else ring1.shape[0]
     r2 = 0 if ring2 is None else ring2.shape[0]
+    if span is not None:
+        _check_span(span, b, x1, "conv2d_step")
+        if counter is None or counter.dtype != torch.int32 or counter.device != x1.device:
+            raise RuntimeError("conv2d_step: span comes with the int32 frame counter on x1's device")
+        check(lib().ps_conv2d_step_slots_f32(ptr(x1), ptr(ring1), c1, r1, ptr(x2), ptr(ring2), c2, r2, ptr(wt), ptr(bias), ptr(y),
+                                             m, f_in, b, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, f_out, int(transposed),
+                                             ACT_KINDS[act], ptr(slope), ptr(counter), ptr(span), int(shift),
+                                             stream_ptr(x1.device)), "ps_conv2d_step_slots_f32")
+        return y
+    if counter is not None or shift:
+        raise RuntimeError("conv2d_step: counter and shift come with span")
     check(lib().ps_conv2d_step_f32(ptr(x1), ptr(ring1), c1, r1, ptr(x2), ptr(ring2), c2, r2, ptr(wt), ptr(bias), ptr(y), m,
                                    f_in, b, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, f_out, int(transposed), ACT_KINDS[act],
                                    ptr(slope), stream_ptr(x1.device)), "ps_conv2d_step_f32")
@@ -924,10 +937,12 @@ def conv2d_step(x1: torch.Tensor, ring1: Optional[torch.Tensor], x2: Optional[to
 
 
 def istft_step(frames: Optional[torch.Tensor], window: torch.Tensor, tail: torch.Tensor, out: torch.Tensor,
-               counter: torch.Tensor, hop: int, out_mode: str = "none", flush: bool = False) -> torch.Tensor:
+               counter: torch.Tensor, hop: int, out_mode: str = "none", flush: bool = False,
+               span: Optional[torch.Tensor] = None, shift: int = 0) -> torch.Tensor:
     """Synthesis of frame t = counter[0] of every stream (ps_istft_step_f32): frames padded [1, n_fft, ldB] -> out [B, hop]
     (a row view of a wider buffer is fine), overlap-add tail [B, n_fft - hop] updated in place; flush: the tail's samples
-    after the last frame -> out [B, n_fft - hop]."""
+    after the last frame -> out [B, n_fft - hop].  span int32 [B, 2]: ps_istft_step_slots_f32, stream b synthesises its own
+    frame counter[0] - shift - span[b, 0] of span[b, 1] - span[b, 0] and adds it iff it is one of them."""
     require_device(tail, "istft_step")
     b, keep = tail.shape
     n_fft = keep + hop
@@ -942,6 +957,14 @@ def istft_step(frames: Optional[torch.Tensor], window: torch.Tensor, tail: torch
         if frames is None or frames.shape[:2] != (1, n_fft) or not frames.is_contiguous():
             raise RuntimeError("istft_step: frames must be a contiguous [1, n_fft, ldB] tensor")
         ldf = frames.shape[2]
+    if span is not None:
+        _check_span(span, b, tail, "istft_step")
+        check(lib().ps_istft_step_slots_f32(ptr(frames), ldf, ptr(window), ptr(tail), ptr(out), out.stride(0), ptr(counter),
+                                            ptr(span), int(shift), b, n_fft, hop, _abi.PS_OUT[out_mode], int(flush),
+                                            stream_ptr(tail.device)), "ps_istft_step_slots_f32")
+        return out
+    if shift:
+        raise RuntimeError("istft_step: shift comes with span")
     check(lib().ps_istft_step_f32(ptr(frames), ldf, ptr(window), ptr(tail), ptr(out), out.stride(0), ptr(counter), b, n_fft,
                                   hop, _abi.PS_OUT[out_mode], int(flush), stream_ptr(tail.device)), "ps_istft_step_f32")
     return out
@@ -1008,13 +1031,14 @@ def dwconv_step(x: torch.Tensor, ring: torch.Tensor, counter: torch.Tensor, w: t
 def gated_tcn_step(y: torch.Tensor, ring: torch.Tensor, counter: torch.Tensor, wl: torch.Tensor, wr: torch.Tensor,
                    taps: int, dilation: int, streams: int, frames: int, pro_left: Optional[Prologue] = None,
                    pro_right: Optional[Prologue] = None, emb_taps: Optional[torch.Tensor] = None,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, span: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The two dense dilated convolutions, norms and gate of a causal GatedTCN block for `frames` new frames of `streams`
     streams (ps_gated_tcn_step_f32): y [1, H, ld] (column f * streams + b, the output of in_conv); wl, wr = pack_wt of the
     [H, taps * H] weights with column j * H + c; earlier frames of y from ring [R, H, streams] (slot g % R = frame g; the
     chunk's frames are stored there too), frame index of column 0 = counter[0]; emb_taps [taps, H, streams]: what the
     embedding adds to the right side per tap whose frame is >= 0 -> g [1, H, ld] (columns past frames * streams are not
-    written)."""
+    written).  span int32 [streams, 2]: ps_gated_tcn_step_slots_f32, a tap reads frame g of stream b and adds its embedding
+    constant iff span[b, 0] <= g < span[b, 1]."""
     require_device(y, "gated_tcn_step")
     _, h, ld = y.shape
     kp = (taps * h + 15) // 16 * 16
@@ -1028,6 +1052,14 @@ def gated_tcn_step(y: torch.Tensor, ring: torch.Tensor, counter: torch.Tensor, w
     g = out if out is not None else torch.zeros_like(y)
     if g.shape != y.shape:
         raise RuntimeError("gated_tcn_step: out must be a contiguous tensor of y's shape")
+    if span is not None:
+        _check_span(span, streams, y, "gated_tcn_step")
+        check(lib().ps_gated_tcn_step_slots_f32(ptr(y), ptr(ring), ring.shape[0], ptr(counter), ptr(span), ptr(wl), ptr(wr),
+                                                ptr(emb_taps), C.byref(pro_left) if pro_left is not None else None,
+                                                C.byref(pro_right) if pro_right is not None else None, ptr(g), h, streams,
+                                                frames, ld, taps, dilation, stream_ptr(y.device)),
+              "ps_gated_tcn_step_slots_f32")
+        return g
     check(lib().ps_gated_tcn_step_f32(ptr(y), ptr(ring), ring.shape[0], ptr(counter), ptr(wl), ptr(wr), ptr(emb_taps),
                                       C.byref(pro_left) if pro_left is not None else None,
                                       C.byref(pro_right) if pro_right is not None else None, ptr(g), h, streams, frames, ld,

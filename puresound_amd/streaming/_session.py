@@ -22,6 +22,13 @@ priming phase and no flush().  A streamer with slots calls `_begin` and then `_m
 that say why), `_open_slot(slot, enroll)` (reset or seed the slot's model state) and a `_flush_into(out, tail)` that takes
 the tail rows to flush.  A streamer whose open() takes other arguments (skim.py: an enrolment or its embedding) overrides
 open(), checks them and ends in `_start_slot`.
+
+Slots and a model delay (unet_tcn.py): a slot is born at its first full window, counter + window / hop - 1 -- the model's
+delay is not part of the birth, the model's state is live from that frame on -- and a slot session has no mute hops: the
+streamer's kernels read every tensor with the shift of its layer, so a frame is live or dead by its own index.  The D hops
+of the session after a slot's last input hop carry its last frames out (the slot's input in those hops is ignored);
+close() before they were stepped raises, as does close() without an earlier end(): end(slot, 0), D hops, close(slot).  The
+tail is flushed per slot through `_flush_slot(out, slot)`, by default `_flush_into(out, tail row)`.
 """
 import contextlib
 from typing import Dict, List, Optional
@@ -181,7 +188,8 @@ class HopSession:
                                f"init_slots() for a new session")
         self._ready()
         step = self.max_hops * self.hop_length if self.max_hops else chunk.shape[1]
-        quiet = min(k, max(self.delay_frames - self.frames, 0)) * self.hop_length   # frames inside the model's delay
+        # frames inside the model's delay (a slot session has none: a slot's frames are live or dead by its span)
+        quiet = 0 if self._slots is not None else min(k, max(self.delay_frames - self.frames, 0)) * self.hop_length
         for i in range(0, quiet, step):
             self._run_piece(chunk[:, i:min(i + step, quiet)], mute=True)
         outs = [self._run_piece(chunk[:, i:i + step]) for i in range(quiet, chunk.shape[1], step)]
@@ -189,7 +197,9 @@ class HopSession:
             return chunk.new_zeros(self.streams, 0)
         for st in self._slots or ():
             if st is not None:
-                st["hops"] = st["hops"] + k if st["total"] is None else min(st["hops"] + k, st["total"])
+                fed = k if st["total"] is None else min(k, st["total"] - st["hops"])
+                st["hops"] += fed
+                st["drained"] = min(st["drained"] + k - fed, self.delay_frames)   # hops past the stream's last input hop
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
     def _capture(self, hops: int) -> torch.cuda.CUDAGraph:
@@ -254,11 +264,13 @@ class HopSession:
 
     # -- slots --------------------------------------------------------------------------------------------------------
     @staticmethod
-    def slot_output_range(samples: int, win: int, hop: int) -> range:
+    def slot_output_range(samples: int, win: int, hop: int, delay_frames: int = 0) -> range:
         """The indices of y that hold model.inference(x, e) for a stream x of `samples` = k * hop samples in a slot, y = every
-        output of the slot from open() on ‖ close(): the offline output after the latency, win - hop samples."""
-        n = HopSession.output_length(samples, win, hop)
-        return range(win - hop, win - hop + n["emitted"] + n["flushed"])
+        output of the slot from open() on ‖ close(): the offline output (`samples` samples) after the latency,
+        win - hop + delay_frames * hop samples."""
+        HopSession.output_length(samples, win, hop, delay_frames)      # (the argument checks)
+        lat = win - hop + delay_frames * hop
+        return range(lat, lat + samples)
 
     @property
     def active(self) -> List[int]:
@@ -317,10 +329,15 @@ class HopSession:
         self._open_slot(slot, seed)
         self._queue[slot].zero_()
         self._tail[slot].zero_()
-        # frames counter .. counter + prime_hops - 1 see a partly filled window: dead.  (device-side add: no read-back)
-        self._span[slot, 0:1] = self._counter + self.prime_hops
+        # frames counter .. counter + window / hop - 2 see a partly filled window: dead.  (device-side add: no read-back)
+        self._span[slot, 0:1] = self._counter + self._fill_hops
         self._span[slot, 1:2] = INT32_MAX
-        self._slots[slot] = dict(hops=0, total=None)
+        self._slots[slot] = dict(hops=0, total=None, drained=0)
+
+    def _flush_slot(self, out: torch.Tensor, slot: int) -> None:
+        """close()'s flush of one slot's tail row -> out [1, window - hop] (a streamer whose flush reads the slot's span
+        overrides this)."""
+        self._flush_into(out, self._tail[slot:slot + 1])
 
     def _needs(self, st: dict, more: int, what: str, slot: int) -> None:
         """flush()'s rule per slot: a stream that ends after fewer than window samples has no frame."""
@@ -353,16 +370,25 @@ class HopSession:
         writes it while the slot is idle, and open() resets it.)"""
         slot = self._slot(slot, "close", idle=False)
         st = self._slots[slot]
+        D = self.delay_frames
         if st["total"] is None:
+            if D:
+                raise RuntimeError(f"{type(self).__name__}.close: the model holds the last {D} frames of the stream in slot "
+                                   f"{slot}: call end({slot}, 0), step {D} more hops of the session (they carry those frames "
+                                   f"out; the slot's input in them is ignored), then close({slot})")
             self._needs(st, 0, "close", slot)
         elif st["hops"] < st["total"]:
             raise RuntimeError(f"{type(self).__name__}.close: end({slot}, ..) announced {st['total'] - st['hops']} more hops "
                                f"of input; step them first")
+        elif st["drained"] < D:
+            raise RuntimeError(f"{type(self).__name__}.close: the model still holds {D - st['drained']} frames of the stream "
+                               f"in slot {slot}: step {D - st['drained']} more hops of the session first (the slot's input in "
+                               f"them is ignored)")
         self._ready()
         if st["total"] is None:
             self.end(slot, 0)
         out = torch.empty(1, self.window - self.hop_length, dtype=torch.float32, device=self.device)
-        self._flush_into(out, self._tail[slot:slot + 1])
+        self._flush_slot(out, slot)
         self._tail[slot].zero_()
         self._span[slot].zero_()
         self._slots[slot] = None

@@ -37,6 +37,22 @@ Arithmetic: exact fp32 products throughout, whatever the model's gemm_precision.
 model's own setting and plans are left as they were.  The embedding is computed once per stream by the model's speaker
 branch (inference_tse_embedding) in the model's own arithmetic, l2-normalised when embed_norm; a deployment may cache it and
 pass `embed=`.
+
+Slots (init_slots / open / end / close, HopSession's): streams that join and leave a running session.  One rule, and no new
+state: frame g of a tensor is read as an exact 0 for stream b unless birth_b <= g < death_b, and up layer j runs j frames
+behind the hop.  The kernels are the *_slots_f32 variants (ps_conv2d_step_slots_f32, ps_gated_tcn_step_slots_f32,
+ps_istft_step_slots_f32) with the session's span [B, 2] and one counter: the down path and the TCN launch with shift 0, up
+layer j with shift j (its "current" tensors are frame counter - j), the synthesis with shift D.  What the block session
+does on the host falls out of the rule per stream: a slot's frames before its birth are the offline zero padding and trimmed
+frames; at the i-th hop after its death layers j < i see only dead frames (skipped), layer i reads a dead (zero) current
+frame and layers j > i run as usual -- the flush schedule -- while its neighbours go on streaming.  So a slot session has
+no priming, no mute hops, no flushing pass and no second counter, one commit per hop, and step() returns [capacity, hop]
+from the first hop on; a slot's last D frames leave in the D hops after its last input hop, then close() flushes its tail.
+open() writes the slot's column of every emb_taps in place (computed over MIN_GEMM_COLUMNS columns: the bits of a
+one-stream session) and clears no ring: dead frames are never read, whatever they hold.  A slot's samples are the bits of the
+block session of its stream at the session's width: the 1x1 convolutions run over `capacity` columns, as init_streams(B)
+runs them over B, and ps_conv1x1_f32 has one kernel up to 16 columns and other orders of summation beyond, so up to a capacity
+of 16 a slot equals an init_streams(1, ...) session of its stream and in a wider session its row of init_streams(capacity).
 """
 from typing import List, Optional
 
@@ -152,6 +168,11 @@ class StreamingUnetTcn(HopSession):
     s.step(hop [B, hop]) -> [B, hop], or None for the first prime_hops hops (the analysis window fills, then the model's
     delay_frames pass); s.step_chunk([B, k*hop]) -> what k step() calls return, concatenated; s.flush() -> the last
     latency_samples samples.
+
+    Streams that join and leave: s.init_slots(capacity); s.open(slot, enroll=e [L']) or s.open(slot, embed=d [E]);
+    s.step / s.step_chunk([capacity, k*hop]) -> [capacity, k*hop] from the first hop on (an idle slot: constrain(0));
+    s.end(slot, hops) when the stream has `hops` more hops of input, delay_frames more hops of the session (they carry the
+    stream's last frames out; its input in them is ignored), then s.close(slot) -> the last window - hop samples.
     """
 
     _flushing = False    # True inside flush(): the first layer _up_path runs reads an all-zero current frame
@@ -190,7 +211,11 @@ class StreamingUnetTcn(HopSession):
                 q["pro_" + side] = hip.make_prologue(PS_NORM_AFFINE, True, None, 0.0, 1e-8, *q[side])
             blocks.append(q)
         self._packs = dict(wt_a=wt_a, rows=rows, wt_s=wt_s, window=window, down=p["down"], up=p["up"], blocks=blocks)
-        if getattr(self, "_emb_taps", None) is not None:       # a running session: its constants are those of the old weights
+        if getattr(self, "_emb_taps", None) is not None and self._slots is not None:
+            for slot, emb in enumerate(self._slot_embeds):     # a running slot session: every open slot's column, in place
+                if emb is not None:
+                    self._write_taps(slot, emb)
+        elif getattr(self, "_emb_taps", None) is not None:     # a running session: its constants are those of the old weights
             self._emb_taps = [self._tap_constants(q, self._emb, self.streams) if (q["E"] > 0 and self._emb is not None) else None
                               for q in blocks]
 
@@ -233,6 +258,71 @@ class StreamingUnetTcn(HopSession):
         self._begin(b, dev, use_graph)
         self._ready()
         self._allocate(b, dev, emb)
+
+    @torch.no_grad()
+    def init_slots(self, capacity: int, use_graph: bool = True) -> None:
+        """Start a slot session of `capacity` columns, every slot idle (every state and every tap constant zeroed); open()
+        starts a stream."""
+        if int(capacity) < 1:
+            raise ValueError("init_slots: capacity >= 1")
+        b, dev = int(capacity), next(self.model.parameters()).device
+        self._emb_taps = None
+        self._begin(b, dev, use_graph)
+        self._make_slots()
+        self._ready()
+        self._slot_embeds = [None] * b                   # per slot the (normalised) embedding [1, E] its stream was opened with
+        self._allocate(b, dev, None)
+
+    def _enrolment_rule(self) -> tuple:
+        e = self.model.masker.embed_dim
+        if self.model.speaker_net is not None:
+            return True, f"the model has a speaker_net: pass exactly one of enroll [L'] and embed [{e}]"
+        return False, "the model has no speaker_net: pass neither enroll nor embed"
+
+    @torch.no_grad()
+    def open(self, slot: int, enroll: Optional[torch.Tensor] = None, embed: Optional[torch.Tensor] = None) -> None:
+        """Start a stream in the idle slot `slot`: its first input hop is the first hop of the next step / step_chunk call.
+        A model with a speaker_net takes exactly one of enroll [L'] or [1, L'] (through model.inference_tse_embedding, here,
+        once) and embed [E], [1, E] or [1, E, 1] (what that call returns; a deployment caches it), on the session's device; a
+        model without one takes neither.  No synchronisation, no captured graph is touched, no ring is cleared."""
+        name = f"{type(self).__name__}.open"
+        slot = self._slot(slot, "open", idle=True)
+        required, why = self._enrolment_rule()
+        if (enroll is not None) + (embed is not None) != int(required):
+            raise ValueError(f"{name}: {why}")
+        if enroll is not None:
+            enroll = self._one_enrolment(enroll, name)
+        if embed is not None:
+            e = self.model.masker.embed_dim
+            hip.require_device(embed, name)
+            if embed.device != self.device:
+                raise RuntimeError(f"{name}: the embedding is on {embed.device}, the session on {self.device}; move it with "
+                                   f".to({str(self.device)!r})")
+            if tuple(embed.shape) not in ((e,), (1, e), (1, e, 1)):
+                raise ValueError(f"{name}: embed must be [{e}], [1, {e}] or [1, {e}, 1] (one stream), got {tuple(embed.shape)}")
+            embed = embed.reshape(1, e)
+        self._start_slot(slot, (enroll, embed), name)
+
+    def _open_slot(self, slot: int, seed: tuple) -> None:
+        """The new stream's tap constants into column `slot` of every block's emb_taps (computed here, once, as init_streams
+        does for one stream).  Nothing is cleared: what the slot's predecessor left in the rings are dead frames."""
+        m = self.model.masker
+        enroll, embed = seed
+        if enroll is not None:
+            embed = self.model.inference_tse_embedding(enroll)[:, :, 0]
+        self._ready()
+        self._slot_embeds[slot] = None
+        if embed is not None and any(m.tcn_with_embed) and m.embed_dim > 0:
+            emb = embed.detach().float().contiguous()
+            self._slot_embeds[slot] = hip.l2_normalize(emb) if m.embed_norm else emb.clone()
+            self._write_taps(slot, self._slot_embeds[slot])
+
+    def _write_taps(self, slot: int, emb: torch.Tensor) -> None:
+        """Column `slot` of every block's emb_taps <- the constants of emb [1, E], the bits of a session of that one stream;
+        in place: a captured graph keeps reading these tensors."""
+        for q, taps in zip(self._packs["blocks"], self._emb_taps):
+            if taps is not None:
+                taps[:, :, slot] = self._tap_constants(q, emb, 1)[:, :, 0]
 
     def _allocate(self, b: int, dev: torch.device, emb: Optional[torch.Tensor]) -> None:
         """Geometry of every convolution (unet.py:219-281), the frame buffers, the rings and the embedding's tap constants."""
@@ -290,9 +380,13 @@ class StreamingUnetTcn(HopSession):
         self._y1, self._g, self._xbuf = z(1, h, ldb), z(1, h, ldb), [z(1, c_tcn, ldb), z(1, c_tcn, ldb)]
         self._tcn_rings = [z((q["P"] - 1) * q["dilation"] + 1, q["H"], b) for q in pk["blocks"]]
         self._emb = emb
-        self._emb_taps = [self._tap_constants(q, emb, b) if (q["E"] > 0 and emb is not None) else None for q in pk["blocks"]]
-        if any(q["E"] > 0 for q in pk["blocks"]) and emb is None:
-            raise ValueError(f"{NAME}.init_streams: the TCN has embedding blocks but no embedding was given")
+        if self._slots is not None:     # (the launches read these tensors for as long as the session lasts: open() writes a column)
+            self._emb_taps = [z(q["P"], q["H"], b) if q["E"] > 0 else None for q in pk["blocks"]]
+        else:
+            self._emb_taps = [self._tap_constants(q, emb, b) if (q["E"] > 0 and emb is not None) else None
+                              for q in pk["blocks"]]
+            if any(q["E"] > 0 for q in pk["blocks"]) and emb is None:
+                raise ValueError(f"{NAME}.init_streams: the TCN has embedding blocks but no embedding was given")
         self._synth = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def _tap_constants(self, q: dict, emb: torch.Tensor, b: int) -> torch.Tensor:
@@ -316,17 +410,18 @@ class StreamingUnetTcn(HopSession):
     def _down_tcn(self, feats: torch.Tensor) -> dict:
         """[1, rows, ldB] features of frame s -> {tensor name: this frame} with the down stack's outputs and the TCN's."""
         b, pk = self.streams, self._packs
+        live = self._live(0)
         cur = dict(self._cur)
         cur["in"] = feats.view(self._in_shape)
         for i, (c, lay) in enumerate(zip(self._down, pk["down"])):
             hip.conv2d_step(cur[c["src"]], self._rings[c["src"]], None, None, lay["wt"], lay["bias"], lay["M"], b, c["f_out"],
                             c["kf"], c["kt"], c["sf"], c["df"], c["dt"], c["pf"], False, lay["act"], lay["slope"],
-                            out=cur[f"d{i}"])
+                            out=cur[f"d{i}"], **live)
         x = cur[f"d{len(self._down) - 1}"].view(1, -1, self._ldb)
         for i, q in enumerate(pk["blocks"]):
             hip.conv1x1(x, b, q["in_wt"], q["H"], out=self._y1)
             hip.gated_tcn_step(self._y1, self._tcn_rings[i], self._counter, q["wl"], q["wr"], q["P"], q["dilation"], b, 1,
-                               q["pro_left"], q["pro_right"], self._emb_taps[i], out=self._g)
+                               q["pro_left"], q["pro_right"], self._emb_taps[i], out=self._g, span=self._span)
             y = self._xbuf[i % 2]
             hip.conv1x1(self._g, b, q["out_wt"], x.shape[1], res=x, out=y)
             x = y
@@ -350,17 +445,26 @@ class StreamingUnetTcn(HopSession):
             if self._flushing and j == first:
                 x1, x2 = torch.zeros_like(x1), torch.zeros_like(x2)
             hip.conv2d_step(x1, r1, x2, r2, lay["wt"], lay["bias"], lay["M"], b, c["f_out"], c["kf"], c["kt"], c["sf"], c["df"],
-                            c["dt"], c["pf"], True, lay["act"], lay["slope"], out=self._upout[j])
+                            c["dt"], c["pf"], True, lay["act"], lay["slope"], out=self._upout[j], **self._live(sh))
         return self._upout[-1].view(1, -1, self._ldb)
 
+    def _live(self, shift: int) -> dict:
+        """What a slot session adds to a ps_conv2d_step launch whose current tensors run `shift` frames behind the hop."""
+        return {} if self._span is None else dict(counter=self._counter, span=self._span, shift=shift)
+
     def _synthesise(self, mask: torch.Tensor, out: torch.Tensor) -> None:
-        """mask of frame s - D x the features of that frame -> its hop of samples (the iSTFT's frame index is _synth)."""
+        """mask of frame s - D x the features of that frame -> its hop of samples (the iSTFT's frame index is _synth; in a
+        slot session counter - D - the slot's birth)."""
         b, pk = self.streams, self._packs
         feats = self._feat_ring[0:1] if self._feat_ring is not None else self._feats
         enh = hip.real_mask(feats, mask, self._mask_act)
         syn, _ = hip.conv1x1(enh, b, pk["wt_s"], self.n_fft,
                              out=torch.empty(1, self.n_fft, self._ldb, dtype=torch.float32, device=self.device))
-        hip.istft_step(syn, pk["window"], self._tail, out, self._synth, self.hop_length, self._out_mode)
+        if self._span is not None:
+            hip.istft_step(syn, pk["window"], self._tail, out, self._counter, self.hop_length, self._out_mode, span=self._span,
+                           shift=self.delay_frames)
+        else:
+            hip.istft_step(syn, pk["window"], self._tail, out, self._synth, self.hop_length, self._out_mode)
 
     def _pairs(self, cur: dict) -> list:
         pairs = [(cur[k], r) for k, r in self._rings.items() if r is not None]
@@ -380,7 +484,10 @@ class StreamingUnetTcn(HopSession):
             cur = self._down_tcn(self._feats)
             mask = self._up_path(cur)
             queue = [(wins[i], self._queue)]
-            if self._mute:
+            if self._span is not None:     # a slot session: every hop synthesises, one commit, one counter
+                self._synthesise(mask, out[:, i * hop:(i + 1) * hop])
+                hip.stream_commit(hip.commit_table(self._pairs(cur) + queue), self._counter, self.device)
+            elif self._mute:
                 hip.stream_commit(hip.commit_table(self._pairs(cur) + queue), self._counter, self.device)
             else:
                 self._synthesise(mask, out[:, i * hop:(i + 1) * hop])
@@ -408,3 +515,8 @@ class StreamingUnetTcn(HopSession):
             self._flushing = False
         hip.istft_step(None, self._packs["window"], self._tail, out[:, held * hop:], self._synth, hop, self._out_mode,
                        flush=True)
+
+    def _flush_slot(self, out: torch.Tensor, slot: int) -> None:
+        """close(): the tail of one slot, with the window sum of its own frames (B = 1 on its tail row and span row)."""
+        hip.istft_step(None, self._packs["window"], self._tail[slot:slot + 1], out, self._counter, self.hop_length,
+                       self._out_mode, flush=True, span=self._span[slot:slot + 1], shift=self.delay_frames)
