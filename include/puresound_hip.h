@@ -566,6 +566,7 @@ int ps_stream_overlap_f32(const float* frames, const float* wins, float* tail, f
  *   the window sum of ps_istft_ola_f32, edge frames included, summed in the same order.  frames [n_fft][ldf] (b < B read),
  *   tail [B][n_fft-hop],
  *   out row stride ld_out; out_mode PS_OUT_*.  n_fft % hop == 0, n_fft <= 8192 (n_fft = hop: no tail, flush emits nothing).
+ *   Any *counter >= 0: the kernel reads window[j + d*hop] for the frame t - d and never forms the sample index t*hop + j.
  * ps_stream_commit_f32: for each of the n_pairs <= PS_MAX_RING_PAIRS entries of the HOST array pairs_host (copied into the
  *   kernel arguments): ring[r] = ring[r+1] for r < slots-1, then ring[slots-1] = src (`count` floats per slot, a multiple of
  *   4, 16-byte aligned; slots = 1 is a plain copy: the window queue, carried recurrent states); then *counter += 1

@@ -245,16 +245,16 @@ __global__ __launch_bounds__(256) void istft_step_kernel(const float* __restrict
       out[(size_t)b * ld_out + j] = acc;
     }
   } else {
-    const int base = t * hop;  // first sample emitted: frame t's first (step), or the first one past the last frame's hop (flush)
-    const int t_last = flush ? t - 1 : t;
+    // Sample g = t * hop + j (the first emitted is frame t's first in a step, the first one past the last frame's hop in a
+    // flush) is covered by the frames u = t - d, d_first >= d >= d_last, at window index g - u * hop = j + d * hop <= n_fft - 1.
+    // Neither t * hop nor g is formed: they pass an int once t reaches 2^31 / hop, long before the counter's own limit.
+    const int d_last = flush ? 1 : 0;
     for (int j = tid; j < emit; j += 256) {
-      const int g = base + j;
-      int t_hi = g / hop;
-      if (t_hi > t_last) t_hi = t_last;
-      const int t_lo = (g - n_fft + 1 <= 0) ? 0 : (g - n_fft + 1 + hop - 1) / hop;
+      int d_first = (n_fft - 1 - j) / hop;
+      if (d_first > t) d_first = t;  // no frame before frame 0
       float wsum = 0.f;
-      for (int u = t_lo; u <= t_hi; ++u) {
-        const float w = window[g - u * hop];
+      for (int d = d_first; d >= d_last; --d) {  // increasing u
+        const float w = window[j + d * hop];
         wsum += w * w;
       }
       float acc = ola[j];

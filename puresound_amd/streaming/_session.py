@@ -6,7 +6,9 @@ A streamer provides: `_build_packs(device)` (sets self._packs from the current p
 run advances), `_body(hops)` (the launches of `hops` hops: self._io[hops] = (input [B, hops*hop], output [B, hops*hop],
 windows [hops, B*window])), `_flush_into(out)`; it may set `max_hops` and override `_around_body`.  Its init_streams checks
 its own arguments, calls `_begin` and allocates what `_state` returns; `_queue` [B, window], `_tail` [B, window - hop] and
-`_counter` (int32 [1], the device frame counter) are allocated here.
+`_counter` (int32 [1], the device frame counter) are allocated here.  Every session, block or slot, stops at FRAME_LIMIT frames
+(`_run`): below it no kernel sees a frame index past INT32_MAX, and a kernel must not form a larger quantity from it in an int
+(the sample index t * hop does not fit: ps_istft_step_f32 indexes its window without it).
 
 A model delay (unet_tcn.py): a streamer whose model looks `delay_frames` = D frames ahead passes D to the constructor.  Its
 first D computed frames run the body with `self._mute` set -- always eagerly -- and emit nothing: the body advances the model
@@ -179,13 +181,16 @@ class HopSession:
         return None if mute else out.clone()
 
     def _run(self, chunk: torch.Tensor) -> torch.Tensor:
-        """Whole hops past the priming -> their output samples, in pieces of at most max_hops hops.  In a slot session: the
-        frame limit before the chunk, the hops each slot's stream was fed after it."""
+        """Whole hops past the priming -> their output samples, in pieces of at most max_hops hops.  The frame limit of every
+        session before the chunk (nothing has moved when it raises); in a slot session the hops each slot's stream was fed
+        after it.  `frames` is the device frame counter of every streamer, and a second counter a streamer keeps runs behind
+        it (unet_tcn.py: _synth = frames - delay_frames), so the one bound covers both."""
         k = chunk.shape[1] // self.hop_length
-        if self._slots is not None and self.frames + k > FRAME_LIMIT:
+        if self.frames + k > FRAME_LIMIT:
+            way_out = ("close the streams and call init_slots()" if self._slots is not None
+                       else "flush the streams and call init_streams()")
             raise RuntimeError(f"{type(self).__name__}: {self.frames} + {k} frames pass this session's limit of {FRAME_LIMIT} "
-                               f"(2**31 - 1 - K_MAX: the device frame counter is an int32); close the streams and call "
-                               f"init_slots() for a new session")
+                               f"(2**31 - 1 - K_MAX: the device frame counter is an int32); {way_out} for a new session")
         self._ready()
         step = self.max_hops * self.hop_length if self.max_hops else chunk.shape[1]
         # frames inside the model's delay (a slot session has none: a slot's frames are live or dead by its span)

@@ -253,15 +253,6 @@ class StreamingDPRNN(HopSession):
                              span=self._span, counter=self._counter if self._span is not None else None)
         hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
 
-    def _run(self, chunk: torch.Tensor) -> torch.Tensor:
-        """(a block session has the frame limit too; the core checks a slot session's, with its own way out)"""
-        k = chunk.shape[1] // self.hop_length
-        if self._slots is None and self.frames + k > FRAME_LIMIT:
-            raise RuntimeError(f"StreamingDPRNN: {self.frames} + {k} frames pass this session's limit of {FRAME_LIMIT} "
-                               f"(2**31 - 1 - K_MAX: the device frame counter is an int32); flush the streams and call "
-                               f"init_streams() for a new session")
-        return super()._run(chunk)
-
     def _flush_into(self, out: torch.Tensor, tail: Optional[torch.Tensor] = None) -> None:
         hip.free_decode_step(None, None, self._packs["dec_w"], self._tail if tail is None else tail, out, self.hop_length,
                              out_mode=self._out_mode, flush=True)

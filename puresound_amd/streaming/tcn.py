@@ -39,7 +39,7 @@ from ..nnet.conv_tasnet import TCN, ConvTasNet
 from ..nnet.lobe.encoder import FreeEncDec
 from ..nnet.lobe.norm import ChanLN, norm_plan
 # K_MAX: frames per launch at most, step_chunk splits longer chunks (the rings hold (P-1)*dilation + K_MAX frames);
-# FRAME_LIMIT: where a slot session stops, INT32_MAX: the death of a stream that has not ended
+# FRAME_LIMIT: where a session stops (HopSession._run), INT32_MAX: the death of a stream that has not ended
 from ._session import FRAME_LIMIT, INT32_MAX, K_MAX, HopSession, check_on_device  # noqa: F401
 
 

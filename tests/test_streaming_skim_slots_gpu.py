@@ -14,6 +14,7 @@ import skim_step_ref as R
 from conftest import rel_max
 from detweights import det_state_dict, det_wave
 from test_streaming_dprnn_slots_gpu import _check_against_offline, _chunks, _cycled_spans, _fp32, _offline, _tiled_spans
+from test_streaming_long_run_gpu import same_bits_at_a_small_counter
 from test_streaming_skim import _build
 from test_streaming_skim_gpu import _Mods, _cols
 from test_streaming_slots_gpu import _run_slots, _zero
@@ -497,7 +498,7 @@ def test_changed_weights_refresh_the_open_slots_terms(dev):
     assert torch.equal(torch.cat(b)[s.latency_samples:], torch.cat(a, dim=1)[0])
 
 
-def test_errors_name_the_way_out(dev):
+def test_errors_name_the_way_out(dev, H):
     from puresound_amd.streaming import StreamingSkiMExtractor, skim
     model, _ = _model(VAD, dev)
     s = StreamingSkiMExtractor(model)
@@ -556,7 +557,8 @@ def test_errors_name_the_way_out(dev):
     s._counter.fill_(near)
     s.frames = near
     s._span[1, 0] = near                                       # (a stream that is live here)
-    y = s.step_chunk(x[:, :8 * hop].contiguous())
+    # ... and what it returns here is what it returns at a small counter that agrees with `near` modulo K * NS
+    y = same_bits_at_a_small_counter(s, H, near, 1, x[:, :8 * hop].contiguous())
     assert bool(torch.isfinite(y).all()) and s.frames == near + 8 and int(s._counter) == near + 8
     with pytest.raises(RuntimeError) as info:
         s.step_chunk(x)
