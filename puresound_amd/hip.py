@@ -919,20 +919,18 @@ def conv2d_step(x1: torch.Tensor, ring1: Optional[torch.Tensor], x2: Optional[to
         raise RuntimeError(f"conv2d_step: out must be a contiguous {(1, m, f_out, ld)} tensor")
     r1 = 0 if ring1 is None else ring1.shape[0]
     r2 = 0 if ring2 is None else ring2.shape[0]
-    if span is not None:
+    slots = span is not None
+    if slots:
         _check_span(span, b, x1, "conv2d_step")
         if counter is None or counter.dtype != torch.int32 or counter.device != x1.device:
             raise RuntimeError("conv2d_step: span comes with the int32 frame counter on x1's device")
-        check(lib().ps_conv2d_step_slots_f32(ptr(x1), ptr(ring1), c1, r1, ptr(x2), ptr(ring2), c2, r2, ptr(wt), ptr(bias), ptr(y),
-                                             m, f_in, b, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, f_out, int(transposed),
-                                             ACT_KINDS[act], ptr(slope), ptr(counter), ptr(span), int(shift),
-                                             stream_ptr(x1.device)), "ps_conv2d_step_slots_f32")
-        return y
-    if counter is not None or shift:
+    elif counter is not None or shift:
         raise RuntimeError("conv2d_step: counter and shift come with span")
-    check(lib().ps_conv2d_step_f32(ptr(x1), ptr(ring1), c1, r1, ptr(x2), ptr(ring2), c2, r2, ptr(wt), ptr(bias), ptr(y), m,
-                                   f_in, b, ld, kf, kt, stride_f, dil_f, dil_t, pad_f, f_out, int(transposed), ACT_KINDS[act],
-                                   ptr(slope), stream_ptr(x1.device)), "ps_conv2d_step_f32")
+    args = (ptr(x1), ptr(ring1), c1, r1, ptr(x2), ptr(ring2), c2, r2, ptr(wt), ptr(bias), ptr(y), m, f_in, b, ld, kf, kt,
+            stride_f, dil_f, dil_t, pad_f, f_out, int(transposed), ACT_KINDS[act], ptr(slope),
+            *((ptr(counter), ptr(span), int(shift)) if slots else ()), stream_ptr(x1.device))
+    rc = lib().ps_conv2d_step_slots_f32(*args) if slots else lib().ps_conv2d_step_f32(*args)
+    check(rc, "ps_conv2d_step_slots_f32" if slots else "ps_conv2d_step_f32")
     return y
 
 
@@ -957,16 +955,16 @@ def istft_step(frames: Optional[torch.Tensor], window: torch.Tensor, tail: torch
         if frames is None or frames.shape[:2] != (1, n_fft) or not frames.is_contiguous():
             raise RuntimeError("istft_step: frames must be a contiguous [1, n_fft, ldB] tensor")
         ldf = frames.shape[2]
-    if span is not None:
+    slots = span is not None
+    if slots:
         _check_span(span, b, tail, "istft_step")
-        check(lib().ps_istft_step_slots_f32(ptr(frames), ldf, ptr(window), ptr(tail), ptr(out), out.stride(0), ptr(counter),
-                                            ptr(span), int(shift), b, n_fft, hop, _abi.PS_OUT[out_mode], int(flush),
-                                            stream_ptr(tail.device)), "ps_istft_step_slots_f32")
-        return out
-    if shift:
+    elif shift:
         raise RuntimeError("istft_step: shift comes with span")
-    check(lib().ps_istft_step_f32(ptr(frames), ldf, ptr(window), ptr(tail), ptr(out), out.stride(0), ptr(counter), b, n_fft,
-                                  hop, _abi.PS_OUT[out_mode], int(flush), stream_ptr(tail.device)), "ps_istft_step_f32")
+    args = (ptr(frames), ldf, ptr(window), ptr(tail), ptr(out), out.stride(0), ptr(counter),
+            *((ptr(span), int(shift)) if slots else ()), b, n_fft, hop, _abi.PS_OUT[out_mode], int(flush),
+            stream_ptr(tail.device))
+    rc = lib().ps_istft_step_slots_f32(*args) if slots else lib().ps_istft_step_f32(*args)
+    check(rc, "ps_istft_step_slots_f32" if slots else "ps_istft_step_f32")
     return out
 
 
@@ -1015,16 +1013,13 @@ def dwconv_step(x: torch.Tensor, ring: torch.Tensor, counter: torch.Tensor, w: t
     y = out if out is not None else torch.zeros_like(x)
     if y.shape != x.shape or not y.is_contiguous():
         raise RuntimeError("dwconv_step: out must be a contiguous tensor of x's shape")
-    pro_ref = C.byref(pro) if pro is not None else None
-    if span is not None:
+    slots = span is not None
+    if slots:
         _check_span(span, streams, x, "dwconv_step")
-        check(lib().ps_dwconv_step_slots_f32(ptr(x), ptr(ring), ring.shape[0], ptr(counter), ptr(span), ptr(w), ptr(b), ptr(y),
-                                             h, streams, frames, ld, p, dilation, pro_ref, stream_ptr(x.device)),
-              "ps_dwconv_step_slots_f32")
-        return y
-    check(lib().ps_dwconv_step_f32(ptr(x), ptr(ring), ring.shape[0], ptr(counter), ptr(w), ptr(b), ptr(y), h, streams, frames,
-                                   ld, p, dilation, pro_ref, stream_ptr(x.device)),
-          "ps_dwconv_step_f32")
+    args = (ptr(x), ptr(ring), ring.shape[0], ptr(counter), *((ptr(span),) if slots else ()), ptr(w), ptr(b), ptr(y), h,
+            streams, frames, ld, p, dilation, C.byref(pro) if pro is not None else None, stream_ptr(x.device))
+    rc = lib().ps_dwconv_step_slots_f32(*args) if slots else lib().ps_dwconv_step_f32(*args)
+    check(rc, "ps_dwconv_step_slots_f32" if slots else "ps_dwconv_step_f32")
     return y
 
 
@@ -1052,18 +1047,15 @@ def gated_tcn_step(y: torch.Tensor, ring: torch.Tensor, counter: torch.Tensor, w
     g = out if out is not None else torch.zeros_like(y)
     if g.shape != y.shape:
         raise RuntimeError("gated_tcn_step: out must be a contiguous tensor of y's shape")
-    if span is not None:
+    slots = span is not None
+    if slots:
         _check_span(span, streams, y, "gated_tcn_step")
-        check(lib().ps_gated_tcn_step_slots_f32(ptr(y), ptr(ring), ring.shape[0], ptr(counter), ptr(span), ptr(wl), ptr(wr),
-                                                ptr(emb_taps), C.byref(pro_left) if pro_left is not None else None,
-                                                C.byref(pro_right) if pro_right is not None else None, ptr(g), h, streams,
-                                                frames, ld, taps, dilation, stream_ptr(y.device)),
-              "ps_gated_tcn_step_slots_f32")
-        return g
-    check(lib().ps_gated_tcn_step_f32(ptr(y), ptr(ring), ring.shape[0], ptr(counter), ptr(wl), ptr(wr), ptr(emb_taps),
-                                      C.byref(pro_left) if pro_left is not None else None,
-                                      C.byref(pro_right) if pro_right is not None else None, ptr(g), h, streams, frames, ld,
-                                      taps, dilation, stream_ptr(y.device)), "ps_gated_tcn_step_f32")
+    args = (ptr(y), ptr(ring), ring.shape[0], ptr(counter), *((ptr(span),) if slots else ()), ptr(wl), ptr(wr),
+            ptr(emb_taps), C.byref(pro_left) if pro_left is not None else None,
+            C.byref(pro_right) if pro_right is not None else None, ptr(g), h, streams, frames, ld, taps, dilation,
+            stream_ptr(y.device))
+    rc = lib().ps_gated_tcn_step_slots_f32(*args) if slots else lib().ps_gated_tcn_step_f32(*args)
+    check(rc, "ps_gated_tcn_step_slots_f32" if slots else "ps_gated_tcn_step_f32")
     return g
 
 
@@ -1095,18 +1087,17 @@ def free_decode_step(feats: Optional[torch.Tensor], mask: Optional[torch.Tensor]
             raise RuntimeError("free_decode_step: feats and mask of one shape expected")
     ws_bytes = 0 if flush else lib().ps_free_decode_step_workspace_bytes(b, frames, win)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=tail.device) if ws_bytes else None
-    if span is not None:
+    slots = span is not None
+    if slots:
         _check_span(span, b, tail, "free_decode_step")
         if flush or counter is None or counter.dtype != torch.int32 or counter.device != tail.device:
             raise RuntimeError("free_decode_step: a span goes with the int32 device frame counter and never with flush")
-        check(lib().ps_free_decode_step_slots_f32(ptr(feats), ptr(mask), _abi.PS_ACT[mask_act], ld, ptr(w), ptr(tail), ptr(out),
-                                                  out.stride(0), ptr(span), ptr(counter), b, frames, c, win, hop,
-                                                  _abi.PS_OUT[out_mode], ptr(ws), ws_bytes, stream_ptr(tail.device)),
-              "ps_free_decode_step_slots_f32")
-        return out
-    check(lib().ps_free_decode_step_f32(ptr(feats), ptr(mask), _abi.PS_ACT[mask_act], ld, ptr(w), ptr(tail), ptr(out),
-                                        out.stride(0), b, frames, c, win, hop, _abi.PS_OUT[out_mode], int(flush), ptr(ws),
-                                        ws_bytes, stream_ptr(tail.device)), "ps_free_decode_step_f32")
+    # (the slot entry takes the span and the counter, and no flush flag: it never flushes)
+    args = (ptr(feats), ptr(mask), _abi.PS_ACT[mask_act], ld, ptr(w), ptr(tail), ptr(out), out.stride(0),
+            *((ptr(span), ptr(counter)) if slots else ()), b, frames, c, win, hop, _abi.PS_OUT[out_mode],
+            *(() if slots else (int(flush),)), ptr(ws), ws_bytes, stream_ptr(tail.device))
+    rc = lib().ps_free_decode_step_slots_f32(*args) if slots else lib().ps_free_decode_step_f32(*args)
+    check(rc, "ps_free_decode_step_slots_f32" if slots else "ps_free_decode_step_f32")
     return out
 
 
@@ -1155,16 +1146,14 @@ def dprnn_block_step(x: torch.Tensor, counter: torch.Tensor, intra: dict, inter:
             or tuple(intra["pt"].shape) != (hidden, c) or tuple(inter["pt"].shape) != (hidden, c) \
             or intra["wt"].device != x.device or inter["wt"].device != x.device:
         raise RuntimeError(f"dprnn_block_step: passes packed for C = {c}, H = {hidden} on {x.device} expected")
-    if span is not None:
+    slots = span is not None
+    if slots:
         _check_span(span, streams, x, "dprnn_block_step")
-        check(lib().ps_dprnn_block_step_slots_f32(ptr(x), ptr(out), ptr(counter), ptr(span), C.byref(intra["struct"]),
-                                                  C.byref(inter["struct"]), ptr(h_intra), ptr(c_intra), ptr(h_bank),
-                                                  ptr(c_bank), c, hidden, k_seg, streams, frames, ld, ldb,
-                                                  stream_ptr(x.device)), "ps_dprnn_block_step_slots_f32")
-        return out
-    check(lib().ps_dprnn_block_step_f32(ptr(x), ptr(out), ptr(counter), C.byref(intra["struct"]), C.byref(inter["struct"]),
-                                        ptr(h_intra), ptr(c_intra), ptr(h_bank), ptr(c_bank), c, hidden, k_seg, streams,
-                                        frames, ld, ldb, stream_ptr(x.device)), "ps_dprnn_block_step_f32")
+    args = (ptr(x), ptr(out), ptr(counter), *((ptr(span),) if slots else ()), C.byref(intra["struct"]),
+            C.byref(inter["struct"]), ptr(h_intra), ptr(c_intra), ptr(h_bank), ptr(c_bank), c, hidden, k_seg, streams,
+            frames, ld, ldb, stream_ptr(x.device))
+    rc = lib().ps_dprnn_block_step_slots_f32(*args) if slots else lib().ps_dprnn_block_step_f32(*args)
+    check(rc, "ps_dprnn_block_step_slots_f32" if slots else "ps_dprnn_block_step_f32")
     return out
 
 
@@ -1250,14 +1239,13 @@ def skim_block_step(x: torch.Tensor, counter: torch.Tensor, block: dict, seg_sta
                 raise RuntimeError(f"{who}: {what}: states [H, ldb], terms [C, ldb] and banks [NS, H, ldb] of one H, ldb and NS "
                                    f"expected (got {tuple(t.shape)} for {name})")
             setattr(st, name, ptr(t))
-    if span is not None:
+    slots = span is not None
+    if slots:
         _check_span(span, streams, x, who)
-        check(lib().ps_skim_block_step_slots_f32(ptr(x), ptr(out), ptr(counter), ptr(span), C.byref(block["struct"]),
-                                                 C.byref(st), c, hidden, int(seg), ns, streams, frames, ld, ldb,
-                                                 stream_ptr(x.device)), "ps_skim_block_step_slots_f32")
-        return out
-    check(lib().ps_skim_block_step_f32(ptr(x), ptr(out), ptr(counter), C.byref(block["struct"]), C.byref(st), c, hidden,
-                                       int(seg), ns, streams, frames, ld, ldb, stream_ptr(x.device)), "ps_skim_block_step_f32")
+    args = (ptr(x), ptr(out), ptr(counter), *((ptr(span),) if slots else ()), C.byref(block["struct"]), C.byref(st), c,
+            hidden, int(seg), ns, streams, frames, ld, ldb, stream_ptr(x.device))
+    rc = lib().ps_skim_block_step_slots_f32(*args) if slots else lib().ps_skim_block_step_f32(*args)
+    check(rc, "ps_skim_block_step_slots_f32" if slots else "ps_skim_block_step_f32")
     return out
 
 

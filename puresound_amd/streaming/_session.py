@@ -1,6 +1,7 @@
-"""The session mechanics the hop-by-hop streamers share (spectral.py, tcn.py): B streams fed whole hops, a priming phase
-while the first analysis window fills, then chunks of hops through the subclass's kernels -- eagerly, or as one captured
-graph per number of hops in a launch -- and a flush of the overlap-add tail.
+"""The session mechanics the hop-by-hop streamers share (spectral.py, unet_tcn.py; tcn.py, dprnn.py and skim.py through
+FreeEncSession, _free.py): B streams fed whole hops, a priming phase while the first analysis window fills, then chunks of
+hops through the subclass's kernels -- eagerly, or as one captured graph per number of hops in a launch -- and a flush of the
+overlap-add tail.
 
 A streamer provides: `_build_packs(device)` (sets self._packs from the current parameters), `_state()` (every tensor a body
 run advances), `_body(hops)` (the launches of `hops` hops: self._io[hops] = (input [B, hops*hop], output [B, hops*hop],

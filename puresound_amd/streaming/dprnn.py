@@ -20,7 +20,8 @@ Arithmetic: exact fp32 products throughout, whatever the model's gemm_precision;
 order (the two 1x1 convolutions always take ps_conv1x1_f32's tiled kernel: MIN_GEMM_COLUMNS), so a stream's output does not depend on B, on its neighbours or on how its hops are split into calls.  The streamer
 packs its own weights from the parameters; the model's own setting and plans are left as they were.  The enrolment states are
 computed once per session by the model's own offline pieces, in the model's own arithmetic.  The session around the kernels
-(priming, step / step_chunk / flush, eager run or graph replay, the capture) is HopSession's: streaming/_session.py.
+(priming, step / step_chunk / flush, eager run or graph replay, the capture) is HopSession's: streaming/_session.py; the
+encoder, output_fc, decoder and commit of a chunk, their checks and packs are RecurrentFreeSession's: streaming/_free.py.
 
 Slots (init_slots / open / end / close; the bookkeeping is HopSession's): a session of fixed capacity B whose columns begin
 and end streams of their own while it runs.  Per slot the device holds a span (birth, death) of absolute frame indices; frame
@@ -38,33 +39,18 @@ from typing import List, Optional
 import torch
 
 from .. import hip
-from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
 from ..nnet.dprnn import DPRNN
-from ..nnet.lobe.encoder import FreeEncDec
+# MIN_GEMM_COLUMNS: the fewest columns a 1x1 convolution of this streamer runs on (unet_tcn.py and callers take it from here)
+from ._free import MIN_GEMM_COLUMNS, RecurrentFreeSession, check_front, check_recurrent  # noqa: F401
 # K_MAX: frames per launch at most, step_chunk splits longer chunks; FRAME_LIMIT: where a session stops (the device frame
 # counter is an int32, and a launch reads up to K_MAX frames past it); INT32_MAX: the death of a stream that has not ended
 from ._session import FRAME_LIMIT, INT32_MAX, K_MAX, HopSession, check_on_device  # noqa: F401
-
-#: the 1x1 convolutions always run on at least this many columns (the rows are at least 128 wide; the columns past the chunk
-#: hold values nobody reads): ps_conv1x1_f32 has another kernel, with another order of summation, for 64 columns or fewer,
-#: and a stream's bits must not depend on how many columns share its launch
-MIN_GEMM_COLUMNS = 65
 
 
 def check_streamable(model) -> None:
     """Raise NotImplementedError naming the reason when `model` is not a configuration this streamer computes exactly."""
     name = "StreamingDPRNN"
-    if not isinstance(model, SoTaskWrapModule):
-        raise NotImplementedError(f"{name}: a SoTaskWrapModule (got {type(model).__name__})")
-    if not isinstance(model.encoder, FreeEncDec):
-        raise NotImplementedError(f"{name}: encoder {type(model.encoder).__name__}: only the free encoder (FreeEncDec) streams "
-                                  f"here; conv-STFT models stream through StreamingSeparator")
-    win, hop = model.encoder.win_length, model.encoder.hop_length
-    if win % hop:
-        raise NotImplementedError(f"{name}: win = {win} is not a multiple of hop = {hop}")
-    if win % 4 or win > 256:
-        raise NotImplementedError(f"{name}: win = {win}: a multiple of 4 up to 256 (the window queue moves in float4 "
-                                  f"columns, the decoder keeps a window per stream in LDS)")
+    check_front(model, name)
     m = model.masker
     if not isinstance(m, DPRNN):
         raise NotImplementedError(f"{name}: masker {type(m).__name__}: DPRNN only (ConvTasNet streams through "
@@ -81,29 +67,12 @@ def check_streamable(model) -> None:
     if bool(model.embedding_free_tse) != bool(m.embedding_free_tse):
         raise NotImplementedError(f"{name}: embedding_free_tse differs between the wrapper ({model.embedding_free_tse}) and "
                                   f"the masker ({m.embedding_free_tse})")
-    if m.output_fc[0].weight.numel() != 1:
-        raise NotImplementedError(f"{name}: PReLU with per-channel slopes is not on the HIP path")
-    pair = (model.mask_type.lower(), model.f_type.lower())
-    if pair != ("real", "real"):
-        raise NotImplementedError(f"{name}: mask pairing {pair}: the free encoder uses (real, real) only")
-    if model.mask_constraint.lower() not in _MASK_ACTS:
-        raise NotImplementedError(f"{name}: mask_constraint {model.mask_constraint!r}")
-    if model.output_constraint.lower() not in ("linear", "sigmoid"):
-        raise NotImplementedError(f"{name}: output_constraint {model.output_constraint!r}: linear or sigmoid")
-    c = model.encoder.encoder.weight.shape[0]
-    if m.input_size != c or m.output_fc[1].out_channels != c:
-        raise NotImplementedError(f"{name}: shapes: the encoder has {c} channels, the DPRNN takes {m.input_size} and returns "
-                                  f"{m.output_fc[1].out_channels}; a mask per encoder channel is needed")
-    if not hip.dprnn_block_step_ok(m.input_size, m.hidden_size, m.seg_size):
-        raise NotImplementedError(f"{name}: shapes: ps_dprnn_block_step_f32 has no kernel for (C, H, K) = ({m.input_size}, "
-                                  f"{m.hidden_size}, {m.seg_size}): a tile of 16 streams needs (2 C + 6 H) * 64 bytes of LDS, "
-                                  f"64 KiB at most")
-    if model.training:
-        raise NotImplementedError(f"{name}: the model is in training mode -- call .eval()")
+    check_recurrent(model, name, "DPRNN", hip.dprnn_block_step_ok, "ps_dprnn_block_step_f32",
+                    "(2 C + 6 H) * 64 bytes of LDS, 64 KiB at most")
     check_on_device(model, name)
 
 
-class StreamingDPRNN(HopSession):
+class StreamingDPRNN(RecurrentFreeSession):
     """Hop-by-hop inference of a causal DPRNN separator / enrolment-seeded speaker extractor for B streams (see the module
     docstring).
 
@@ -118,27 +87,15 @@ class StreamingDPRNN(HopSession):
     and bit-identical to a block session of that stream.
     """
 
-    max_hops = K_MAX
-    _how_to_start = "call init_streams() first (or init_slots())"
-
-    def __init__(self, model: SoTaskWrapModule):
-        check_streamable(model)
-        super().__init__(model, model.encoder.win_length, model.encoder.hop_length)
-        self.win_length = self.window
+    check_streamable = staticmethod(check_streamable)
 
     # -- weights ------------------------------------------------------------------------------------------------------
     def _build_packs(self, dev: torch.device) -> None:
         """fp32 weights packed for the kernels, held by the streamer: a captured graph keeps reading these tensors."""
-        f32 = dict(dtype=torch.float32, device=dev)
-        enc, m = self.model.encoder, self.model.masker
+        m = self.model.masker
         blocks = [(hip.pack_dprnn_pass(m.intra_rnn[i], m.intra_proj[i], m.intra_norm[i], dev),
                    hip.pack_dprnn_pass(m.inter_rnn[i], m.inter_proj[i], m.inter_norm[i], dev)) for i in range(m.n_blocks)]
-        slope = m.output_fc[0].weight.detach().to(**f32).contiguous()
-        self._packs = dict(enc_wt=hip.pack_wt(enc.encoder.weight.detach().to(**f32)[:, 0, :]),
-                           dec_w=enc.decoder.weight.detach().to(**f32).contiguous(), blocks=blocks,
-                           out_wt=hip.pack_wt(m.output_fc[1].weight.detach().to(**f32)),
-                           out_b=m.output_fc[1].bias.detach().to(**f32).contiguous(), out_slope=slope,
-                           out_pro=hip.make_prologue(0, True, None, 0.0, 0.0, None, None, slope))
+        self._packs = dict(self._free_packs(dev), blocks=blocks)
 
     # -- session ------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -146,19 +103,15 @@ class StreamingDPRNN(HopSession):
         """Start `streams` new streams.  enroll [streams, L'] on the model's device: the enrolment of each stream, required iff
         the model is embedding_free_tse; the inter-LSTM states its pass ends in are computed here, once, and seed the banks.
         Every other state is zeroed."""
-        if int(streams) < 1:
-            raise ValueError("init_streams: streams >= 1")
+        b = self._at_least_one(streams, "init_streams: streams")
         model, m = self.model, self.model.masker
         if (enroll is not None) != bool(model.embedding_free_tse):
             raise ValueError("StreamingDPRNN.init_streams: an enrolment [streams, L'] is required iff the model is "
                              "embedding_free_tse")
         dev = next(model.parameters()).device
-        b = int(streams)
         seeds = None
         if enroll is not None:
-            hip.require_device(enroll, "StreamingDPRNN.init_streams")
-            if enroll.dim() != 2 or enroll.shape[0] != b:
-                raise ValueError(f"StreamingDPRNN.init_streams: enroll must be [{b}, L'], got {tuple(enroll.shape)}")
+            self._check_enrolments(enroll, b)
             seeds = self._seeds(enroll)
         self._new_session(b, dev, use_graph)
         if seeds is not None:
@@ -191,9 +144,7 @@ class StreamingDPRNN(HopSession):
     @torch.no_grad()
     def init_slots(self, capacity: int, use_graph: bool = True) -> None:
         """Start a slot session of `capacity` columns, every slot idle (every state zeroed); open() starts a stream."""
-        if int(capacity) < 1:
-            raise ValueError("init_slots: capacity >= 1")
-        self._new_session(int(capacity), next(self.model.parameters()).device, use_graph)
+        self._new_session(self._at_least_one(capacity, "init_slots: capacity"), next(self.model.parameters()).device, use_graph)
         self._make_slots()
 
     def _enrolment_rule(self) -> tuple:
@@ -219,40 +170,12 @@ class StreamingDPRNN(HopSession):
         return [self._queue, self._tail, self._counter] + [t for pair in self._intra + self._banks for t in pair]
 
     # -- one chunk ----------------------------------------------------------------------------------------------------
-    def _buffers(self, hops: int) -> dict:
-        """Activation buffers of a `hops`-frame chunk: [1, C, ld] over N = hops * B columns."""
-        if hops not in self._bufs:
-            n = hops * self.streams
-            ld = hip.padded_frames(n)
-            c = self.model.masker.input_size
-            z = lambda: torch.zeros(1, c, ld, dtype=torch.float32, device=self.device)  # noqa: E731
-            self._bufs[hops] = dict(n=n, feats=z(), x0=z(), x1=z(), mask=z())
-        return self._bufs[hops]
-
-    def _body(self, hops: int) -> None:
-        """`hops` frames of every stream: input _io[hops][0] [B, hops*hop] -> output _io[hops][1] [B, hops*hop]."""
-        chunk, out, wins = self._io[hops]
-        hop, win, pk = self.hop_length, self.win_length, self._packs
-        bufs = self._buffers(hops)
-        c, n = self.model.masker.input_size, bufs["n"]
-        feats = bufs["feats"]
-        hip.stream_windows(self._queue, chunk, wins, hop)
-        frames, _ = hip.frame(wins.view(1, -1), win, win)               # [1, win, ld]: column f*B + b
-        cols = max(n, MIN_GEMM_COLUMNS)
-        hip.conv1x1(frames, cols, pk["enc_wt"], c, out=feats)
-        if self.model.encoder.output_active:
-            hip.activation_(feats, "relu", None, n)
+    def _masker(self, hops: int, bufs: dict, feats: torch.Tensor) -> torch.Tensor:
+        """The blocks, one launch each, alternating between two buffers, then output_fc."""
         x = feats
-        for i, (intra, inter) in enumerate(pk["blocks"]):
+        for i, (intra, inter) in enumerate(self._packs["blocks"]):
             y = bufs["x0"] if i % 2 == 0 else bufs["x1"]
             hip.dprnn_block_step(x, self._counter, intra, inter, *self._intra[i], *self._banks[i], self.streams, hops, out=y,
                                  span=self._span)
             x = y
-        hip.conv1x1(x, cols, pk["out_wt"], c, pk["out_pro"], pk["out_b"], out=bufs["mask"])
-        hip.free_decode_step(feats, bufs["mask"], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode,
-                             span=self._span, counter=self._counter if self._span is not None else None)
-        hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
-
-    def _flush_into(self, out: torch.Tensor, tail: Optional[torch.Tensor] = None) -> None:
-        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail if tail is None else tail, out, self.hop_length,
-                             out_mode=self._out_mode, flush=True)
+        return self._mask_head(x, bufs)

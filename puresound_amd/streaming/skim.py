@@ -30,7 +30,8 @@ Arithmetic: exact fp32 products throughout, whatever the model's gemm_precision;
 order (the 1x1 convolutions always take ps_conv1x1_f32's tiled kernel: MIN_GEMM_COLUMNS), so a stream's output does not depend
 on B, on its neighbours or on how its hops are split into calls.  The streamer packs its own weights from the parameters; the
 model's own setting and plans are left as they were.  The session around the kernels (priming, step / step_chunk / flush,
-eager run or graph replay, the capture) is HopSession's: streaming/_session.py.
+eager run or graph replay, the capture) is HopSession's: streaming/_session.py; the encoder, output_fc, decoder and commit of
+a chunk, their checks and packs are RecurrentFreeSession's: streaming/_free.py.
 
 Slots (init_slots / open / end / close; the bookkeeping is HopSession's): a session of fixed capacity B whose columns begin
 and end streams of their own while it runs.  Per slot the device holds a span (birth, death) of absolute frame indices; frame
@@ -51,28 +52,16 @@ from typing import List, Optional
 import torch
 
 from .. import hip
-from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
-from ..nnet.lobe.encoder import FreeEncDec
 from ..nnet.lobe.trivial import FiLM, Gate
 from ..nnet.skim import SkiM
+from ._free import MIN_GEMM_COLUMNS, RecurrentFreeSession, check_front, check_recurrent
 from ._session import FRAME_LIMIT, INT32_MAX, K_MAX, HopSession, check_on_device  # noqa: F401
-from .dprnn import MIN_GEMM_COLUMNS
 
 
 def check_streamable(model) -> None:
     """Raise NotImplementedError naming the reason when `model` is not a configuration this streamer computes exactly."""
     name = "StreamingSkiMExtractor"
-    if not isinstance(model, SoTaskWrapModule):
-        raise NotImplementedError(f"{name}: a SoTaskWrapModule (got {type(model).__name__})")
-    if not isinstance(model.encoder, FreeEncDec):
-        raise NotImplementedError(f"{name}: encoder {type(model.encoder).__name__}: only the free encoder (FreeEncDec) streams "
-                                  f"here; conv-STFT models stream through StreamingSeparator")
-    win, hop = model.encoder.win_length, model.encoder.hop_length
-    if win % hop:
-        raise NotImplementedError(f"{name}: win = {win} is not a multiple of hop = {hop}")
-    if win % 4 or win > 256:
-        raise NotImplementedError(f"{name}: win = {win}: a multiple of 4 up to 256 (the window queue moves in float4 "
-                                  f"columns, the decoder keeps a window per stream in LDS)")
+    check_front(model, name)
     m = model.masker
     if not isinstance(m, SkiM):
         raise NotImplementedError(f"{name}: masker {type(m).__name__}: SkiM only (DPRNN streams through StreamingDPRNN, "
@@ -95,29 +84,12 @@ def check_streamable(model) -> None:
     for i, f in enumerate(fusions):
         if f is not None and not (isinstance(f, FiLM) and f.inp_norm):
             raise NotImplementedError(f"{name}: block {i}: fusion {type(f).__name__}: FiLM with its input norm, or none")
-    if m.output_fc[0].weight.numel() != 1:
-        raise NotImplementedError(f"{name}: PReLU with per-channel slopes is not on the HIP path")
-    pair = (model.mask_type.lower(), model.f_type.lower())
-    if pair != ("real", "real"):
-        raise NotImplementedError(f"{name}: mask pairing {pair}: the free encoder uses (real, real) only")
-    if model.mask_constraint.lower() not in _MASK_ACTS:
-        raise NotImplementedError(f"{name}: mask_constraint {model.mask_constraint!r}")
-    if model.output_constraint.lower() not in ("linear", "sigmoid"):
-        raise NotImplementedError(f"{name}: output_constraint {model.output_constraint!r}: linear or sigmoid")
-    c = model.encoder.encoder.weight.shape[0]
-    if m.input_size != c or m.output_fc[1].out_channels != c:
-        raise NotImplementedError(f"{name}: shapes: the encoder has {c} channels, the SkiM takes {m.input_size} and returns "
-                                  f"{m.output_fc[1].out_channels}; a mask per encoder channel is needed")
-    if not hip.skim_block_step_ok(m.input_size, m.hidden_size, m.seg_size):
-        raise NotImplementedError(f"{name}: shapes: ps_skim_block_step_f32 has no kernel for (C, H, K) = ({m.input_size}, "
-                                  f"{m.hidden_size}, {m.seg_size}): a tile of 16 streams needs (2 max(C, H) + 2 H + "
-                                  f"max(4 H, 2 C)) * 64 bytes of LDS, 160 KiB at most")
-    if model.training:
-        raise NotImplementedError(f"{name}: the model is in training mode -- call .eval()")
+    check_recurrent(model, name, "SkiM", hip.skim_block_step_ok, "ps_skim_block_step_f32",
+                    "(2 max(C, H) + 2 H + max(4 H, 2 C)) * 64 bytes of LDS, 160 KiB at most")
     check_on_device(model, name)
 
 
-class StreamingSkiMExtractor(HopSession):
+class StreamingSkiMExtractor(RecurrentFreeSession):
     """Hop-by-hop inference of a causal SkiM speaker extractor (or plain SkiM separator) for B streams (see the module
     docstring).
 
@@ -134,26 +106,13 @@ class StreamingSkiMExtractor(HopSession):
     that stream.
     """
 
-    max_hops = K_MAX
-    _how_to_start = "call init_streams() first (or init_slots())"
-
-    def __init__(self, model: SoTaskWrapModule):
-        check_streamable(model)
-        super().__init__(model, model.encoder.win_length, model.encoder.hop_length)
-        self.win_length = self.window
+    check_streamable = staticmethod(check_streamable)
 
     # -- weights ------------------------------------------------------------------------------------------------------
     def _build_packs(self, dev: torch.device) -> None:
         """fp32 weights packed for the kernels, held by the streamer: a captured graph keeps reading these tensors."""
-        f32 = dict(dtype=torch.float32, device=dev)
-        enc, m = self.model.encoder, self.model.masker
-        slope = m.output_fc[0].weight.detach().to(**f32).contiguous()
-        self._packs = dict(enc_wt=hip.pack_wt(enc.encoder.weight.detach().to(**f32)[:, 0, :]),
-                           dec_w=enc.decoder.weight.detach().to(**f32).contiguous(),
-                           blocks=[hip.pack_skim_block(m, i, dev) for i in range(m.n_blocks)],
-                           out_wt=hip.pack_wt(m.output_fc[1].weight.detach().to(**f32)),
-                           out_b=m.output_fc[1].bias.detach().to(**f32).contiguous(), out_slope=slope,
-                           out_pro=hip.make_prologue(0, True, None, 0.0, 0.0, None, None, slope))
+        m = self.model.masker
+        self._packs = dict(self._free_packs(dev), blocks=[hip.pack_skim_block(m, i, dev) for i in range(m.n_blocks)])
         if self._slots is not None:                                # (changed weights in a session: FiLM's terms follow them;
             for slot, embed in enumerate(self._slot_embeds):       # a slot session's, in place, for the slots that are open)
                 if embed is not None and self._slots[slot] is not None:
@@ -170,10 +129,8 @@ class StreamingSkiMExtractor(HopSession):
         model's device; a masker without takes neither.  The masker's own L2 normalisation is applied here, and what the
         embedding adds to every FiLM's scale and bias is computed here, once.  Every other state is zeroed."""
         name = "StreamingSkiMExtractor.init_streams"
-        if int(streams) < 1:
-            raise ValueError("init_streams: streams >= 1")
+        b = self._at_least_one(streams, "init_streams: streams")
         model, m = self.model, self.model.masker
-        b = int(streams)
         if m.embed_dim > 0 and (enroll is None) == (embed is None):
             raise ValueError(f"{name}: the masker takes an embedding (embed_dim = {m.embed_dim}): pass exactly one of enroll "
                              f"[streams, L'] and embed [streams, {m.embed_dim}]")
@@ -181,9 +138,7 @@ class StreamingSkiMExtractor(HopSession):
             raise ValueError(f"{name}: the masker takes no embedding (embed_dim = 0): pass neither enroll nor embed")
         dev = next(model.parameters()).device
         if enroll is not None:
-            hip.require_device(enroll, name)
-            if enroll.dim() != 2 or enroll.shape[0] != b:
-                raise ValueError(f"{name}: enroll must be [{b}, L'], got {tuple(enroll.shape)}")
+            self._check_enrolments(enroll, b)
             embed = model.inference_tse_embedding(enroll)
         if embed is not None:
             hip.require_device(embed, name)
@@ -208,10 +163,8 @@ class StreamingSkiMExtractor(HopSession):
     def init_slots(self, capacity: int, use_graph: bool = True) -> None:
         """Start a slot session of `capacity` columns, every slot idle (every state and every FiLM term zeroed); open() starts
         a stream."""
-        if int(capacity) < 1:
-            raise ValueError("init_slots: capacity >= 1")
         m = self.model.masker
-        b, dev = int(capacity), next(self.model.parameters()).device
+        b, dev = self._at_least_one(capacity, "init_slots: capacity"), next(self.model.parameters()).device
         self._begin(b, dev, use_graph)
         self._make_slots()
         h, c, ldb = m.hidden_size, m.input_size, hip.padded_frames(max(b, MIN_GEMM_COLUMNS))
@@ -324,43 +277,15 @@ class StreamingSkiMExtractor(HopSession):
         return [self._queue, self._tail, self._counter] + [t for group in self._seg + self._mem + self._banks for t in group]
 
     # -- one chunk ----------------------------------------------------------------------------------------------------
-    def _buffers(self, hops: int) -> dict:
-        """Activation buffers of a `hops`-frame chunk: [1, C, ld] over N = hops * B columns."""
-        if hops not in self._bufs:
-            n = hops * self.streams
-            ld = hip.padded_frames(max(n, MIN_GEMM_COLUMNS))
-            c = self.model.masker.input_size
-            z = lambda: torch.zeros(1, c, ld, dtype=torch.float32, device=self.device)  # noqa: E731
-            self._bufs[hops] = dict(n=n, feats=z(), x0=z(), x1=z(), mask=z())
-        return self._bufs[hops]
-
-    def _body(self, hops: int) -> None:
-        """`hops` frames of every stream: input _io[hops][0] [B, hops*hop] -> output _io[hops][1] [B, hops*hop]."""
-        chunk, out, wins = self._io[hops]
-        hop, win, pk = self.hop_length, self.win_length, self._packs
+    def _masker(self, hops: int, bufs: dict, feats: torch.Tensor) -> torch.Tensor:
+        """The blocks, one launch each, alternating between two buffers, then output_fc."""
         m = self.model.masker
-        bufs = self._buffers(hops)
-        c, n = m.input_size, bufs["n"]
-        feats = bufs["feats"]
-        hip.stream_windows(self._queue, chunk, wins, hop)
-        frames, _ = hip.frame(wins.view(1, -1), win, win)               # [1, win, ld]: column f*B + b
-        cols = max(n, MIN_GEMM_COLUMNS)
-        hip.conv1x1(frames, cols, pk["enc_wt"], c, out=feats)
-        if self.model.encoder.output_active:
-            hip.activation_(feats, "relu", None, n)
         x = feats
         last = m.n_blocks - 1
-        for i, block in enumerate(pk["blocks"]):
+        for i, block in enumerate(self._packs["blocks"]):
             y = bufs["x0"] if i % 2 == 0 else bufs["x1"]
             hip.skim_block_step(x, self._counter, block, self._seg[i], m.seg_size, self.streams, hops, y, terms=self._terms[i],
                                 bank_in=self._banks[i - 1] if i > 0 else None, mem_state=self._mem[i] if i < last else None,
                                 bank_out=self._banks[i] if i < last else None, span=self._span)
             x = y
-        hip.conv1x1(x, cols, pk["out_wt"], c, pk["out_pro"], pk["out_b"], out=bufs["mask"])
-        hip.free_decode_step(feats, bufs["mask"], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode,
-                             span=self._span, counter=self._counter if self._span is not None else None)
-        hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
-
-    def _flush_into(self, out: torch.Tensor, tail: Optional[torch.Tensor] = None) -> None:
-        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail if tail is None else tail, out, self.hop_length,
-                             out_mode=self._out_mode, flush=True)
+        return self._mask_head(x, bufs)

@@ -26,7 +26,9 @@ birth[b] <= g < death[b].  ps_dwconv_step_slots_f32 reads a frame that is not li
 ps_free_decode_step_slots_f32 adds nothing for it; everything else in a hop is column-wise, so dead columns compute values
 nobody reads.  A slot's output is the offline output of its stream delayed by latency_samples, whatever the other slots do.
 The session around the kernels (priming, step / step_chunk / flush, eager run or graph replay, the capture) and the slot
-bookkeeping (open / end / close, the spans, the frame limit) are HopSession's: streaming/_session.py.
+bookkeeping (open / end / close, the spans, the frame limit) are HopSession's: streaming/_session.py.  What follows from the
+free encoder and decoder (their checks and packs, the front and back of a chunk, the flush) is FreeEncSession's:
+streaming/_free.py; this file has the checks of the masker, its packs, rings and buffers, and the TCN blocks (`_masker`).
 """
 from typing import Dict, List, Optional
 
@@ -34,10 +36,9 @@ import torch
 
 from .. import hip
 from .._abi import PS_NORM_AFFINE
-from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
 from ..nnet.conv_tasnet import TCN, ConvTasNet
-from ..nnet.lobe.encoder import FreeEncDec
 from ..nnet.lobe.norm import ChanLN, norm_plan
+from ._free import FreeEncSession, check_back, check_front
 # K_MAX: frames per launch at most, step_chunk splits longer chunks (the rings hold (P-1)*dilation + K_MAX frames);
 # FRAME_LIMIT: where a session stops (HopSession._run), INT32_MAX: the death of a stream that has not ended
 from ._session import FRAME_LIMIT, INT32_MAX, K_MAX, HopSession, check_on_device  # noqa: F401
@@ -46,17 +47,7 @@ from ._session import FRAME_LIMIT, INT32_MAX, K_MAX, HopSession, check_on_device
 def check_streamable(model) -> None:
     """Raise NotImplementedError naming the reason when `model` is not a configuration this streamer computes exactly."""
     name = "StreamingConvTasNet"
-    if not isinstance(model, SoTaskWrapModule):
-        raise NotImplementedError(f"{name}: a SoTaskWrapModule (got {type(model).__name__})")
-    if not isinstance(model.encoder, FreeEncDec):
-        raise NotImplementedError(f"{name}: encoder {type(model.encoder).__name__}: only the free encoder (FreeEncDec) streams "
-                                  f"here; conv-STFT models stream through StreamingSeparator")
-    win, hop = model.encoder.win_length, model.encoder.hop_length
-    if win % hop:
-        raise NotImplementedError(f"{name}: win = {win} is not a multiple of hop = {hop}")
-    if win % 4 or win > 256:
-        raise NotImplementedError(f"{name}: win = {win}: a multiple of 4 up to 256 (the window queue moves in float4 "
-                                  f"columns, the decoder keeps a window per stream in LDS)")
+    check_front(model, name)
     m = model.masker
     if not isinstance(m, ConvTasNet):
         raise NotImplementedError(f"{name}: masker {type(m).__name__}: ConvTasNet only")
@@ -73,13 +64,7 @@ def check_streamable(model) -> None:
         raise NotImplementedError(f"{name}: embedding_free_tse (the enrolment seeds the masker) does not stream")
     if any(m.tcn_with_embed) and model.speaker_net is None:
         raise NotImplementedError(f"{name}: tcn_with_embed blocks without a speaker_net to compute the embedding")
-    pair = (model.mask_type.lower(), model.f_type.lower())
-    if pair != ("real", "real"):
-        raise NotImplementedError(f"{name}: mask pairing {pair}: the free encoder uses (real, real) only")
-    if model.mask_constraint.lower() not in _MASK_ACTS:
-        raise NotImplementedError(f"{name}: mask_constraint {model.mask_constraint!r}")
-    if model.output_constraint.lower() not in ("linear", "sigmoid"):
-        raise NotImplementedError(f"{name}: output_constraint {model.output_constraint!r}: linear or sigmoid")
+    check_back(model, name)
     for blk in (b for stack in m.tcn_list for b in stack):
         dsc = blk.dconv[0]
         if any(a.weight.numel() != 1 for a in (blk.in_conv[2], dsc.depthwise[2], dsc.pointwise[2])):
@@ -87,7 +72,7 @@ def check_streamable(model) -> None:
     check_on_device(model, name)
 
 
-class StreamingConvTasNet(HopSession):
+class StreamingConvTasNet(FreeEncSession):
     """Hop-by-hop inference of a causal Conv-TasNet separator / speaker extractor for B streams (see the module docstring).
 
     s = StreamingConvTasNet(model); s.init_streams(B, enroll); s.step(hop [B, hop]) -> [B, hop] or None while the first
@@ -101,20 +86,13 @@ class StreamingConvTasNet(HopSession):
     after latency_samples samples of constrain(0): slot_output_range(L, win, hop).
     """
 
-    max_hops = K_MAX
-    _how_to_start = "call init_streams() first (or init_slots())"
-
-    def __init__(self, model: SoTaskWrapModule):
-        check_streamable(model)
-        super().__init__(model, model.encoder.win_length, model.encoder.hop_length)
-        self.win_length = self.window
+    check_streamable = staticmethod(check_streamable)
 
     # -- weights ------------------------------------------------------------------------------------------------------
     def _build_packs(self, dev: torch.device) -> None:
         """Weights packed for the kernels (eval BatchNorm1d folded to scale / shift), held by the streamer: a captured
         graph keeps reading these tensors."""
         f32 = dict(dtype=torch.float32, device=dev)
-        enc = self.model.encoder
         blocks = []
         for blk in self._blocks:
             dsc = blk.dconv[0]
@@ -136,27 +114,22 @@ class StreamingConvTasNet(HopSession):
                 pro = None if kind == "cln" else hip.make_prologue(PS_NORM_AFFINE, True, None, 0.0, 1e-8, g, b, slope)
                 p[key] = (kind, g, b, slope, pro)
             blocks.append(p)
-        self._packs = dict(enc_wt=hip.pack_wt(enc.encoder.weight.detach().to(**f32)[:, 0, :]),
-                           dec_w=enc.decoder.weight.detach().to(**f32).contiguous(), blocks=blocks)
+        self._packs = dict(self._free_packs(dev), blocks=blocks)
 
     # -- session ------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def init_streams(self, streams: int = 1, enroll: Optional[torch.Tensor] = None, use_graph: bool = True) -> None:
         """Start `streams` new streams (every state zeroed).  enroll [streams, L'] on the model's device: the enrolment of
         each stream, required iff the model has a speaker_net; its embedding is computed here, once."""
-        if int(streams) < 1:
-            raise ValueError("init_streams: streams >= 1")
+        b = self._at_least_one(streams, "init_streams: streams")
         model, m = self.model, self.model.masker
         if (enroll is not None) != (model.speaker_net is not None):
             raise ValueError("StreamingConvTasNet.init_streams: an enrolment [streams, L'] is required iff the model has a "
                              "speaker_net")
         dev = next(model.parameters()).device
-        b = int(streams)
         self._emb = None
         if enroll is not None:
-            hip.require_device(enroll, "StreamingConvTasNet.init_streams")
-            if enroll.dim() != 2 or enroll.shape[0] != b:
-                raise ValueError(f"StreamingConvTasNet.init_streams: enroll must be [{b}, L'], got {tuple(enroll.shape)}")
+            self._check_enrolments(enroll, b)
             if any(m.tcn_with_embed):
                 dvec = model.inference_tse_embedding(enroll)[..., 0].float().contiguous()   # [B, E]
                 self._emb = hip.l2_normalize(dvec) if m.embed_norm else dvec
@@ -175,11 +148,9 @@ class StreamingConvTasNet(HopSession):
     @torch.no_grad()
     def init_slots(self, capacity: int, use_graph: bool = True) -> None:
         """Start a slot session of `capacity` columns, every slot idle (every state zeroed); open() starts a stream."""
-        if int(capacity) < 1:
-            raise ValueError("init_slots: capacity >= 1")
+        b = self._at_least_one(capacity, "init_slots: capacity")
         model, m = self.model, self.model.masker
         dev = next(model.parameters()).device
-        b = int(capacity)
         self._emb = None
         if model.speaker_net is not None and any(m.tcn_with_embed):
             self._emb = torch.zeros(b, m.embed_dim, dtype=torch.float32, device=dev)
@@ -221,7 +192,8 @@ class StreamingConvTasNet(HopSession):
                 rows = self._emb.t().repeat(1, hops)   # [E, N]
                 for r in res:
                     r[0, c:, :n] = rows
-            self._bufs[hops] = dict(n=n, ld=ld, res=res, y1=z(h), a1=z(h), y2=z(h), a2=z(h), y3=z(h), a3=z(h))
+            self._bufs[hops] = dict(n=n, ld=ld, res=res, feats=res[0][:, :c], y1=z(h), a1=z(h), y2=z(h), a2=z(h), y3=z(h),
+                                    a3=z(h))
         return self._bufs[hops]
 
     def _block(self, i: int, p: dict, x: torch.Tensor, out: torch.Tensor, bufs: dict, hops: int) -> None:
@@ -245,27 +217,11 @@ class StreamingConvTasNet(HopSession):
         src, pro = settle(y3, "pw", bufs["a3"])
         hip.conv1x1(src, n, p["out_wt"], c, pro, p["out_b"], res=x[:, :c], out=out[:, :c])
 
-    def _body(self, hops: int) -> None:
-        """`hops` frames of every stream: input _io[hops][0] [B, hops*hop] -> output _io[hops][1] [B, hops*hop]."""
-        chunk, out, wins = self._io[hops]
-        hop, win, pk = self.hop_length, self.win_length, self._packs
-        bufs = self._buffers(hops)
-        c, n = self.model.masker.input_dim, bufs["n"]
-        feats, x0, x1 = bufs["res"]
-        hip.stream_windows(self._queue, chunk, wins, hop)
-        frames, _ = hip.frame(wins.view(1, -1), win, win)               # [1, win, ld]: column f*B + b
-        hip.conv1x1(frames, n, pk["enc_wt"], c, out=feats[:, :c])
-        if self.model.encoder.output_active:
-            hip.activation_(feats[:, :c], "relu", None, n)
-        x = feats
-        for i, p in enumerate(pk["blocks"]):
+    def _masker(self, hops: int, bufs: dict, feats: torch.Tensor) -> torch.Tensor:
+        """The TCN blocks on the residual stream, alternating between two buffers -> the last block's output."""
+        x, x0, x1 = bufs["res"]
+        for i, p in enumerate(self._packs["blocks"]):
             y = x0 if i % 2 == 0 else x1
             self._block(i, p, x, y, bufs, hops)
             x = y
-        hip.free_decode_step(feats[:, :c], x[:, :c], pk["dec_w"], self._tail, out, hop, hops, self._mask_act, self._out_mode,
-                             span=self._span, counter=self._counter if self._span is not None else None)
-        hip.stream_commit_frames(hip.commit_table([(wins[hops - 1], self._queue)]), self._counter, hops, self.device)
-
-    def _flush_into(self, out: torch.Tensor, tail: Optional[torch.Tensor] = None) -> None:
-        hip.free_decode_step(None, None, self._packs["dec_w"], self._tail if tail is None else tail, out, self.hop_length,
-                             out_mode=self._out_mode, flush=True)
+        return x[:, :feats.shape[1]]
