@@ -443,6 +443,22 @@ size_t ps_lstm_fmajor_coop_workspace_bytes(const ps_lstm_args* args, int ldm);
 int ps_lstm_fmajor_coop_f16x2_f32(const ps_lstm_args* args, int ldm, const void* whh_image, const float* acc_scale,
                                   void* workspace, size_t workspace_bytes, void* stream);
 int ps_lstm_fmajor_f16x2_f32(const ps_lstm_args* args, int ldm, void* stream);
+/* ps_lstm_f32 for H = 256 / 192 with the recurrent product in v_mfma_f32_16x16x4_f32: fp32 operands and accumulation, every
+ * product exact, so the result differs from ps_lstm_f32's in the order of the H-term sums alone, and there is no range
+ * condition on h0 or on the weights.  args as ps_lstm_f32 -- gx CHANNEL-MAJOR [N][D*4H][ldt] (ps_conv1x1_f32's output), the
+ * same walks, states and state_shift, hout [N][D*H][ldt]; args->whh_t is not read.  W_hh is streamed from L2 every step (16
+ * sequences per workgroup, H / 32 waves of 32 hidden units each) out of whh_image, the host-packed fp32 image
+ * [D][H/32][H/16][2][4][64][4] floats (wave, k-group, row block, gate, lane, e), 16-byte aligned: element (w, kg, rb, g, lane, e) =
+ * W_hh[g*H + 32 w + 16 rb + lane % 16][16 kg + 4 (lane / 16) + e] of direction d (= whh_t[d][k][row]).  A sequence's result does
+ * not depend on N, on the sequences that share its workgroup, or on the grid.  No cross-workgroup dependency: any number of
+ * launches may be in flight.
+ * ps_lstm_h256_ok(args) = 1 when a launch qualifies, else 0: H = 256 or 192; D = 1 or 2; positive sizes, non-negative strides;
+ * the last frame (Q-1)*q_stride + (steps-1)*step_stride < ldt; state_shift 0 or 1; ldq >= Q when a state is given; gx and hout
+ * 4-byte aligned; N*Q < 2^30; and min(N, ceil(15/Q) + 1) * D*4H * ldt * 4 bytes < 2^31 (the gx of the utterances that 16
+ * consecutive sequences can touch lies under one buffer descriptor).  Refusals: PS_E_INVALID for null args, a null or
+ * unaligned image; PS_E_UNSUPPORTED when ps_lstm_h256_ok says 0. */
+int ps_lstm_h256_ok(const ps_lstm_args* args);
+int ps_lstm_h256_f32(const ps_lstm_args* args, const void* whh_image, void* stream);
 
 /* 50 % overlapped segmentation of the dual-path maskers (SplitMerge.split / merge, lobe/trivial.py:178-241; SkiM.split /
  * merge, skim.py:334-408) on rows of frames:

@@ -167,6 +167,8 @@ SIGNATURES = {
     "ps_lstm_fmajor_f16x2_f32": (C.c_int, [C.POINTER(LstmArgs), C.c_int, _vp]),
     "ps_lstm_fmajor_h256_ok": (C.c_int, [C.POINTER(LstmArgs), C.c_int]),
     "ps_lstm_fmajor_h256_f16x2_f32": (C.c_int, [C.POINTER(LstmArgs), C.c_int, _vp, C.POINTER(C.c_float), _vp]),
+    "ps_lstm_h256_ok": (C.c_int, [C.POINTER(LstmArgs)]),
+    "ps_lstm_h256_f32": (C.c_int, [C.POINTER(LstmArgs), _vp, _vp]),
     "ps_lstm_fmajor_coop_workspace_bytes": (C.c_size_t, [C.POINTER(LstmArgs), C.c_int]),
     "ps_lstm_fmajor_coop_f16x2_f32": (C.c_int, [C.POINTER(LstmArgs), C.c_int, _vp, C.POINTER(C.c_float), _vp, C.c_size_t, _vp]),
     "ps_unfold_taps_f32": (C.c_int, [_vp, _vp] + [C.c_int] * 7 + [_vp, _vp, _vp, C.c_int, _vp]),

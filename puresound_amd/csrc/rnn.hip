@@ -1012,6 +1012,7 @@ typedef unsigned u32x4l __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 #include "lstm_fm256.inc"
 #include "lstm_coop.inc"
+#include "lstm_fm256_f32.inc"
 
 }  // namespace ps
 
@@ -1049,6 +1050,18 @@ static bool lstm_fmajor_fits(const ps_lstm_args& a, int ldm) {
 static bool lstm_h256_fits(const ps_lstm_args& a, int ldm) {
   return sizes_ok(a, false) && (a.H == 256 || a.H == 192) && shift_ok(a, 1) && last_frame(a) < a.ldt && fmajor_ok(a, ldm) &&
          states_ok(a) && (long long)a.N * a.Q < (1LL << 30);
+}
+
+// channel-major gx, exact fp32 product (ps_lstm_h256_f32): the utterances that 16 consecutive flat sequences can touch lie
+// under one buffer descriptor of the kernel, so their gx must stay below 2 GiB
+static int h256_f32_span(const ps_lstm_args& a) {
+  const long long span = (15 + (long long)a.Q - 1) / a.Q + 1;
+  return (int)(span < a.N ? span : a.N);
+}
+static bool lstm_h256_f32_fits(const ps_lstm_args& a) {
+  return sizes_ok(a, false) && (a.H == 256 || a.H == 192) && shift_ok(a, 1) && last_frame(a) < a.ldt && states_ok(a) &&
+         !((uintptr_t)a.gx & 3) && !((uintptr_t)a.hout & 3) && (long long)a.N * a.Q < (1LL << 30) &&
+         (long long)h256_f32_span(a) * a.D * 4 * a.H * a.ldt * 4 < (1LL << 31);
 }
 
 // ---- dispatch: store widths, the cooperative launch's layout, the kernel choice ------------------------------------------
@@ -1274,6 +1287,30 @@ extern "C" int ps_lstm_fmajor_h256_f16x2_f32(const ps_lstm_args* args, int ldm, 
     });
   }
   return launch_status("ps_lstm_fmajor_h256_f16x2_f32");
+}
+
+extern "C" int ps_lstm_h256_ok(const ps_lstm_args* args) { return args && lstm_h256_f32_fits(*args) ? 1 : 0; }
+
+extern "C" int ps_lstm_h256_f32(const ps_lstm_args* args, const void* whh_image, void* stream) {
+  if (!args || !whh_image || ((uintptr_t)whh_image & 15)) {
+    set_error("ps_lstm_h256_f32: null argument or unaligned weight image");
+    return PS_E_INVALID;
+  }
+  if (!lstm_h256_f32_fits(*args)) {
+    set_error("ps_lstm_h256_f32: H = 256 or 192, D = 1 or 2, every frame inside the row, the gx of 16 sequences' utterances below "
+              "2 GiB (ps_lstm_h256_ok)");
+    return PS_E_UNSUPPORTED;
+  }
+  const ps_lstm_args& a = *args;
+  LstmH256F32 k{a, whh_image, h256_f32_span(a)};
+  const long long seqs = (long long)a.N * a.Q;
+  dim3 grid((unsigned)((seqs + 15) / 16), 1, a.D);
+  {
+    LaunchTimer timer("lstm", (hipStream_t)stream);
+    if (a.H == 256) hipLaunchKernelGGL((lstm_h256_f32_kernel<256>), grid, dim3(512), 0, (hipStream_t)stream, k);
+    else hipLaunchKernelGGL((lstm_h256_f32_kernel<192>), grid, dim3(384), 0, (hipStream_t)stream, k);
+  }
+  return launch_status("ps_lstm_h256_f32");
 }
 
 extern "C" size_t ps_lstm_fmajor_coop_workspace_bytes(const ps_lstm_args* args, int ldm) { return args ? coop_layout(*args, ldm).bytes : 0; }

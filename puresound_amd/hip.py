@@ -648,6 +648,65 @@ def lstm_fmajor_h256(gx_fm: torch.Tensor, whh_image: torch.Tensor, acc_scale, di
     return hout, state
 
 
+H256_F32_LSTM = os.environ.get("PS_H256_F32_LSTM", "1") != "0"   # 0: the fp32 arithmetic keeps ps_lstm_f32 at H = 256 / 192
+# (hidden size, directions) -> sequences per launch from which the models take ps_lstm_h256_f32; fewer, or a pair that is not
+# listed, stay on ps_lstm_f32.  A 16-sequence workgroup takes 21-45 us per step however few there are, the generic kernel's
+# 4-sequence workgroups ~25 us until they crowd the L2 -- which two directions do at half the sequences.  Each entry is the
+# smallest measured count at which the new entry wins by more than the runs' spread on both kinds of walk (SkiM's segments; one
+# sequence per utterance), with no measured loss above it; H = 192 in one direction lost at 128 on both walks and is not
+# listed (tools/bench_recurrent.py --which h256, profiles/lstm_h256_f32.txt).
+H256_F32_MIN_SEQS = {(256, 1): 128, (256, 2): 128, (192, 2): 128}
+
+
+def pack_whh_h256_f32(whh_t: torch.Tensor) -> torch.Tensor:
+    """weight_hh^T [D, H, 4H], H = 256 or 192 -> the fp32 image [D, H/32, H/16, 2, 4, 64, 4] of lstm_h256_f32 (wave, k-group,
+    row block, gate, lane, e; layout: include/puresound_hip.h).  A permutation alone: no host read-back, any device."""
+    d, hh, g = whh_t.shape
+    if hh not in (256, 192) or g != 4 * hh:
+        raise ValueError("pack_whh_h256_f32: whh_t must be [D, H, 4H] with H = 256 or 192")
+    nw, kgs = hh // 32, hh // 16
+    w = whh_t.detach().float().transpose(1, 2)                   # [D, 4H gate rows, H k]
+    w = w.reshape(d, 4, nw, 2, 16, kgs, 4, 4)                    # d, g, w, rb, row, kg, kq, e
+    w = w.permute(0, 2, 5, 3, 1, 6, 4, 7)                        # d, w, kg, rb, g, kq, row, e
+    return w.reshape(d, nw, kgs, 2, 4, 64, 4).contiguous()
+
+
+def lstm_h256_f32_pays(hidden: int, dirs: int, n: int, q: int) -> bool:
+    """The models' choice between lstm_h256_f32 and lstm() in the fp32 arithmetic: the switch, and enough sequences."""
+    return H256_F32_LSTM and n * q >= H256_F32_MIN_SEQS.get((hidden, dirs), n * q + 1)
+
+
+def lstm_h256_f32_ok(n: int, ldt: int, hidden: int, dirs: int, q: int, q_stride: int, steps: int, step_stride: int,
+                     ldq: int = 0, state_shift: int = 0) -> bool:
+    """Does ps_lstm_h256_f32 take this pass?  Asks ps_lstm_h256_ok with aligned stand-in pointers (never dereferenced); ldq: the
+    state tensors' row stride when the launch carries states (0: none)."""
+    a = LstmArgs()
+    a.gx = a.hout = 256
+    if ldq:
+        a.h0 = 256
+    a.N, a.H, a.D, a.ldt, a.ldq, a.state_shift = n, hidden, dirs, ldt, ldq, state_shift
+    a.Q, a.q_stride, a.steps, a.step_stride = q, q_stride, steps, step_stride
+    return bool(lib().ps_lstm_h256_ok(C.byref(a)))
+
+
+def lstm_h256_f32(gx: torch.Tensor, whh_image: torch.Tensor, dirs: int, q: int, q_stride: int, steps: int, step_stride: int,
+                  h0: Optional[torch.Tensor] = None, c0: Optional[torch.Tensor] = None, want_state: bool = False,
+                  state_shift: int = 0, state_out: Optional[tuple] = None, out: Optional[torch.Tensor] = None):
+    """ps_lstm_h256_f32: the H = 256 / 192 recurrence of lstm() with the product W_hh h in exact fp32 MFMA and W_hh streamed
+    from its packed image (pack_whh_h256_f32): gx padded [N, D*4H, ldt] -> (hout [N, D*H, ldt], final (h, c) or None)."""
+    require_device(gx, "lstm_h256_f32")
+    hidden = whh_image.shape[1] * 32
+    n, rows, ldt = gx.shape
+    if (rows != dirs * 4 * hidden or hidden not in (256, 192)
+            or tuple(whh_image.shape) != (dirs, hidden // 32, hidden // 16, 2, 4, 64, 4)):
+        raise RuntimeError("lstm_h256_f32: gx must be [N, D*4H, ldt] and the image pack_whh_h256_f32's")
+    _require_operand("lstm_h256_f32", gx.device, gx=gx, whh_image=whh_image)
+    a, hout, state = _lstm_args("lstm_h256_f32", gx, n, ldt, None, out, hidden, dirs, (q, q_stride, steps, step_stride),
+                                h0, c0, want_state, state_shift, state_out)
+    check(lib().ps_lstm_h256_f32(C.byref(a), ptr(whh_image), stream_ptr(gx.device)), "ps_lstm_h256_f32")
+    return hout, state
+
+
 def _coop_slices(dirs: int, groups: int, hidden: int) -> int:
     """slices per group the launcher picks: H / 32 (two waves each) while the launch fits the chip, else H / 64"""
     rounds = (groups * dirs + 7) // 8 * 8   # (both directions in one launch; one launch per direction beyond that: H / 64 too)

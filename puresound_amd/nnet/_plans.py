@@ -98,10 +98,14 @@ def lstm_plan(lstm: nn.LSTM, device, gemm: str = "fp32") -> dict:
         wih.append(_f32(getattr(lstm, "weight_ih_l0" + suf), device))
         bias.append(_f32(getattr(lstm, "bias_ih_l0" + suf), device) + _f32(getattr(lstm, "bias_hh_l0" + suf), device))
         whh.append(_f32(getattr(lstm, "weight_hh_l0" + suf), device).t().contiguous())
-    return dict(wih=hip.pack_wt(torch.cat(wih, 0)), wih_rows=torch.cat(wih, 0).contiguous(), wih_planes={},
+    plan = dict(wih=hip.pack_wt(torch.cat(wih, 0)), wih_rows=torch.cat(wih, 0).contiguous(), wih_planes={},
                 bias=torch.cat(bias).contiguous(),
                 whh_t=torch.stack(whh).contiguous(), H=hid, D=dirs, rows=dirs * 4 * hid, I=lstm.input_size,
                 planes=_PLANES[gemm])
+    if plan["planes"] == 0 and hid in (256, 192):
+        # fp32 arithmetic: W_hh's image for ps_lstm_h256_f32, packed here so that a graph capture holds no packing
+        plan["whh_h256_f32"] = hip.pack_whh_h256_f32(plan["whh_t"])
+    return plan
 
 
 def rnn_plan(rnn: nn.Module, device) -> dict:
@@ -263,6 +267,14 @@ def lstm_path(x: torch.Tensor, t: int, rnn: dict, proj: dict, norm: dict, q: int
     else:
         gx = torch.empty(n, rnn["rows"], ldt, dtype=torch.float32, device=dev)
         hip.conv1x1(x, t, rnn["wih"], rnn["rows"], None, rnn["bias"], out=gx)
+    if ("whh_h256_f32" in rnn and hip.lstm_h256_f32_pays(rnn["H"], rnn["D"], n, q)
+            and hip.lstm_h256_f32_ok(n, ldt, rnn["H"], rnn["D"], q, q_stride, steps, step_stride, state_shift=state_shift,
+                                     ldq=min([s.shape[2] for s in (h0, c0) + tuple(state_out or ()) if s is not None], default=0))):
+        # fp32 arithmetic at H = 256 / 192 (SkiM) with enough sequences: W_hh streamed in fragment order into exact fp32 MFMA
+        # (ps_lstm_h256_f32)
+        hseq, state = hip.lstm_h256_f32(gx, rnn["whh_h256_f32"], rnn["D"], q, q_stride, steps, step_stride, h0, c0, want_state,
+                                        state_shift, state_out, out=_h_rows(rnn, x, t, q, q_stride, steps, step_stride, lane))
+        return _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip), state
     hseq, state = hip.lstm(gx, rnn["whh_t"], rnn["H"], rnn["D"], q, q_stride, steps, step_stride, h0, c0, want_state,
                            state_shift, state_out, f16x2=rnn["planes"] == 2,
                            out=_h_rows(rnn, x, t, q, q_stride, steps, step_stride, lane))

@@ -68,7 +68,13 @@ class SingleRNN(PlanCache, nn.Module):
         else:
             hip.conv1x1(x, t, rnn["wih"], rnn["rows"], None, rnn["bias"], out=gx)
         # one sequence per utterance: q = 1, the steps walk the frame axis
-        hseq, _ = hip.lstm(gx, rnn["whh_t"], rnn["H"], rnn["D"], 1, ldt, t, 1)
+        if ("whh_h256_f32" in rnn and hip.lstm_h256_f32_pays(rnn["H"], rnn["D"], n, 1)
+                and hip.lstm_h256_f32_ok(n, ldt, rnn["H"], rnn["D"], 1, ldt, t, 1)):
+            # fp32 arithmetic at H = 256 / 192 with enough utterances (hip.H256_F32_MIN_SEQS): the exact fp32 MFMA recurrence
+            # (ps_lstm_h256_f32); the bidirectional speaker LSTM of tse_skim_v1 takes it from a batch of 128 on
+            hseq, _ = hip.lstm_h256_f32(gx, rnn["whh_h256_f32"], rnn["D"], 1, ldt, t, 1)
+        else:
+            hseq, _ = hip.lstm(gx, rnn["whh_t"], rnn["H"], rnn["D"], 1, ldt, t, 1)
         y, _ = hip.conv1x1(hseq, t, proj["wt"], proj["M"], None, proj["bias"],
                            out=torch.empty(n, proj["M"], ldt, dtype=torch.float32, device=x.device))
         return y

@@ -1,6 +1,9 @@
 """Timing of the recurrent configs (not the bench.py headline): BASELINE config 4 (DPRNN, 32 x 4 s per GPU) as
 ms/forward + samples/s, config 5 (demo preset, 64 streams, 320-sample chunks) as p50/p90 chunk latency.
-Prints one JSON line per config.  --profile brackets every kernel launch with events (ps_profile_*)."""
+Prints one JSON line per config.  --profile brackets every kernel launch with events (ps_profile_*).
+--which h256: per-launch time of the H = 256 / 192 recurrence entries side by side -- ps_lstm_h256_f32 (exact fp32 MFMA),
+ps_lstm_f32 (the generic kernel) and ps_lstm_fmajor_h256_f16x2_f32 (streamed fp16x2) -- on SkiM's launches at 32 x 4 s and on the
+sequence counts around hip.H256_F32_MIN_SEQS; --runs repeats every measurement (profiles/lstm_h256_f32.txt)."""
 import argparse
 import json
 import os
@@ -151,6 +154,74 @@ def cfg5(args):
                       "chunk_ms_p90": r["p90_ms"], "chunk_ms_max": r["max_ms"], "budget_ms": 20.0}))
 
 
+# name, H, D, N, Q, q_stride (None: the row), steps, step_stride, frames of a row
+H256_LAUNCHES = [
+    ("segment 864x150 H=256 D=1", 256, 1, 32, 27, 150, 150, 1, 4050),       # SkiM's segment LSTM at 32 x 4 s, causal
+    ("segment 864x150 H=256 D=2", 256, 2, 32, 27, 150, 150, 1, 4050),       # ... non-causal
+    ("segment 32x150 H=256 D=1", 256, 1, 2, 16, 150, 150, 1, 2400),
+    ("segment 64x150 H=256 D=1", 256, 1, 4, 16, 150, 150, 1, 2400),
+    ("segment 128x150 H=256 D=1", 256, 1, 8, 16, 150, 150, 1, 2400),
+    ("segment 128x150 H=256 D=2", 256, 2, 8, 16, 150, 150, 1, 2400),
+    ("segment 256x150 H=256 D=1", 256, 1, 16, 16, 150, 150, 1, 2400),
+    ("segment 432x150 H=256 D=1", 256, 1, 16, 27, 150, 150, 1, 4050),
+    ("mem 32x27 H=256 D=1", 256, 1, 32, 1, 0, 27, 1, 27),                   # SkiM's Mem-LSTM
+    ("mem 32x27 H=256 D=2", 256, 2, 32, 1, 0, 27, 1, 27),
+    ("single 128x1000 H=256 D=1", 256, 1, 128, 1, None, 1000, 1, 1000),     # one sequence per utterance (SingleRNN)
+    ("single 128x1000 H=256 D=2", 256, 2, 128, 1, None, 1000, 1, 1000),
+    ("segment 128x150 H=192 D=1", 192, 1, 8, 16, 150, 150, 1, 2400),
+    ("segment 128x150 H=192 D=2", 192, 2, 8, 16, 150, 150, 1, 2400),
+    ("segment 864x150 H=192 D=2", 192, 2, 32, 27, 150, 150, 1, 4050),
+    ("single 128x1000 H=192 D=1", 192, 1, 128, 1, None, 1000, 1, 1000),
+    ("single 128x1000 H=192 D=2", 192, 2, 128, 1, None, 1000, 1, 1000),
+    ("single 64x1000 H=192 D=2", 192, 2, 64, 1, None, 1000, 1, 1000),
+    ("speaker 32x3999 H=192 D=2", 192, 2, 32, 1, None, 3999, 1, 3999),      # the speaker LSTM of tse_skim_v1 at 32 x 4 s
+]
+
+
+def h256(args):
+    """One JSON line per launch of H256_LAUNCHES: ms of each entry, --runs times (a run: the median of 5 launches after 2; 3
+    after 1 for the two siblings), and the new entry's time per step."""
+    import statistics
+    from puresound_amd import hip
+    dev = "cuda:0"
+
+    def timed(fn, warm, reps):
+        for _ in range(warm):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+        return statistics.median(ts)
+
+    g = torch.Generator().manual_seed(3)
+    coop, hip.COOP_LSTM = hip.COOP_LSTM, False   # the streamed fp16x2 kernel, not the cooperative one
+    for name, h, d, n, q, qs, steps, ss, frames in H256_LAUNCHES:
+        ldt = hip.padded_frames(frames)
+        walk = (q, ldt if qs is None else qs, steps, ss)
+        gx = ((torch.rand(n, d * 4 * h, ldt, generator=g) * 2 - 1) * 3).to(dev)
+        whh = ((torch.rand(d, h, 4 * h, generator=g) * 2 - 1) * 0.06).to(dev)
+        img32 = hip.pack_whh_h256_f32(whh)
+        img16, sc16 = hip.pack_whh_h256(whh)
+        gx_fm = gx.transpose(1, 2).contiguous()
+        assert hip.lstm_h256_f32_ok(n, ldt, h, d, *walk)
+        ms = {"ps_lstm_h256_f32": [], "ps_lstm_f32": [], "ps_lstm_fmajor_h256_f16x2_f32": []}
+        for _ in range(args.runs):
+            ms["ps_lstm_h256_f32"].append(timed(lambda: hip.lstm_h256_f32(gx, img32, d, *walk), 2, 5))
+            ms["ps_lstm_f32"].append(timed(lambda: hip.lstm(gx, whh, h, d, *walk, f16x2=False), 1, 3))
+            ms["ps_lstm_fmajor_h256_f16x2_f32"].append(timed(lambda: hip.lstm_fmajor_h256(gx_fm, img16, sc16, d, *walk), 1, 3))
+        print(json.dumps({"launch": name, "steps": steps, "ms": {k: [round(v, 3) for v in vs] for k, vs in ms.items()},
+                          "us_per_step_h256_f32": round(1e3 * statistics.median(ms["ps_lstm_h256_f32"]) / steps, 2),
+                          "models_take_h256_f32": hip.lstm_h256_f32_pays(h, d, n, q)}), flush=True)
+        del gx, gx_fm
+    hip.COOP_LSTM = coop
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", default="cfg4,cfg5")
@@ -162,6 +233,7 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--streams", type=int, default=64)
     ap.add_argument("--chunks", type=int, default=500)
+    ap.add_argument("--runs", type=int, default=3, help="h256: repetitions of every measurement")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--flags", default="", help="kernel variant switches: PS_DBG_* names without the prefix, comma-separated")
     ap.add_argument("--gemm", default="fp32", choices=["fp32", "fp16x2", "bf16x3", "bf16"],
@@ -181,3 +253,5 @@ if __name__ == "__main__":
         cfg5(a)
     if "dpcrn" in a.which:
         dpcrn(a)
+    if "h256" in a.which:
+        h256(a)
