@@ -4,9 +4,11 @@ memory and streams only; all arithmetic happens in the HIP kernels.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
+import threading
 from typing import Optional, Sequence
 
 import torch
@@ -468,9 +470,20 @@ def attn_weights(logits: torch.Tensor, t: int, lengths: Optional[torch.Tensor] =
     return out
 
 
-COOP_LSTM = os.environ.get("PS_COOP_LSTM", "1") != "0"   # 0: always the streamed-weight kernel
+COOP_LSTM = os.environ.get("PS_COOP_LSTM", "1") != "0"   # the process default; 0: always the streamed-weight kernel
+_COOP_OFF = type("_CoopOff", (threading.local,), {"depth": 0})()   # .depth: coop_lstm_off() blocks this thread is inside
 _COOP_LAST = [None]
 RNN_KINDS = {"RNN": 0, "GRU": 2}
+
+
+@contextlib.contextmanager
+def coop_lstm_off():
+    """Inside the block, and in this thread only, lstm_fmajor_h256 takes the streamed-weight kernel whatever COOP_LSTM says."""
+    _COOP_OFF.depth += 1
+    try:
+        yield
+    finally:
+        _COOP_OFF.depth -= 1
 
 
 def _lstm_state_args(who: str, a: LstmArgs, n: int, rows: int, q: int, h0, c0, want_state: bool, state_out, device,
@@ -636,7 +649,7 @@ def lstm_fmajor_h256(gx_fm: torch.Tensor, whh_image: torch.Tensor, acc_scale, di
     sc = (C.c_float * 2)(float(acc_scale[0]), float(acc_scale[-1]))
     # few sequence groups (a speaker LSTM over all frames, SkiM's Mem-LSTMs): the cooperative kernel -- W_hh resident in the
     # registers of H / 32 CUs per group -- instead of streaming 1 MiB of it through one CU every step
-    ws_bytes = lib().ps_lstm_fmajor_coop_workspace_bytes(C.byref(a), ldm) if COOP_LSTM else 0
+    ws_bytes = lib().ps_lstm_fmajor_coop_workspace_bytes(C.byref(a), ldm) if COOP_LSTM and not _COOP_OFF.depth else 0
     if ws_bytes:
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=gx_fm.device)
         check(lib().ps_lstm_fmajor_coop_f16x2_f32(C.byref(a), ldm, ptr(whh_image), sc, ptr(ws), ws_bytes,

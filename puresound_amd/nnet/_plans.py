@@ -4,15 +4,14 @@ A plan holds the packed / transposed fp32 copies of a module's parameters that t
 fingerprint of the parameters so that load_state_dict / .to(device) / in-place edits invalidate it.  Plans hold
 raw device pointers through the tensors they keep alive; they are never pickled.
 """
+import os
+from collections import namedtuple
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from .. import hip
-
-
-import os
 
 FUSE_PROJ_LN = os.environ.get("PS_FUSE_PROJ_LN", "1") == "1"   # 0: separate projection GEMM + LayerNorm kernels
 FUSE_PROJ_LN_MAX_FRAMES = int(os.environ.get("PS_FUSE_PROJ_LN_MAX_FRAMES", "8192"))
@@ -98,8 +97,7 @@ def lstm_plan(lstm: nn.LSTM, device, gemm: str = "fp32") -> dict:
         wih.append(_f32(getattr(lstm, "weight_ih_l0" + suf), device))
         bias.append(_f32(getattr(lstm, "bias_ih_l0" + suf), device) + _f32(getattr(lstm, "bias_hh_l0" + suf), device))
         whh.append(_f32(getattr(lstm, "weight_hh_l0" + suf), device).t().contiguous())
-    plan = dict(wih=hip.pack_wt(torch.cat(wih, 0)), wih_rows=torch.cat(wih, 0).contiguous(), wih_planes={},
-                bias=torch.cat(bias).contiguous(),
+    plan = dict(wih=hip.pack_wt(torch.cat(wih, 0)), wih_rows=torch.cat(wih, 0).contiguous(), bias=torch.cat(bias).contiguous(),
                 whh_t=torch.stack(whh).contiguous(), H=hid, D=dirs, rows=dirs * 4 * hid, I=lstm.input_size,
                 planes=_PLANES[gemm])
     if plan["planes"] == 0 and hid in (256, 192):
@@ -151,6 +149,19 @@ def layernorm_plan(ln: nn.Module, device) -> dict:
     return dict(gamma=_f32(ln.gamma, device), beta=_f32(ln.beta, device), eps=float(ln.eps))
 
 
+def packed(plan: dict, key, build, *args):
+    """plan[key], made by build(*args) at the first call: a weight image that only some routes read."""
+    image = plan.get(key)
+    if image is None:
+        image = plan[key] = build(*args)
+    return image
+
+
+def packed_ln_image(lin: dict):
+    """linear_plan's 128 weight rows as the fp16x2 image hip.conv1x1_f16x2_ln reads: zero padded to 256 rows."""
+    return packed(lin, "f16x2_ln", lambda w: hip.pack_wt_f16x2(torch.cat([w, torch.zeros_like(w)])), lin["w_rows"])
+
+
 def _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip=True):
     """x + LN(proj(h)) behind a recurrence (second half of lstm_path); skip=False: LN(proj(h)) alone."""
     res = x if skip else None
@@ -171,11 +182,7 @@ def _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip=True):
     if (FUSE_GEMM_LN and rnn["planes"] == 2 and proj["M"] == 128 and proj["K"] % 32 == 0
             and hip.conv1x1_f16x2_ln_ok(n, proj["K"], 128, t)):
         # projection, LayerNorm and skip as ONE launch: the fp16x2 GEMM with the norm as its epilogue (|h| < 1 is its range)
-        if "f16x2_ln" not in proj:
-            w256 = torch.zeros(256, proj["K"], dtype=torch.float32, device=dev)
-            w256[:128] = proj["w_rows"]
-            proj["f16x2_ln"] = hip.pack_wt_f16x2(w256)
-        wf, we = proj["f16x2_ln"]
+        wf, we = packed_ln_image(proj)
         if amax is not None:   # the maxima of |y| ride along: the next recurrence's GEMM needs no pass of its own over y
             y, amax[0] = hip.conv1x1_f16x2_ln(hseq, t, wf, we, 128, proj["bias"], norm["gamma"], norm["beta"], norm["eps"], res,
                                               x_bound=1.0, want_amax=True)
@@ -184,9 +191,8 @@ def _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip=True):
     p = torch.empty(n, proj["M"], ldt, dtype=torch.float32, device=dev)
     if rnn["planes"] == 2 and proj["K"] >= 64:
         # the recurrence's arithmetic for its projection too: h is an LSTM output, |h| < 1 is its range
-        if "f16x2" not in proj:
-            proj["f16x2"] = hip.pack_wt_f16x2(proj["w_rows"])
-        hip.conv1x1_f16x2(hseq, t, proj["f16x2"][0], proj["f16x2"][1], proj["M"], None, proj["bias"], out=p, x_bound=1.0)
+        wf, we = packed(proj, "f16x2", hip.pack_wt_f16x2, proj["w_rows"])
+        hip.conv1x1_f16x2(hseq, t, wf, we, proj["M"], None, proj["bias"], out=p, x_bound=1.0)
     else:
         hip.conv1x1(hseq, t, proj["wt"], proj["M"], None, proj["bias"], out=p)
     return hip.chan_layernorm(p, t, norm["gamma"], norm["beta"], norm["eps"], res=res)
@@ -217,6 +223,84 @@ def _h_rows(rnn: dict, x: torch.Tensor, t: int, q: int, q_stride: int, steps: in
     return kept[1]
 
 
+# What one LSTM pass runs (lstm_route).  gemm: the input projection's arithmetic, "fp32" | "bf16" | "f16x2"; planes: of "bf16", 1
+# (operands rounded) or 3 (the fp32-accurate split), else 0; layout: of the gate pre-activations, "rows" (channel-major) |
+# "fmajor" (frame-major); kernel: the recurrence, "generic" | "generic_f16x2" | "fmajor128" | "fmajor256" | "h256_f32".
+Route = namedtuple("Route", "gemm planes layout kernel")
+
+
+def lstm_route(rnn: dict, n: int, ldt: int, t: int, walk: tuple, carried: bool = False, state_shift: int = 0,
+               standalone: bool = False) -> Route:
+    """Which input-projection GEMM, in which layout, feeding which recurrence entry: the one place that chooses, for every
+    LSTM pass of the models.  Launches nothing.  rnn: lstm_plan's scalars (planes, I, H, D, rows, whether it holds
+    "whh_h256_f32"); n, ldt, t: the rows [N, C, ldt] with t valid frames; walk = (Q, q_stride, steps, step_stride); carried:
+    the launch takes or returns states (h0, c0, want_state or state_out).  "h256_f32" stands under ps_lstm_h256_ok, which
+    lstm_recurrence asks behind the GEMM's launch, where it has always been asked (refused: "generic").
+
+    standalone: SingleRNN as a layer of its own (the speaker LSTM of tse_skim_v1), where no range is carried from pass to
+    pass.  Its choice differs from the maskers' in four ways, kept as found because each changes bits (a later decision):
+      1. H = 128 never takes the frame-major route (the maskers: in fp16x2 without carried states).
+      2. FMAJOR_LSTM is not consulted: H = 256 / 192 in fp16x2 is frame-major whatever the switch says.
+      3. fp16x2 off the frame-major routes runs the bf16x3 GEMM, which needs no range pass, and ps_lstm_f32 (the maskers:
+         hip.absmax, the fp16x2 GEMM, ps_lstm_f16x2_f32).
+      4. fp16x2 with I < 64 runs the fp32 GEMM and ps_lstm_f32 (the maskers: ps_lstm_f16x2_f32)."""
+    planes, I, H, D = rnn["planes"], rnn["I"], rnn["H"], rnn["D"]
+    gemm = ("bf16", planes) if planes and I >= 64 else ("fp32", 0)
+    if planes == 2 and I >= 64:
+        # H = 128 (the bottleneck LSTMs of DPCRN / DPARN): the 16-sequence recurrence that streams frame-major pre-activations
+        if (not standalone and FMAJOR_LSTM and H == 128 and not carried and state_shift == 0
+                and hip.lstm_fmajor_ok(n, ldt, H, D, *walk) and hip.conv1x1_f16x2_fmajor_ok(n, I, rnn["rows"], t, ldt)):
+            return Route("f16x2", 0, "fmajor", "fmajor128")
+        # H = 256 / 192 (SkiM's segment LSTMs, the speaker LSTM): W_hh streamed from L2 or resident in registers, states carried
+        if ((standalone or FMAJOR_LSTM) and H in (256, 192) and hip.lstm_fmajor_h256_ok(n, ldt, D, *walk)
+                and hip.conv1x1_f16x2_fmajor_ok(n, I, rnn["rows"], t, ldt)):
+            return Route("f16x2", 0, "fmajor", "fmajor256")
+        gemm = ("bf16", 3) if standalone else ("f16x2", 0)
+    # fp32 arithmetic at H = 256 / 192 with enough sequences (hip.H256_F32_MIN_SEQS): W_hh streamed into exact fp32 MFMA
+    if "whh_h256_f32" in rnn and hip.lstm_h256_f32_pays(H, D, n, walk[0]):
+        return Route(*gemm, "rows", "h256_f32")
+    return Route(*gemm, "rows", "generic_f16x2" if planes == 2 and not standalone else "generic")
+
+
+def lstm_gates(x: torch.Tensor, t: int, rnn: dict, route: Route, x_amax: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The input projection of every frame in route's arithmetic and layout -> gate pre-activations.  x_amax: the partial
+    maxima of |x| for the fp16x2 GEMM (None: measured here)."""
+    if route.gemm == "f16x2":
+        wf, we = packed(rnn, "wih_f16x2", hip.pack_wt_f16x2, rnn["wih_rows"])
+    if route.layout == "rows":
+        gx = torch.empty(x.shape[0], rnn["rows"], x.shape[2], dtype=torch.float32, device=x.device)
+    if route.gemm == "f16x2":
+        x_amax = x_amax if x_amax is not None else hip.absmax(x, t)
+        if route.layout == "fmajor":
+            return hip.conv1x1_f16x2_fmajor(x, t, wf, we, rnn["rows"], rnn["bias"], x_amax=x_amax)
+        hip.conv1x1_f16x2(x, t, wf, we, rnn["rows"], None, rnn["bias"], out=gx, x_amax=x_amax)
+    elif route.gemm == "bf16":
+        image = packed(rnn, ("wih_bf16", route.planes), hip.pack_wt_bf16, rnn["wih_rows"], route.planes)
+        hip.conv1x1_bf16(x, t, image, rnn["rows"], None, rnn["bias"], out=gx)
+    else:
+        hip.conv1x1(x, t, rnn["wih"], rnn["rows"], None, rnn["bias"], out=gx)
+    return gx
+
+
+def lstm_recurrence(gx: torch.Tensor, x: torch.Tensor, t: int, rnn: dict, kernel: str, walk: tuple, h0=None, c0=None,
+                    want_state: bool = False, state_shift: int = 0, state_out=None, lane: int = 0):
+    """The recurrence entry `kernel` (Route.kernel) over lstm_gates' pre-activations -> (hout [N, D*H, ldt], final states or
+    None); x: the pass's input rows (with the walk they decide where the output rows come from, see _h_rows)."""
+    states = (h0, c0, want_state, state_shift, state_out)
+    if kernel == "fmajor256":
+        image, scales = packed(rnn, "whh_h256", hip.pack_whh_h256, rnn["whh_t"])
+    out = _h_rows(rnn, x, t, *walk, lane)
+    if kernel == "fmajor256":
+        return hip.lstm_fmajor_h256(gx, image, scales, rnn["D"], *walk, *states, out=out)
+    if kernel == "fmajor128":
+        return hip.lstm_fmajor(gx, rnn["whh_t"], rnn["H"], rnn["D"], *walk, out=out), None
+    if kernel == "h256_f32" and hip.lstm_h256_f32_ok(
+            x.shape[0], x.shape[2], rnn["H"], rnn["D"], *walk, state_shift=state_shift,
+            ldq=min([s.shape[2] for s in (h0, c0) + tuple(state_out or ()) if s is not None], default=0)):
+        return hip.lstm_h256_f32(gx, rnn["whh_h256_f32"], rnn["D"], *walk, *states, out=out)
+    return hip.lstm(gx, rnn["whh_t"], rnn["H"], rnn["D"], *walk, *states, f16x2=kernel == "generic_f16x2", out=out)
+
+
 def lstm_path(x: torch.Tensor, t: int, rnn: dict, proj: dict, norm: dict, q: int, q_stride: int, steps: int,
               step_stride: int, h0=None, c0=None, want_state: bool = False, state_shift: int = 0, state_out=None,
               amax: Optional[list] = None, skip: bool = True, lane: int = 0):
@@ -224,58 +308,12 @@ def lstm_path(x: torch.Tensor, t: int, rnn: dict, proj: dict, norm: dict, q: int
     `amax`: a one-element list carried from recurrence to recurrence in the fp16x2 arithmetic -- on entry the partial maxima
     of |x| per utterance (or None: measured here), on return those of x' (None when the kernel that made x' has none).
     `lane`: which of the caller's concurrent HIP streams this is (selects the kept output rows, see _h_rows)."""
-    n, _, ldt = x.shape
-    dev = x.device
-    planes = rnn["planes"]
     x_amax = amax[0] if amax is not None else None
     if amax is not None:
         amax[0] = None
-    if planes == 2 and rnn["I"] >= 64:
-        if "wih_f16x2" not in rnn:
-            rnn["wih_f16x2"] = hip.pack_wt_f16x2(rnn["wih_rows"])
-        wf, we = rnn["wih_f16x2"]
-        # H = 128 without carried states (the bottleneck LSTMs of DPCRN / DPARN): gate pre-activations frame-major and the
-        # 16-sequence fp16x2 recurrence that streams them (ps_lstm_fmajor_f16x2_f32)
-        if (FMAJOR_LSTM and rnn["H"] == 128 and h0 is None and c0 is None and not want_state and state_out is None
-                and state_shift == 0 and hip.lstm_fmajor_ok(n, ldt, rnn["H"], rnn["D"], q, q_stride, steps, step_stride)
-                and hip.conv1x1_f16x2_fmajor_ok(n, rnn["I"], rnn["rows"], t, ldt)):
-            gx_fm = hip.conv1x1_f16x2_fmajor(x, t, wf, we, rnn["rows"], rnn["bias"],
-                                             x_amax=x_amax if x_amax is not None else hip.absmax(x, t))
-            hseq = hip.lstm_fmajor(gx_fm, rnn["whh_t"], rnn["H"], rnn["D"], q, q_stride, steps, step_stride,
-                                   out=_h_rows(rnn, x, t, q, q_stride, steps, step_stride, lane))
-            return _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip), None
-        # H = 256 (SkiM's segment LSTMs): W_hh streamed from L2 in fragment order, states carried (ps_lstm_fmajor_h256_f16x2_f32)
-        if (FMAJOR_LSTM and rnn["H"] in (256, 192) and hip.lstm_fmajor_h256_ok(n, ldt, rnn["D"], q, q_stride, steps, step_stride)
-                and hip.conv1x1_f16x2_fmajor_ok(n, rnn["I"], rnn["rows"], t, ldt)):
-            if "whh_h256" not in rnn:
-                rnn["whh_h256"] = hip.pack_whh_h256(rnn["whh_t"])
-            gx_fm = hip.conv1x1_f16x2_fmajor(x, t, wf, we, rnn["rows"], rnn["bias"],
-                                             x_amax=x_amax if x_amax is not None else hip.absmax(x, t))
-            hseq, state = hip.lstm_fmajor_h256(gx_fm, rnn["whh_h256"][0], rnn["whh_h256"][1], rnn["D"], q, q_stride, steps,
-                                               step_stride, h0, c0, want_state, state_shift, state_out,
-                                               out=_h_rows(rnn, x, t, q, q_stride, steps, step_stride, lane))
-            return _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip), state
-        gx = torch.empty(n, rnn["rows"], ldt, dtype=torch.float32, device=dev)
-        hip.conv1x1_f16x2(x, t, wf, we, rnn["rows"], None, rnn["bias"], out=gx,
-                          x_amax=x_amax if x_amax is not None else hip.absmax(x, t))
-    elif planes and rnn["I"] >= 64:
-        gx = torch.empty(n, rnn["rows"], ldt, dtype=torch.float32, device=dev)
-        planes = 3 if planes == 2 else planes
-        if planes not in rnn["wih_planes"]:
-            rnn["wih_planes"][planes] = hip.pack_wt_bf16(rnn["wih_rows"], planes)
-        hip.conv1x1_bf16(x, t, rnn["wih_planes"][planes], rnn["rows"], None, rnn["bias"], out=gx)
-    else:
-        gx = torch.empty(n, rnn["rows"], ldt, dtype=torch.float32, device=dev)
-        hip.conv1x1(x, t, rnn["wih"], rnn["rows"], None, rnn["bias"], out=gx)
-    if ("whh_h256_f32" in rnn and hip.lstm_h256_f32_pays(rnn["H"], rnn["D"], n, q)
-            and hip.lstm_h256_f32_ok(n, ldt, rnn["H"], rnn["D"], q, q_stride, steps, step_stride, state_shift=state_shift,
-                                     ldq=min([s.shape[2] for s in (h0, c0) + tuple(state_out or ()) if s is not None], default=0))):
-        # fp32 arithmetic at H = 256 / 192 (SkiM) with enough sequences: W_hh streamed in fragment order into exact fp32 MFMA
-        # (ps_lstm_h256_f32)
-        hseq, state = hip.lstm_h256_f32(gx, rnn["whh_h256_f32"], rnn["D"], q, q_stride, steps, step_stride, h0, c0, want_state,
-                                        state_shift, state_out, out=_h_rows(rnn, x, t, q, q_stride, steps, step_stride, lane))
-        return _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip), state
-    hseq, state = hip.lstm(gx, rnn["whh_t"], rnn["H"], rnn["D"], q, q_stride, steps, step_stride, h0, c0, want_state,
-                           state_shift, state_out, f16x2=rnn["planes"] == 2,
-                           out=_h_rows(rnn, x, t, q, q_stride, steps, step_stride, lane))
+    walk = (q, q_stride, steps, step_stride)
+    route = lstm_route(rnn, x.shape[0], x.shape[2], t, walk,
+                       h0 is not None or c0 is not None or want_state or state_out is not None, state_shift)
+    gx = lstm_gates(x, t, rnn, route, x_amax)
+    hseq, state = lstm_recurrence(gx, x, t, rnn, route.kernel, walk, h0, c0, want_state, state_shift, state_out, lane)
     return _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip), state

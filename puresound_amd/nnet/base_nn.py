@@ -354,8 +354,7 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         object.__setattr__(self, "_lanes_warm", True)
         # (the cooperative LSTM's workgroups spin on each other and must all be resident at once: two lanes launching it side
         #  by side could each hold CUs the other is waiting for until both give up -- the lanes take the streamed kernel)
-        coop, hip.COOP_LSTM = hip.COOP_LSTM, False
-        try:
+        with hip.coop_lstm_off():
             for i, s in enumerate(pool):
                 s.wait_stream(cur)
                 if first and i > 0:
@@ -366,8 +365,6 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
                               None if ref is None else ref[bounds[i]:bounds[i + 1]])
                     if ref is not None:
                         moments[bounds[i]:bounds[i + 1]] = got[1]
-        finally:
-            hip.COOP_LSTM = coop
         for s in pool:
             cur.wait_stream(s)
         return out if ref is None else (out, moments)

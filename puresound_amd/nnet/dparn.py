@@ -8,7 +8,7 @@ import torch.nn as nn
 
 from .. import hip
 from ..ops import op_module, same_shape
-from ._plans import PlanCache, layernorm_plan, linear_plan, lstm_path, lstm_plan
+from ._plans import PlanCache, layernorm_plan, linear_plan, lstm_path, lstm_plan, packed_ln_image
 from .lobe.attention import MhaSelfAttenLayer
 from .lobe.rnn import SingleRNN
 from .unet import Unet, _unet_shape
@@ -50,11 +50,7 @@ class DPARNblock2D(PlanCache, nn.Module):
         amax[0] = None
         if (self.gemm_precision == "fp16x2" and bound is not None and ch == 128 and hip.conv1x1_f16x2_ln_ok(n, ch, 128, frames)):
             # Linear + LayerNorm + skip as one launch (the LayerNorm epilogue of the fp16x2 GEMM); its maxima feed the recurrence
-            if "f16x2_ln" not in p["fc"]:
-                w256 = torch.zeros(256, ch, dtype=torch.float32, device=x.device)
-                w256[:ch] = p["fc"]["w_rows"]
-                p["fc"]["f16x2_ln"] = hip.pack_wt_f16x2(w256)
-            wf, we = p["fc"]["f16x2_ln"]
+            wf, we = packed_ln_image(p["fc"])
             y, amax[0] = hip.conv1x1_f16x2_ln(a, frames, wf, we, ch, p["fc"]["bias"], fn["gamma"], fn["beta"], fn["eps"],
                                               y if intra_skip else None, x_bound=bound, want_amax=True)
         else:
@@ -75,6 +71,9 @@ class DPARNblock2D(PlanCache, nn.Module):
         frames = (f - 1) * ld + b
         a = self.intra_atten1.forward_padded(y, frames, b, 1, f, ld)
         a = self.intra_atten2.forward_padded(a, frames, b, 1, f, ld)
+        if b < ld:   # the attention writes the b streams of each row only: zero the pad frames between the rows, so that
+            # what runs over all `frames` from here on, the carried LSTM states included, holds no stale memory
+            a = hip.fill_span(a.view(n, ch * f, ld), 2, b, ld, 0.0).view(n, ch, f * ld)
         fn = p["fc_norm"]
         y, _ = hip.proj_layernorm(a, frames, p["fc"]["wt"], p["fc"]["bias"], ch, fn["gamma"], fn["beta"], fn["eps"], y)
         y, _ = lstm_path(y, frames, *p["inter"], q=frames, q_stride=1, steps=1, step_stride=0, h0=h0, c0=c0,

@@ -1,13 +1,14 @@
 """Recurrent lobes (mirror of puresound/nnet/lobe/rnn.py:9-55): SingleRNN holds an nn.LSTM (or nn.GRU / nn.RNN) and its projection under
-the reference's keys (`rnn.*`, `proj.*`).  The dual-path blocks of DPCRN / DPARN drive its LSTM through ps_lstm_f32
+the reference's keys (`rnn.*`, `proj.*`).  The dual-path blocks of DPCRN / DPARN drive its LSTM through _plans.lstm_path
 with their own strided walks; as a layer of its own (the speaker net of tse_skim_v1_causal, egs/tse/model.py:487-495)
-it runs one sequence per utterance over the frame axis: input projection GEMM, ps_lstm_f32, output projection GEMM."""
+it runs one sequence per utterance over the frame axis: input projection GEMM, recurrence, output projection GEMM, on the
+kernels _plans.lstm_route(standalone=True) names."""
 import torch
 import torch.nn as nn
 
 from ... import hip
 from ...ops import op_module, same_shape
-from .._plans import PlanCache, linear_plan, lstm_plan, rnn_plan
+from .._plans import PlanCache, linear_plan, lstm_gates, lstm_plan, lstm_recurrence, lstm_route, packed, rnn_plan
 
 
 @op_module("single_rnn_fwd", same_shape)
@@ -44,39 +45,17 @@ class SingleRNN(PlanCache, nn.Module):
             y, _ = hip.conv1x1(hseq, t, proj["wt"], proj["M"], None, proj["bias"],
                                out=torch.empty(n, proj["M"], ldt, dtype=torch.float32, device=x.device))
             return y
-        if (rnn["planes"] == 2 and rnn["I"] >= 64 and rnn["H"] in (256, 192)
-                and hip.lstm_fmajor_h256_ok(n, ldt, rnn["D"], 1, ldt, t, 1)
-                and hip.conv1x1_f16x2_fmajor_ok(n, rnn["I"], rnn["rows"], t, ldt)):
-            # fp16x2 arithmetic: frame-major pre-activations + the recurrence that streams W_hh (ps_lstm_fmajor_h256_f16x2_f32;
-            # the bidirectional 192-unit LSTM over the enrolment of tse_skim_v1: 4000 dependent steps), projection in fp16x2
-            if "wih_f16x2" not in rnn:
-                rnn["wih_f16x2"] = hip.pack_wt_f16x2(rnn["wih_rows"])
-                rnn["whh_h256"] = hip.pack_whh_h256(rnn["whh_t"])
-                proj["f16x2"] = hip.pack_wt_f16x2(proj["w_rows"])
-            gx_fm = hip.conv1x1_f16x2_fmajor(x, t, rnn["wih_f16x2"][0], rnn["wih_f16x2"][1], rnn["rows"], rnn["bias"],
-                                             x_amax=hip.absmax(x, t))
-            hseq, _ = hip.lstm_fmajor_h256(gx_fm, rnn["whh_h256"][0], rnn["whh_h256"][1], rnn["D"], 1, ldt, t, 1)
-            y, _, _ = hip.conv1x1_f16x2(hseq, t, proj["f16x2"][0], proj["f16x2"][1], proj["M"], None, proj["bias"], x_bound=1.0,
-                                        out=torch.empty(n, proj["M"], ldt, dtype=torch.float32, device=x.device))
-            return y
-        gx = torch.empty(n, rnn["rows"], ldt, dtype=torch.float32, device=x.device)
-        if rnn["planes"] and rnn["I"] >= 64:
-            planes = 3 if rnn["planes"] == 2 else rnn["planes"]   # (fp16x2 needs a range pass: the fp32-class bf16 split here)
-            if planes not in rnn["wih_planes"]:
-                rnn["wih_planes"][planes] = hip.pack_wt_bf16(rnn["wih_rows"], planes)
-            hip.conv1x1_bf16(x, t, rnn["wih_planes"][planes], rnn["rows"], None, rnn["bias"], out=gx)
+        # one sequence per utterance: q = 1, the steps walk the frame axis (the bidirectional 192-unit LSTM over the enrolment
+        # of tse_skim_v1: 4000 dependent steps); _plans.lstm_route(standalone=True) says which kernels run
+        route = lstm_route(rnn, n, ldt, t, (1, ldt, t, 1), standalone=True)
+        gx = lstm_gates(x, t, rnn, route)
+        hseq, _ = lstm_recurrence(gx, x, t, rnn, route.kernel, (1, ldt, t, 1))
+        y = torch.empty(n, proj["M"], ldt, dtype=torch.float32, device=x.device)
+        if route.layout == "fmajor":   # the fp16x2 arithmetic all the way: h is an LSTM output, |h| < 1 is its range
+            wf, we = packed(proj, "f16x2", hip.pack_wt_f16x2, proj["w_rows"])
+            hip.conv1x1_f16x2(hseq, t, wf, we, proj["M"], None, proj["bias"], x_bound=1.0, out=y)
         else:
-            hip.conv1x1(x, t, rnn["wih"], rnn["rows"], None, rnn["bias"], out=gx)
-        # one sequence per utterance: q = 1, the steps walk the frame axis
-        if ("whh_h256_f32" in rnn and hip.lstm_h256_f32_pays(rnn["H"], rnn["D"], n, 1)
-                and hip.lstm_h256_f32_ok(n, ldt, rnn["H"], rnn["D"], 1, ldt, t, 1)):
-            # fp32 arithmetic at H = 256 / 192 with enough utterances (hip.H256_F32_MIN_SEQS): the exact fp32 MFMA recurrence
-            # (ps_lstm_h256_f32); the bidirectional speaker LSTM of tse_skim_v1 takes it from a batch of 128 on
-            hseq, _ = hip.lstm_h256_f32(gx, rnn["whh_h256_f32"], rnn["D"], 1, ldt, t, 1)
-        else:
-            hseq, _ = hip.lstm(gx, rnn["whh_t"], rnn["H"], rnn["D"], 1, ldt, t, 1)
-        y, _ = hip.conv1x1(hseq, t, proj["wt"], proj["M"], None, proj["bias"],
-                           out=torch.empty(n, proj["M"], ldt, dtype=torch.float32, device=x.device))
+            hip.conv1x1(hseq, t, proj["wt"], proj["M"], None, proj["bias"], out=y)
         return y
 
     def forward(self, x: torch.Tensor):
