@@ -12,6 +12,7 @@ through the same `capture`.)
 Results are bit-identical to the eager call.  One graph is kept per (input shapes, dtype); the graphs are dropped when
 a parameter of the model is updated in place or `reset()` is called.
 """
+import gc
 from typing import Optional
 
 import torch
@@ -20,31 +21,13 @@ from . import hip
 
 
 def _cached_tensors(model: torch.nn.Module) -> list:
-    """Every tensor the model's modules cache outside their parameters / buffers: scratch workspaces, packed-weight
-    plans, identity tables.  A captured graph holds raw pointers into them, so the graph entry keeps them alive: a
-    module may replace a cache entry later (a larger workspace for a larger batch, a new plan) without pulling memory
-    from under an older graph."""
-    seen, out = set(), []
-
-    def walk(obj, depth):
-        if torch.is_tensor(obj):
-            if obj.is_cuda and id(obj) not in seen:
-                seen.add(id(obj))
-                out.append(obj)
-        elif depth < 6:
-            if isinstance(obj, dict):
-                for v in obj.values():
-                    walk(v, depth + 1)
-            elif isinstance(obj, (list, tuple)):
-                for v in obj:
-                    walk(v, depth + 1)
-
-    for m in model.modules():
-        for k, v in m.__dict__.items():
-            if k not in ("_parameters", "_buffers", "_modules"):
-                walk(v, 0)
-    walk(hip._EYE, 0)
-    return out
+    """Every device tensor the model's modules keep outside their parameters / buffers -- the packed-weight plans and kept
+    scratch of nnet/_plans.py: PlanCache -- and the identity tables of hip.py.  A captured graph holds raw pointers into them,
+    so the graph entry keeps them alive: a module may replace a cache entry later (a larger workspace for a larger batch, a
+    new plan) without pulling memory from under an older graph."""
+    from .nnet._plans import PlanCache
+    kept = [t for m in model.modules() if isinstance(m, PlanCache) for t in m.cached_tensors()] + list(hip._EYE.values())
+    return list({id(t): t for t in kept if t.is_cuda}.values())   # (ConvTasNet's block array keeps its blocks' plans too)
 
 
 def capture(body, device, state=(), warmups: int = 1) -> tuple:
@@ -62,8 +45,17 @@ def capture(body, device, state=(), warmups: int = 1) -> tuple:
     for t, v in zip(state, saved):
         t.copy_(v)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out = body()
+    # No cyclic garbage collection inside the capture: it may finalize a dead session's or GraphedInference's graphs (kept in a
+    # reference cycle, by a traceback for instance), and destroying a graph synchronizes the device, which a capture forbids
+    # -- the process aborts.  (torch.cuda.graph no longer collects on entry.)  What is dead is collected after the capture.
+    collecting = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            out = body()
+    finally:
+        if collecting:
+            gc.enable()
     return graph, out
 
 

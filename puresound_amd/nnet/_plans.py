@@ -19,13 +19,13 @@ FUSE_GEMM_LN = os.environ.get("PS_FUSE_GEMM_LN", "1") == "1"    # 0: projection 
 FMAJOR_LSTM = os.environ.get("PS_FMAJOR_LSTM", "1") == "1"      # 0: H = 128 recurrences stay on the channel-major kernels
 
 
-# Arithmetic of the LSTM input projections (the large GEMMs of the recurrent maskers: [4H*D x C] over every frame):
-# "fp32" = v_mfma_f32 on fp32 operands, "bf16x3" = fp32-accurate 3 x bf16 split, "bf16" = operands rounded to bf16 (what
-# BASELINE.json names for the DPRNN configuration).  A per-module attribute, like TCN.gemm_precision: every PlanCache
-# module carries `gemm_precision` and hands it to the LSTM plans it builds (no process-wide switch).
-# "fp16x2" (the TCN blocks' default: two fp16 terms, three products) needs the range of the GEMM's input per utterance:
-# lstm_path takes it from the caller (`amax`: the partial maxima the projection + LayerNorm row kernel of the previous
-# recurrence left behind) or measures it (hip.absmax, one pass over the rows: the first GEMM of a masker).
+# Arithmetic of the GEMMs a module builds (the LSTM input projections of the recurrent maskers: [4H*D x C] over every frame; the
+# 1x1 convs of the TCN blocks): "fp32" = v_mfma_f32 on fp32 operands, "bf16x3" = fp32-accurate 3 x bf16 split, "bf16" = operands
+# rounded to bf16 (what BASELINE.json names for its bf16 configurations), "fp16x2" (the default: two fp16 terms, three products;
+# fp32-class results, 1e-6 against exact fp32 products on every preset measured, at 1.6-3.4 x the speed on the egs presets).
+# fp16x2 needs the range of the GEMM's input per utterance: lstm_path takes it from the caller (`amax`: the partial maxima the
+# projection + LayerNorm row kernel of the previous recurrence left behind) or measures it (hip.absmax, one pass over the rows:
+# the first GEMM of a masker).  A per-module attribute `gemm_precision` (GemmPlanCache; no process-wide switch).
 _PLANES = {"fp32": 0, "bf16": 1, "bf16x3": 3, "fp16x2": 2}
 
 
@@ -38,47 +38,103 @@ def tensor_signature(module: nn.Module) -> tuple:
 
 
 def param_signature(module: nn.Module) -> tuple:
-    """tensor_signature and the training switch: the key of a packed plan (the caller appends the device and its own
-    arithmetic switches)."""
+    """tensor_signature and the training switch: the key of a packed plan (PlanCache appends the device and the module's own
+    switches)."""
     return tensor_signature(module) + (module.training,)
 
 
+def _tensors_in(obj, seen: set, out: list) -> None:
+    if torch.is_tensor(obj):
+        if id(obj) not in seen:
+            seen.add(id(obj))
+            out.append(obj)
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            _tensors_in(v, seen, out)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            _tensors_in(v, seen, out)
+
+
 class PlanCache:
-    """Mixin: `self._plan_get(device, builder)` caches builder(device) until a parameter changes."""
+    """Mixin of every module under nnet/ that keeps something from call to call: packed weights ("plans": the kernel-side
+    copies of its parameters, with the ctypes structs that point into them) and scratch.
 
-    _plan = None
-    _plan_sig = None
-    # arithmetic of the GEMMs (and, where kernels for it exist, the recurrent products) built by this module (see _PLANES).
-    # Round 4: "fp16x2" is the default here as it has been for the TCN blocks since round 2 -- fp32-class results (two fp16
-    # terms per operand, three products, fp32 accumulation: 1e-6 against exact fp32 products on every preset measured) at
-    # 1.6-3.4 x the speed on the egs presets; set_gemm_precision("fp32") selects exact fp32 products.
-    gemm_precision = "fp16x2"
+    Plans: `self._plan_get(device, builder)` is builder(device) of the last call, as long as no parameter or buffer below the
+    module, its training switch, the device or one of the module's own switches (`_plan_switches`) has changed; one plan per
+    builder.  `prepare_plans(device)` builds or re-validates, on the current stream, every plan inference() reads.
+    Scratch: `keep_scratch(name, lane, value)` / `scratch(name, lane)`, one entry per concurrent HIP stream of the caller.
+    Neither is pickled or deep-copied (`__getstate__`), and `cached_tensors()` lists the tensors both keep alive."""
 
-    def set_gemm_precision(self, name: str):
-        """"fp32" | "bf16x3" | "fp16x2" | "bf16" for the LSTM input projections of this module and of every module below
-        it."""
-        if name not in _PLANES:
-            raise ValueError(f"gemm precision must be one of {sorted(_PLANES)}")
-        for m in self.modules():
-            if isinstance(m, PlanCache):
-                m.gemm_precision = name
-                m._plan = None
-        return self
+    _plans = None      # {builder's name: (key, plan)}
+    _scratch = None    # {(name, lane): value}
+
+    def _plan_switches(self) -> tuple:
+        """The module's own switches that a plan depends on beside its parameters."""
+        return ()
+
+    def _plan_build(self, name: str, builder, device):
+        return builder(device)
+
+    def _plan_get(self, device, builder, key=None):
+        """`key`: of a plan made of the children's plans (ConvTasNet's block array: their identities), which have validated
+        their fingerprints already."""
+        if key is None:
+            key = param_signature(self) + (str(device),) + self._plan_switches()
+        if self._plans is None:
+            self._plans = {}
+        name = builder.__name__
+        kept = self._plans.get(name)
+        if kept is None or kept[0] != key:
+            self._plans[name] = kept = (key, self._plan_build(name, builder, device))
+        return kept[1]
+
+    def prepare_plans(self, device) -> None:
+        self._plan_get(device, self._build)
+
+    def scratch(self, name: str, lane: int = 0):
+        return None if self._scratch is None else self._scratch.get((name, lane))
+
+    def keep_scratch(self, name: str, lane: int, value):
+        if self._scratch is None:
+            self._scratch = {}
+        self._scratch[name, lane] = value
+        return value
+
+    def kept_scratch(self) -> list:
+        return [] if self._scratch is None else list(self._scratch.values())
+
+    def cached_tensors(self) -> list:
+        """Every tensor this module's plans and kept scratch hold (not its submodules')."""
+        out = []
+        _tensors_in([[plan for _, plan in (self._plans or {}).values()], self.kept_scratch()], set(), out)
+        return out
 
     def __getstate__(self):
         state = dict(self.__dict__)
-        state["_plan"] = None
-        state["_plan_sig"] = None
-        if "_last_amax" in state:   # (DPRNN: a device tensor handed from the block stack to the output conv within one call)
-            state["_last_amax"] = None
+        state.pop("_plans", None)
+        state.pop("_scratch", None)
         return state
 
-    def _plan_get(self, device, builder):
-        sig = param_signature(self) + (str(device), self.gemm_precision)
-        if self._plan is None or self._plan_sig != sig:
-            self._plan = builder(device)
-            self._plan_sig = sig
-        return self._plan
+    def set_gemm_precision(self, name: str):
+        """"fp32" | "bf16x3" | "fp16x2" | "bf16" for this module and every module below it that has the choice (the TCN
+        blocks' 1x1 convs, the recurrent maskers' LSTM input projections, attention layers, SingleRNN, the pooling).
+        Assigning `m.gemm_precision` directly does the same for one module; either takes effect at the next call."""
+        if name not in _PLANES:
+            raise ValueError(f"gemm precision must be one of {sorted(_PLANES)}")
+        for m in self.modules():
+            if hasattr(m, "gemm_precision"):
+                m.gemm_precision = name
+        return self
+
+
+class GemmPlanCache(PlanCache):
+    """PlanCache of a module whose plans depend on `gemm_precision`."""
+
+    gemm_precision = "fp16x2"
+
+    def _plan_switches(self) -> tuple:
+        return (self.gemm_precision,)
 
 
 def _f32(t: torch.Tensor, device) -> torch.Tensor:

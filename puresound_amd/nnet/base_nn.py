@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from .. import hip
 from .._abi import TcnBlock
+from ._plans import PlanCache
 from .conv_tasnet import TCN, ConvTasNet, GatedTCN
 from .lobe.trivial import Magnitude, SpecAugment
 from .dprnn import DPRNN
@@ -34,8 +35,9 @@ def _side_streams(dev: torch.device, n: int):
     return pool[:n]
 
 
-class BaseModel(nn.Module):
-    """base_nn.py:11-32."""
+class BaseModel(PlanCache, nn.Module):
+    """base_nn.py:11-32.  A PlanCache: a wrapper keeps scratch of its own (the speaker branch's driver workspace) and hands
+    `set_gemm_precision` to everything below it."""
 
     def __init__(self) -> None:
         super().__init__()
@@ -201,27 +203,6 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
             "inference path only -- use .inference()")
 
     # -- the hot path -----------------------------------------------------------------------------
-    @torch.no_grad()
-    def set_gemm_precision(self, name: str):
-        """One switch for the whole model (not in the reference: the HIP path's arithmetic): "fp16x2" | "fp32" | "bf16x3" |
-        "bf16" for every module of the masker and the speaker branch that has a choice (TCN stacks, recurrent maskers,
-        attention layers, SingleRNN)."""
-        from ._plans import PlanCache, _PLANES
-        if name not in _PLANES:
-            raise ValueError(f"gemm precision must be one of {sorted(_PLANES)}")
-        for root in (self.masker, self.speaker_net):
-            if root is None:
-                continue
-            for m in root.modules():
-                if isinstance(m, PlanCache):
-                    m.gemm_precision = name
-                    m._plan = None
-                elif hasattr(m, "gemm_precision"):
-                    m.gemm_precision = name
-            if hasattr(root, "set_gemm_precision") and not isinstance(root, PlanCache):
-                root.set_gemm_precision(name)
-        return self
-
     def inference(self, noisy: torch.Tensor, enroll: Optional[torch.Tensor] = None) -> torch.Tensor:
         """noisy [N,L] (+ enroll [N,L']) -> enhanced waveform [N,L_out] (base_nn.py:690-722)."""
         if noisy.device.type == "cpu":  # BASELINE configs[0] / the recipes' --backend cpu: stock ATen (nnet/cpu_path.py)
@@ -350,8 +331,8 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         # would be read by lane 1 with no ordering.  What is still created lazily inside a lane (per-precision weight
         # planes, identity tables) is created once: the first forked call runs its lanes one after the other.
         self._prepare_plans(dev)
-        first = not getattr(self, "_lanes_warm", False)
-        object.__setattr__(self, "_lanes_warm", True)
+        first = not self.scratch("lanes_warm")
+        self.keep_scratch("lanes_warm", 0, True)
         # (the cooperative LSTM's workgroups spin on each other and must all be resident at once: two lanes launching it side
         #  by side could each hold CUs the other is waiting for until both give up -- the lanes take the streamed kernel)
         with hip.coop_lstm_off():
@@ -369,19 +350,17 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
             cur.wait_stream(s)
         return out if ref is None else (out, moments)
 
+    def prepare_plans(self, device) -> None:
+        """The wrapper packs nothing itself; it tells its STFT encoders which bins their plans cover."""
+        for enc in (self.encoder, self.encoder_spk):
+            if isinstance(enc, ConvEncDec):
+                enc.encoder.drop_first_bin = bool(self.drop_first_bin)
+
     def _prepare_plans(self, dev: torch.device) -> None:
-        """Build / re-validate every kernel-side plan of the masker and the speaker branch on the current stream."""
-        from ._plans import PlanCache
-        for m in self.modules():
-            if isinstance(m, ConvTasNet):
-                if m.tcn_layer.lower() == "normal":
-                    m.block_array(dev)
-            elif isinstance(m, (TCN, GatedTCN)):
-                m.plan(dev)
-            elif isinstance(m, AttentiveStatisticsPooling):
-                m._get_plan(dev)
-            elif isinstance(m, PlanCache) and hasattr(m, "_build"):
-                m._plan_get(dev, m._build)
+        """Build / re-validate every kernel-side plan that inference() reads, on the current stream."""
+        for m in self.modules():   # (the wrapper first)
+            if isinstance(m, PlanCache):
+                m.prepare_plans(dev)
 
     def _align_waveform(self, enh_wav: torch.Tensor, ref_wav: torch.Tensor):
         """base_nn.py:398-412: a shorter reference is left-padded with zeros ("align from last"), a longer one is cut."""
@@ -393,7 +372,7 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         """speaker_net layer by layer on padded enrolment features (base_nn.py:697-705): Magnitude, TCN (consecutive
         plain blocks go through the fused driver together), GatedTCN, AttentiveStatisticsPooling, then the k=1
         projection conv(s) on the pooled vector -> dvec [N, E].  `lane` selects the fused driver's kept scratch: one
-        buffer per concurrent HIP stream of inference(), as ConvTasNet._workspace."""
+        buffer per concurrent HIP stream of inference(), as ConvTasNet's."""
         layers = list(self.speaker_net) if isinstance(self.speaker_net, (nn.ModuleList, nn.Sequential)) else None
         if layers is None:
             raise NotImplementedError("HIP speaker branch: speaker_net must be a ModuleList / Sequential")
@@ -426,12 +405,8 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
                     # (x_amax: a bound on the features for fp16x2 blocks -- without one the driver measures them: 93 us)
                     # the driver's scratch (three hidden maps: 415 MB at 32 x 4 s) is kept, not re-allocated and
                     # zero-filled per call as hip.conv_tasnet does for callers without one
-                    kept = self.__dict__.get("_spk_workspace")
-                    if kept is None:
-                        kept = {}
-                        object.__setattr__(self, "_spk_workspace", kept)
-                    ws = kept[lane] = hip.conv_tasnet_workspace(x.shape[0], run[0].in_channels, run[0].hid_channels, t,
-                                                                x.device, kept.get(lane))
+                    ws = self.keep_scratch("spk_workspace", lane, hip.conv_tasnet_workspace(
+                        x.shape[0], run[0].in_channels, run[0].hid_channels, t, x.device, self.scratch("spk_workspace", lane)))
                     x = hip.conv_tasnet(blocks, len(plans), x, t, run[0].in_channels, run[0].hid_channels, None, False,
                                         workspace=ws, x_amax=x_amax, bf16_rows=all(p["rows_bf16"] for p in plans))
                 else:

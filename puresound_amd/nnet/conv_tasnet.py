@@ -15,32 +15,13 @@ import torch.nn as nn
 from .. import hip
 from ..ops import op_module, same_shape
 from .._abi import PS_NORM_AFFINE, PS_NORM_GLOBAL, TcnBlock, ptr
-from ._plans import param_signature
+from ._plans import _PLANES as GEMM_PLANES, GemmPlanCache, PlanCache
 from .lobe.cnn import DepthwiseSeparableConv1d
 from .lobe.norm import ChanLN, GlobLN, get_norm, norm_plan
 
 
-_PLAN_SERIAL = [0]
-
-
-GEMM_PLANES = {"fp32": 0, "bf16": 1, "fp16x2": 2, "bf16x3": 3}
-
-
-class _PlanCache:
-    """Packed-weight caches hold raw device pointers (ctypes) -- never pickle / deepcopy them."""
-
-    _CACHE_ATTRS = ("_plan", "_plan_sig", "_blocks", "_blocks_sig", "_workspace")
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        for k in self._CACHE_ATTRS:
-            if k in state:
-                state[k] = None
-        return state
-
-
 @op_module("tcn_block_fwd", same_shape, cpu="tcn_block")
-class TCN(_PlanCache, nn.Module):
+class TCN(GemmPlanCache, nn.Module):
     """Input 1x1 conv -> norm -> PReLU -> depthwise-separable conv -> output 1x1 conv -> + residual
     (conv_tasnet.py:11-90)."""
 
@@ -59,8 +40,6 @@ class TCN(_PlanCache, nn.Module):
                                      norm_cls=dconv_norm),
             nn.Dropout(p=dropout))
         self.out_conv = nn.Conv1d(hid_channels, in_channels, kernel_size=1, stride=1)
-        self._plan = None
-        self._plan_sig = None
 
     # -- kernel-side weight layout ----------------------------------------------------------------
     #: arithmetic of the three 1x1 convs (fp32 tensors, fp32 accumulation in every case):
@@ -97,12 +76,16 @@ class TCN(_PlanCache, nn.Module):
                 return 3
         return planes
 
-    def plan(self, device: torch.device) -> dict:
+    def _plan_switches(self) -> tuple:
         planes = self.gemm_planes_for_plan()
         hb = bool(self.hidden_bf16) and planes == 1 and self.kernel == 3 and 2 * self.dilation + 8 <= 288
-        sig = (param_signature(self), str(device), planes, hb, bool(self.stream_bf16))
-        if self._plan is not None and self._plan_sig == sig:
-            return self._plan
+        return planes, hb, bool(self.stream_bf16)
+
+    def plan(self, device: torch.device) -> dict:
+        return self._plan_get(device, self._build)
+
+    def _build(self, device: torch.device) -> dict:
+        planes, hb, _ = self._plan_switches()
         if self.training and self.dconv[1].p > 0:
             raise RuntimeError("TCN: dropout is active; the HIP path is inference only -- call .eval()")
         if not self.causal and self.kernel % 2 == 0:
@@ -169,12 +152,8 @@ class TCN(_PlanCache, nn.Module):
                 f16_images(("in_wf", "pw_wf", "out_wf"))
         for k, v in t.items():
             setattr(b, k, ptr(v))
-        _PLAN_SERIAL[0] += 1
         # tensors kept alive alongside the raw pointers
-        self._plan = {"block": b, "tensors": t, "serial": _PLAN_SERIAL[0], "kinds": kinds, "fused": fused,
-                      "rows_bf16": rows_bf16}
-        self._plan_sig = sig
-        return self._plan
+        return {"block": b, "tensors": t, "kinds": kinds, "fused": fused, "rows_bf16": rows_bf16}
 
     def forward_padded_staged(self, x: torch.Tensor, t: int, embed: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Stage-by-stage block for norm mixes the fused driver has no form for (cLN): every 1x1 conv is its own
@@ -223,7 +202,7 @@ class TCN(_PlanCache, nn.Module):
 
 
 @op_module("gated_tcn_fwd", same_shape, cpu="gated_tcn_block")
-class GatedTCN(_PlanCache, nn.Module):
+class GatedTCN(PlanCache, nn.Module):
     """Gated TCN block (conv_tasnet.py:93-215): 1x1 in_conv; left = PReLU(norm(dense dilated conv)); right =
     sigmoid(PReLU(norm(dense dilated conv of [h; e] or of FiLM(h)))); out_conv(left * right); + residual.
 
@@ -257,8 +236,6 @@ class GatedTCN(_PlanCache, nn.Module):
                       padding=self.padd, groups=1),
             norm_cls(hid_channels), nn.PReLU(), nn.Dropout(p=dropout), nn.Sigmoid())
         self.out_conv = nn.Conv1d(hid_channels, in_channels, kernel_size=1, bias=False, groups=1)
-        self._plan = None
-        self._plan_sig = None
 
     @staticmethod
     def _unfolded(w: torch.Tensor) -> torch.Tensor:
@@ -266,9 +243,9 @@ class GatedTCN(_PlanCache, nn.Module):
         return w.permute(0, 2, 1).reshape(w.shape[0], -1).contiguous()
 
     def plan(self, device: torch.device) -> dict:
-        sig = (param_signature(self), str(device))
-        if self._plan is not None and self._plan_sig == sig:
-            return self._plan
+        return self._plan_get(device, self._build)
+
+    def _build(self, device: torch.device) -> dict:
         if self.training and (self.left_conv[3].p > 0 or self.right_conv[3].p > 0):
             raise RuntimeError("GatedTCN: dropout is active; the HIP path is inference only -- call .eval()")
         span = (self.kernel - 1) * self.dilation
@@ -295,7 +272,6 @@ class GatedTCN(_PlanCache, nn.Module):
         if self.use_film:
             t["w_film"] = torch.cat([self.cond_scale.weight.detach()[:, :, 0], self.cond_bias.weight.detach()[:, :, 0]],
                                     0).to(**f32).contiguous()
-        self._plan, self._plan_sig = t, sig
         return t
 
     def forward_padded(self, x: torch.Tensor, t: int, embed: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -359,7 +335,7 @@ class GatedTCN(_PlanCache, nn.Module):
 
 
 @op_module("conv_tasnet_fwd", same_shape, cpu="conv_tasnet")
-class ConvTasNet(_PlanCache, nn.Module):
+class ConvTasNet(PlanCache, nn.Module):
     """R repeats of X dilated TCN blocks with optional speaker-embedding injection
     (conv_tasnet.py:218-377).  Encoder/decoder live outside, as in the reference."""
 
@@ -399,32 +375,27 @@ class ConvTasNet(_PlanCache, nn.Module):
                     kw["dconv_norm"] = dconv_norm
                 stack.append(tcn_cls(input_dim, tcn_dim, **kw))
             self.tcn_list.append(nn.ModuleList(stack))
-        self._blocks = None
-        self._blocks_sig = None
-        self._workspace = None
-
-    def set_gemm_precision(self, name: str) -> "ConvTasNet":
-        """"fp16x2" (default: two fp16 terms per operand, three products) | "bf16x3" | "fp32" | "bf16" for the 1x1 convs of
-        every normal TCN block (see TCN.gemm_precision).  The switch is per module; the process-wide
-        set_recurrent_gemm_precision / PS_RECURRENT_GEMM of round 1 no longer exist."""
-        if name not in GEMM_PLANES:
-            raise ValueError(f"gemm precision must be one of {sorted(GEMM_PLANES)}")
-        for stack in self.tcn_list:
-            for m in stack:
-                m.gemm_precision = name
-        return self
 
     # -- plan: one ps_tcn_block per TCN, in execution order -------------------------------------------
+    def _stack(self, device: torch.device) -> dict:
+        """The normal TCN stack in ONE pass over its blocks (each validates its own fingerprint, once): the ps_tcn_block
+        array and what the driver needs to know of all of them, kept until a block hands out another plan object."""
+        plans = [m.plan(device) for stack in self.tcn_list for m in stack]
+
+        def _build_stack(_):
+            return dict(plans=plans, array=(TcnBlock * len(plans))(*[p["block"] for p in plans]),
+                        fused=all(p["fused"] for p in plans), rows_bf16=all(p["rows_bf16"] for p in plans))
+        return self._plan_get(device, _build_stack, key=tuple(map(id, plans)))
+
+    def prepare_plans(self, device) -> None:
+        if self.tcn_layer.lower() == "normal":
+            self._stack(device)
+
     def block_array(self, device: torch.device):
         if self.tcn_layer.lower() != "normal":
             raise RuntimeError("block_array: only the normal TCN stack runs through ps_conv_tasnet_f32")
-        mods = [m for stack in self.tcn_list for m in stack]
-        plans = [m.plan(device) for m in mods]  # each TCN re-validates its own fingerprint
-        sig = tuple(p["serial"] for p in plans)
-        if self._blocks is None or self._blocks_sig != sig:
-            self._blocks = (TcnBlock * len(plans))(*[p["block"] for p in plans])
-            self._blocks_sig = sig
-        return self._blocks, len(plans)
+        stack = self._stack(device)
+        return stack["array"], len(stack["plans"])
 
     #: forward_padded takes `x_amax` (per-utterance bounds on |x_pad|) for blocks in the fp16x2 arithmetic
     takes_input_range = True
@@ -436,23 +407,20 @@ class ConvTasNet(_PlanCache, nn.Module):
         values whose per-utterance maximum bounds |x_pad| (only the fused normal-TCN path uses it)."""
         if self.tcn_layer.lower() == "gated":
             return self._forward_gated(x_pad, t, dvec)
-        if not all(m.plan(x_pad.device)["fused"] for stack in self.tcn_list for m in stack):
+        stack = self._stack(x_pad.device)
+        if not stack["fused"]:
             return self._forward_staged(x_pad, t, dvec)
-        blocks, n_blocks = self.block_array(x_pad.device)
         need_embed = any(self.tcn_with_embed)
         if need_embed and dvec is None:
             # the reference would call TCN(x, None) on a block whose in_conv expects C+E channels and fail there
             raise RuntimeError("ConvTasNet.forward: tcn_with_embed is set but no dvec was given")
         if not need_embed:
             dvec = None  # reference ignores dvec when no block takes it (conv_tasnet.py:354-357)
-        if self._workspace is None:
-            self._workspace = {}
-        ws = self._workspace[lane] = hip.conv_tasnet_workspace(x_pad.shape[0], self.input_dim, self.tcn_dim, t, x_pad.device,
-                                                               self._workspace.get(lane))
-        rows_bf16 = all(m.plan(x_pad.device)["rows_bf16"] for stack in self.tcn_list for m in stack)
-        return hip.conv_tasnet(blocks, n_blocks, x_pad, t, self.input_dim, self.tcn_dim,
+        ws = self.keep_scratch("workspace", lane, hip.conv_tasnet_workspace(
+            x_pad.shape[0], self.input_dim, self.tcn_dim, t, x_pad.device, self.scratch("workspace", lane)))
+        return hip.conv_tasnet(stack["array"], len(stack["plans"]), x_pad, t, self.input_dim, self.tcn_dim,
                                None if dvec is None else dvec.contiguous().float(),
-                               bool(self.embed_norm), ws, x_amax, bf16_rows=rows_bf16)
+                               bool(self.embed_norm), ws, x_amax, bf16_rows=stack["rows_bf16"])
 
     def _forward_staged(self, x: torch.Tensor, t: int, dvec: Optional[torch.Tensor]) -> torch.Tensor:
         """Normal TCN blocks with a cLN somewhere: block by block, stage by stage."""

@@ -8,13 +8,13 @@ import torch.nn as nn
 
 from .. import hip
 from ..ops import op_module, same_shape
-from ._plans import PlanCache, layernorm_plan, linear_plan, lstm_path, lstm_plan, packed_ln_image
+from ._plans import GemmPlanCache, layernorm_plan, linear_plan, lstm_path, lstm_plan, packed_ln_image
 from .lobe.attention import MhaSelfAttenLayer
 from .lobe.rnn import SingleRNN
 from .unet import Unet, _unet_shape
 
 
-class DPARNblock2D(PlanCache, nn.Module):
+class DPARNblock2D(GemmPlanCache, nn.Module):
     """dparn.py:12-108."""
 
     def __init__(self, input_size: int, hidden_size: int, nhead: int, dropout: float = 0.0) -> None:

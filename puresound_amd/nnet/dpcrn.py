@@ -11,12 +11,12 @@ import torch.nn as nn
 
 from .. import hip
 from ..ops import op_module, same_shape
-from ._plans import PlanCache, layernorm_plan, linear_plan, lstm_path, lstm_plan
+from ._plans import GemmPlanCache, layernorm_plan, linear_plan, lstm_path, lstm_plan
 from .lobe.rnn import SingleRNN
 from .unet import Unet
 
 
-class DPRNNblock2D(PlanCache, nn.Module):
+class DPRNNblock2D(GemmPlanCache, nn.Module):
     """dpcrn.py:11-81."""
 
     def __init__(self, input_size: int, hidden_size: int, dropout: float = 0.0) -> None:

@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from .. import hip
 from ..ops import op_module
-from ._plans import PlanCache, _f32, layernorm_plan, linear_plan, lstm_path, lstm_plan
+from ._plans import GemmPlanCache, _f32, layernorm_plan, linear_plan, lstm_path, lstm_plan
 from .lobe.trivial import FiLM
 
 
@@ -22,7 +22,7 @@ def _out_size(ctor, x, aux, params):
 
 
 @op_module("dprnn_fwd", _out_size)
-class DPRNN(PlanCache, nn.Module):
+class DPRNN(GemmPlanCache, nn.Module):
     """Deep dual-path RNN (dprnn.py:10-109); constructor order as the reference (dprnn.py:27-40)."""
 
     def __init__(self, input_size: int, hidden_size: int, output_size: int, n_blocks: int = 2, seg_size: int = 20,
@@ -39,7 +39,6 @@ class DPRNN(PlanCache, nn.Module):
         self.embed_norm = embed_norm
         self.block_with_embed = block_with_embed
         self.embedding_free_tse = embedding_free_tse
-        self._last_amax = None
 
         self.input_film = nn.ModuleList()
         self.intra_rnn = nn.ModuleList()
@@ -90,8 +89,8 @@ class DPRNN(PlanCache, nn.Module):
         into a buffer of their own, so the input rows only need their T frames."""
         return t if self.seg_overlap else t + self.seg_size - t % self.seg_size
 
-    def _run_blocks(self, x: torch.Tensor, tp: int, embed, init_states, want_states: bool):
-        p = self._plan_get(x.device, self._build)
+    def _run_blocks(self, p: dict, x: torch.Tensor, tp: int, embed, init_states, want_states: bool):
+        """-> (x', the inter-LSTM states per block, the partial maxima of |x'| or None)."""
         k = self.seg_size
         s = tp // k
         states = []
@@ -105,10 +104,9 @@ class DPRNN(PlanCache, nn.Module):
             x, st = lstm_path(x, tp, *blk["inter"], q=k, q_stride=1, steps=s, step_stride=k, h0=h0, c0=c0,
                               want_state=want_states, amax=amax)
             states.append(st)
-        self._last_amax = amax[0]   # (partial maxima of the block stack's output, or None; read by forward_padded only)
-        return x, states
+        return x, states, amax[0]
 
-    def hidden_states_padded(self, e_pad: torch.Tensor, te: int):
+    def hidden_states_padded(self, e_pad: torch.Tensor, te: int, p: Optional[dict] = None):
         """DPRNN._get_hidden_states (dprnn.py:193-244): final inter-LSTM states of an enrolment pass, per block,
         in state layout [N, D*H, ldq]."""
         if self.seg_overlap:
@@ -117,7 +115,7 @@ class DPRNN(PlanCache, nn.Module):
             tp = self.padded_frames_needed(te)
         if e_pad.shape[-1] < tp:
             raise RuntimeError("DPRNN: enrolment rows are shorter than the segment padding")
-        _, states = self._run_blocks(e_pad, tp, None, None, True)
+        _, states, _ = self._run_blocks(p or self._plan_get(e_pad.device, self._build), e_pad, tp, None, None, True)
         return states
 
     def forward_padded(self, x_pad: torch.Tensor, t: int, embed: Optional[torch.Tensor] = None, lane: int = 0,
@@ -130,19 +128,17 @@ class DPRNN(PlanCache, nn.Module):
             tp = self.padded_frames_needed(t)
         if x_pad.shape[-1] < tp:
             raise RuntimeError(f"DPRNN: rows hold {x_pad.shape[-1]} frames, the segment padding needs {tp}")
+        p = self._plan_get(x_pad.device, self._build)
         init = None
         if self.embedding_free_tse:
             # the reference asserts on embed.dim() == 3 (dprnn.py:121-124)
             assert embed is not None and embed.dim() == 3, "embedding free tse need enrollment waveform as input."
-            init = self.hidden_states_padded(embed, embed_frames)
+            init = self.hidden_states_padded(embed, embed_frames, p)
             embed = None
-        x, _ = self._run_blocks(x_pad, tp, embed, init, False)
-        x_amax = self._last_amax
-        self._last_amax = None
+        x, _, x_amax = self._run_blocks(p, x_pad, tp, embed, init, False)
         if self.seg_overlap:
             x = hip.segment_merge(x, tp, t, self.seg_size)              # SplitMerge.merge (dprnn.py:182-185)
             x_amax = None
-        p = self._plan
         pro = hip.make_prologue(0, True, None, 0.0, 0.0, None, None, p["out_slope"])
         if "out_f16x2" in p:
             wf, we = p["out_f16x2"]

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from ... import hip
-from .._plans import PlanCache, _f32, layernorm_plan, linear_plan, lstm_plan
+from .._plans import GemmPlanCache, _f32, layernorm_plan, linear_plan, lstm_plan
 
 
 class PositionalEncoding(nn.Module):
@@ -45,7 +45,7 @@ class MHA(nn.Module):
         raise NotImplementedError("MHA runs inside MhaSelfAttenLayer on the HIP path")
 
 
-class MhaSelfAttenLayer(PlanCache, nn.Module):
+class MhaSelfAttenLayer(GemmPlanCache, nn.Module):
     """Transformer encoder block (lobe/attention.py:115-232)."""
 
     def __init__(self, feats_dim: int, hidden_dim: int, nhead: int, dropout: float = 0.0, improved: bool = False,

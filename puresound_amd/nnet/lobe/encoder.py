@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from ... import hip
 from ...ops import op_module
+from .._plans import PlanCache
 
 
 class _EncoderConv(nn.Conv1d):
@@ -32,7 +33,7 @@ class _DecoderConvT(nn.ConvTranspose1d):
             return torch.ops.puresound_amd.free_decode(x, self.weight, self.stride[0]).unsqueeze(1)
 
 
-class FreeEncDec(nn.Module):
+class FreeEncDec(PlanCache, nn.Module):
     """Free (learned) filters: waveform -> latent feats -> waveform (encoder.py:16-94)."""
 
     def __init__(self, win_length: int = 512, laten_length: int = 512, hop_length: int = 128,
@@ -52,16 +53,16 @@ class FreeEncDec(nn.Module):
         segment padding of the dual-path maskers needs them."""
         return hip.free_encode(x, self.encoder.weight.detach(), self.hop_length, self.output_active, min_frames)
 
+    def _build(self, device) -> float:
+        """The largest row sum of |w| of the encoder, read back to the host (once per weight version)."""
+        return float(self.encoder.weight.detach().abs().sum(dim=(1, 2)).max())
+
     def feature_bound(self, x: torch.Tensor) -> torch.Tensor:
         """[N,L] -> [N,1]: an upper bound on |forward(x)[n]|: max |x[n]| times the largest row sum of |w| (the ReLU only
         shrinks).  Consumers that scale their input into a narrow exponent range (the fp16x2 GEMMs) take it instead of
-        measuring the features.  (The row sum is read back to the host once per weight version.)"""
-        w = self.encoder.weight
-        key = (w.data_ptr(), w._version)
-        if getattr(self, "_l1_key", None) != key:
-            self._l1 = float(w.detach().abs().sum(dim=(1, 2)).max())
-            self._l1_key = key
-        return torch.linalg.vector_norm(x.detach().float(), ord=float("inf"), dim=1, keepdim=True) * self._l1
+        measuring the features."""
+        l1 = self._plan_get(x.device, self._build)
+        return torch.linalg.vector_norm(x.detach().float(), ord=float("inf"), dim=1, keepdim=True) * l1
 
     def decode_padded(self, feats_pad: torch.Tensor, t: int, mask_pad: Optional[torch.Tensor] = None,
                       mask_act: str = "linear", out_mode: str = "none",
@@ -115,7 +116,7 @@ def _stft_rebuild(a):
 
 @op_module("istft_decode", _istft_shape, method="_istft", rebuild=_stft_rebuild, cpu="istft_decode")
 @op_module("stft_encode", _stft_shape, rebuild=_stft_rebuild, cpu="stft_encode")
-class ConvSTFT(nn.Module):
+class ConvSTFT(PlanCache, nn.Module):
     """Conv-STFT with trainable analysis kernels (encoder.py:275-456).  Parameter / buffer holder."""
 
     def __init__(self, window_mask: torch.Tensor, n_fft: int = 2048, win_length: Optional[int] = None,
@@ -161,45 +162,51 @@ class ConvSTFT(nn.Module):
                     iSTFT=self.iSTFT, trainable=self.trainable, output_format=self.output_format)
 
     # -- kernel-side plans (rebuilt when a table changes) -----------------------------------------------
-    def _sig(self):
-        return tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+    #: whether the plans leave the DC bin out (base_nn.py:341-345): the wrapper's switch, set by the last call that named it
+    drop_first_bin = False
+
+    def _plan_switches(self) -> tuple:
+        return (self.drop_first_bin,)
+
+    def prepare_plans(self, device) -> None:
+        self._analysis_plan(self.drop_first_bin)
+        if self.iSTFT:
+            self._synthesis_plan(self.drop_first_bin)
 
     def _analysis_plan(self, drop_first_bin: bool):
+        """-> (packed weight, rows) of the analysis product."""
+        self.drop_first_bin = bool(drop_first_bin)
+        return self._plan_get(self.wcos.device, self._build_analysis)
+
+    def _synthesis_plan(self, drop_first_bin: bool):
+        """-> (packed weight, window) of the synthesis product."""
+        self.drop_first_bin = bool(drop_first_bin)
+        return self._plan_get(self.wcos.device, self._build_synthesis)
+
+    def _build_analysis(self, device):
         """Packed weight of the analysis product in the wrapper's channel order [re bins ; im bins]:
         re = conv(x, wcos), im = -conv(x, wsin) (encoder.py:370-382), optionally without the DC bin
         (base_nn.py:341-345)."""
-        key = ("a", drop_first_bin, self._sig())
-        if getattr(self, "_plan_a", None) is None or self._plan_a[0] != key:
-            lo = 1 if drop_first_bin else 0
-            bins = self.freq_bins if self.freq_bins is not None else self.wcos.shape[0]
-            w = torch.cat([self.wcos.detach()[lo:bins, 0, :], -self.wsin.detach()[lo:bins, 0, :]], dim=0).float()
-            self._plan_a = (key, hip.pack_wt(w), w.shape[0])
-        return self._plan_a[1], self._plan_a[2]
+        lo = 1 if self.drop_first_bin else 0
+        bins = self.freq_bins if self.freq_bins is not None else self.wcos.shape[0]
+        w = torch.cat([self.wcos.detach()[lo:bins, 0, :], -self.wsin.detach()[lo:bins, 0, :]], dim=0).float()
+        return hip.pack_wt(w), w.shape[0]
 
-    def _synthesis_plan(self, drop_first_bin: bool):
+    def _build_synthesis(self, device):
         """Packed weight of the synthesis product with the Hermitian extension (extend_fbins, stft.py:118-125)
         folded in: out[s] = sum_f re[f]*(Kc[s][f] + Kc[s][N-f]) - im[f]*(Ks[s][f] - Ks[s][N-f]), the mirrored
         terms only for 0 < f < N/2 (encoder.py:419-433); input channels [re bins ; im bins]."""
-        key = ("s", drop_first_bin, self._sig())
-        if getattr(self, "_plan_s", None) is None or self._plan_s[0] != key:
-            kc = self.kernel_cos_inv.detach()[:, 0, :, 0].float()  # [out sample s][bin h], h = 0..N-1
-            ks = self.kernel_sin_inv.detach()[:, 0, :, 0].float()
-            n = self.n_fft
-            f = torch.arange(n // 2 + 1, device=kc.device)
-            mirror = ((f > 0) & (f < n // 2)).float().unsqueeze(0)
-            mf = (n - f) % n
-            wre = kc[:, f] + mirror * kc[:, mf]
-            wim = -(ks[:, f] - mirror * ks[:, mf])
-            lo = 1 if drop_first_bin else 0
-            w = torch.cat([wre[:, lo:], wim[:, lo:]], dim=1).contiguous()  # [n_fft, 2*bins]
-            self._plan_s = (key, hip.pack_wt(w), self.window_mask.detach().flatten().float().contiguous())
-        return self._plan_s[1], self._plan_s[2]
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop("_plan_a", None)
-        state.pop("_plan_s", None)
-        return state
+        kc = self.kernel_cos_inv.detach()[:, 0, :, 0].float()  # [out sample s][bin h], h = 0..N-1
+        ks = self.kernel_sin_inv.detach()[:, 0, :, 0].float()
+        n = self.n_fft
+        f = torch.arange(n // 2 + 1, device=kc.device)
+        mirror = ((f > 0) & (f < n // 2)).float().unsqueeze(0)
+        mf = (n - f) % n
+        wre = kc[:, f] + mirror * kc[:, mf]
+        wim = -(ks[:, f] - mirror * ks[:, mf])
+        lo = 1 if self.drop_first_bin else 0
+        w = torch.cat([wre[:, lo:], wim[:, lo:]], dim=1).contiguous()  # [n_fft, 2*bins]
+        return hip.pack_wt(w), self.window_mask.detach().flatten().float().contiguous()
 
     # -- padded-layout entry points used by the fused wrapper ------------------------------------------
     def encode_padded(self, x: torch.Tensor, drop_first_bin: bool):
@@ -342,6 +349,13 @@ class ConvMelSpectrogram(ConvSTFT):
             self.register_buffer("filterbank", mel_fb)
             self.register_buffer("inv_filterbank", inv_mel_fb)
 
+    def _build_mel(self, device):
+        return hip.pack_wt(self.filterbank.detach().float().t().contiguous())
+
+    def prepare_plans(self, device) -> None:
+        self._analysis_plan(False)
+        self._plan_get(device, self._build_mel)
+
     def encode_padded(self, x: torch.Tensor):
         """[N, L] -> (mel features padded [N, n_mels, ldt], T)."""
         fmt = self.output_format.lower()
@@ -352,11 +366,8 @@ class ConvMelSpectrogram(ConvSTFT):
         spec, t = ConvSTFT.encode_padded(self, x, False)                                    # [re bins ; im bins]
         bins = spec.shape[1] // 2
         power = hip.magnitude(spec, t, False, False, kind="power_eps" if self.trainable else "power")
-        key = (self.filterbank.data_ptr(), self.filterbank._version)
-        if getattr(self, "_mel_plan", None) is None or self._mel_plan[0] != key:
-            self._mel_plan = (key, hip.pack_wt(self.filterbank.detach().float().t().contiguous()))
         n_mels = self.filterbank.shape[1]
-        y, _ = hip.conv1x1(power, t, self._mel_plan[1], n_mels,
+        y, _ = hip.conv1x1(power, t, self._plan_get(x.device, self._build_mel), n_mels,
                            out=torch.empty(x.shape[0], n_mels, spec.shape[-1], dtype=torch.float32, device=x.device))
         assert bins == self.filterbank.shape[0]
         return y, t

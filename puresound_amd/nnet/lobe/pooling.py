@@ -11,6 +11,7 @@ import torch.nn as nn
 from ... import hip
 from ...ops import op_module
 from ..._abi import PS_NORM_AFFINE
+from .._plans import GemmPlanCache
 
 
 def _pool_shape(ctor, x, aux, params):
@@ -18,10 +19,9 @@ def _pool_shape(ctor, x, aux, params):
 
 
 @op_module("attn_stats_pool_fwd", _pool_shape, method="_pool")
-class AttentiveStatisticsPooling(nn.Module):
-    # arithmetic of the two 1x1 convs: "fp16x2" (two fp16 terms per operand, three MFMA products, fp32 accumulation -- the
-    # TCN blocks' default; the first conv measures its input's range, the second one's input is a tanh) or "fp32"
-    gemm_precision = "fp16x2"
+class AttentiveStatisticsPooling(GemmPlanCache, nn.Module):
+    # gemm_precision: arithmetic of the two 1x1 convs, "fp16x2" (two fp16 terms per operand, three MFMA products, fp32
+    # accumulation -- the default; the first conv measures its input's range, the second one's input is a tanh) or "fp32"
 
     def __init__(self, channels, attention_channels=128):
         super().__init__()
@@ -32,36 +32,26 @@ class AttentiveStatisticsPooling(nn.Module):
             nn.ReLU(), nn.BatchNorm1d(attention_channels))
         self.tanh = nn.Tanh()
         self.conv = nn.Conv1d(in_channels=attention_channels, out_channels=channels, kernel_size=1)
-        self._plan = None
 
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state["_plan"] = None
-        return state
-
-    def _get_plan(self, device):
-        sig = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers())) + \
-            (self.training, str(device), self.gemm_precision)
-        if self._plan is None or self._plan["sig"] != sig:
-            bn = self.tdnn[2]
-            if bn.training:
-                raise RuntimeError("AttentiveStatisticsPooling: BatchNorm1d must be in eval() mode on the HIP path")
-            f32 = dict(dtype=torch.float32, device=device)
-            scale = (bn.weight.detach() / torch.sqrt(bn.running_var.detach() + bn.eps)).to(**f32).contiguous()
-            shift = (bn.bias.detach().to(**f32) - bn.running_mean.detach().to(**f32) * scale).contiguous()
-            self._plan = dict(sig=sig,
-                              w1=hip.pack_wt(self.tdnn[0].weight.detach().to(**f32)),
-                              b1=self.tdnn[0].bias.detach().to(**f32).contiguous(),
-                              w2=hip.pack_wt(self.conv.weight.detach().to(**f32)),
-                              b2=self.conv.bias.detach().to(**f32).contiguous(), scale=scale, shift=shift)
-            if self.gemm_precision == "fp16x2" and min(self.channels, self.attention_channels) >= 64:
-                self._plan["w1_f16x2"] = hip.pack_wt_f16x2(self.tdnn[0].weight.detach().to(**f32))
-                self._plan["w2_f16x2"] = hip.pack_wt_f16x2(self.conv.weight.detach().to(**f32))
-        return self._plan
+    def _build(self, device):
+        bn = self.tdnn[2]
+        if bn.training:
+            raise RuntimeError("AttentiveStatisticsPooling: BatchNorm1d must be in eval() mode on the HIP path")
+        f32 = dict(dtype=torch.float32, device=device)
+        scale = (bn.weight.detach() / torch.sqrt(bn.running_var.detach() + bn.eps)).to(**f32).contiguous()
+        shift = (bn.bias.detach().to(**f32) - bn.running_mean.detach().to(**f32) * scale).contiguous()
+        plan = dict(w1=hip.pack_wt(self.tdnn[0].weight.detach().to(**f32)),
+                    b1=self.tdnn[0].bias.detach().to(**f32).contiguous(),
+                    w2=hip.pack_wt(self.conv.weight.detach().to(**f32)),
+                    b2=self.conv.bias.detach().to(**f32).contiguous(), scale=scale, shift=shift)
+        if self.gemm_precision == "fp16x2" and min(self.channels, self.attention_channels) >= 64:
+            plan["w1_f16x2"] = hip.pack_wt_f16x2(self.tdnn[0].weight.detach().to(**f32))
+            plan["w2_f16x2"] = hip.pack_wt_f16x2(self.conv.weight.detach().to(**f32))
+        return plan
 
     def forward_padded(self, x_pad: torch.Tensor, t: int, lengths=None, return_weight: bool = False) -> torch.Tensor:
         """padded [N,C,ldt] (+ relative lengths [N]) -> [N,2C] (mean ; std), or the padded attention map [N,C,ldt]."""
-        p = self._get_plan(x_pad.device)
+        p = self._plan_get(x_pad.device, self._build)
         n, _, ldt = x_pad.shape
         pro = hip.make_prologue(PS_NORM_AFFINE, False, None, 0.0, 0.0, p["scale"], p["shift"], None,
                                 pre_relu=True, post_tanh=True)

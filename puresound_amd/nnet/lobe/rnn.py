@@ -8,11 +8,11 @@ import torch.nn as nn
 
 from ... import hip
 from ...ops import op_module, same_shape
-from .._plans import PlanCache, linear_plan, lstm_gates, lstm_plan, lstm_recurrence, lstm_route, packed, rnn_plan
+from .._plans import GemmPlanCache, linear_plan, lstm_gates, lstm_plan, lstm_recurrence, lstm_route, packed, rnn_plan
 
 
 @op_module("single_rnn_fwd", same_shape)
-class SingleRNN(PlanCache, nn.Module):
+class SingleRNN(GemmPlanCache, nn.Module):
     def __init__(self, rnn_type: str, input_size: int, hidden_size: int, bidirectional: bool = False,
                  dropout: float = 0.0):
         super().__init__()

@@ -11,7 +11,7 @@ import torch.nn as nn
 
 from ... import hip
 from ...ops import op_module
-from .._plans import PlanCache, _f32, layernorm_plan
+from .._plans import GemmPlanCache, _f32, layernorm_plan
 from .norm import ChanLN
 
 
@@ -123,7 +123,7 @@ class _PerFrameCondition:
         return None, self._per_frame
 
 
-class FiLM(_PerFrameCondition, PlanCache, nn.Module):
+class FiLM(_PerFrameCondition, GemmPlanCache, nn.Module):
     """Feature-wise linear modulation (lobe/trivial.py:129-167)."""
 
     def __init__(self, feats_size: int, embed_size: int, input_norm: bool = True):
@@ -174,7 +174,7 @@ class FiLM(_PerFrameCondition, PlanCache, nn.Module):
         return hip.unpad_rows(self.forward_padded(hip.pad_rows(x), t, condition), t)
 
 
-class Gate(_PerFrameCondition, PlanCache, nn.Module):
+class Gate(_PerFrameCondition, GemmPlanCache, nn.Module):
     """Gated conditioning (lobe/trivial.py:61-126)."""
 
     def __init__(self, input_size: int, hidden_size: int, embed_size: int, dropout: float = 0.0):

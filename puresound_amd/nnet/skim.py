@@ -13,11 +13,11 @@ import torch.nn as nn
 
 from .. import hip
 from ..ops import op_module
-from ._plans import PlanCache, _f32, layernorm_plan, linear_plan, lstm_path, lstm_plan
+from ._plans import GemmPlanCache, _f32, layernorm_plan, linear_plan, lstm_path, lstm_plan
 from .lobe.trivial import FiLM, Gate
 
 
-class MemLSTM(PlanCache, nn.Module):
+class MemLSTM(GemmPlanCache, nn.Module):
     """skim.py:11-43 (parameters), :45-114 (forward)."""
 
     def __init__(self, hidden_size: int, causal: bool = True, dropout: float = 0.0):
@@ -107,7 +107,7 @@ class MemLSTM(PlanCache, nn.Module):
         return back(ho), back(co)
 
 
-class SegLSTM(PlanCache, nn.Module):
+class SegLSTM(GemmPlanCache, nn.Module):
     """skim.py:168-229."""
 
     def __init__(self, input_size: int, hidden_size: int, causal: bool = True, dropout: float = 0.0):
@@ -166,7 +166,7 @@ def _out_size(ctor, x, aux, params):
 
 
 @op_module("skim_fwd", _out_size)
-class SkiM(PlanCache, nn.Module):
+class SkiM(GemmPlanCache, nn.Module):
     """Skipping memory LSTM (skim.py:251-469); constructor order as the reference (skim.py:280-294)."""
 
     def __init__(self, input_size: int, hidden_size: int, output_size: int, n_blocks: int = 2, seg_size: int = 20,

@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from .. import hip
 from ..ops import op_module, same_shape
-from ._plans import PlanCache, _f32
+from ._plans import GemmPlanCache, _f32
 from .conv_tasnet import TCN, GatedTCN, TcnBlock
 from .lobe.activation import activation_kind, get_activation
 from .._abi import PS_NORM_GLOBAL
@@ -41,7 +41,7 @@ def _unet_shape(ctor, x, aux, params):
 
 
 @op_module("unet_fwd", _unet_shape)
-class Unet(PlanCache, nn.Module):
+class Unet(GemmPlanCache, nn.Module):
     """unet.py:13-296; constructor order as the reference (unet.py:35-53)."""
 
     def __init__(self, input_type: str = "RI", input_dim: int = 512, activation_type: str = "PReLU",
@@ -143,6 +143,9 @@ class Unet(PlanCache, nn.Module):
         if kind == "prelu" and mod.weight.numel() != 1:
             raise NotImplementedError("PReLU with per-channel slopes is not on the HIP path")
         return kind, (_f32(mod.weight, device) if kind == "prelu" else None)
+
+    def prepare_plans(self, device) -> None:
+        self._plan_get(device, self._build_unet)
 
     def _build_unet(self, device):
         if any(st != 1 for _, st in self.stride):

@@ -34,7 +34,7 @@ from ..nnet.dpcrn import DPCRN
 from ..nnet.lobe.encoder import ConvEncDec
 from ._session import HopSession, check_on_device
 
-_SWAP = ("gemm_precision", "_plan", "_plan_sig")
+_SWAP = ("gemm_precision", "_plans")
 
 
 def check_streamable(model) -> None:

@@ -773,7 +773,7 @@ def test_bn_block_in_fp16x2_over_input_scales(PA, dev, scale, dilation):
     outs = {}
     for prec in ("fp32", "fp16x2"):
         blk.gemm_precision = prec
-        blk._plan = None
+        blk._plans = None
         assert blk.gemm_planes_for_plan() == (2 if prec == "fp16x2" else 0)
         outs[prec] = blk(x)
     assert torch.isfinite(outs["fp16x2"]).all()

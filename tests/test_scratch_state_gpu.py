@@ -1,6 +1,6 @@
 """A result is a function of the inputs and the weights only: not of what a kept scratch buffer held before the call, and
-not of which other lane is running.  Three kinds of scratch live from call to call -- ConvTasNet._workspace[lane] and the
-wrapper's _spk_workspace[lane] (the fused masker driver's hidden maps, fp64 statistics partials, bias_n and range maxima,
+not of which other lane is running.  Three kinds of scratch live from call to call -- the workspaces ConvTasNet and the
+wrapper keep per lane (the fused masker driver's hidden maps, fp64 statistics partials, bias_n and range maxima,
 re-carved at other offsets whenever a smaller (N, T) reuses them) and the zeroed LSTM output rows of DPCRN / DPARN
 (_plans._h_rows) -- and none of them is reached by NaN in the caching allocator: they are zero-filled when created.
 
@@ -226,7 +226,7 @@ def test_staged_cln_masker_keeps_no_scratch(PA, H, dev, arith):
             _fill_allocator_cache(dev, junk)
             outs.append(model.forward_padded(x_pad, t)[..., :t].clone())
             torch.cuda.synchronize()
-        assert model._workspace is None
+        assert model.kept_scratch() == []
         assert rel_max(outs[0].cpu().double().numpy(), ref.numpy()) < TOL, (n, t)    # test_masker_matches_reference_golden
         assert torch.equal(outs[0], outs[1]), (n, t)
 

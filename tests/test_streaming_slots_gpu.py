@@ -386,14 +386,14 @@ def test_model_left_intact(dev):
     e = det_wave(c["seed"] + 1, c["B"], c["L_enroll"]).to(dev)
     before = model.inference(x, e)
     params = [p.detach().clone() for p in model.parameters()]
-    plans = [m._plan for stack in model.masker.tcn_list for m in stack if hasattr(m, "_plan")]
+    plans = [m.plan(dev) for stack in model.masker.tcn_list for m in stack]
     s = StreamingConvTasNet(model)
     streams = _streams(model, s, dev, [(0, 0, 120, 0), (1, 3, 60, 1), (1, 80, 70, 0)], seed=1000)
     _run_slots(s, 2, streams, (4,))
     _run_slots(s, 2, streams, SCHEDULE, use_graph=False)
     assert all(m.gemm_precision == "fp16x2" for stack in model.masker.tcn_list for m in stack)
     assert all(torch.equal(p, q) for p, q in zip(model.parameters(), params))
-    assert all(a is b for a, b in zip(plans, [m._plan for stack in model.masker.tcn_list for m in stack if hasattr(m, "_plan")]))
+    assert all(a is b for a, b in zip(plans, [m.plan(dev) for stack in model.masker.tcn_list for m in stack]))
     assert torch.equal(model.inference(x, e), before)
 
 

@@ -49,11 +49,7 @@ def cfg3(dev, steps=5, warmup=2, modes=("fp16x2", "bf16"), batch=32):
     model.hip_streams = 1   # (one stream: every launch covers the whole batch, as in bench.py's timed path; two lanes: 14.2 ms)
     noisy, enroll = _waves(batch, 1234, dev), _waves(batch, 1235, dev)
 
-    def set_mode(prec):
-        model.masker.set_gemm_precision(prec)
-        for m in model.speaker_net:
-            if hasattr(m, "gemm_precision"):
-                m.gemm_precision = prec
+    set_mode = model.set_gemm_precision
     set_mode("fp32")
     ref = model.inference(noisy, enroll)
     out = {"workload": f"td_tse_conv_tasnet_v0, {batch} x (4 s mixture + 4 s enrolment), 1 GPU", "steps": steps}

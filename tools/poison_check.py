@@ -1,8 +1,8 @@
 """Uninitialised-memory check at the benchmark's batch (GPU box): the caching allocator is filled with NaN blocks of the sizes
 a 32 x 4 s forward allocates (maps, partial-statistics slots, outputs), released, and the forward must return the bits of a
 clean run.  NaN in the allocator reaches `torch.empty` memory only.  The scratch a model KEEPS from call to call -- the fused
-masker driver's workspaces, ConvTasNet._workspace[lane] and the wrapper's _spk_workspace[lane] -- is zero-filled when it
-is created, and the clean reference call creates it before anything is poisoned: so every kept workspace is overwritten
+masker driver's workspaces, which ConvTasNet and the wrapper keep per lane (nnet/_plans.py: PlanCache.keep_scratch) -- is
+zero-filled when it is created, and the clean reference call creates it before anything is poisoned: so every kept workspace is overwritten
 with 0xFF bytes (NaN as fp32 and as fp64) as well.  (The zeroed LSTM output rows of DPCRN / DPARN are left alone: their
 pad frames are zero by contract, _plans._h_rows.)  tests/test_hip_parity.py::
 test_results_do_not_depend_on_uninitialised_memory and tests/test_scratch_state_gpu.py do this at the fixtures' batch of 2,
@@ -36,11 +36,8 @@ def poison(dev):
 
 def kept_workspaces(model):
     """every fused-driver workspace the model holds on to (uint8 tensors)"""
-    kept = list((model.__dict__.get("_spk_workspace") or {}).values())
-    for m in model.modules():
-        if isinstance(m, PA.ConvTasNet) and m._workspace:
-            kept += list(m._workspace.values())
-    return kept
+    from puresound_amd.nnet._plans import PlanCache
+    return [ws for m in model.modules() if isinstance(m, PlanCache) for ws in m.kept_scratch() if torch.is_tensor(ws)]
 
 
 def main():
