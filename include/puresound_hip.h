@@ -987,6 +987,42 @@ int ps_conv_tasnet_ranged_f32(const ps_tcn_block* blocks, int n_blocks, const fl
 int ps_conv_tasnet_bf16_rows(const ps_tcn_block* blocks, int n_blocks, const void* x_in, void* x_out, const float* dvec,
                              int embed_norm, int N, int T, int ldt, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batches of utterances of unequal length through the Conv-TasNet masker (csrc/ragged.hip).  Row n of a padded
+ * [N][R][ldt] tensor holds t_rows[n] valid frames, 1 <= t_rows[n] <= T, and ANYTHING behind them (the features of whatever
+ * follows a short utterance in its row, NaN included): no result depends on it.  t_rows / limit are int32 DEVICE arrays
+ * [N]; the host validates the values it copies there, the kernels clamp what they read to [0, T] (or [0, ld]) so that no
+ * access leaves a row.  In a TCN block frames meet each other only in the statistics of the global norms, in the taps of
+ * the depthwise convolution and in the decoder's overlap-add: these entries stand there, the 1x1 GEMMs run over all T
+ * frames on ps_conv1x1_f32 (column t >= t_rows[n] of a hidden map is junk that nothing reads as data).
+ *
+ * ps_ragged_stats_f32: ostats[n][p] = (sum, sum of squares) of y[n][r][t] over r = p, p + parts, ... < R and t < t_rows[n],
+ *   in fp64, in a fixed order (no atomics), TIMES count_full / (R * t_rows[n]).  Every one of the `parts` slots is written (0
+ *   where a slot has no rows).  A consumer's ps_prologue keeps its layout and its launch-wide count = count_full = R * T:
+ *   it derives mean = S1 / (R T_n) and var = S2 / (R T_n) - mean^2, the statistics of the utterance on its own.
+ * ps_dwconv_ragged_f32: ps_dwconv_f32 (same P <= 8, dilation, left, prologue) with a = prologue(x) read as 0 outside
+ *   [0, t_rows[n]) -- a select per element, not a product -- and y[n][h][t] = 0 for t_rows[n] <= t < T.  A workgroup owns 16
+ *   channels x 1024 frames; tiles at or behind t_rows[n] store zeros without loading.  ostats (or NULL):
+ *   [N][ps_dwconv_stats_parts(H, T)][2] over t < t_rows[n], scaled by count_full / (H * t_rows[n]) as above.  y != x.
+ * ps_zero_tail_f32: x[n][r][t] = 0.0 for limit[n] <= t < ld on x [N][R][ld]; nothing is read.  In front of the decoder on the
+ *   features and the mask logits (frames >= t_rows[n] then add exact zeros to the overlap-add whatever the mask
+ *   activation), behind it with R = 1 on the waveform's samples >= (t_rows[n] - 1) * hop + win.
+ * ps_conv_tasnet_ragged_f32: ps_conv_tasnet_f32 for such a batch, always in the exact-fp32 arithmetic whatever
+ *   blocks[i].gemm_planes says (it reads in_wt / pw_wt / out_wt).  Per block: in_conv; ps_ragged_stats_f32 of y1 (global
+ *   in_norm); ps_dwconv_ragged_f32; the pointwise conv; ps_ragged_stats_f32 of y3 (global pw_norm); out_conv + residual.
+ *   Same workspace (ps_conv_tasnet_workspace_bytes) and argument rules as ps_conv_tasnet_f32; refused before any launch.
+ *   x_out[n][c][t] for t >= t_rows[n] is junk: ps_zero_tail_f32 it before a decoder.
+ * ------------------------------------------------------------------------------------------- */
+int ps_ragged_stats_f32(const float* y, const int* t_rows, double* ostats, int N, int R, int T, int ldt, int parts,
+                        double count_full, void* stream);
+int ps_dwconv_ragged_f32(const float* x, const float* w, const float* b, float* y, const int* t_rows, int N, int H, int T,
+                         int ldt, int P, int dilation, int left, const ps_prologue* pro, double* ostats, double count_full,
+                         void* stream);
+int ps_zero_tail_f32(float* x, const int* limit, int N, int R, int ld, void* stream);
+int ps_conv_tasnet_ragged_f32(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out, const float* dvec,
+                              int embed_norm, int N, int T, int ldt, const int* t_rows, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* Five moments of an (estimate, reference) waveform pair per row -- sum a, sum b, sum a^2, sum b^2, sum ab over L
  * samples, fp64 -- as per-workgroup partials [N][ps_wave_moments_chunks(L)][5] (the caller adds them up).  Every
  * SDR / SI-SNR variant of the reference's SDRLoss.forward (puresound/nnet/loss/sdr.py:104-183), si_snr (:263-299) and

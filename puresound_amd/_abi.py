@@ -250,6 +250,11 @@ SIGNATURES = {
     "ps_conv1x1_f16_rows": (C.c_int, [_vp, _vp, C.POINTER(F16x2Range), _vp] + [C.c_int] * 5 + [C.POINTER(Prologue), _vp, _vp, _vp, _vp, _vp]),
     "ps_conv_tasnet_bf16_rows": (C.c_int, [C.POINTER(TcnBlock), C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
                                            C.c_int, _vp, C.c_size_t, _vp]),
+    "ps_ragged_stats_f32": (C.c_int, [_vp, _vp, _vp] + [C.c_int] * 5 + [C.c_double, _vp]),
+    "ps_dwconv_ragged_f32": (C.c_int, [_vp] * 5 + [C.c_int] * 7 + [C.POINTER(Prologue), _vp, C.c_double, _vp]),
+    "ps_zero_tail_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "ps_conv_tasnet_ragged_f32": (C.c_int, [C.POINTER(TcnBlock), C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, _vp, _vp, C.c_size_t, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

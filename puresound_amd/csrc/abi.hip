@@ -172,21 +172,9 @@ extern "C" int ps_stats_parts(int channels, int frames) {
   return gemm > dw ? gemm : dw;
 }
 
-// Workspace carve-up for ps_conv_tasnet_f32:
-//   y1, y2, y3 : 3 x [N][H][ldt] fp32
-//   stats      : 3 x [N][parts][2] fp64
-//   bias_n     : [N][H] fp32 (only with an embedding)
-//   amax       : 2 x [N][amax_parts] fp32 partial maxima of the residual stream (gemm_planes = 2: the range the next
-//                block's in_conv scales its input by; written by out_conv's epilogue, or by ps_absmax_f32 for block 0)
-struct TasnetWs {
-  float *y1, *y2, *y3, *bias_n;
-  float* amax[2];
-  double *s1, *s2, *s3;
-  int parts, amax_parts;
-  size_t bytes;
-};
-
-static TasnetWs carve(void* base, int N, int C, int H, int T) {
+// Workspace carve-up for ps_conv_tasnet_f32 (TasnetWs, ps_common.h)
+namespace ps {
+TasnetWs carve(void* base, int N, int C, int H, int T) {
   TasnetWs w{};
   const int ldt = ps_padded_frames(T);
   // parts must cover producers with up to max(C,H) channels; H is what every stats producer emits
@@ -210,6 +198,7 @@ static TasnetWs carve(void* base, int N, int C, int H, int T) {
   w.bytes = (size_t)(p - (char*)base);
   return w;
 }
+}  // namespace ps
 
 extern "C" size_t ps_conv_tasnet_workspace_bytes(int N, int C, int H, int T) {
   if (N <= 0 || C <= 0 || H <= 0 || T <= 0) return 0;
@@ -217,7 +206,9 @@ extern "C" size_t ps_conv_tasnet_workspace_bytes(int N, int C, int H, int T) {
 }
 
 // The driver: helpers, the checks, the per-block plan, the launch path, the three entries.
-static int dw_left(int P, int dilation, int causal) { return causal ? (P - 1) * dilation : ((P - 1) / 2) * dilation; }
+namespace ps {
+int dw_left(int P, int dilation, int causal) { return causal ? (P - 1) * dilation : ((P - 1) / 2) * dilation; }
+}  // namespace ps
 
 // gemm_planes = 2 behind a folded BatchNorm (bN1d blocks: no bound on the normalised values exists): the producer leaves the
 // maxima of its output behind -- in the statistics slots such a norm has no use for -- and the consumer maps them through the
@@ -244,10 +235,12 @@ static bool leaves_maxima(const ps_tcn_block& b, int sb, int N, int T) {
 }
 
 // norm + PReLU in front of a consumer: GlobLN.eps and gGN's eps (lobe/norm.py:10,96); a folded BN carries its own
-static ps_prologue norm_prelu(int norm, const double* stats, int parts, double count, const float* gamma, const float* beta,
-                              const float* slope) {
+namespace ps {
+ps_prologue norm_prelu(int norm, const double* stats, int parts, double count, const float* gamma, const float* beta,
+                       const float* slope) {
   return ps_prologue{norm, /*prelu*/ 1, stats, parts, count, /*eps*/ 1e-8f, gamma, beta, slope, /*pre_relu*/ 0, /*post_tanh*/ 0};
 }
+}  // namespace ps
 
 // The range descriptor of GEMM `which` (0 / 1 / 2: in_conv, pointwise, out_conv) in the fp16x2 and the f16-rows arithmetic.
 // in_conv: the maxima of the stream (x_amax).  Behind a norm (gmax / bmax: its largest scale and shift, times
@@ -282,11 +275,11 @@ static int refuse(int code, const char* fmt, ...) {
   return code;
 }
 
-// Everything a call can be refused for, before the first launch: the arguments, then block by block
-static int check_call(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out, const float* dvec,
-                      int embed_norm, int N, int T, int ldt, void* workspace, size_t workspace_bytes, const float* x_amax,
-                      int x_amax_parts, void* stream, int sb) {
-  if (x_amax && x_amax_parts <= 0) return refuse(PS_E_INVALID, "ps_conv_tasnet_ranged_f32: x_amax needs x_amax_parts > 0");
+// The rules of the arguments and of the blocks' sizes that every masker driver shares (ragged.hip's too), in the order the
+// entries have always given them
+namespace ps {
+int check_stack(const ps_tcn_block* blocks, int n_blocks, const float* x_in, const float* x_out, int N, int T, int ldt,
+                const void* workspace, size_t workspace_bytes) {
   if (!blocks || n_blocks <= 0 || !x_in || !x_out || !workspace || N <= 0 || T <= 0)
     return refuse(PS_E_INVALID, "ps_conv_tasnet_f32: null pointer or non-positive size");
   if (x_in == x_out)
@@ -307,6 +300,17 @@ static int check_call(const ps_tcn_block* blocks, int n_blocks, const float* x_i
   if (workspace_bytes < need)
     return refuse(PS_E_INVALID, "ps_conv_tasnet_f32: workspace too small (%zu < %zu)", workspace_bytes, need);
   if ((uintptr_t)workspace & 255) return refuse(PS_E_ALIGN, "ps_conv_tasnet_f32: workspace must be 256-byte aligned");
+  return 0;
+}
+}  // namespace ps
+
+// Everything a call can be refused for, before the first launch: the arguments, then block by block
+static int check_call(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out, const float* dvec,
+                      int embed_norm, int N, int T, int ldt, void* workspace, size_t workspace_bytes, const float* x_amax,
+                      int x_amax_parts, void* stream, int sb) {
+  if (x_amax && x_amax_parts <= 0) return refuse(PS_E_INVALID, "ps_conv_tasnet_ranged_f32: x_amax needs x_amax_parts > 0");
+  if (const int rc = check_stack(blocks, n_blocks, x_in, x_out, N, T, ldt, workspace, workspace_bytes)) return rc;
+  const int H = blocks[0].H;
   const int ws_parts = ps_stats_parts(H, T);
   const auto ranged = [](int norm) { return norm == PS_NORM_GLOBAL || norm == PS_NORM_AFFINE; };
   for (int i = 0; i < n_blocks; ++i) {

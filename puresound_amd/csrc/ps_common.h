@@ -96,6 +96,29 @@ int conv1x1_small_launch(const float* x, const float* wt, float* y, int N, int K
                          const ps_prologue* pro, const float* bias, const float* bias_n, const float* res,
                          hipStream_t stream);
 
+// abi.hip: what the Conv-TasNet masker drivers (abi.hip's three entries, ragged.hip's one) share.
+// Workspace carve-up for ps_conv_tasnet_f32:
+//   y1, y2, y3 : 3 x [N][H][ldt] fp32
+//   stats      : 3 x [N][parts][2] fp64
+//   bias_n     : [N][H] fp32 (only with an embedding)
+//   amax       : 2 x [N][amax_parts] fp32 partial maxima of the residual stream (gemm_planes = 2: the range the next
+//                block's in_conv scales its input by; written by out_conv's epilogue, or by ps_absmax_f32 for block 0)
+struct TasnetWs {
+  float *y1, *y2, *y3, *bias_n;
+  float* amax[2];
+  double *s1, *s2, *s3;
+  int parts, amax_parts;
+  size_t bytes;
+};
+TasnetWs carve(void* base, int N, int C, int H, int T);
+int dw_left(int P, int dilation, int causal);
+// norm + PReLU in front of a consumer
+ps_prologue norm_prelu(int norm, const double* stats, int parts, double count, const float* gamma, const float* beta,
+                       const float* slope);
+// the argument, size and workspace rules of a masker call: 0, or the code with the message set
+int check_stack(const ps_tcn_block* blocks, int n_blocks, const float* x_in, const float* x_out, int N, int T, int ldt,
+                const void* workspace, size_t workspace_bytes);
+
 __device__ __forceinline__ float prelu(float v, float slope) { return v >= 0.f ? v : slope * v; }
 // torch.relu / clamp keep a NaN a NaN (fmaxf / fminf would return the other operand): the reference's own look-ahead
 // probe (base_nn.py:740-777) reads NaNs off the output

@@ -1623,3 +1623,90 @@ def conv_tasnet(blocks: "C.Array[TcnBlock]", n_blocks: int, x_pad: torch.Tensor,
                                               ptr(workspace), workspace.numel(), ptr(x_amax), parts, stream_ptr(dev)),
               "ps_conv_tasnet_ranged_f32")
     return out
+
+
+# ---- batches of utterances of unequal length (csrc/ragged.hip) ----------------------------------------------------------------
+def row_limits(who: str, values: Sequence[Sequence[int]], device: torch.device) -> torch.Tensor:
+    """Host integers [K][N] -> one int32 device tensor [K, N] by ONE host-to-device copy: the per-row limits of a ragged call
+    (frames per utterance, valid output samples, ...), already validated by the caller; row k is contiguous."""
+    host = torch.tensor(values, dtype=torch.int32)
+    if host.dim() != 2:
+        raise ValueError(f"{who}: the limits must be K sequences of N integers")
+    return host.to(device)
+
+
+def _require_limits(who: str, lim: torch.Tensor, n: int, device: torch.device) -> None:
+    _require_operand(who, device, torch.int32, limits=lim)
+    if tuple(lim.shape) != (n,):
+        raise ValueError(f"{who}: the per-row limits must be an int32 tensor [N={n}], got {tuple(lim.shape)}")
+
+
+def ragged_stats(y: torch.Tensor, t: int, t_rows: torch.Tensor, parts: Optional[int] = None) -> torch.Tensor:
+    """y padded [N,R,ldt], t_rows int32 [N] -> partial (sum, sum of squares) [N,parts,2] fp64 over t < t_rows[n], scaled so
+    that a prologue with count = R * t derives the statistics of the R * t_rows[n] valid elements."""
+    require_device(y, "ragged_stats")
+    n, r, ldt = y.shape
+    _require_limits("ragged_stats", t_rows, n, y.device)
+    parts = lib().ps_stats_parts(r, t) if parts is None else int(parts)
+    if parts <= 0 or not y.is_contiguous():
+        raise RuntimeError(f"ragged_stats: contiguous rows and parts > 0 (got parts={parts}, strides {y.stride()})")
+    stats = _stats_buffer(n, parts, y.device)
+    check(lib().ps_ragged_stats_f32(ptr(y), ptr(t_rows), ptr(stats), n, r, t, ldt, parts, float(r) * float(t),
+                                    stream_ptr(y.device)), "ps_ragged_stats_f32")
+    return stats
+
+
+def dwconv_ragged(x: torch.Tensor, t: int, t_rows: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], dilation: int,
+                  left: int, pro: Optional[Prologue] = None, want_stats: bool = False
+                  ) -> tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """dwconv with a per-row frame limit: x padded [N,H,ldt], w [H,1,P] -> y padded [N,H,ldt], 0 on [t_rows[n], t) (+ the
+    partial statistics over t < t_rows[n], scaled as ragged_stats')."""
+    require_device(x, "dwconv_ragged")
+    _require_operand("dwconv_ragged", x.device, w=w, b=b)
+    n, h, ldt = x.shape
+    _require_limits("dwconv_ragged", t_rows, n, x.device)
+    y = torch.empty_like(x)
+    stats = _stats_buffer(n, lib().ps_dwconv_stats_parts(h, t), x.device) if want_stats else None
+    check(lib().ps_dwconv_ragged_f32(ptr(x), ptr(w), ptr(b), ptr(y), ptr(t_rows), n, h, t, ldt, w.shape[-1], dilation, left,
+                                     C.byref(pro) if pro is not None else None, ptr(stats), float(h) * float(t),
+                                     stream_ptr(x.device)), "ps_dwconv_ragged_f32")
+    return y, stats
+
+
+def zero_tail(x: torch.Tensor, limits: torch.Tensor) -> torch.Tensor:
+    """x [N,R,ld] (or a waveform batch [N,ld]), in place: 0.0 at columns >= limits[n]; nothing is read."""
+    require_device(x, "zero_tail")
+    if x.dim() not in (2, 3) or not x.is_contiguous():
+        raise RuntimeError(f"zero_tail: a contiguous [N, R, ld] or [N, ld] tensor (got {tuple(x.shape)}, strides {x.stride()})")
+    n, ld = x.shape[0], x.shape[-1]
+    _require_limits("zero_tail", limits, n, x.device)
+    check(lib().ps_zero_tail_f32(ptr(x), ptr(limits), n, x.numel() // (n * ld), ld, stream_ptr(x.device)), "ps_zero_tail_f32")
+    return x
+
+
+def conv_tasnet_ragged(blocks: "C.Array[TcnBlock]", n_blocks: int, x_pad: torch.Tensor, t: int, c: int, h: int,
+                       t_rows: torch.Tensor, dvec: Optional[torch.Tensor], embed_norm: bool,
+                       workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_tasnet for a batch whose row n holds t_rows[n] <= t valid frames (int32 [N] on the device) and anything behind
+    them: padded [N,C,ldt] -> padded mask logits, row n those of its utterance alone on [0, t_rows[n]) and junk behind.
+    Exact fp32 products whatever the blocks' gemm_planes."""
+    require_device(x_pad, "conv_tasnet_ragged")
+    if x_pad.dim() != 3 or x_pad.shape[1] != c or not x_pad.is_contiguous():
+        raise RuntimeError(f"conv_tasnet_ragged: x_pad must be contiguous [N, C={c}, ldt] (got {tuple(x_pad.shape)}, "
+                           f"strides {x_pad.stride()})")
+    n, _, ldt = x_pad.shape
+    dev = x_pad.device
+    _require_limits("conv_tasnet_ragged", t_rows, n, dev)
+    _require_operand("conv_tasnet_ragged", dev, dvec=dvec)
+    if dvec is not None:
+        sizes = _embed_sizes(blocks, n_blocks)
+        if dvec.dim() != 2 or dvec.shape[0] != n or sizes - {dvec.shape[1]}:
+            raise RuntimeError(f"conv_tasnet_ragged: dvec must be [N={n}, E], the blocks' E={sorted(sizes)} "
+                               f"(got {tuple(dvec.shape)})")
+    workspace = conv_tasnet_workspace(n, c, h, t, dev, workspace)
+    _require_operand("conv_tasnet_ragged", dev, torch.uint8, workspace=workspace)
+    out = torch.empty_like(x_pad)
+    check(lib().ps_conv_tasnet_ragged_f32(blocks, n_blocks, ptr(x_pad), ptr(out), ptr(dvec), int(embed_norm), n, t, ldt,
+                                          ptr(t_rows), ptr(workspace), workspace.numel(), stream_ptr(dev)),
+          "ps_conv_tasnet_ragged_f32")
+    return out

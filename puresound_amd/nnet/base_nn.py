@@ -203,22 +203,78 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
             "inference path only -- use .inference()")
 
     # -- the hot path -----------------------------------------------------------------------------
-    def inference(self, noisy: torch.Tensor, enroll: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """noisy [N,L] (+ enroll [N,L']) -> enhanced waveform [N,L_out] (base_nn.py:690-722)."""
+    def inference(self, noisy: torch.Tensor, enroll: Optional[torch.Tensor] = None, lengths=None,
+                  enroll_lengths=None) -> torch.Tensor:
+        """noisy [N,L] (+ enroll [N,L']) -> enhanced waveform [N,L_out] (base_nn.py:690-722).
+
+        lengths / enroll_lengths (not in the reference; N Python ints or a CPU integer tensor [N], host values): row n of
+        noisy (enroll) is an utterance of lengths[n] (enroll_lengths[n]) samples and junk behind it that no result depends
+        on.  Row n of the result is, on its first output_lengths(lengths)[n] samples, what inference(noisy[n:n+1,
+        :lengths[n]], enroll[n:n+1, :enroll_lengths[n]]) returns for that utterance alone, and exact 0.0 behind them.  Exact
+        fp32 products whatever gemm_precision says, one lane (hip_streams is ignored).  Covered: FreeEncDec + a normal-TCN
+        ConvTasNet on the fused driver, with an enrolment the td_tse_conv_tasnet_v0 speaker net; nnet/ragged.py lists the
+        refusals, all raised before any launch."""
         if noisy.device.type == "cpu":  # BASELINE configs[0] / the recipes' --backend cpu: stock ATen (nnet/cpu_path.py)
             from . import cpu_path
-            return cpu_path.wrapper_inference(self, noisy, enroll)
+            return cpu_path.wrapper_inference(self, noisy, enroll, lengths, enroll_lengths)
+        if lengths is not None or enroll_lengths is not None:
+            return self._inference_ragged(noisy, enroll, lengths, enroll_lengths)
         return self._inference(noisy, enroll, None)
+
+    def output_lengths(self, lengths) -> list:
+        """The valid sample counts of inference(..., lengths=lengths): (T_n - 1) * hop + win, T_n = (lengths[n] - win) //
+        hop + 1, per row."""
+        from . import ragged
+        win, hop = self.encoder.win_length, self.encoder.hop_length
+        lens = ragged.host_lengths("lengths", lengths, len(lengths), None, win)
+        return [(ragged.frames(v, win, hop) - 1) * hop + win for v in lens]
+
+    @torch.no_grad()
+    def _inference_ragged(self, noisy: torch.Tensor, enroll: Optional[torch.Tensor], lengths, enroll_lengths):
+        """inference() with per-row lengths on the HIP path: the encoder and the decoder run over all T frames of the rows
+        as they are, the masker through ConvTasNet's ragged driver, and ps_zero_tail_f32 clears features and mask logits
+        behind each row's last frame in front of the decoder (those frames then add exact zeros to the overlap-add
+        whatever the mask activation) and the waveform behind each row's last valid sample."""
+        from . import ragged
+        hip.require_device(noisy, "SoTaskWrapModule.inference")
+        if enroll is not None:
+            hip.require_device(enroll, "SoTaskWrapModule.inference")
+        mask_act = self.check_mask_constraint(self.mask_constraint)
+        out_mode = self.output_constraint.lower()
+        if out_mode not in ("linear", "sigmoid"):
+            raise NameError("Non support type.")  # base_nn.py:421-422
+        rp = ragged.plan(self, noisy, enroll, lengths, enroll_lengths)
+        dev = noisy.device
+        # every host value of the call in ONE host-to-device copy: frames and valid samples per row, the enrolment's frames
+        # and, as the bits of fp32 values, the relative lengths the pooling takes
+        rows = [rp.t_rows, rp.out_lengths]
+        if enroll is not None:
+            rel = torch.tensor(ragged.relative_lengths(rp.enroll_t_rows, rp.enroll_frames), dtype=torch.float32)
+            rows += [rp.enroll_t_rows, rel.view(torch.int32).tolist()]
+        limits = hip.row_limits("inference", rows, dev)
+        dvec = None
+        if enroll is not None:
+            dvec = self._speaker_embedding(enroll.contiguous(), 0, limits[2], limits[3].view(torch.float32))
+        feats, t = self.encoder.encode_padded(noisy.contiguous())
+        mask = self.masker.forward_padded(feats, t, dvec, t_rows=limits[0])
+        hip.zero_tail(feats, limits[0])
+        hip.zero_tail(mask, limits[0])
+        wav = self.encoder.decode_padded(feats, t, mask, mask_act, out_mode)
+        return hip.zero_tail(wav, limits[1])
 
     @torch.no_grad()
     def inference_scored(self, noisy: torch.Tensor, ref_clean: torch.Tensor, enroll: Optional[torch.Tensor] = None,
-                         loss_func: Optional[nn.Module] = None, inactive_labels: Optional[torch.Tensor] = None):
+                         loss_func: Optional[nn.Module] = None, inactive_labels: Optional[torch.Tensor] = None,
+                         lengths=None, enroll_lengths=None):
         """inference() and the signal score of its result against ref_clean [N, L_ref] in one go -> (enhanced [N, L_out],
         score).  Not a method of the reference: it is what its evaluation loops do after inference (`_align_waveform`,
         base_nn.py:398-412, then SDRLoss / si_snr, loss/sdr.py:104-299), with the score's five moments gathered by the
         decoder kernel while it writes the waveform instead of by further passes over it.  loss_func: an
         SDRLoss (default self.loss_func_wav, else SDRLoss.init_mode("sisnr")); the score is its forward value."""
         from .loss.sdr import SDRLoss
+        if lengths is not None or enroll_lengths is not None:
+            raise NotImplementedError("inference_scored: per-row lengths are not covered (the decoder gathers the score's "
+                                      "moments over whole rows); score the rows of inference(..., lengths=...) one by one")
         loss = loss_func if loss_func is not None else getattr(self, "loss_func_wav", None)
         if loss is None:
             loss = SDRLoss.init_mode("sisnr")
@@ -368,11 +424,15 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
 
     # -- speaker branch (base_nn.py:697-705, 724-738) ---------------------------------------------------
     def _speaker_embedding_from_feats(self, x: torch.Tensor, t: int, x_amax: Optional[torch.Tensor] = None,
-                                      lane: int = 0) -> torch.Tensor:
+                                      lane: int = 0, t_rows: Optional[torch.Tensor] = None,
+                                      rel_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """speaker_net layer by layer on padded enrolment features (base_nn.py:697-705): Magnitude, TCN (consecutive
         plain blocks go through the fused driver together), GatedTCN, AttentiveStatisticsPooling, then the k=1
         projection conv(s) on the pooled vector -> dvec [N, E].  `lane` selects the fused driver's kept scratch: one
-        buffer per concurrent HIP stream of inference(), as ConvTasNet's."""
+        buffer per concurrent HIP stream of inference(), as ConvTasNet's.
+        `t_rows` (int32 [N] on the device) with `rel_lengths` (fp32 [N]: nnet/ragged.py relative_lengths): row n holds that
+        many valid frames; the plain TCN blocks run through the ragged driver, the pooling takes the relative lengths, both
+        with exact fp32 products (a speaker net of another shape is refused by ragged.check_model beforehand)."""
         layers = list(self.speaker_net) if isinstance(self.speaker_net, (nn.ModuleList, nn.Sequential)) else None
         if layers is None:
             raise NotImplementedError("HIP speaker branch: speaker_net must be a ModuleList / Sequential")
@@ -400,7 +460,12 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
                     run.append(layers[i])
                     i += 1
                 plans = [m.plan(x.device) for m in run]
-                if all(p["fused"] for p in plans):
+                if t_rows is not None:
+                    ws = self.keep_scratch("spk_workspace", lane, hip.conv_tasnet_workspace(
+                        x.shape[0], run[0].in_channels, run[0].hid_channels, t, x.device, self.scratch("spk_workspace", lane)))
+                    x = hip.conv_tasnet_ragged((TcnBlock * len(plans))(*[p["block"] for p in plans]), len(plans), x, t,
+                                               run[0].in_channels, run[0].hid_channels, t_rows, None, False, ws)
+                elif all(p["fused"] for p in plans):
                     blocks = (TcnBlock * len(plans))(*[p["block"] for p in plans])
                     # (x_amax: a bound on the features for fp16x2 blocks -- without one the driver measures them: 93 us)
                     # the driver's scratch (three hidden maps: 415 MB at 32 x 4 s) is kept, not re-allocated and
@@ -419,7 +484,7 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
                 x = lay.forward_padded(x, t)
                 i += 1
             elif isinstance(lay, AttentiveStatisticsPooling):
-                pooled = lay.forward_padded(x, t)                                # [N, 2C]
+                pooled = lay.forward_padded(x, t, rel_lengths, exact_fp32=t_rows is not None)   # [N, 2C]
                 i += 1
             else:
                 raise NotImplementedError(f"HIP speaker branch: no kernel path for {type(lay).__name__}")
@@ -427,9 +492,11 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
             raise NotImplementedError("HIP speaker branch: speaker_net must end in pooling + projection")
         return pooled
 
-    def _speaker_embedding(self, enroll: torch.Tensor, lane: int = 0) -> torch.Tensor:
+    def _speaker_embedding(self, enroll: torch.Tensor, lane: int = 0, t_rows: Optional[torch.Tensor] = None,
+                           rel_lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """enroll [N,L'] -> dvec [N,E]; the enrolment goes through encoder_spk when there is one, else through the
-        shared encoder (base_nn.py:347-375).  `lane`: the HIP stream lane of inference() this call runs in."""
+        shared encoder (base_nn.py:347-375).  `lane`: the HIP stream lane of inference() this call runs in.  `t_rows`,
+        `rel_lengths`: the enrolments' valid frames (_speaker_embedding_from_feats)."""
         enc = self.encoder_spk if self.encoder_spk is not None else self.encoder
         if isinstance(enc, ConvEncDec):
             x, t = enc.encoder.encode_padded(enroll, self.drop_first_bin)
@@ -437,8 +504,9 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
             x, t = enc.encode_padded(enroll)
         else:
             raise NotImplementedError(f"HIP speaker branch: no kernel path for a {type(enc).__name__} enrolment encoder")
-        bound = enc.feature_bound(enroll) if isinstance(enc, FreeEncDec) else None
-        return self._speaker_embedding_from_feats(x, t, bound, lane)
+        # (a ragged call needs no range: exact fp32 products; and the junk behind a row's end would be part of it)
+        bound = enc.feature_bound(enroll) if isinstance(enc, FreeEncDec) and t_rows is None else None
+        return self._speaker_embedding_from_feats(x, t, bound, lane, t_rows, rel_lengths)
 
     @torch.no_grad()
     def inference_tse_embedding(self, enroll: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -534,8 +602,12 @@ class SiMoTaskWrapModule(EncDecMaskerBaseModel):
         return _align_waveform_simo(enh_wav, ref_wav)
 
     @torch.no_grad()
-    def inference(self, noisy: torch.Tensor) -> torch.Tensor:
-        """noisy [N, L] -> separated waveforms [N, M, L_out] (base_nn.py:922-939)."""
+    def inference(self, noisy: torch.Tensor, lengths=None) -> torch.Tensor:
+        """noisy [N, L] -> separated waveforms [N, M, L_out] (base_nn.py:922-939).  Per-row `lengths` (the single-output
+        wrapper's ragged batches) are not covered here."""
+        if lengths is not None:
+            raise NotImplementedError("SiMoTaskWrapModule.inference: per-row lengths are not covered (any masker with the "
+                                      "reference contract runs here; only SoTaskWrapModule has the ragged Conv-TasNet path)")
         return self._inference(noisy, None)
 
     def _inference(self, noisy: torch.Tensor, ref: Optional[torch.Tensor]):

@@ -81,6 +81,12 @@ class TCN(GemmPlanCache, nn.Module):
         hb = bool(self.hidden_bf16) and planes == 1 and self.kernel == 3 and 2 * self.dilation + 8 <= 288
         return planes, hb, bool(self.stream_bf16)
 
+    def fused_norms(self) -> bool:
+        """Every norm of the block has a prologue form (no cLN): plan()["fused"], from the module types alone -- what a
+        caller that must refuse before any launch asks."""
+        dsc = self.dconv[0]
+        return not any(isinstance(m, ChanLN) for m in (self.in_conv[1], dsc.depthwise[1], dsc.pointwise[1]))
+
     def plan(self, device: torch.device) -> dict:
         return self._plan_get(device, self._build)
 
@@ -401,10 +407,16 @@ class ConvTasNet(PlanCache, nn.Module):
     takes_input_range = True
 
     def forward_padded(self, x_pad: torch.Tensor, t: int, dvec: Optional[torch.Tensor] = None,
-                       lane: int = 0, x_amax: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       lane: int = 0, x_amax: Optional[torch.Tensor] = None,
+                       t_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Padded-layout entry used by the fused wrapper: [N,C,ldt] -> mask logits [N,C,ldt].
         `lane` selects the cached scratch buffer (one per concurrent HIP stream of the caller); `x_amax` [N, parts]:
-        values whose per-utterance maximum bounds |x_pad| (only the fused normal-TCN path uses it)."""
+        values whose per-utterance maximum bounds |x_pad| (only the fused normal-TCN path uses it).
+        `t_rows` (int32 [N] on the device, 1 <= t_rows[n] <= t): row n holds that many valid frames and anything behind
+        them -- the ragged driver (exact fp32 products whatever gemm_precision says; x_amax is not needed): row n of the
+        result is that of its utterance alone on [0, t_rows[n]) and junk behind."""
+        if t_rows is not None and (self.tcn_layer.lower() != "normal" or not self._stack(x_pad.device)["fused"]):
+            raise NotImplementedError("ConvTasNet.forward_padded: t_rows needs normal TCN blocks on the fused driver (no cLN)")
         if self.tcn_layer.lower() == "gated":
             return self._forward_gated(x_pad, t, dvec)
         stack = self._stack(x_pad.device)
@@ -418,6 +430,9 @@ class ConvTasNet(PlanCache, nn.Module):
             dvec = None  # reference ignores dvec when no block takes it (conv_tasnet.py:354-357)
         ws = self.keep_scratch("workspace", lane, hip.conv_tasnet_workspace(
             x_pad.shape[0], self.input_dim, self.tcn_dim, t, x_pad.device, self.scratch("workspace", lane)))
+        if t_rows is not None:
+            return hip.conv_tasnet_ragged(stack["array"], len(stack["plans"]), x_pad, t, self.input_dim, self.tcn_dim, t_rows,
+                                          None if dvec is None else dvec.contiguous().float(), bool(self.embed_norm), ws)
         return hip.conv_tasnet(stack["array"], len(stack["plans"]), x_pad, t, self.input_dim, self.tcn_dim,
                                None if dvec is None else dvec.contiguous().float(),
                                bool(self.embed_norm), ws, x_amax, bf16_rows=stack["rows_bf16"])

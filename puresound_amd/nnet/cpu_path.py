@@ -149,11 +149,23 @@ def conv_tasnet(m, x: torch.Tensor, dvec: Optional[torch.Tensor] = None) -> torc
 
 
 # ---- the wrapper -----------------------------------------------------------------------------------------------------
-def wrapper_inference(w, noisy: torch.Tensor, enroll: Optional[torch.Tensor] = None) -> torch.Tensor:
+def wrapper_inference(w, noisy: torch.Tensor, enroll: Optional[torch.Tensor] = None, lengths=None,
+                      enroll_lengths=None) -> torch.Tensor:
     """SoTaskWrapModule.inference on CPU tensors (base_nn.py:690-722): _get_feature -> masker -> get_mask ->
-    apply_tf_masks -> _get_waveform -> _wav_output_constrain, through the modules' reference-API calls."""
+    apply_tf_masks -> _get_waveform -> _wav_output_constrain, through the modules' reference-API calls.
+    With `lengths` (nnet/ragged.py): the definition of a ragged batch -- each row's utterance on its own through this
+    forward, written to the head of its row of a zero-filled [N, (T - 1) * hop + win] result."""
     from .conv_tasnet import ConvTasNet
     from .lobe.encoder import ConvEncDec, FreeEncDec
+    if lengths is not None or enroll_lengths is not None:
+        from . import ragged
+        rp = ragged.plan(w, noisy, enroll, lengths, enroll_lengths)
+        win, hop = w.encoder.win_length, w.encoder.hop_length
+        out = torch.zeros(noisy.shape[0], (ragged.frames(noisy.shape[1], win, hop) - 1) * hop + win, dtype=torch.float32)
+        for n, length in enumerate(rp.lengths):
+            row_enroll = None if enroll is None else enroll[n:n + 1, :rp.enroll_lengths[n]]
+            out[n, :rp.out_lengths[n]] = wrapper_inference(w, noisy[n:n + 1, :length], row_enroll)[0]
+        return out
     if enroll is not None or w.embedding_free_tse:
         raise NotImplementedError("CPU path: inference without a speaker branch (the speaker nets run on the HIP path only)")
     if not isinstance(w.masker, ConvTasNet) or not isinstance(w.encoder, (FreeEncDec, ConvEncDec)):

@@ -49,15 +49,18 @@ class AttentiveStatisticsPooling(GemmPlanCache, nn.Module):
             plan["w2_f16x2"] = hip.pack_wt_f16x2(self.conv.weight.detach().to(**f32))
         return plan
 
-    def forward_padded(self, x_pad: torch.Tensor, t: int, lengths=None, return_weight: bool = False) -> torch.Tensor:
-        """padded [N,C,ldt] (+ relative lengths [N]) -> [N,2C] (mean ; std), or the padded attention map [N,C,ldt]."""
+    def forward_padded(self, x_pad: torch.Tensor, t: int, lengths=None, return_weight: bool = False,
+                       exact_fp32: bool = False) -> torch.Tensor:
+        """padded [N,C,ldt] (+ relative lengths [N]) -> [N,2C] (mean ; std), or the padded attention map [N,C,ldt].
+        exact_fp32: the two convs on ps_conv1x1_f32 whatever gemm_precision says (ragged batches: the fp16x2 route scales
+        a row by its maximum over all t frames, and the frames behind a short row's end hold junk)."""
         p = self._plan_get(x_pad.device, self._build)
         n, _, ldt = x_pad.shape
         pro = hip.make_prologue(PS_NORM_AFFINE, False, None, 0.0, 0.0, p["scale"], p["shift"], None,
                                 pre_relu=True, post_tanh=True)
         h = torch.empty(n, self.attention_channels, ldt, device=x_pad.device)
         logits = torch.empty(n, self.channels, ldt, device=x_pad.device)
-        if "w1_f16x2" in p:
+        if "w1_f16x2" in p and not exact_fp32:
             (w1, e1), (w2, e2) = p["w1_f16x2"], p["w2_f16x2"]
             hip.conv1x1_f16x2(x_pad, t, w1, e1, self.attention_channels, None, p["b1"], out=h,
                               x_amax=hip.absmax(x_pad, t))

@@ -1,0 +1,125 @@
+"""Batches of utterances of unequal length through SoTaskWrapModule.inference(noisy, enroll, lengths, enroll_lengths): the
+host side -- what a call is refused for, and the per-row limits the kernels of csrc/ragged.hip read.
+
+Row n of noisy [N, L] is an utterance of lengths[n] samples followed by junk; the result's row n is, on its first
+(T_n - 1) * hop + win samples (T_n = (lengths[n] - win) // hop + 1), what inference(noisy[n:n+1, :lengths[n]]) returns for
+that utterance alone, and exact 0.0 behind them.  Everything here runs on the host, before any launch, and is shared by the
+HIP path (base_nn.py) and the CPU path (cpu_path.py), which loops over the rows and so defines the semantics without a GPU.
+
+Covered: FreeEncDec encoder, the normal-TCN ConvTasNet masker on the fused driver (no cLN), and for `enroll_lengths` a
+speaker net of plain TCN blocks -> AttentiveStatisticsPooling -> k=1 projection(s) (td_tse_conv_tasnet_v0[_causal]).
+Everything else raises NotImplementedError."""
+from typing import List, NamedTuple, Optional, Sequence
+
+import torch
+import torch.nn as nn
+
+
+def host_lengths(name: str, values, n: int, upper: Optional[int], win: int) -> List[int]:
+    """`values` (a sequence of N Python ints or a CPU integer tensor [N]) -> the list, validated against the row length
+    `upper` (None: there are no rows) and the encoder's window."""
+    if torch.is_tensor(values):
+        if values.is_cuda or values.is_floating_point() or values.dtype == torch.bool or values.dim() != 1:
+            raise ValueError(f"inference: {name} must be a sequence of ints or a CPU integer tensor [N] "
+                             f"(got {values.dtype} {tuple(values.shape)} on {values.device})")
+        values = values.tolist()
+    else:
+        values = list(values)
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in values):
+            raise ValueError(f"inference: {name} must hold Python ints")
+    if len(values) != n:
+        raise ValueError(f"inference: {name} holds {len(values)} values for a batch of {n} rows")
+    for i, v in enumerate(values):
+        if upper is not None and v > upper:
+            raise ValueError(f"inference: {name}[{i}] = {v} exceeds the row length {upper}")
+        if v < win:  # (the wording of free_encode for an utterance shorter than one frame)
+            raise RuntimeError(f"inference: {name}[{i}]: input length {v} is shorter than the window {win}")
+    return values
+
+
+def frames(length: int, win: int, hop: int) -> int:
+    return (length - win) // hop + 1
+
+
+def _plain_speaker_net(net) -> bool:
+    """plain TCN blocks on the fused driver -> AttentiveStatisticsPooling -> Conv1d(k=1, bias=False) projection(s)"""
+    from .conv_tasnet import TCN
+    from .lobe.pooling import AttentiveStatisticsPooling
+    if not isinstance(net, (nn.ModuleList, nn.Sequential)):
+        return False
+    layers = list(net)
+    i = 0
+    while i < len(layers) and isinstance(layers[i], TCN) and layers[i].emb_dim == 0 and layers[i].fused_norms():
+        i += 1
+    if i == 0 or i >= len(layers) - 1 or not isinstance(layers[i], AttentiveStatisticsPooling):
+        return False
+    return all(isinstance(m, nn.Conv1d) and m.kernel_size == (1,) and m.bias is None for m in layers[i + 1:])
+
+
+def check_model(w, enroll: Optional[torch.Tensor], enroll_lengths) -> None:
+    """What the lengths path does not cover: raised before any launch, each with its reason."""
+    from .conv_tasnet import ConvTasNet
+    from .lobe.encoder import FreeEncDec
+    if enroll_lengths is not None and enroll is None:
+        raise ValueError("inference: enroll_lengths was given without enroll")
+    who = "inference with lengths"
+    if not isinstance(w.encoder, FreeEncDec):
+        raise NotImplementedError(f"{who}: the FreeEncDec encoder only (got {type(w.encoder).__name__}; the STFT encoders' "
+                                  f"overlap-add and window normalisation have no per-row form)")
+    if not isinstance(w.masker, ConvTasNet):
+        raise NotImplementedError(f"{who}: the Conv-TasNet masker only (got {type(w.masker).__name__}; the DPRNN, SkiM and "
+                                  f"Unet-family maskers have no per-row frame limit)")
+    if w.masker.tcn_layer.lower() != "normal":
+        raise NotImplementedError(f'{who}: tcn_layer="{w.masker.tcn_layer}" is not covered (normal TCN blocks only)')
+    if not all(m.fused_norms() for stack in w.masker.tcn_list for m in stack):
+        raise NotImplementedError(f"{who}: a TCN stack with a cLN runs stage by stage, not on the fused driver, and is not covered")
+    if w.embedding_free_tse:
+        raise NotImplementedError(f"{who}: embedding_free_tse is not covered")
+    if w.check_mask_pairing(w.mask_type, w.f_type) != "real":
+        raise NotImplementedError(f"{who}: FreeEncDec encoder with (real, real) masks")
+    if enroll is not None:
+        if w.speaker_net is None:
+            raise NotImplementedError(f"{who}: an enrolment needs a speaker_net")
+        enc = w.encoder_spk if w.encoder_spk is not None else w.encoder
+        if not isinstance(enc, FreeEncDec) or not _plain_speaker_net(w.speaker_net):
+            raise NotImplementedError(f"{who}: with an enrolment, a FreeEncDec enrolment encoder and a speaker net of plain TCN "
+                                      f"blocks -> AttentiveStatisticsPooling -> k=1 projection(s) only")
+
+
+class Plan(NamedTuple):
+    """The host side of one ragged call."""
+    lengths: List[int]
+    t_rows: List[int]            # T_n
+    out_lengths: List[int]       # (T_n - 1) * hop + win
+    enroll_lengths: Optional[List[int]]
+    enroll_t_rows: Optional[List[int]]
+    enroll_frames: int           # T' of the enrolment rows (0 without one)
+
+
+def plan(w, noisy: torch.Tensor, enroll: Optional[torch.Tensor], lengths, enroll_lengths) -> Plan:
+    """Refusals first, then the limits: everything a ragged call needs from the host."""
+    check_model(w, enroll, enroll_lengths)
+    if noisy.dim() != 2:
+        raise ValueError(f"inference with lengths: noisy must be [N, L] (got {tuple(noisy.shape)})")
+    n, length = noisy.shape
+    win, hop = w.encoder.win_length, w.encoder.hop_length
+    if enroll is not None and (enroll.dim() != 2 or enroll.shape[0] != n):
+        raise RuntimeError("inference: noisy and enroll must have the same batch size")
+    lens = host_lengths("lengths", [length] * n if lengths is None else lengths, n, length, win)
+    t_rows = [frames(v, win, hop) for v in lens]
+    e_lens = e_rows = None
+    e_frames = 0
+    if enroll is not None:
+        enc = w.encoder_spk if w.encoder_spk is not None else w.encoder
+        e_len = enroll.shape[1]
+        e_lens = host_lengths("enroll_lengths", [e_len] * n if enroll_lengths is None else enroll_lengths, n, e_len,
+                              enc.win_length)
+        e_rows = [frames(v, enc.win_length, enc.hop_length) for v in e_lens]
+        e_frames = frames(e_len, enc.win_length, enc.hop_length)
+    return Plan(lens, t_rows, [(t - 1) * hop + win for t in t_rows], e_lens, e_rows, e_frames)
+
+
+def relative_lengths(t_rows: Sequence[int], t: int) -> List[float]:
+    """What AttentiveStatisticsPooling takes as `lengths` for T'_n of T' frames: (T'_n - 0.5) / T'.  The kernel keeps frame f
+    iff float(f) < lengths[n] * float(T'); T'_n / T' can round across T'_n, the half-frame offset cannot."""
+    return [(v - 0.5) / t for v in t_rows]
