@@ -57,7 +57,7 @@ const char* ps_last_error(void);
  * of one kernel family ("conv1x1", "dwconv", "free_encode", "free_decode", "embed_bias", "pad_rows",
  * "unpad_rows", "frame", "complex_mask", "istft_ola", "attn_stats_pool", "lstm", "lstm_cell", "chan_layernorm", "unfold_taps", "gated_product", "segment_overlap",
  * "film_conv", "lstm_gates_cell", "proj_layernorm", "overlap_average", "stream_windows", "stream_overlap", "conv2d_step", "istft_step", "stream_commit", "conv1x1_bf16", "unfold2d", "conv2d", "activation", "add", "magnitude", "real_mask", "norm_activation", "self_attention", "add_position",
- * "film_apply").  Not for use under stream capture. */
+ * "film_apply", "frame_reflect", "spec_pair_moments").  Not for use under stream capture. */
 int ps_profile_enable(int on);
 int ps_profile_read(const char* kernel, double* total_ms, int* launches);
 
@@ -1030,6 +1030,37 @@ int ps_conv_tasnet_ragged_f32(const ps_tcn_block* blocks, int n_blocks, const fl
  * the reference become one streaming pass.  lda / ldb: row strides in floats. */
 int ps_wave_moments_chunks(int L);
 int ps_wave_moments_f64(const float* a, const float* b, double* partials, int N, int L, int lda, int ldb, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The spectral scores of the reference's loss/stft_loss.py (stft :8-24, SpectralConvergengeLoss :27-42,
+ * LogSTFTMagnitudeLoss :45-60, STFTLoss :63-92, MultiResolutionSTFTLoss :95-141, over_suppression_loss :144-153), forward
+ * only.  With x / y the clamped magnitudes sqrt(max(re^2 + im^2, 1e-7)) of estimate / reference, every score is algebra on
+ * four sums over frames and bins: S0 = sum (y-x)^2, S1 = sum y^2, S2 = sum |log y - log x|, S3 = sum relu(y^p - x^p)^2.
+ * torch.stft(center=True, pad_mode="reflect") with a fixed window is a dense product: per resolution (n_fft, hop, win),
+ * off = (n_fft - win)/2, T = 1 + (L - n_fft % 2)/hop (the padded L + 2 (n_fft/2) samples hold that many frames of n_fft: an odd
+ * n_fft has one fewer when hop divides L), bins = n_fft/2 + 1,
+ *   ps_frame_reflect_f32       frames[r][k][t] = wav[r][refl(t*hop + k + off - n_fft/2)], k < win (the window's support only),
+ *                              refl(p) = -p for p < 0, 2(L-1) - p for p >= L; needs L > n_fft/2, as torch.stft does
+ *   ps_conv1x1_f32             against the basis [2*bins][win]: rows m < bins w[k] cos(2 pi m (k+off) / n_fft), rows bins + m the
+ *                              same with sin (the caller builds it from the window) -> spectrogram [re rows; im rows]
+ *   ps_spec_pair_moments_f64   the four sums of each (estimate, reference) pair of spectrogram rows
+ *
+ * ps_frame_reflect_f32: a, b [N][lda / ldb] waveforms of L samples (b may be NULL) -> frames [R][win][ldt], R = 2N (N without
+ *   b): rows n from a, rows N + n from b, so that one GEMM launch transforms estimate and reference.  Columns t >= T are
+ *   written as zeros.  N <= 32767, win <= n_fft, win <= 65535, T == 1 + (L - n_fft % 2)/hop (any other T is
+ *   refused: it is what keeps every reflected index inside the row), ldt % 128 == 0.
+ * ps_spec_pair_moments_f64: spec [2N][2*bins][ldt] (rows n: estimate, rows N + n: reference) -> partials [N][P][4] in fp64,
+ *   P = ps_spec_pair_moments_parts(bins, T): one writer per slot, no atomics, every slot written; the caller adds the P slots
+ *   up in order.  Only t < T and the first `bins` rows of each half are read as data: what columns t >= T hold (a NaN
+ *   included) changes no bit.  Magnitudes are formed in fp32, as the reference forms them, and everything behind them in fp64.
+ *   mag (or NULL): [2N][bins][ldt] receives the clamped magnitudes; its columns t >= T are zero where written and otherwise
+ *   untouched.  0 < p < 64.
+ * ------------------------------------------------------------------------------------------- */
+int ps_frame_reflect_f32(const float* a, const float* b, float* frames, int N, int L, int lda, int ldb, int n_fft, int win,
+                         int hop, int T, int ldt, void* stream);
+int ps_spec_pair_moments_parts(int bins, int T);
+int ps_spec_pair_moments_f64(const float* spec, double* partials, float* mag /* or NULL */, int N, int bins, int T, int ldt,
+                             double p, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1518,6 +1518,63 @@ def wave_moments(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return part.sum(1)
 
 
+def stft_frames(length: int, n_fft: int, hop: int) -> int:
+    """Frames of torch.stft(center=True): the length + 2 (n_fft // 2) padded samples hold 1 + (length - n_fft % 2) // hop
+    frames of n_fft samples (an odd n_fft has one fewer when hop divides the length)."""
+    return 1 + (length - n_fft % 2) // hop
+
+
+def frame_reflect(a: torch.Tensor, b: Optional[torch.Tensor], n_fft: int, win: int, hop: int,
+                  out: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, int]:
+    """a (and b) [N, L] -> (frames padded [R, win, ldt], T): torch.stft's frames (center=True, reflect padding) on the
+    support of a window of `win` samples centred in n_fft, T = stft_frames(L, n_fft, hop); R = 2N with rows N + n from b, else N
+    (ps_frame_reflect_f32).  `out`: a contiguous [R, win, ldt] tensor to write into."""
+    require_device(a, "frame_reflect")
+    if a.dim() != 2 or (b is not None and (b.shape != a.shape or b.device != a.device or b.dtype != torch.float32)):
+        raise RuntimeError("frame_reflect: fp32 waveforms [N, L] of one shape on one device")
+    n, length = a.shape
+    if win > n_fft or win < 1 or hop < 1:
+        raise RuntimeError(f"frame_reflect: need 1 <= win <= n_fft and hop >= 1 (got win={win}, n_fft={n_fft}, hop={hop})")
+    if length <= n_fft // 2:
+        raise RuntimeError(f"frame_reflect: reflect padding needs more than n_fft // 2 samples (length {length}, "
+                           f"fft_size {n_fft})")
+    if a.stride(1) != 1:
+        a = a.contiguous()
+    if b is not None and b.stride(1) != 1:
+        b = b.contiguous()
+    rows = n if b is None else 2 * n
+    t = stft_frames(length, n_fft, hop)
+    ldt = padded_frames(t)
+    if out is None:
+        out = torch.empty(rows, win, ldt, dtype=torch.float32, device=a.device)
+    elif tuple(out.shape) != (rows, win, ldt):
+        raise RuntimeError(f"frame_reflect: `out` must be [{rows}, {win}, {ldt}]")
+    _require_operand("frame_reflect", a.device, out=out)
+    check(lib().ps_frame_reflect_f32(ptr(a), ptr(b), ptr(out), n, length, a.stride(0), 0 if b is None else b.stride(0),
+                                     n_fft, win, hop, t, ldt, stream_ptr(a.device)), "ps_frame_reflect_f32")
+    return out, t
+
+
+def spec_pair_moments(spec: torch.Tensor, bins: int, t: int, p: float = 0.5,
+                      mag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """spec padded [2N, 2*bins, ldt] ([re rows; im rows]; rows n: estimate, rows N + n: reference) -> fp64 [N, 4]:
+    S0 = sum (y-x)^2, S1 = sum y^2, S2 = sum |log y - log x|, S3 = sum relu(y^p - x^p)^2 over t frames and bins of the
+    clamped magnitudes x (estimate), y (reference) (ps_spec_pair_moments_f64).  `mag`: a contiguous [2N, bins, ldt] tensor
+    that receives those magnitudes (columns >= t undefined)."""
+    require_device(spec, "spec_pair_moments")
+    if spec.dim() != 3 or spec.shape[0] % 2 or spec.shape[1] != 2 * bins or not spec.is_contiguous():
+        raise RuntimeError("spec_pair_moments: spec must be a contiguous [2N, 2*bins, ldt] tensor")
+    n, ldt = spec.shape[0] // 2, spec.shape[2]
+    if mag is not None and tuple(mag.shape) != (2 * n, bins, ldt):
+        raise RuntimeError(f"spec_pair_moments: `mag` must be [{2 * n}, {bins}, {ldt}]")
+    _require_operand("spec_pair_moments", spec.device, mag=mag)
+    parts = lib().ps_spec_pair_moments_parts(bins, t)
+    part = torch.empty(n, max(parts, 1), 4, dtype=torch.float64, device=spec.device)
+    check(lib().ps_spec_pair_moments_f64(ptr(spec), ptr(part), ptr(mag), n, bins, t, ldt, float(p),
+                                         stream_ptr(spec.device)), "ps_spec_pair_moments_f64")
+    return part.sum(1)
+
+
 def lstm_cell(gates: torch.Tensor, c: torch.Tensor, h: torch.Tensor, hidden: int, dirs: int, t: int) -> None:
     """One cell update per (unit, frame): gates padded [N,D*4H,ld] (complete pre-activations), c in place, h out
     (both [N,D*H,ld'] rows, possibly views into larger row blocks)."""

@@ -270,22 +270,31 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         score).  Not a method of the reference: it is what its evaluation loops do after inference (`_align_waveform`,
         base_nn.py:398-412, then SDRLoss / si_snr, loss/sdr.py:104-299), with the score's five moments gathered by the
         decoder kernel while it writes the waveform instead of by further passes over it.  loss_func: an
-        SDRLoss (default self.loss_func_wav, else SDRLoss.init_mode("sisnr")); the score is its forward value."""
-        from .loss.sdr import SDRLoss
+        SDRLoss (default self.loss_func_wav, else SDRLoss.init_mode("sisnr")); the score is its forward value.  Any other
+        loss_func scores the waveform of inference() against the aligned reference: an STFTLoss / MultiResolutionSTFTLoss as
+        loss(enh, ref), everything else by the three-argument call of the reference's forward (base_nn.py:475), which is
+        the form of the recipes' `lambda enh, ref, dummy:` closures."""
+        from .loss.sdr import SDRLoss, cpu_moments
+        from .loss.stft_loss import MultiResolutionSTFTLoss, STFTLoss
         if lengths is not None or enroll_lengths is not None:
             raise NotImplementedError("inference_scored: per-row lengths are not covered (the decoder gathers the score's "
                                       "moments over whole rows); score the rows of inference(..., lengths=...) one by one")
         loss = loss_func if loss_func is not None else getattr(self, "loss_func_wav", None)
         if loss is None:
             loss = SDRLoss.init_mode("sisnr")
-        if not isinstance(loss, SDRLoss) or loss.source_aggregated:
+        if isinstance(loss, SDRLoss) and loss.source_aggregated:
             raise NotImplementedError("inference_scored: an SDRLoss on [N, L] signals (not a source-aggregated mode)")
         if ref_clean.dim() != 2 or ref_clean.shape[0] != noisy.shape[0]:
             raise RuntimeError("inference_scored: ref_clean must be [N, L_ref] with the batch of `noisy`")
+        if not isinstance(loss, SDRLoss):
+            enh = self.inference(noisy, enroll)
+            ref = hip.align_reference(ref_clean, enh.shape[-1])
+            if isinstance(loss, (STFTLoss, MultiResolutionSTFTLoss)):
+                return enh, loss(enh, ref)
+            return enh, loss(enh, ref, inactive_labels)
         if noisy.device.type == "cpu":  # (the recipes' --backend cpu: stock ATen forward, the moments as five fp64 sums)
             enh = self.inference(noisy, enroll)
-            a, b = enh.double(), hip.align_reference(ref_clean, enh.shape[-1]).double()
-            moments = torch.stack([a.sum(-1), b.sum(-1), (a * a).sum(-1), (b * b).sum(-1), (a * b).sum(-1)], -1)
+            moments = cpu_moments(enh, hip.align_reference(ref_clean, enh.shape[-1]))
             return enh, loss.from_moments(moments, enh.shape[-1], inactive_labels)
         hip.require_device(ref_clean, "SoTaskWrapModule.inference_scored")
         enh, moments = self._inference(noisy, enroll, ref_clean.float())

@@ -22,6 +22,13 @@ def _moments(s1: torch.Tensor, s2: torch.Tensor) -> torch.Tensor:
     return hip.wave_moments(s1.reshape(-1, length), s2.reshape(-1, length)).reshape(*lead, 5)
 
 
+def cpu_moments(s1: torch.Tensor, s2: torch.Tensor) -> torch.Tensor:
+    """The same moments [..., 5] of CPU tensors as five fp64 sums in stock ATen (SDRLoss.forward and
+    SoTaskWrapModule.inference_scored on CPU tensors)."""
+    a, b = s1.double(), s2.double()
+    return torch.stack([a.sum(-1), b.sum(-1), (a * a).sum(-1), (b * b).sum(-1), (a * b).sum(-1)], -1)
+
+
 def _inner_of(m: torch.Tensor, length: int, zero_mean: bool):
     """moments [..., 5] over `length` samples -> fp64 (<a,a>, <b,b>, <a,b>) of shape [..., 1] (optionally of the
     zero-mean signals)."""
@@ -109,6 +116,10 @@ class SDRLoss(nn.Module):
     def forward(self, s1: torch.Tensor, s2: torch.Tensor, inactive_labels: Optional[torch.Tensor] = None) -> torch.Tensor:
         self.check_input_shape(s1)
         self.check_input_shape(s2)
+        if s1.device.type == "cpu" and s2.device.type == "cpu":
+            # the recipes' --backend cpu (init_loss's SDRLoss called on CPU tensors); the functions of this file stay on the
+            # HIP path
+            return self.from_moments(cpu_moments(s1, s2), s1.shape[-1], inactive_labels)
         return self.from_moments(_moments(s1, s2), s1.shape[-1], inactive_labels)
 
     @torch.no_grad()
