@@ -313,7 +313,9 @@ __global__ __launch_bounds__(H * 4) void lstm_mfma_kernel(LstmK k) {
   __syncthreads();
 
   for (int s0 = 0; s0 < steps; s0 += PF) {
-    float hst[4][4];  // CONTIG: h' of the group, [r][u]
+    // CONTIG: h' of the group, [r][u].  A forward pass may end in a partial group, whose 16-byte store reaches up to 3 frames
+    // past the last step: those are pad frames, and they get zeros (the rows of _plans._h_rows keep their pads zero)
+    float hst[4][4] = {};
     if constexpr (CONTIG) {
       take_group();
       load_group(s0 + 4);
@@ -784,7 +786,7 @@ __global__ __launch_bounds__(H * 4) void lstm_m4_kernel(LstmK k) {
   __syncthreads();
 
   for (int s0 = 0; s0 < steps; s0 += PF) {
-    float hst[4];
+    float hst[4] = {};  // (a partial last group stores zeros into the pad frames past the last step, as lstm_mfma_kernel)
     if constexpr (CONTIG) {
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -1073,9 +1075,10 @@ static bool store_pairs(const ps_lstm_args& a) {
 }
 
 // 16-byte step groups: steps are consecutive frames starting on a 16-byte boundary.  A forward-only pass may end
-// in a partial group: it reads / writes up to 3 frames past its last step, which must still lie inside the row
-// (pad frames; they are never read as data).  Without the groups a long pass over consecutive frames re-fetches
-// every 128-byte line of the gate pre-activations once per step (DPCRN's inter pass: 10.8 ms instead of ~3).
+// in a partial group: it reads up to 3 frames past its last step and writes zeros there, which must still lie inside
+// the row (pad frames; they are never read as data, but projection, LayerNorm and range maxima run over them).
+// Without the groups a long pass over consecutive frames re-fetches every 128-byte line of the gate pre-activations
+// once per step (DPCRN's inter pass: 10.8 ms instead of ~3).
 // gx_too: gx is read in groups as well (channel-major gx; the frame-major entry has its gx rule in lstm_fmajor_fits).
 static bool step_groups(const ps_lstm_args& a, bool gx_too) {
   const int steps4 = (a.steps + 3) / 4 * 4;

@@ -11,6 +11,19 @@ through the same `capture`.)
 
 Results are bit-identical to the eager call.  One graph is kept per (input shapes, dtype); the graphs are dropped when
 a parameter of the model is updated in place or `reset()` is called.
+
+Who owns what a captured graph reads.  A graph holds raw addresses of tensors the model keeps from call to call: the plans
+and kept scratch of nnet/_plans.py: PlanCache (`cached_tensors()`), the zeroed LSTM output rows inside the recurrence plans
+(_plans._h_rows) and the identity tables of hip.py.  The rule, for every holder of a graph in the package:
+  * the MODULE may replace a cache entry at any call (a larger workspace for a larger batch, a plan after a changed
+    parameter or switch, LSTM rows for another geometry) and never frees, clears or rewrites in place what it handed out
+    before for another shape or geometry: an entry is written only by launches that were handed that entry for that use;
+  * the HOLDER of a graph (GraphedInference's entry, a streaming session, the demo harness, StreamingSkiM) pins
+    `_cached_tensors(model)` as they are right after the capture, keeps the pins exactly as long as the graph, and drops
+    both together (a changed parameter, reset(), a new session);
+so a replay reads and writes live memory that no later call on the model -- another shape, an eager call, another capture,
+another session -- is handed for anything else, and a replay needs no host-side bookkeeping to stay correct
+(tests/test_graph_interleave_gpu.py, tests/test_h_rows.py).
 """
 import gc
 from typing import Optional

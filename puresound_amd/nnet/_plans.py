@@ -254,29 +254,42 @@ def _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip=True):
     return hip.chan_layernorm(p, t, norm["gamma"], norm["beta"], norm["eps"], res=res)
 
 
+#: zeroed LSTM output rows a recurrence plan keeps per lane (_h_rows): one per (shape, geometry) lately seen, as long as
+#: they stay under H_ROWS_BYTES together (the one in use is always kept: a full batch's rows alone are past a gigabyte)
+H_ROWS_KEPT = 8
+H_ROWS_BYTES = 256 << 20
+
+
 def _h_rows(rnn: dict, x: torch.Tensor, t: int, q: int, q_stride: int, steps: int, step_stride: int, lane: int = 0):
     """Output rows of a recurrence.  When the sequences do not cover the span of t frames (the 2-D maps of DPCRN / DPARN:
     F rows of ld frames, pad frames between them) the recurrence never writes the pad frames, and what follows it --
     projection, LayerNorm, the next GEMM's range maximum -- runs over the whole span: the rows then come from a zeroed
-    buffer kept with the plan, so stale memory (a NaN, an Inf) cannot reach the maximum.  One buffer per `lane` (the
-    caller's concurrent HIP streams must not write the same rows).  The pads stay zero from call to call as long as the
-    recurrence writes the same frames: when the sequence geometry changes (another utterance length inside one row
-    length: frames the longer call wrote are pad frames of the shorter one) the kept buffer is cleared on the current
-    stream, and only a change of its shape allocates a new one.  None = let the kernel wrapper allocate (every frame is
-    written)."""
+    buffer kept with the plan, so stale memory (a NaN, an Inf) cannot reach the maximum.
+
+    One buffer per `lane` (the caller's concurrent HIP streams must not write the same rows), shape, device and sequence
+    geometry (t, q, q_stride, steps, step_stride): rnn["h_rows"][lane][(shape, device, geometry)].  Whoever is handed a
+    buffer -- an eager call or a captured graph, at any later time, in any order -- writes the frames of that one
+    geometry into it and no others, so its pad frames are zero for as long as it lives and nothing ever has to clear it:
+    the invariant rests on no host-side record that a graph replay would bypass.  (Two utterance lengths inside one row
+    length share a shape and differ in their geometry: frames the longer call writes are pad frames of the shorter one.)
+    A lane keeps its most recently used buffers, H_ROWS_KEPT at most and H_ROWS_BYTES together (the one in use always stays); an
+    older one is dropped from the plan, never cleared or handed out again, so a captured graph that pinned it
+    (graphs._cached_tensors) keeps it, with its pads, to itself, and an eager caller pays one fill per change of geometry.
+    None = let the kernel wrapper allocate (every frame is written)."""
     if q * steps >= t:
         return None
     n, _, ldt = x.shape
     shape = (n, rnn["D"] * rnn["H"], ldt)
-    geometry = (t, q, q_stride, steps, step_stride)
-    bufs = rnn.setdefault("h_rows", {})
-    kept = bufs.get(lane)
-    if kept is None or tuple(kept[1].shape) != shape or kept[1].device != x.device:
-        bufs[lane] = kept = (geometry, torch.zeros(shape, dtype=torch.float32, device=x.device))
-    elif kept[0] != geometry:
-        kept[1].zero_()
-        bufs[lane] = kept = (geometry, kept[1])
-    return kept[1]
+    key = (shape, str(x.device), (t, q, q_stride, steps, step_stride))
+    bufs = rnn.setdefault("h_rows", {}).setdefault(lane, {})
+    buf = bufs.pop(key, None)
+    if buf is None:
+        size = 4 * n * shape[1] * ldt
+        while bufs and (len(bufs) >= H_ROWS_KEPT or size + sum(4 * b.numel() for b in bufs.values()) > H_ROWS_BYTES):
+            bufs.pop(next(iter(bufs)))
+        buf = torch.zeros(shape, dtype=torch.float32, device=x.device)
+    bufs[key] = buf       # (dicts keep insertion order: the most recently used buffer is the last)
+    return buf
 
 
 # What one LSTM pass runs (lstm_route).  gemm: the input projection's arithmetic, "fp32" | "bf16" | "f16x2"; planes: of "bf16", 1

@@ -39,7 +39,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import hip
-from ..graphs import capture
+from ..graphs import _cached_tensors, capture
 from ..nnet._plans import tensor_signature
 
 
@@ -101,6 +101,7 @@ class HopSession:
     def _drop_weights(self) -> None:
         """Forget graphs and weight packs (they are rebuilt from the current parameters on next use)."""
         self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        self._pinned: Dict[int, list] = {}
         self._packs = None
         self._sig = tensor_signature(self.model)
 
@@ -118,7 +119,7 @@ class HopSession:
     def _begin(self, streams: int, device: torch.device, use_graph: bool) -> None:
         """A new session of `streams` columns: counters at zero, no graph, window queue and overlap-add tail zeroed."""
         self._check_parameters()
-        self._graphs = {}
+        self._graphs, self._pinned = {}, {}
         self.streams, self.device, self._use_graph = int(streams), device, bool(use_graph)
         self._hops = 0           # hops taken in, priming included
         self.frames = 0          # hops past the priming: frames computed
@@ -209,9 +210,13 @@ class HopSession:
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
     def _capture(self, hops: int) -> torch.cuda.CUDAGraph:
-        """Warm up once eagerly on a side stream (allocates what the launches need), put the state back, capture."""
+        """Warm up once eagerly on a side stream (allocates what the launches need), put the state back, capture.  The body
+        reads the streamer's own packs, buffers and state, which live as long as the session's graphs do; what it reads of
+        the model's plan caches besides (inside _around_body: the plans that are in place while the body runs) is pinned
+        with the graph, and dropped with it -- the model may replace a cache entry for another caller at any time."""
         with self._around_body():
             g, _ = capture(lambda: self._body(hops), self.device, self._state())
+            self._pinned[hops] = _cached_tensors(self.model)
         self._graphs[hops] = g
         return g
 

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip
-from ..graphs import capture
+from ..graphs import _cached_tensors, capture
 from ..nnet._plans import tensor_signature
 from ..nnet.lobe.encoder import FreeEncDec
 from .skim_inference import StreamingSkiM
@@ -61,6 +61,7 @@ class DemoTseNet(nn.Module):
         self.queue = None
         self._graph = None
         self._chunk_graphs = {}
+        self._pinned = {}          # graph key -> the plan-cache tensors its launches read, kept for as long as the graph
         self._tail = None
         self._sig = None
         self._use_graph = use_graph
@@ -99,6 +100,7 @@ class DemoTseNet(nn.Module):
         else:
             if self._graph is None:
                 self._graph, self._gen = capture(self._hop_body, chunk.device, m._seg_h + m._seg_c)
+                self._pinned["hop"] = _cached_tensors(self)
             self._graph.replay()
             gen = self._gen
         m._end_of_frame()
@@ -110,6 +112,7 @@ class DemoTseNet(nn.Module):
         if sig != self._sig:
             self._graph = None
             self._chunk_graphs = {}
+            self._pinned = {}
             self._sig = sig
             self.masker._forget_embedding()
 
@@ -224,8 +227,10 @@ class DemoTseNet(nn.Module):
         state = m._seg_h + m._seg_c + [t for pair in m._mem_h + m._mem_c for t in pair] + [self.queue, self._tail]
         g, _ = capture(lambda: self._chunk_body(hops, updates), device, state)   # (the warm-up: plans, embedding terms)
         while len(self._chunk_graphs) >= self._CHUNK_GRAPH_CAP:
+            self._pinned.pop(next(iter(self._chunk_graphs)), None)
             self._chunk_graphs.pop(next(iter(self._chunk_graphs)))
         self._chunk_graphs[key] = g
+        self._pinned[key] = _cached_tensors(self)
 
     def _chunk_body_by_hops(self, hops: int, updates: tuple):
         """The same, hop by hop (window shift, hop body, averaging overlap-add per hop)."""
@@ -269,6 +274,7 @@ class DemoTseNet(nn.Module):
             self._wins = torch.empty(hops, b * self.win_size, dtype=torch.float32, device=dev)
             self._masks = None
             self._chunk_graphs = {}
+            self._pinned = {k: v for k, v in self._pinned.items() if k == "hop"}
         self._chunk_in.copy_(chunk[:, :hops * h])
         self._tail.copy_(pre_wav[:, pre_wav.shape[-1] - self.ola_size:])
         key = (hops, updates)

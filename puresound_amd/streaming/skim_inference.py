@@ -13,7 +13,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from .. import hip
-from ..graphs import capture
+from ..graphs import _cached_tensors, capture
 from ..nnet._plans import lstm_path, tensor_signature
 from ..nnet.lobe.trivial import FiLM
 from ..nnet.skim import SkiM
@@ -135,7 +135,7 @@ class StreamingSkiM(SkiM):
         for m in getattr(self, "seg_input_fusion", []):
             if m is not None:
                 m._per_frame = None
-        self._graph = None
+        self._graph = self._pinned = None
         self._graph_sig = None
         self._use_graph = use_graph
         self._out = None
@@ -357,7 +357,7 @@ class StreamingSkiM(SkiM):
         # old pointers and the per-frame conditioning terms were made with the old weights -- both are redone
         sig = tensor_signature(self)
         if sig != self._graph_sig:
-            self._graph = None
+            self._graph = self._pinned = None
             self._graph_sig = sig
             self._forget_embedding()
         if embed is not None:
@@ -370,6 +370,7 @@ class StreamingSkiM(SkiM):
             if self._graph is None:
                 # the warm-up fills plan caches / per-frame embedding terms
                 self._graph, self._out = capture(self._frame_body, x.device, self._seg_h + self._seg_c)
+                self._pinned = _cached_tensors(self)      # the plans the launches read, for as long as the graph is kept
             self._graph.replay()
             out = self._out
         res = out[0, :, :b].t().reshape(b, -1, 1).clone()
