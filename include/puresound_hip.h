@@ -1019,6 +1019,13 @@ int ps_dwconv_ragged_f32(const float* x, const float* w, const float* b, float* 
                          int ldt, int P, int dilation, int left, const ps_prologue* pro, double* ostats, double count_full,
                          void* stream);
 int ps_zero_tail_f32(float* x, const int* limit, int N, int R, int ld, void* stream);
+/* The reference of a score aligned to each row's valid output length (_align_waveform, base_nn.py:398-412, per row):
+ * out [N][L_out] from ref [N][ldr] with a = a_len[n] in [0, L_out] valid output samples, b = b_len[n] in [0, L_ref] reference
+ * samples, d = max(0, a - b):  out[n][s] = s < a ? (s >= d ? ref[n][s - d] : 0) : 0  -- a shorter reference is left-padded with
+ * zeros, a longer one is cut, and every sample behind a is 0.0.  Both limits are clamped to their range; nothing at or behind
+ * ref[n][b] is loaded.  out != ref. */
+int ps_align_rows_f32(const float* ref, float* out, const int* a_len, const int* b_len, int N, int L_out, int L_ref, int ldr,
+                      void* stream);
 int ps_conv_tasnet_ragged_f32(const ps_tcn_block* blocks, int n_blocks, const float* x_in, float* x_out, const float* dvec,
                               int embed_norm, int N, int T, int ldt, const int* t_rows, void* workspace,
                               size_t workspace_bytes, void* stream);
@@ -1030,6 +1037,11 @@ int ps_conv_tasnet_ragged_f32(const ps_tcn_block* blocks, int n_blocks, const fl
  * the reference become one streaming pass.  lda / ldb: row strides in floats. */
 int ps_wave_moments_chunks(int L);
 int ps_wave_moments_f64(const float* a, const float* b, double* partials, int N, int L, int lda, int ldb, void* stream);
+/* The same over s < len_rows[n] (int32 device array [N], clamped to [0, L]): row n is an utterance of that many samples and
+ * anything behind them, a NaN included.  Partials [N][ps_wave_moments_chunks(L)][5], every slot written; a chunk at or behind
+ * the row's end loads nothing and writes zeros.  len_rows[n] == L gives the bits of ps_wave_moments_f64. */
+int ps_wave_moments_rows_f64(const float* a, const float* b, const int* len_rows, double* partials, int N, int L, int lda,
+                             int ldb, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The spectral scores of the reference's loss/stft_loss.py (stft :8-24, SpectralConvergengeLoss :27-42,
@@ -1061,6 +1073,19 @@ int ps_frame_reflect_f32(const float* a, const float* b, float* frames, int N, i
 int ps_spec_pair_moments_parts(int bins, int T);
 int ps_spec_pair_moments_f64(const float* spec, double* partials, float* mag /* or NULL */, int N, int bins, int T, int ldt,
                              double p, void* stream);
+/* The two byte movers with per-row limits (int32 device arrays [N] that the host validated; clamped all the same), for batches
+ * whose row n is an utterance of len_rows[n] <= L samples and anything behind them.  The product between them stays
+ * ps_conv1x1_f32 over all T columns: those behind T_n are the zeros the framing wrote.
+ * ps_frame_reflect_rows_f32: ps_frame_reflect_f32 with rows n and N + n framed as utterances of len_rows[n] samples on their own:
+ *   T_n = 1 + (len_rows[n] - n_fft % 2)/hop frames, refl() at len_rows[n] instead of L, zeros on T_n <= t < ldt.  L and T are
+ *   checked as above; a limit at or below n_fft/2 frames nothing.
+ * ps_spec_pair_moments_rows_f64: ps_spec_pair_moments_f64 over t < t_rows[n] (clamped to [0, T]), without `mag`.  Partials
+ *   [N][ps_spec_pair_moments_parts(bins, T)][4], every slot written; a workgroup entirely behind t_rows[n] loads nothing and
+ *   writes zeros.  t_rows[n] == T gives the bits of ps_spec_pair_moments_f64. */
+int ps_frame_reflect_rows_f32(const float* a, const float* b, const int* len_rows, float* frames, int N, int L, int lda, int ldb,
+                              int n_fft, int win, int hop, int T, int ldt, void* stream);
+int ps_spec_pair_moments_rows_f64(const float* spec, const int* t_rows, double* partials, int N, int bins, int T, int ldt,
+                                  double p, void* stream);
 
 #ifdef __cplusplus
 }

@@ -239,6 +239,9 @@ SIGNATURES = {
     "ps_frame_reflect_f32": (C.c_int, [_vp, _vp, _vp] + [C.c_int] * 9 + [_vp]),
     "ps_spec_pair_moments_parts": (C.c_int, [C.c_int, C.c_int]),
     "ps_spec_pair_moments_f64": (C.c_int, [_vp, _vp, _vp] + [C.c_int] * 4 + [C.c_double, _vp]),
+    "ps_wave_moments_rows_f64": (C.c_int, [_vp, _vp, _vp, _vp] + [C.c_int] * 4 + [_vp]),
+    "ps_frame_reflect_rows_f32": (C.c_int, [_vp, _vp, _vp, _vp] + [C.c_int] * 9 + [_vp]),
+    "ps_spec_pair_moments_rows_f64": (C.c_int, [_vp, _vp, _vp] + [C.c_int] * 4 + [C.c_double, _vp]),
     "ps_conv_tasnet_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "ps_conv_tasnet_f32": (C.c_int, [C.POINTER(TcnBlock), C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
                                      C.c_int, _vp, C.c_size_t, _vp]),
@@ -256,6 +259,7 @@ SIGNATURES = {
     "ps_ragged_stats_f32": (C.c_int, [_vp, _vp, _vp] + [C.c_int] * 5 + [C.c_double, _vp]),
     "ps_dwconv_ragged_f32": (C.c_int, [_vp] * 5 + [C.c_int] * 7 + [C.POINTER(Prologue), _vp, C.c_double, _vp]),
     "ps_zero_tail_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "ps_align_rows_f32": (C.c_int, [_vp] * 4 + [C.c_int] * 4 + [_vp]),
     "ps_conv_tasnet_ragged_f32": (C.c_int, [C.POINTER(TcnBlock), C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
                                             C.c_int, _vp, _vp, C.c_size_t, _vp]),
 }

@@ -42,6 +42,13 @@ struct NormScalars {
   float rstd;
 };
 
+// A per-row limit of a ragged batch (int32 device array [N], validated by the host), clamped to [0, hi] all the same: no
+// access leaves a row whatever the array holds.
+__device__ __forceinline__ int row_limit(const int* lim, int n, int hi) {
+  const int v = lim[n];
+  return v < 0 ? 0 : (v > hi ? hi : v);
+}
+
 // 64-lane butterfly sum of a double (two 32-bit shuffles per step).
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

@@ -8,6 +8,7 @@
 //   ps_ragged_stats_f32    the (sum, sum of squares) partials of a GEMM's output over t < t_rows[n] only,
 //   ps_dwconv_ragged_f32   ps_dwconv_f32 with a per-row frame limit: a = prologue(x) is 0 outside [0, t_rows[n]),
 //   ps_zero_tail_f32       0.0 behind a per-row limit: features and mask logits in front of the decoder, the waveform after it,
+//   ps_align_rows_f32      the clean reference of a score, aligned to each row's valid output length (behind the decoder),
 //   ps_conv_tasnet_ragged_f32   the block loop of ps_conv_tasnet_f32 over them, always in the exact-fp32 arithmetic.
 // Both statistics kernels scale their partials by count_full / (R * t_rows[n]): the consumers divide the sums by the launch-wide
 // ps_prologue.count = R * T (load_norm_scalars), which then gives mean = S1 / (R T_n) and var = S2 / (R T_n) - mean^2.
@@ -16,11 +17,6 @@
 #include "ps_common.h"
 
 namespace ps {
-
-__device__ __forceinline__ int row_limit(const int* lim, int n, int hi) {
-  const int v = lim[n];
-  return v < 0 ? 0 : (v > hi ? hi : v);
-}
 
 // ---- statistics of [N][R][ldt] over t < t_rows[n] ----------------------------------------------------------------------------
 // Workgroup (p, n) sums rows p, p + parts, ... of utterance n with 16-byte loads, in fp64, in a fixed order (no atomics), and
@@ -69,6 +65,37 @@ __global__ __launch_bounds__(256) void zero_tail_kernel(float* __restrict__ x, c
     for (int t = up + 4 * threadIdx.x; t < ld; t += 1024) *reinterpret_cast<f32x4*>(row + t) = f32x4{0.f, 0.f, 0.f, 0.f};
   } else {
     for (int t = lim + threadIdx.x; t < ld; t += 256) row[t] = 0.f;
+  }
+}
+
+// ---- a reference aligned to each row's valid output length -----------------------------------------------------------------------
+// _align_waveform's rule (base_nn.py:398-412) per row: with a = a_len[n] valid output samples and b = b_len[n] reference samples,
+// d = max(0, a - b): out[n][s] = ref[n][s - d] on d <= s < a (a shorter reference is left-padded with zeros, a longer one is
+// cut) and 0.0 everywhere else.  s - d < min(a, b) <= b: no load leaves the reference's valid samples, and what lies behind them
+// is never loaded.  The source index is shifted by d, so the loads are dwords; VEC: one 16-byte store per thread (rows of a
+// multiple of 4 floats at a 16-byte aligned base), otherwise four coalesced dword stores.
+template <bool VEC>
+__global__ __launch_bounds__(256) void align_rows_kernel(const float* __restrict__ ref, float* __restrict__ out,
+                                                         const int* __restrict__ a_len, const int* __restrict__ b_len, int L_out,
+                                                         int L_ref, int ldr) {
+  const int n = blockIdx.y;
+  const int a = row_limit(a_len, n, L_out), b = row_limit(b_len, n, L_ref);
+  const int d = a > b ? a - b : 0;
+  const float* src = ref + (size_t)n * ldr;
+  float* dst = out + (size_t)n * L_out;
+  if constexpr (VEC) {
+    const int s = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (s >= L_out) return;
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (s + e >= d && s + e < a) ? src[s + e - d] : 0.f;
+    *reinterpret_cast<f32x4*>(dst + s) = v;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int s = blockIdx.x * 1024 + e * 256 + threadIdx.x;
+      if (s < L_out) dst[s] = (s >= d && s < a) ? src[s - d] : 0.f;
+    }
   }
 }
 
@@ -390,6 +417,30 @@ extern "C" int ps_zero_tail_f32(float* x, const int* limit, int N, int R, int ld
       hipLaunchKernelGGL(zero_tail_kernel<false>, dim3(R, N), dim3(256), 0, (hipStream_t)stream, x, limit, R, ld);
   }
   return launch_status("ps_zero_tail_f32");
+}
+
+extern "C" int ps_align_rows_f32(const float* ref, float* out, const int* a_len, const int* b_len, int N, int L_out, int L_ref,
+                                 int ldr, void* stream) {
+  using namespace ps;
+  if (!ref || !out || !a_len || !b_len || N <= 0 || N > 65535 || L_out <= 0 || L_ref <= 0 || ldr < L_ref) {
+    set_error("ps_align_rows_f32: null pointer or a size outside its range (N=%d in 1 .. 65535, L_out=%d, L_ref=%d, ldr=%d)", N,
+              L_out, L_ref, ldr);
+    return PS_E_INVALID;
+  }
+  if (ref == out) {
+    set_error("ps_align_rows_f32: out must not alias ref (a row is read at a shifted index)");
+    return PS_E_INVALID;
+  }
+  {
+    LaunchTimer timer("align_rows", (hipStream_t)stream);
+    const dim3 grid((L_out + 1023) / 1024, N);
+    if (L_out % 4 == 0 && !((uintptr_t)out & 15))
+      hipLaunchKernelGGL(align_rows_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, ref, out, a_len, b_len, L_out, L_ref, ldr);
+    else
+      hipLaunchKernelGGL(align_rows_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, ref, out, a_len, b_len, L_out, L_ref,
+                         ldr);
+  }
+  return launch_status("ps_align_rows_f32");
 }
 
 extern "C" int ps_dwconv_ragged_f32(const float* x, const float* w, const float* b, float* y, const int* t_rows, int N, int H,

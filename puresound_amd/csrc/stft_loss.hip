@@ -13,13 +13,23 @@ namespace ps {
 // reflection is enough: L > n_fft/2 and T = 1 + (L + 2 (n_fft/2) - n_fft) / hop frames (one fewer for an odd n_fft when hop
 // divides L) keep every index in [-(n_fft/2), L + n_fft/2 - 1]; the entry refuses any other T.  Rows r < N come from a, rows N + r from b.  One thread per (k, 4 frames): 16-byte
 // coalesced stores, gathered dword loads; zeros in the pad columns t >= T.
+// ROWS (ps_frame_reflect_rows_f32): rows n and N + n hold len_rows[n] <= L samples and anything behind them; the row is framed
+// as an utterance of that length on its own -- T_n = 1 + (L_n - n_fft % 2) / hop frames, reflected at the row's OWN end -- and
+// columns T_n <= t < ldt are zeros.  The bound above holds with (L_n, T_n) in the place of (L, T); a limit at or below n_fft/2,
+// which the host refuses, frames nothing (T_n = 0), so that no index leaves the row whatever the array holds.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void frame_reflect_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                            float* __restrict__ frames, int N, int L, int lda, int ldb,
-                                                            int shift, int win, int hop, int T, int ldt) {
+                                                            const int* __restrict__ len_rows, float* __restrict__ frames,
+                                                            int N, int L, int lda, int ldb, int shift, int win, int hop,
+                                                            int n_fft, int T, int ldt) {
   const int r = blockIdx.z, k = blockIdx.y;
   const int t = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (t >= ldt) return;
   const float* x = r < N ? a + (size_t)r * lda : b + (size_t)(r - N) * ldb;
+  if constexpr (ROWS) {
+    L = row_limit(len_rows, r < N ? r : r - N, L);
+    T = L > n_fft / 2 ? 1 + (L - n_fft % 2) / hop : 0;   // <= the launch-wide T
+  }
   f32x4 v;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -46,16 +56,21 @@ constexpr int SPM_FRAMES = 256;  // frames per workgroup: 4 per lane
 // (row n) and of the reference (row N + n) as 16-byte loads.  Magnitudes in fp32 as the reference forms them, everything
 // behind them in fp64; frames t >= T and bins >= bins are selected out, never multiplied out (a NaN there changes no bit).
 // The four sums of the workgroup go to its own slot of partials [N][parts][4], in a fixed order.
-__global__ __launch_bounds__(256) void spec_pair_moments_kernel(const float* __restrict__ spec, double* __restrict__ partials,
-                                                                float* __restrict__ mag, int N, int bins, int T, int ldt,
-                                                                int tchunks, double p) {
+// ROWS (ps_spec_pair_moments_rows_f64): utterance n holds t_rows[n] <= T frames; lanes whose four frames lie at or behind them
+// load nothing, so a workgroup entirely behind them writes its slot as zeros without a load, and the frames in front of them
+// sum in the order of the whole-row kernel (t_rows[n] == T gives its bits).  No `mag`.
+template <bool ROWS>
+__global__ __launch_bounds__(256) void spec_pair_moments_kernel(const float* __restrict__ spec, const int* __restrict__ t_rows,
+                                                                double* __restrict__ partials, float* __restrict__ mag, int N,
+                                                                int bins, int T, int ldt, int tchunks, double p) {
   __shared__ double red[4 * 4];
   const int n = blockIdx.y, part = blockIdx.x, tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int b0 = (part / tchunks) * SPM_BINS, t = (part % tchunks) * SPM_FRAMES + lane * 4;
   const size_t rows = 2 * (size_t)bins;
   double s[4] = {0.0, 0.0, 0.0, 0.0};
-  if (t < ldt) {
+  if constexpr (ROWS) T = row_limit(t_rows, n, T);
+  if (ROWS ? t < T : t < ldt) {
 #pragma unroll
     for (int j = 0; j < SPM_BINS / 4; ++j) {
       const int bin = b0 + wave + 4 * j;
@@ -83,7 +98,7 @@ __global__ __launch_bounds__(256) void spec_pair_moments_kernel(const float* __r
           s[3] += o * o;
         }
       }
-      if (mag) {
+      if (!ROWS && mag) {
         *reinterpret_cast<f32x4*>(mag + ((size_t)n * bins + bin) * ldt + t) = mx;
         *reinterpret_cast<f32x4*>(mag + (((size_t)N + n) * bins + bin) * ldt + t) = my;
       }
@@ -102,20 +117,43 @@ __global__ __launch_bounds__(256) void spec_pair_moments_kernel(const float* __r
 
 using namespace ps;
 
-extern "C" int ps_frame_reflect_f32(const float* a, const float* b, float* frames, int N, int L, int lda, int ldb, int n_fft,
-                                    int win, int hop, int T, int ldt, void* stream) {
+// The two framing entries: one check, one launch (len_rows == NULL: whole rows)
+static int frame_reflect(const char* who, const float* a, const float* b, const int* len_rows, float* frames, int N, int L,
+                         int lda, int ldb, int n_fft, int win, int hop, int T, int ldt, void* stream) {
   const int rows = b ? 2 * N : N;
   if (!a || !frames || N <= 0 || N > 32767 || n_fft <= 0 || win <= 0 || win > n_fft || win > 65535 || hop <= 0 ||
       L <= n_fft / 2 || lda < L || (b && ldb < L) || T != 1 + (L - n_fft % 2) / hop || ldt < T || ldt % kTileT != 0 ||
       ((uintptr_t)frames & 15)) {
-    set_error("ps_frame_reflect_f32: bad argument (N=%d L=%d lda=%d ldb=%d n_fft=%d win=%d hop=%d T=%d ldt=%d; reflect "
-              "padding needs L > n_fft/2)", N, L, lda, ldb, n_fft, win, hop, T, ldt);
+    set_error("%s: bad argument (N=%d L=%d lda=%d ldb=%d n_fft=%d win=%d hop=%d T=%d ldt=%d; reflect "
+              "padding needs L > n_fft/2)", who, N, L, lda, ldb, n_fft, win, hop, T, ldt);
     return PS_E_INVALID;
   }
-  LaunchTimer timer("frame_reflect", (hipStream_t)stream);
-  hipLaunchKernelGGL(frame_reflect_kernel, dim3((ldt / 4 + 255) / 256, win, rows), dim3(256), 0, (hipStream_t)stream, a, b,
-                     frames, N, L, lda, ldb, (n_fft - win) / 2 - n_fft / 2, win, hop, T, ldt);
-  return launch_status("ps_frame_reflect_f32");
+  const dim3 grid((ldt / 4 + 255) / 256, win, rows);
+  const int shift = (n_fft - win) / 2 - n_fft / 2;
+  {
+    LaunchTimer timer(len_rows ? "frame_reflect_rows" : "frame_reflect", (hipStream_t)stream);
+    if (len_rows)
+      hipLaunchKernelGGL(frame_reflect_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a, b, len_rows, frames, N, L, lda,
+                         ldb, shift, win, hop, n_fft, T, ldt);
+    else
+      hipLaunchKernelGGL(frame_reflect_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a, b, nullptr, frames, N, L, lda,
+                         ldb, shift, win, hop, n_fft, T, ldt);
+  }
+  return launch_status(who);
+}
+
+extern "C" int ps_frame_reflect_f32(const float* a, const float* b, float* frames, int N, int L, int lda, int ldb, int n_fft,
+                                    int win, int hop, int T, int ldt, void* stream) {
+  return frame_reflect("ps_frame_reflect_f32", a, b, nullptr, frames, N, L, lda, ldb, n_fft, win, hop, T, ldt, stream);
+}
+
+extern "C" int ps_frame_reflect_rows_f32(const float* a, const float* b, const int* len_rows, float* frames, int N, int L,
+                                         int lda, int ldb, int n_fft, int win, int hop, int T, int ldt, void* stream) {
+  if (!len_rows) {
+    set_error("ps_frame_reflect_rows_f32: len_rows is NULL");
+    return PS_E_INVALID;
+  }
+  return frame_reflect("ps_frame_reflect_rows_f32", a, b, len_rows, frames, N, L, lda, ldb, n_fft, win, hop, T, ldt, stream);
 }
 
 extern "C" int ps_spec_pair_moments_parts(int bins, int T) {
@@ -124,16 +162,38 @@ extern "C" int ps_spec_pair_moments_parts(int bins, int T) {
   return parts > 0x7fffffffLL ? 0 : (int)parts;
 }
 
-extern "C" int ps_spec_pair_moments_f64(const float* spec, double* partials, float* mag, int N, int bins, int T, int ldt,
-                                        double p, void* stream) {
+// The two reduction entries: one check, one launch (t_rows == NULL: whole rows)
+static int spec_pair_moments(const char* who, const float* spec, const int* t_rows, double* partials, float* mag, int N, int bins,
+                             int T, int ldt, double p, void* stream) {
   const int parts = ps_spec_pair_moments_parts(bins, T);
   if (!spec || !partials || N <= 0 || N > 32767 || parts <= 0 || ldt < T || ldt % kTileT != 0 || !(p > 0.0) || !(p < 64.0) ||
       ((uintptr_t)spec & 15) || ((uintptr_t)mag & 15)) {
-    set_error("ps_spec_pair_moments_f64: bad argument (N=%d bins=%d T=%d ldt=%d p=%g)", N, bins, T, ldt, p);
+    set_error("%s: bad argument (N=%d bins=%d T=%d ldt=%d p=%g)", who, N, bins, T, ldt, p);
     return PS_E_INVALID;
   }
-  LaunchTimer timer("spec_pair_moments", (hipStream_t)stream);
-  hipLaunchKernelGGL(spec_pair_moments_kernel, dim3(parts, N), dim3(256), 0, (hipStream_t)stream, spec, partials, mag, N, bins,
-                     T, ldt, (T + SPM_FRAMES - 1) / SPM_FRAMES, p);
-  return launch_status("ps_spec_pair_moments_f64");
+  const int tchunks = (T + SPM_FRAMES - 1) / SPM_FRAMES;
+  {
+    LaunchTimer timer(t_rows ? "spec_pair_moments_rows" : "spec_pair_moments", (hipStream_t)stream);
+    if (t_rows)
+      hipLaunchKernelGGL(spec_pair_moments_kernel<true>, dim3(parts, N), dim3(256), 0, (hipStream_t)stream, spec, t_rows, partials,
+                         nullptr, N, bins, T, ldt, tchunks, p);
+    else
+      hipLaunchKernelGGL(spec_pair_moments_kernel<false>, dim3(parts, N), dim3(256), 0, (hipStream_t)stream, spec, nullptr,
+                         partials, mag, N, bins, T, ldt, tchunks, p);
+  }
+  return launch_status(who);
+}
+
+extern "C" int ps_spec_pair_moments_f64(const float* spec, double* partials, float* mag, int N, int bins, int T, int ldt,
+                                        double p, void* stream) {
+  return spec_pair_moments("ps_spec_pair_moments_f64", spec, nullptr, partials, mag, N, bins, T, ldt, p, stream);
+}
+
+extern "C" int ps_spec_pair_moments_rows_f64(const float* spec, const int* t_rows, double* partials, int N, int bins, int T,
+                                             int ldt, double p, void* stream) {
+  if (!t_rows) {
+    set_error("ps_spec_pair_moments_rows_f64: t_rows is NULL");
+    return PS_E_INVALID;
+  }
+  return spec_pair_moments("ps_spec_pair_moments_rows_f64", spec, t_rows, partials, nullptr, N, bins, T, ldt, p, stream);
 }

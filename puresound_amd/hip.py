@@ -1741,6 +1741,96 @@ def zero_tail(x: torch.Tensor, limits: torch.Tensor) -> torch.Tensor:
     return x
 
 
+def align_rows(ref: torch.Tensor, a_len: torch.Tensor, b_len: torch.Tensor, length: int) -> torch.Tensor:
+    """align_reference per row: ref [N, L_ref] (last-dim contiguous) -> [N, length] with row n's b_len[n] reference samples
+    aligned to a_len[n] valid output samples -- left-padded with zeros when shorter, cut when longer -- and exact 0.0 behind
+    a_len[n]; a_len, b_len int32 [N] on the device.  What ref holds behind b_len[n] is not read (ps_align_rows_f32)."""
+    require_device(ref, "align_rows")
+    if ref.dim() != 2 or ref.dtype != torch.float32 or ref.shape[1] < 1 or length < 1:
+        raise RuntimeError(f"align_rows: an fp32 [N, L_ref] reference and length >= 1 (got {tuple(ref.shape)} {ref.dtype}, "
+                           f"length {length})")
+    if ref.stride(1) != 1:
+        ref = ref.contiguous()
+    n, l_ref = ref.shape
+    _require_limits("align_rows", a_len, n, ref.device)
+    _require_limits("align_rows", b_len, n, ref.device)
+    out = torch.empty(n, length, dtype=torch.float32, device=ref.device)
+    check(lib().ps_align_rows_f32(ptr(ref), ptr(out), ptr(a_len), ptr(b_len), n, length, l_ref, ref.stride(0),
+                                  stream_ptr(ref.device)), "ps_align_rows_f32")
+    return out
+
+
+def wave_moments_rows(a: torch.Tensor, b: torch.Tensor, len_rows: torch.Tensor) -> torch.Tensor:
+    """wave_moments over the first len_rows[n] samples of row n (int32 [R] on the device): what the rows hold behind them, a
+    NaN included, changes no bit; len_rows[n] == L gives wave_moments' bits (ps_wave_moments_rows_f64)."""
+    require_device(a, "wave_moments_rows")
+    require_device(b, "wave_moments_rows")
+    if a.dim() != 2 or a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise RuntimeError("wave_moments_rows: two fp32 tensors of the same shape [R, L]")
+    if a.stride(1) != 1:
+        a = a.contiguous()
+    if b.stride(1) != 1:
+        b = b.contiguous()
+    r, length = a.shape
+    _require_limits("wave_moments_rows", len_rows, r, a.device)
+    chunks = lib().ps_wave_moments_chunks(length)
+    part = torch.empty(r, chunks, 5, dtype=torch.float64, device=a.device)
+    check(lib().ps_wave_moments_rows_f64(ptr(a), ptr(b), ptr(len_rows), ptr(part), r, length, a.stride(0), b.stride(0),
+                                         stream_ptr(a.device)), "ps_wave_moments_rows_f64")
+    return part.sum(1)
+
+
+def frame_reflect_rows(a: torch.Tensor, b: Optional[torch.Tensor], len_rows: torch.Tensor, n_fft: int, win: int, hop: int,
+                       out: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, int]:
+    """frame_reflect with rows n (and N + n) framed as utterances of len_rows[n] samples on their own (int32 [N] on the
+    device, each > n_fft // 2: the host's check): stft_frames(len_rows[n], n_fft, hop) frames reflected at the row's own end,
+    zeros in every column behind them; T = stft_frames(L, n_fft, hop) is the launch's (ps_frame_reflect_rows_f32)."""
+    require_device(a, "frame_reflect_rows")
+    if a.dim() != 2 or (b is not None and (b.shape != a.shape or b.device != a.device or b.dtype != torch.float32)):
+        raise RuntimeError("frame_reflect_rows: fp32 waveforms [N, L] of one shape on one device")
+    n, length = a.shape
+    if win > n_fft or win < 1 or hop < 1:
+        raise RuntimeError(f"frame_reflect_rows: need 1 <= win <= n_fft and hop >= 1 (got win={win}, n_fft={n_fft}, hop={hop})")
+    if length <= n_fft // 2:
+        raise RuntimeError(f"frame_reflect_rows: reflect padding needs more than n_fft // 2 samples (length {length}, "
+                           f"fft_size {n_fft})")
+    _require_limits("frame_reflect_rows", len_rows, n, a.device)
+    if a.stride(1) != 1:
+        a = a.contiguous()
+    if b is not None and b.stride(1) != 1:
+        b = b.contiguous()
+    rows = n if b is None else 2 * n
+    t = stft_frames(length, n_fft, hop)
+    ldt = padded_frames(t)
+    if out is None:
+        out = torch.empty(rows, win, ldt, dtype=torch.float32, device=a.device)
+    elif tuple(out.shape) != (rows, win, ldt):
+        raise RuntimeError(f"frame_reflect_rows: `out` must be [{rows}, {win}, {ldt}]")
+    _require_operand("frame_reflect_rows", a.device, out=out)
+    check(lib().ps_frame_reflect_rows_f32(ptr(a), ptr(b), ptr(len_rows), ptr(out), n, length, a.stride(0),
+                                          0 if b is None else b.stride(0), n_fft, win, hop, t, ldt, stream_ptr(a.device)),
+          "ps_frame_reflect_rows_f32")
+    return out, t
+
+
+def spec_pair_moments_rows(spec: torch.Tensor, bins: int, t: int, t_rows: torch.Tensor, p: float = 0.5,
+                           slots: bool = False) -> torch.Tensor:
+    """spec_pair_moments over the first t_rows[n] <= t frames of utterance n (int32 [N] on the device): what the columns
+    behind them hold changes no bit; t_rows[n] == t gives spec_pair_moments' bits (ps_spec_pair_moments_rows_f64).
+    slots: the partials [N, parts, 4] as the kernel wrote them (slot (bins // 16) * ceil(t / 256) + t // 256 holds 16 bins x
+    256 frames), not their sum."""
+    require_device(spec, "spec_pair_moments_rows")
+    if spec.dim() != 3 or spec.shape[0] % 2 or spec.shape[1] != 2 * bins or not spec.is_contiguous():
+        raise RuntimeError("spec_pair_moments_rows: spec must be a contiguous [2N, 2*bins, ldt] tensor")
+    n, ldt = spec.shape[0] // 2, spec.shape[2]
+    _require_limits("spec_pair_moments_rows", t_rows, n, spec.device)
+    parts = lib().ps_spec_pair_moments_parts(bins, t)
+    part = torch.empty(n, max(parts, 1), 4, dtype=torch.float64, device=spec.device)
+    check(lib().ps_spec_pair_moments_rows_f64(ptr(spec), ptr(t_rows), ptr(part), n, bins, t, ldt, float(p),
+                                              stream_ptr(spec.device)), "ps_spec_pair_moments_rows_f64")
+    return part if slots else part.sum(1)
+
+
 def conv_tasnet_ragged(blocks: "C.Array[TcnBlock]", n_blocks: int, x_pad: torch.Tensor, t: int, c: int, h: int,
                        t_rows: torch.Tensor, dvec: Optional[torch.Tensor], embed_norm: bool,
                        workspace: Optional[torch.Tensor] = None) -> torch.Tensor:

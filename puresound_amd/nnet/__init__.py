@@ -3,7 +3,7 @@ from types import SimpleNamespace
 
 from .base_nn import SiMoTaskWrapModule, SoTaskWrapModule
 from .loss.sdr import SDRLoss
-from .loss.stft_loss import MultiResolutionSTFTLoss, STFTLoss, over_suppression_loss
+from .loss.stft_loss import MultiResolutionSTFTLoss, STFTLoss, over_suppression_loss, over_suppression_loss_ragged
 from .conv_tasnet import TCN, ConvTasNet, GatedTCN
 from .dprnn import DPRNN
 from .lobe.encoder import ConvEncDec, FbankEnc, FreeEncDec

@@ -244,14 +244,22 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         if out_mode not in ("linear", "sigmoid"):
             raise NameError("Non support type.")  # base_nn.py:421-422
         rp = ragged.plan(self, noisy, enroll, lengths, enroll_lengths)
+        return self._ragged_forward(noisy, enroll, rp, [])[0]
+
+    def _ragged_forward(self, noisy: torch.Tensor, enroll: Optional[torch.Tensor], rp, more_rows: list):
+        """The launches of _inference_ragged behind its host side `rp` (ragged.plan) -> (waveform, limits): every host value
+        of the call goes to the device in ONE copy, `more_rows` (further [N] integer rows of the caller: a score's limits)
+        included; they are limits[-len(more_rows):], and limits[1] holds the valid output samples."""
+        from . import ragged
+        mask_act, out_mode = self.mask_constraint.lower(), self.output_constraint.lower()
         dev = noisy.device
-        # every host value of the call in ONE host-to-device copy: frames and valid samples per row, the enrolment's frames
-        # and, as the bits of fp32 values, the relative lengths the pooling takes
+        # frames and valid samples per row, the enrolment's frames and, as the bits of fp32 values, the relative lengths the
+        # pooling takes
         rows = [rp.t_rows, rp.out_lengths]
         if enroll is not None:
             rel = torch.tensor(ragged.relative_lengths(rp.enroll_t_rows, rp.enroll_frames), dtype=torch.float32)
             rows += [rp.enroll_t_rows, rel.view(torch.int32).tolist()]
-        limits = hip.row_limits("inference", rows, dev)
+        limits = hip.row_limits("inference", rows + list(more_rows), dev)
         dvec = None
         if enroll is not None:
             dvec = self._speaker_embedding(enroll.contiguous(), 0, limits[2], limits[3].view(torch.float32))
@@ -260,7 +268,86 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         hip.zero_tail(feats, limits[0])
         hip.zero_tail(mask, limits[0])
         wav = self.encoder.decode_padded(feats, t, mask, mask_act, out_mode)
-        return hip.zero_tail(wav, limits[1])
+        return hip.zero_tail(wav, limits[1]), limits
+
+    @torch.no_grad()
+    def inference_scored_ragged(self, noisy: torch.Tensor, ref_clean: torch.Tensor, enroll: Optional[torch.Tensor] = None,
+                                loss_func=None, inactive_labels: Optional[torch.Tensor] = None, lengths=None,
+                                ref_lengths=None, enroll_lengths=None):
+        """inference(noisy, enroll, lengths, enroll_lengths) and the score of every row against its clean reference in one
+        call -> (enhanced [N, L_out], score): an evaluation loop's batch of utterances of unequal length.  Not a method of the
+        reference.  `enhanced` is bit-identical to that inference call.
+
+        Row n of ref_clean [N, L_ref] holds ref_lengths[n] samples (default: lengths[n]; each in [1, L_ref]) and anything
+        behind them.  It is aligned to row n's valid output length out_n = output_lengths(lengths)[n] by _align_waveform's
+        rule, per row: shorter it is left-padded with zeros, longer it is cut; the aligned row is 0.0 behind out_n.
+        loss_func: an SDRLoss (default self.loss_func_wav, else SDRLoss.init_mode("sisnr")) -- its from_moments value over the
+        rows' out_n samples; an STFTLoss / MultiResolutionSTFTLoss -- loss(enh, aligned, lengths=out_lengths); any other
+        callable is called as loss_func(enh, aligned, inactive_labels, lengths=out_lengths) and must take `lengths` (or
+        **kwargs).  The refusals are those of inference with lengths (nnet/ragged.py), a source-aggregated SDRLoss and a
+        callable without `lengths`; everything is raised before any launch.  CPU tensors: the rows one by one in stock ATen."""
+        import inspect
+        from . import ragged
+        from .loss import stft_loss
+        from .loss.sdr import SDRLoss
+        who = "inference_scored_ragged"
+        if lengths is None:
+            raise ValueError(f"{who}: lengths is needed (a batch of whole rows is inference_scored's)")
+        loss = loss_func if loss_func is not None else getattr(self, "loss_func_wav", None)
+        if loss is None:
+            loss = SDRLoss.init_mode("sisnr")
+        spectral = isinstance(loss, (stft_loss.STFTLoss, stft_loss.MultiResolutionSTFTLoss))
+        if isinstance(loss, SDRLoss):
+            if loss.source_aggregated:
+                raise NotImplementedError(f"{who}: an SDRLoss on [N, L] signals (not a source-aggregated mode)")
+        elif not spectral:
+            params = inspect.signature(loss.forward if isinstance(loss, nn.Module) else loss).parameters.values()
+            if not any(p.name == "lengths" or p.kind is inspect.Parameter.VAR_KEYWORD for p in params):
+                raise NotImplementedError(
+                    f"{who}: loss_func must take `lengths` (it is called as loss_func(enh, ref, inactive_labels, lengths="
+                    f"out_lengths)); a three-argument closure such as the recipes' `lambda enh, ref, dummy:` cannot know where "
+                    f"the rows end and would score the zeros behind them")
+        rp = ragged.plan(self, noisy, enroll, lengths, enroll_lengths)
+        self.check_mask_constraint(self.mask_constraint)
+        if self.output_constraint.lower() not in ("linear", "sigmoid"):
+            raise NameError("Non support type.")  # base_nn.py:421-422
+        n = noisy.shape[0]
+        if ref_clean.dim() != 2 or ref_clean.shape[0] != n:
+            raise RuntimeError(f"{who}: ref_clean must be [N, L_ref] with the batch of `noisy`")
+        r_lens = ragged.host_lengths("ref_lengths", rp.lengths if ref_lengths is None else ref_lengths, n, ref_clean.shape[1],
+                                     None, who=who)
+        out = rp.out_lengths
+        win, hop = self.encoder.win_length, self.encoder.hop_length
+        l_out = (ragged.frames(noisy.shape[1], win, hop) - 1) * hop + win
+        resolutions = stft_loss.check_rows(who, loss, n, l_out, out) if spectral else []
+
+        def score(enh, aligned, limits):
+            if isinstance(loss, SDRLoss):
+                return loss(enh, aligned, inactive_labels, lengths=out)   # (CPU tensors: each row's five sums alone)
+            if spectral:
+                return loss(enh, aligned, lengths=out, limits=limits)
+            return loss(enh, aligned, inactive_labels, lengths=out)
+
+        if noisy.device.type == "cpu":
+            enh = self.inference(noisy, enroll, lengths=rp.lengths, enroll_lengths=rp.enroll_lengths)
+            aligned = torch.zeros_like(enh)
+            for i, (a, b) in enumerate(zip(out, r_lens)):
+                aligned[i, :a] = hip.align_reference(ref_clean[i, :b].float(), a)
+            return enh, score(enh, aligned, None)
+        hip.require_device(noisy, f"SoTaskWrapModule.{who}")
+        hip.require_device(ref_clean, f"SoTaskWrapModule.{who}")
+        if enroll is not None:
+            hip.require_device(enroll, f"SoTaskWrapModule.{who}")
+        more = [r_lens] + stft_loss.limit_rows(out, resolutions)[1:]
+        enh, limits = self._ragged_forward(noisy, enroll, rp, more)
+        ref_lim, t_lims = limits[-len(more)], list(limits[len(limits) - len(more) + 1:])
+        aligned = hip.align_rows(ref_clean.float(), limits[1], ref_lim, enh.shape[1])
+        if isinstance(loss, SDRLoss):
+            moments = hip.wave_moments_rows(enh, aligned, limits[1])
+            return enh, loss.from_moments(moments, limits[1].double().unsqueeze(1), inactive_labels)
+        if isinstance(loss, stft_loss.STFTLoss):
+            return enh, score(enh, aligned, (limits[1], t_lims[0]))
+        return enh, score(enh, aligned, [limits[1]] + t_lims if spectral else None)
 
     @torch.no_grad()
     def inference_scored(self, noisy: torch.Tensor, ref_clean: torch.Tensor, enroll: Optional[torch.Tensor] = None,
@@ -278,7 +365,7 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         from .loss.stft_loss import MultiResolutionSTFTLoss, STFTLoss
         if lengths is not None or enroll_lengths is not None:
             raise NotImplementedError("inference_scored: per-row lengths are not covered (the decoder gathers the score's "
-                                      "moments over whole rows); score the rows of inference(..., lengths=...) one by one")
+                                      "moments over whole rows); inference_scored_ragged enhances and scores such a batch")
         loss = loss_func if loss_func is not None else getattr(self, "loss_func_wav", None)
         if loss is None:
             loss = SDRLoss.init_mode("sisnr")

@@ -13,6 +13,13 @@ CPU tensors: stock ATen (`torch.stft(..., return_complex=True)` and elementwise 
 device: hip.frame_reflect -> hip.conv1x1 against the windowed Fourier basis (exact fp32 products, the window's support
 only) -> hip.spec_pair_moments; estimate and reference share each launch as rows n and N + n.  The scores are formed from
 the sums on the device, without a host sync.
+
+Rows of unequal length (`lengths=`, not in the reference: N host ints): row n's sums are those of its first lengths[n]
+samples alone -- T_n = hip.stft_frames(lengths[n], fft_size, hop) frames, reflect-padded at the row's own end, whatever the
+row holds behind them -- and the batch values are the same formulas over the elements that exist:
+  sc = sqrt(sum_n S0) / sqrt(sum_n S1)      mag = sum_n S2 / (bins sum_n T_n)      ov = sum_n S3 / (bins sum_n T_n)
+CPU tensors: each row alone through the path above.  Device: hip.frame_reflect_rows -> hip.conv1x1 over all T columns (those
+behind T_n are zeros) -> hip.spec_pair_moments_rows, the lengths and the T_n of every resolution in one int32 copy.
 """
 import math
 
@@ -43,6 +50,38 @@ def _check_resolution(who: str, length: int, fft_size: int, hop_size: int, win_l
     if length <= fft_size // 2:
         raise RuntimeError(f"{who}: reflect padding needs more than fft_size // 2 samples: length {length} with "
                            f"fft_size {fft_size}")
+
+
+def _host_rows(who: str, n: int, length: int, lengths, fft_sizes) -> list:
+    """Per-row `lengths` of a batch [N, L] (N Python ints or a CPU integer tensor [N]; host values) -> the list, validated
+    against the row length and against every resolution of the call: reflect padding at a row's own end needs
+    lengths[n] > fft_size // 2."""
+    from ..ragged import host_lengths
+    lens = host_lengths("lengths", lengths, n, length, None, who=who)
+    for fft_size in fft_sizes:
+        for i, v in enumerate(lens):
+            if v <= fft_size // 2:
+                raise RuntimeError(f"{who}: reflect padding needs more than fft_size // 2 samples: lengths[{i}] = {v} with "
+                                   f"fft_size {fft_size}")
+    return lens
+
+
+def limit_rows(lens, resolutions) -> list:
+    """The host integers a device call with per-row lengths reads, [1 + R][N]: the lengths, then per resolution
+    (fft_size, hop_size) the frame counts T_n.  A caller with limits of its own (inference_scored_ragged) appends them to its
+    one copy (hip.row_limits) and hands the device rows back as `limits`."""
+    return [list(lens)] + [[hip.stft_frames(v, f, h) for v in lens] for f, h in resolutions]
+
+
+def check_rows(who: str, loss, n: int, length: int, lengths) -> list:
+    """What `loss` (an STFTLoss or a MultiResolutionSTFTLoss) would refuse signals [N, length] with per-row `lengths` for,
+    raised here: a caller that launches before it scores (inference_scored_ragged) asks first.  -> [(fft_size, hop_size)] per
+    resolution."""
+    parts = list(loss.stft_losses) if isinstance(loss, MultiResolutionSTFTLoss) else [loss]
+    for f in parts:
+        _check_resolution(who, length, f.fft_size, f.shift_size, f.win_length, f.window)
+    _host_rows(who, n, length, lengths, [f.fft_size for f in parts])
+    return [(f.fft_size, f.shift_size) for f in parts]
 
 
 def fourier_basis(window: torch.Tensor, fft_size: int) -> torch.Tensor:
@@ -92,8 +131,10 @@ def _work(device: torch.device, floats: int) -> torch.Tensor:
 
 
 def _device_moments(x: torch.Tensor, y: torch.Tensor, fft_size: int, hop_size: int, win_length: int, wt: torch.Tensor,
-                    p: float, want_mag: bool = False):
-    """-> (fp64 sums [N, 4], T, magnitudes [2N, bins, ldt] or None) on the HIP path."""
+                    p: float, want_mag: bool = False, limits=None):
+    """-> (fp64 sums [N, 4], T, magnitudes [2N, bins, ldt] or None) on the HIP path.  limits: (lengths, T_n) as int32 [N] on
+    the device -- row n is framed as an utterance of lengths[n] samples on its own and summed over its T_n frames; the product
+    in between runs over all T columns, those behind T_n being the zeros the framing wrote."""
     hip.require_device(x, "stft_loss")
     hip.require_device(y, "stft_loss")
     n, length = x.shape
@@ -103,6 +144,10 @@ def _device_moments(x: torch.Tensor, y: torch.Tensor, fft_size: int, hop_size: i
     buf = _work(x.device, f_floats + s_floats)
     frames = buf[:f_floats].view(2 * n, win_length, ldt)
     spec = buf[f_floats:f_floats + s_floats].view(2 * n, 2 * bins, ldt)
+    if limits is not None:
+        hip.frame_reflect_rows(x, y, limits[0], fft_size, win_length, hop_size, out=frames)
+        hip.conv1x1(frames, t, wt, 2 * bins, out=spec)
+        return hip.spec_pair_moments_rows(spec, bins, t, limits[1], p), t, None
     hip.frame_reflect(x, y, fft_size, win_length, hop_size, out=frames)
     hip.conv1x1(frames, t, wt, 2 * bins, out=spec)
     mag = torch.empty(2 * n, bins, ldt, dtype=torch.float32, device=x.device) if want_mag else None
@@ -122,22 +167,38 @@ def _cpu_moments(x_mag: torch.Tensor, y_mag: torch.Tensor, p: float) -> torch.Te
 
 
 def _moments(who: str, x: torch.Tensor, y: torch.Tensor, fft_size: int, hop_size: int, win_length: int,
-             window: torch.Tensor, p: float, packed):
-    """-> (fp64 sums [N, 4], elements per utterance).  packed: () -> the packed basis on x's device."""
+             window: torch.Tensor, p: float, packed, lengths=None, limits=None):
+    """-> (fp64 sums [N, 4], elements of the batch's spectrograms).  packed: () -> the packed basis on x's device.
+    lengths: row n's sums are those of x[n:n+1, :lengths[n]], y[n:n+1, :lengths[n]] alone -- T_n = stft_frames(lengths[n]) frames,
+    reflect-padded at the row's own end -- and the elements are bins * sum_n T_n.  CPU tensors take each row alone through
+    torch.stft; on a device the lengths and the T_n go there in one int32 copy, unless the caller hands them in as `limits` =
+    (lengths, T_n), int32 [N] each."""
     _check_pair(who, x, y)
     _check_resolution(who, x.shape[1], fft_size, hop_size, win_length, window)
     bins = fft_size // 2 + 1
+    if lengths is None:
+        if x.device.type == "cpu":
+            x_mag = _cpu_magnitudes(x, fft_size, hop_size, win_length, window)
+            y_mag = _cpu_magnitudes(y, fft_size, hop_size, win_length, window)
+            return _cpu_moments(x_mag, y_mag, p), x.shape[0] * x_mag.shape[1] * bins
+        m, t, _ = _device_moments(x, y, fft_size, hop_size, win_length, packed(), p)
+        return m, x.shape[0] * t * bins
+    lens = _host_rows(who, x.shape[0], x.shape[1], lengths, [fft_size])
+    rows = limit_rows(lens, [(fft_size, hop_size)])
+    count = bins * sum(rows[1])
     if x.device.type == "cpu":
-        x_mag = _cpu_magnitudes(x, fft_size, hop_size, win_length, window)
-        y_mag = _cpu_magnitudes(y, fft_size, hop_size, win_length, window)
-        return _cpu_moments(x_mag, y_mag, p), x_mag.shape[1] * bins
-    m, t, _ = _device_moments(x, y, fft_size, hop_size, win_length, packed(), p)
-    return m, t * bins
+        return torch.cat([_cpu_moments(_cpu_magnitudes(x[n:n + 1, :v], fft_size, hop_size, win_length, window),
+                                       _cpu_magnitudes(y[n:n + 1, :v], fft_size, hop_size, win_length, window), p)
+                          for n, v in enumerate(lens)]), count
+    if limits is None:
+        limits = hip.row_limits(who, rows, x.device)
+    m, _, _ = _device_moments(x, y, fft_size, hop_size, win_length, packed(), p, limits=limits)
+    return m, count
 
 
 def _sc_mag(m: torch.Tensor, count: int):
-    """fp64 (spectral convergence, log-magnitude distance) of a batch from its sums [N, 4]"""
-    return torch.sqrt(m[:, 0].sum()) / torch.sqrt(m[:, 1].sum()), m[:, 2].sum() / (m.shape[0] * count)
+    """fp64 (spectral convergence, log-magnitude distance) of a batch from its sums [N, 4] over `count` elements"""
+    return torch.sqrt(m[:, 0].sum()) / torch.sqrt(m[:, 1].sum()), m[:, 2].sum() / count
 
 
 @torch.no_grad()
@@ -202,19 +263,29 @@ class STFTLoss(PlanCache, nn.Module):
             return _cpu_magnitudes(x, self.fft_size, self.shift_size, self.win_length, self.window)
         return _device_magnitudes(x, self.fft_size, self.shift_size, self.win_length, self._plan_get(x.device, self._build))
 
-    def _sums(self, x: torch.Tensor, y: torch.Tensor, p: float = 0.5):
+    def _sums(self, x: torch.Tensor, y: torch.Tensor, p: float = 0.5, lengths=None, limits=None):
         return _moments("STFTLoss", x, y, self.fft_size, self.shift_size, self.win_length, self.window, p,
-                        lambda: self._plan_get(x.device, self._build))
+                        lambda: self._plan_get(x.device, self._build), lengths, limits)
 
     @torch.no_grad()
-    def moments(self, x: torch.Tensor, y: torch.Tensor, p: float = 0.5) -> torch.Tensor:
+    def moments(self, x: torch.Tensor, y: torch.Tensor, p: float = 0.5, lengths=None) -> torch.Tensor:
         """Not in the reference: x (estimate), y (reference) [N, L] -> fp64 [N, 4] = (S0, S1, S2, S3) of this resolution, on
-        the signals' device."""
-        return self._sums(x, y, p)[0]
+        the signals' device.  lengths (N Python ints or a CPU integer tensor [N], each in (fft_size // 2, L]): row n's sums
+        are those of x[n:n+1, :lengths[n]], y[n:n+1, :lengths[n]] alone, whatever the rows hold behind them; with
+        frame_counts(lengths) a caller forms per-utterance scores from them."""
+        return self._sums(x, y, p, lengths)[0]
+
+    def frame_counts(self, lengths) -> list:
+        """Not in the reference: T_n = frames of an utterance of lengths[n] samples at this resolution (its spectrogram holds
+        T_n * (fft_size // 2 + 1) elements)."""
+        return [hip.stft_frames(int(v), self.fft_size, self.shift_size) for v in lengths]
 
     @torch.no_grad()
-    def forward(self, x: torch.Tensor, y: torch.Tensor):
-        sc, mag = _sc_mag(*self._sums(x, y))
+    def forward(self, x: torch.Tensor, y: torch.Tensor, lengths=None, limits=None):
+        """lengths: the reference's formulas over the elements that exist -- sc = sqrt(sum_n S0) / sqrt(sum_n S1),
+        mag = sum_n S2 / (bins * sum_n T_n) with row n's sums those of its first lengths[n] samples alone.  limits: the device
+        rows of limit_rows(lengths, ...) from a caller that copied them already."""
+        sc, mag = _sc_mag(*self._sums(x, y, 0.5, lengths, limits))
         return sc.float(), mag.float()
 
 
@@ -232,23 +303,36 @@ class MultiResolutionSTFTLoss(nn.Module):
         self.factor_mag = factor_mag
 
     @torch.no_grad()
-    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    def resolutions(self) -> list:
+        """(fft_size, hop_size) per resolution: what limit_rows takes"""
+        return [(f.fft_size, f.shift_size) for f in self.stft_losses]
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor, y: torch.Tensor, lengths=None, limits=None) -> torch.Tensor:
+        """lengths / limits: as STFTLoss.forward's, per resolution; the lengths and every resolution's T_n go to the device in
+        one copy (limits: int32 [1 + R, N], the device rows of limit_rows(lengths, self.resolutions()))."""
         _check_pair("MultiResolutionSTFTLoss", x, y)
         for f in self.stft_losses:   # every refusal before the first launch
             _check_resolution("MultiResolutionSTFTLoss", x.shape[1], f.fft_size, f.shift_size, f.win_length, f.window)
+        per_res = [None] * len(self.stft_losses)
+        if lengths is not None:
+            lengths = _host_rows("MultiResolutionSTFTLoss", x.shape[0], x.shape[1], lengths,
+                                 [f.fft_size for f in self.stft_losses])
+            if x.device.type != "cpu":
+                if limits is None:
+                    limits = hip.row_limits("MultiResolutionSTFTLoss", limit_rows(lengths, self.resolutions()), x.device)
+                per_res = [(limits[0], limits[1 + i]) for i in range(len(self.stft_losses))]
         sc_loss, mag_loss = 0.0, 0.0
-        for f in self.stft_losses:
-            sc, mag = _sc_mag(*f._sums(x, y))
+        for f, lim in zip(self.stft_losses, per_res):
+            sc, mag = _sc_mag(*f._sums(x, y, 0.5, lengths, lim))
             sc_loss = sc_loss + sc
             mag_loss = mag_loss + mag
         count = len(self.stft_losses)
         return (self.factor_sc * (sc_loss / count) + self.factor_mag * (mag_loss / count)).float()
 
 
-@torch.no_grad()
-def over_suppression_loss(enh: torch.Tensor, ref: torch.Tensor, p: float = 0.5, fft_size: int = 512, hop_size: int = 128,
-                          win_length: int = 512) -> torch.Tensor:
-    """stft_loss.py:144-153: mean(relu(ref_mag^p - enh_mag^p)^2) with a Hann window."""
+def _over_suppression(who: str, enh: torch.Tensor, ref: torch.Tensor, p: float, fft_size: int, hop_size: int, win_length: int,
+                      lengths) -> torch.Tensor:
     window = torch.hann_window(win_length)
 
     def packed():
@@ -257,5 +341,21 @@ def over_suppression_loss(enh: torch.Tensor, ref: torch.Tensor, p: float = 0.5, 
             _OV_BASIS[key] = _packed_basis(window, fft_size, enh.device)
         return _OV_BASIS[key]
 
-    m, count = _moments("over_suppression_loss", enh, ref, fft_size, hop_size, win_length, window, p, packed)
-    return (m[:, 3].sum() / (m.shape[0] * count)).float()
+    m, count = _moments(who, enh, ref, fft_size, hop_size, win_length, window, p, packed, lengths)
+    return (m[:, 3].sum() / count).float()
+
+
+@torch.no_grad()
+def over_suppression_loss(enh: torch.Tensor, ref: torch.Tensor, p: float = 0.5, fft_size: int = 512, hop_size: int = 128,
+                          win_length: int = 512) -> torch.Tensor:
+    """stft_loss.py:144-153: mean(relu(ref_mag^p - enh_mag^p)^2) with a Hann window."""
+    return _over_suppression("over_suppression_loss", enh, ref, p, fft_size, hop_size, win_length, None)
+
+
+@torch.no_grad()
+def over_suppression_loss_ragged(enh: torch.Tensor, ref: torch.Tensor, lengths, p: float = 0.5, fft_size: int = 512,
+                                 hop_size: int = 128, win_length: int = 512) -> torch.Tensor:
+    """Not in the reference: over_suppression_loss of rows of unequal length -- the mean over the elements that exist,
+    sum_n S3 / (bins * sum_n T_n), with row n's sum that of its first lengths[n] samples alone (STFTLoss.moments).  A function
+    of its own: over_suppression_loss keeps the reference's signature, which the recipes' closures rely on."""
+    return _over_suppression("over_suppression_loss_ragged", enh, ref, p, fft_size, hop_size, win_length, lengths)

@@ -8,32 +8,38 @@ HIP path (base_nn.py) and the CPU path (cpu_path.py), which loops over the rows 
 
 Covered: FreeEncDec encoder, the normal-TCN ConvTasNet masker on the fused driver (no cLN), and for `enroll_lengths` a
 speaker net of plain TCN blocks -> AttentiveStatisticsPooling -> k=1 projection(s) (td_tse_conv_tasnet_v0[_causal]).
-Everything else raises NotImplementedError."""
+Everything else raises NotImplementedError.  Scoring such a batch: SoTaskWrapModule.inference_scored_ragged (base_nn.py), whose
+model refusals are check_model's and whose length values -- like the `lengths` of the scores in nnet/loss/ -- go through
+host_lengths."""
 from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 import torch.nn as nn
 
 
-def host_lengths(name: str, values, n: int, upper: Optional[int], win: int) -> List[int]:
+def host_lengths(name: str, values, n: int, upper: Optional[int], win: Optional[int], who: str = "inference") -> List[int]:
     """`values` (a sequence of N Python ints or a CPU integer tensor [N]) -> the list, validated against the row length
-    `upper` (None: there are no rows) and the encoder's window."""
+    `upper` (None: there are no rows) and the encoder's window (None: the values of a score, which need one sample).  `who`
+    names the caller in the messages: the scores of nnet/loss/ validate their `lengths` here too."""
     if torch.is_tensor(values):
         if values.is_cuda or values.is_floating_point() or values.dtype == torch.bool or values.dim() != 1:
-            raise ValueError(f"inference: {name} must be a sequence of ints or a CPU integer tensor [N] "
+            raise ValueError(f"{who}: {name} must be a sequence of ints or a CPU integer tensor [N] "
                              f"(got {values.dtype} {tuple(values.shape)} on {values.device})")
         values = values.tolist()
     else:
         values = list(values)
         if not all(isinstance(v, int) and not isinstance(v, bool) for v in values):
-            raise ValueError(f"inference: {name} must hold Python ints")
+            raise ValueError(f"{who}: {name} must hold Python ints")
     if len(values) != n:
-        raise ValueError(f"inference: {name} holds {len(values)} values for a batch of {n} rows")
+        raise ValueError(f"{who}: {name} holds {len(values)} values for a batch of {n} rows")
     for i, v in enumerate(values):
         if upper is not None and v > upper:
-            raise ValueError(f"inference: {name}[{i}] = {v} exceeds the row length {upper}")
-        if v < win:  # (the wording of free_encode for an utterance shorter than one frame)
-            raise RuntimeError(f"inference: {name}[{i}]: input length {v} is shorter than the window {win}")
+            raise ValueError(f"{who}: {name}[{i}] = {v} exceeds the row length {upper}")
+        if win is None:
+            if v < 1:
+                raise ValueError(f"{who}: {name}[{i}] = {v} must be at least 1")
+        elif v < win:  # (the wording of free_encode for an utterance shorter than one frame)
+            raise RuntimeError(f"{who}: {name}[{i}]: input length {v} is shorter than the window {win}")
     return values
 
 
