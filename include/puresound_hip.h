@@ -909,7 +909,12 @@ int ps_dwconv_amax_f32(const float* x, const float* w, const float* b, float* y,
  *                With amax_mul > 0 the maxima are those of the producer's output BEFORE the prologue f (a per-channel
  *                affine map -- an eval BatchNorm -- and a PReLU): the range of f(x) is taken as amax_mul * max|x| + amax_add
  *                (max |scale| and max |shift| of the map, times max(1, |slope|)); 0 = the maxima as they are.
- *   y_amax       optional, [N][ps_conv1x1_stats_parts(M, T)]: partial maxima of |y| over the valid frames. */
+ *                A range that is not finite is no range: an utterance whose maxima hold an infinity or a NaN (it holds an
+ *                infinity; the caller's bound was computed from a NaN) comes back NaN as a whole, and so does the whole
+ *                launch for an x_bound that is inf or NaN -- never finite values scaled by the bits of an infinity.
+ *                (Maxima measured by this library skip a NaN element: the finite ones keep their range, the NaN carries
+ *                itself through the product.)
+ *   y_amax      optional, [N][ps_conv1x1_stats_parts(M, T)]: partial maxima of |y| over the valid frames. */
 typedef struct ps_f16x2_range {
   int w_exp;
   float x_bound;

@@ -105,13 +105,20 @@ __device__ __forceinline__ void f16_scales(const BfArgs& a, int n, int lane, flo
   if (a.x_amax) {
     float m = 0.f;
     const float* src = a.x_amax + (size_t)n * a.x_amax_parts;
-    for (int i = lane; i < a.x_amax_parts; i += 64) m = fmaxf(m, src[i]);
+    for (int i = lane; i < a.x_amax_parts; i += 64) {
+      const float v = src[i];
+      m = fmaxf(m, v == v ? v : __builtin_inff());  // (fmaxf would drop a NaN partial: it counts as an unbounded one)
+    }
     m = wave_max(m);
     if (a.amax_mul > 0.f) m = m * a.amax_mul + a.amax_add;
     // max |x| in [2^e, 2^(e+1)) goes to [2^14, 2^15) (fp16 holds up to 65504); an all-zero utterance keeps 1
     int e = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 255) - 127;
     e = e < -100 ? -100 : (e > 100 ? 100 : e);
     xs = m > 0.f ? ldexpf(1.f, 14 - e) : 1.f;
+    // A range that is inf or NaN (the utterance holds an infinity, or the caller's bound was computed from a NaN) is no
+    // range: a scale of 2^-86 would flush every finite value of the utterance to zero and return bias -- finite and
+    // wrong.  The utterance comes back NaN as a whole instead (x * NaN in the split, acc * NaN in the epilogue).
+    if (!(m < __builtin_inff())) xs = __builtin_nanf("");
   }
   os = a.winv / xs;  // (powers of two: exact)
 }
@@ -587,7 +594,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_bf16_pp_kernel(BfArgs a) {
         sq = wave_sum(sq);
         const double m = sa / a.pro.count;
         double var = sq / a.pro.count - m * m;
-        var = var > 0.0 ? var : 0.0;
+        var = var < 0.0 ? 0.0 : var;  // (a NaN variance -- the utterance holds an infinity -- stays NaN, as in torch)
         mean = (float)m;
         rstd = (float)(1.0 / sqrt(var + (double)a.pro.eps));
       }
@@ -1071,8 +1078,12 @@ static void set_range(BfArgs& a, const ps_f16x2_range& rng, bool tr) {
     x_exp = x_exp < -100 ? -100 : (x_exp > 100 ? 100 : x_exp);
   }
   a.xscale = ldexpf(1.f, x_exp);
+  // (a bound that is inf or NaN -- computed from weights that are -- bounds nothing: the launch comes back NaN, as an
+  //  utterance with a non-finite measured range does in f16_scales)
+  const bool no_bound = !(rng.x_bound < __builtin_inff());
+  if (no_bound) a.xscale = __builtin_nanf("");
   a.winv = ldexpf(1.f, -rng.w_exp);
-  a.x_amax = rng.x_bound > 0.f ? nullptr : rng.x_amax;
+  a.x_amax = (rng.x_bound > 0.f || no_bound) ? nullptr : rng.x_amax;
   a.x_amax_parts = rng.x_amax_parts;
   a.y_amax = rng.y_amax;  // [N][ps_conv1x1_stats_parts(M, T)] partial maxima of |y| (the next GEMM's input range) or NULL
   a.amax_mul = rng.amax_mul > 0.f ? rng.amax_mul : 0.f;

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x2_rb_kernel(BfArgs a) {
         sq = wave_sum(sq);
         const double m = sa / a.pro.count;
         double var = sq / a.pro.count - m * m;
-        var = var > 0.0 ? var : 0.0;
+        var = var < 0.0 ? 0.0 : var;  // (a NaN variance -- the utterance holds an infinity -- stays NaN, as in torch)
         mean = (float)m;
         rstd = (float)(1.0 / sqrt(var + (double)a.pro.eps));
       }

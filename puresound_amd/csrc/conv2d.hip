@@ -299,6 +299,7 @@ __global__ __launch_bounds__(256) void conv2d_f16x2_kernel(Conv2dF16Args fa) {
   for (int rb = 0; rb < RB; ++rb) acc[rb][0] = acc[rb][1] = f32x4{0.f, 0.f, 0.f, 0.f};
   float S = 1.0995116e12f;  // 2^40: the first chunk with a non-zero value sets the scale
   int se = 40;              // S = 2^se
+  bool bad = false;         // a chunk's range was infinite
 
   float bv[2][8];
   auto fetch = [&](int ch) {
@@ -323,6 +324,7 @@ __global__ __launch_bounds__(256) void conv2d_f16x2_kernel(Conv2dF16Args fa) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) m = fmaxf(m, fmaxf(fabsf(bv[0][e]), fabsf(bv[1][e])));
     m = wave_max(m);
+    bad |= !(m < __builtin_inff());  // (uniform) an infinity among the wave's values: see `osc` below
     {
       int ex = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 255) - 127;  // |x| < 2^(ex + 1)
       ex = ex > 100 ? 100 : ex;
@@ -364,7 +366,9 @@ __global__ __launch_bounds__(256) void conv2d_f16x2_kernel(Conv2dF16Args fa) {
     __syncthreads();
   }
 
-  const float osc = fa.winv * ldexpf(1.f, -se);
+  // An infinite range is no range: the scale it gives (2^-86) flushes the finite values of the wave's 32 frames to zero, and
+  // the frames whose own taps hold no infinity would come out as bias -- finite and wrong.  The wave's frames are NaN instead.
+  const float osc = bad ? __builtin_nanf("") : fa.winv * ldexpf(1.f, -se);
   const float s = a.slope ? a.slope[0] : 0.f;
   float fsum = 0.f, fsq = 0.f;
 #pragma unroll

@@ -92,7 +92,7 @@ __device__ __forceinline__ NormScalars load_norm_scalars(const ps_prologue& p, i
   block_sum2(a, b, red);
   const double mean = a / p.count;
   double var = b / p.count - mean * mean;
-  var = var > 0.0 ? var : 0.0;
+  var = var < 0.0 ? 0.0 : var;  // (a NaN variance -- the utterance holds an infinity -- stays NaN, as in torch)
   s.mean = (float)mean;
   s.rstd = (float)(1.0 / sqrt(var + (double)p.eps));
   return s;

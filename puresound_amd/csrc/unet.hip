@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void norm_activation_kernel(NormActArgs a) {
     sq -= a.corr_sq;
     mean = sa / a.pro.count;
     double var = sq / a.pro.count - mean * mean;
-    var = var > 0.0 ? var : 0.0;
+    var = var < 0.0 ? 0.0 : var;  // (a NaN variance -- the utterance holds an infinity -- stays NaN, as in torch)
     rstd = (float)(1.0 / sqrt(var + (double)a.pro.eps));
   }
   const int ch = row / a.rows_per_channel;

@@ -614,7 +614,12 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
     def probe_lookahead_receptive_field(self, device=None):
         """The reference's NaN-propagation probe (base_nn.py:746-772) on the HIP path: a 10 s input whose second
         (first) half is +inf; the first (last) NaN of the output gives the look-ahead (receptive field) in samples.
-        Returns (lookahead, receptive_field), each an int or the string "infinite" exactly as the reference prints."""
+        Returns (lookahead, receptive_field), each an int or the string "infinite" exactly as the reference prints.
+
+        The two inferences run in the exact-fp32 arithmetic whatever `gemm_precision` the modules have, and every module's
+        setting is put back afterwards: the probe measures the model's structure, not an arithmetic, and an arithmetic
+        that scales by a range (fp16x2) returns an utterance that holds an infinity as NaN as a whole (DESIGN.md,
+        "Non-finite input"), which would read as "infinite" for every model."""
         import numpy as np
         dev = torch.device(device) if device is not None else next(self.parameters()).device
         hip.require_device(torch.empty(0, device=dev), "probe_lookahead_receptive_field")
@@ -627,14 +632,25 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
             except (RuntimeError, NotImplementedError, TypeError):
                 return self.inference(x.to(dev)).cpu().numpy()
 
-        x = torch.rand(1, 10 * 16000, generator=g)
-        x[..., 5 * 16000:] = float("inf")
-        first = int(np.where(np.isnan(run(x)))[-1][0])
-        lookahead = "infinite" if first == 0 else 80000 - first
-        x = torch.rand(1, 10 * 16000, generator=g)
-        x[..., :-5 * 16000] = float("inf")
-        last = int(np.where(np.isnan(run(x)))[-1][-1])
-        receptive = "infinite" if last - (80000 - 1) == 80000 else last - (80000 - 1)
+        unset = object()
+        saved = [(m, m.__dict__.get("gemm_precision", unset)) for m in self.modules() if hasattr(m, "gemm_precision")]
+        try:
+            for m, _ in saved:
+                m.gemm_precision = "fp32"
+            x = torch.rand(1, 10 * 16000, generator=g)
+            x[..., 5 * 16000:] = float("inf")
+            first = int(np.where(np.isnan(run(x)))[-1][0])
+            lookahead = "infinite" if first == 0 else 80000 - first
+            x = torch.rand(1, 10 * 16000, generator=g)
+            x[..., :-5 * 16000] = float("inf")
+            last = int(np.where(np.isnan(run(x)))[-1][-1])
+            receptive = "infinite" if last - (80000 - 1) == 80000 else last - (80000 - 1)
+        finally:
+            for m, was in saved:
+                if was is unset:
+                    del m.gemm_precision
+                else:
+                    m.gemm_precision = was
         return lookahead, receptive
 
     def _verbose(self):

@@ -58,11 +58,14 @@ class FreeEncDec(PlanCache, nn.Module):
         return float(self.encoder.weight.detach().abs().sum(dim=(1, 2)).max())
 
     def feature_bound(self, x: torch.Tensor) -> torch.Tensor:
-        """[N,L] -> [N,1]: an upper bound on |forward(x)[n]|: max |x[n]| times the largest row sum of |w| (the ReLU only
-        shrinks).  Consumers that scale their input into a narrow exponent range (the fp16x2 GEMMs) take it instead of
-        measuring the features."""
+        """[N,L] -> [N,1]: an upper bound on |forward(x)[n]|: max |x[n]| over the samples the frames cover, times the
+        largest row sum of |w| (the ReLU only shrinks).  Consumers that scale their input into a narrow exponent range (the
+        fp16x2 GEMMs) take it instead of measuring the features.  A NaN or an infinity among those samples makes the
+        bound NaN / inf, and such a consumer returns that utterance as NaN ("Non-finite input"); the tail
+        samples that no frame reaches (L - win not a multiple of hop) cannot reach a feature and do not count."""
         l1 = self._plan_get(x.device, self._build)
-        return torch.linalg.vector_norm(x.detach().float(), ord=float("inf"), dim=1, keepdim=True) * l1
+        covered = (x.shape[1] - self.win_length) // self.hop_length * self.hop_length + self.win_length
+        return torch.linalg.vector_norm(x.detach().float()[:, :covered], ord=float("inf"), dim=1, keepdim=True) * l1
 
     def decode_padded(self, feats_pad: torch.Tensor, t: int, mask_pad: Optional[torch.Tensor] = None,
                       mask_act: str = "linear", out_mode: str = "none",
