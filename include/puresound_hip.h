@@ -603,7 +603,7 @@ int ps_istft_step_f32(const float* frames, int ldf, const float* window, float* 
                       const int* counter, int B, int n_fft, int hop, int out_mode, int flush, void* stream);
 int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs, int* counter, void* stream);
 
-/* Slots for the conv-STFT streamers (puresound_amd/streaming/unet_tcn.py): streams that begin and end on their own while the
+/* Slots for the conv-STFT streamers (puresound_amd/streaming/unet_tcn.py, spectral.py): streams that begin and end on their own while the
  * session runs.  span [B][2] (device int, 8-byte aligned) is the (birth, death) of ps_dwconv_step_slots_f32 below: frame g of
  * stream b is LIVE iff span[b][0] <= g < span[b][1], an idle column has an empty span, and a column may hold anything while
  * it is not live (inf / NaN included): every gate is a select, never a product.  A NULL or misaligned span, a NULL counter
@@ -621,7 +621,25 @@ int ps_stream_commit_f32(const ps_ring_pair* pairs_host, int n_pairs, int* count
  *   after its death with the normalisation its flush would use, an idle column emits constrain(0).  flush = 1: n_fft - hop
  *   samples from the tail at base u_b*hop, frames up to T_b - 1, the tail left as it is; a session flushes one stream with
  *   B = 1 on that stream's tail row and span row.  With span = (0, INT32_MAX) and shift = 0, step and flush are
- *   bit-identical to ps_istft_step_f32. */
+ *   bit-identical to ps_istft_step_f32.
+ * ps_state_gate_slots_f32: the span rule for a CARRIED state (puresound_amd/streaming/spectral.py: the inter-LSTM's h / c,
+ *   the one tensor of DPCRN / DPARN that remembers earlier frames outside a ring).  For each of the n_states <=
+ *   PS_MAX_RING_PAIRS entries of the HOST array states_host (copied into the kernel arguments) and each stream b < B:
+ *   x[r][b] = 0.0f for every r < rows unless frame g = *counter - shift is live in stream b (x [rows][ld], 16-byte aligned,
+ *   ld % 4 == 0, ld >= B).  A state read at frame t is "the tensor at frame t - 1": launched with shift = 1 before the hop's
+ *   first reader, a stream reads zeros at its birth, as offline, and through the hops between open() and its birth.  A store
+ *   of zeros under a select, never a product, and x is never read: a dead column that held inf / NaN holds 0 afterwards.
+ *   Live columns and the pad columns b >= B are neither read nor written; with every stream live the launch reads the span
+ *   and writes nothing.  g is formed from *counter >= 0 and shift >= 0 without a product (no int overflow).  It only reads
+ *   the counter -- the commit that advances it is another launch.  NULL states_host, n_states outside 1 ..
+ *   PS_MAX_RING_PAIRS, a NULL or misaligned x, rows <= 0, B <= 0, ld < B or ld % 4 is PS_E_INVALID before any launch, as
+ *   are the span / counter / shift refusals above. */
+typedef struct ps_state_rows {
+  float* x;
+  int64_t rows;
+} ps_state_rows;
+int ps_state_gate_slots_f32(const ps_state_rows* states_host, int n_states, const int* counter, const int* span, int shift,
+                            int B, int ld, void* stream);
 int ps_conv2d_step_slots_f32(const float* x1, const float* ring1, int C1, int R1, const float* x2, const float* ring2, int C2,
                              int R2, const float* wt, const float* bias, float* y, int M, int Fin, int B, int ld, int kf, int kt,
                              int stride_f, int dil_f, int dil_t, int pad_f, int Fout, int transposed, int act,

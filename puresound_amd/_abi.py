@@ -83,6 +83,10 @@ class RingPair(C.Structure):
     _fields_ = [("src", _vp), ("ring", _vp), ("count", C.c_int64), ("slots", C.c_int), ("reserved", C.c_int)]
 
 
+class StateRows(C.Structure):
+    _fields_ = [("x", _vp), ("rows", C.c_int64)]
+
+
 class DprnnPass(C.Structure):
     _fields_ = [(k, _vp) for k in ("wt", "bias", "pt", "pbias", "gamma", "beta")] + [("eps", C.c_float), ("reserved", C.c_int)]
 
@@ -197,6 +201,7 @@ SIGNATURES = {
     "ps_conv2d_step_slots_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]
                                  + [C.c_int] * 13 + [_vp, _vp, _vp, C.c_int, _vp]),
     "ps_istft_step_slots_f32": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp] + [C.c_int] * 6 + [_vp]),
+    "ps_state_gate_slots_f32": (C.c_int, [C.POINTER(StateRows), C.c_int, _vp, _vp] + [C.c_int] * 3 + [_vp]),
     "ps_dwconv_step_f32": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp] + [C.c_int] * 6 + [C.POINTER(Prologue), _vp]),
     "ps_free_decode_step_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "ps_free_decode_step_f32": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp] + [C.c_int] * 8 + [_vp, C.c_size_t, _vp]),

@@ -8,6 +8,7 @@
 // ps_istft_step_f32   synthesis of one frame per stream (window, / n_fft, overlap-add into the tail, / window sum)
 // ps_stream_commit_f32   the history commit behind every hop: rings shift by one frame, the counter advances
 // ps_stream_commit_frames_f32   the same commit with the counter advanced by k frames (the Conv-TasNet streamer's chunk)
+// ps_state_gate_slots_f32   a slot session's carried states (the inter-LSTM's h / c) read through the span: dead columns <- 0
 #include "ps_common.h"
 
 namespace ps {
@@ -289,6 +290,52 @@ __global__ __launch_bounds__(256) void stream_commit_kernel(CommitTable tab, int
   *reinterpret_cast<f32x4*>(q.ring + (size_t)(q.slots - 1) * q.count + i) = *reinterpret_cast<const f32x4*>(q.src + i);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// ps_state_gate_slots_f32.  The span rule for a carried state x [rows][ld] (column = stream): column b of every row becomes
+// an exact 0 unless frame g = *counter - shift is live in stream b.  A launch of its own, on the read side: the commit
+// advances *counter from one thread while its other workgroups copy, so nothing in that launch may read it.
+//
+// A lane owns four neighbouring columns, a wave a strip of 256 columns: grid (chunks of kGateRows rows, strips, states), the
+// four waves of a workgroup take every fourth row of the chunk.  The lane reads its columns' span once, before the row loop,
+// and leaves when none of them is dead -- with every stream live the launch is those reads and no store.  Four dead columns
+// are one 16-byte store, fewer (or a lane that straddles B: the pad columns are not written) scalar stores.  x is never read.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kGateRows = 256;
+
+struct StateGateTable {
+  ps_state_rows s[PS_MAX_RING_PAIRS];
+};
+
+__global__ __launch_bounds__(256) void state_gate_kernel(StateGateTable tab, const int* __restrict__ counter,
+                                                         const int* __restrict__ span, int shift, int B, int ld) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c0 = (blockIdx.y * 64 + lane) * 4;
+  if (c0 >= B) return;
+  const int g = *counter - shift;  // both >= 0: no overflow
+  unsigned dead = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (c0 + j < B) {
+      const int2 sp = reinterpret_cast<const int2*>(span)[c0 + j];
+      if (!(sp.x <= g && g < sp.y)) dead |= 1u << j;
+    }
+  }
+  if (!dead) return;
+  const ps_state_rows& q = tab.s[blockIdx.z];
+  const int64_t r0 = (int64_t)blockIdx.x * kGateRows;
+  const int64_t r1 = r0 + kGateRows < q.rows ? r0 + kGateRows : q.rows;
+  for (int64_t r = r0 + wave; r < r1; r += 4) {
+    float* p = q.x + (size_t)r * ld + c0;
+    if (dead == 0xfu) {
+      *reinterpret_cast<f32x4*>(p) = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (dead >> j & 1u) p[j] = 0.f;
+    }
+  }
+}
+
 }  // namespace ps
 
 using namespace ps;
@@ -412,7 +459,46 @@ extern "C" int ps_istft_step_slots_f32(const float* frames, int ldf, const float
                            n_fft, hop, out_mode, flush, stream);
 }
 
-static int stream_commit(const char* who, const ps_ring_pair* pairs_host, int n_pairs, int* counter, int advance,
+extern "C" int ps_state_gate_slots_f32(const ps_state_rows* states_host, int n_states, const int* counter, const int* span,
+                                       int shift, int B, int ld, void* stream) {
+  const char* who = "ps_state_gate_slots_f32";
+  if (!states_host || n_states <= 0 || n_states > PS_MAX_RING_PAIRS) {
+    set_error("%s: 1 .. %d states (got %d)", who, PS_MAX_RING_PAIRS, n_states);
+    return PS_E_INVALID;
+  }
+  if (B <= 0 || ld < B || ld % 4) {
+    set_error("%s: bad argument (B=%d ld=%d: B >= 1, ld >= B, ld a multiple of 4)", who, B, ld);
+    return PS_E_INVALID;
+  }
+  if (!span_ok(who, span)) return PS_E_INVALID;
+  if (!counter || shift < 0) {
+    set_error("%s: counter (device int) is required and shift >= 0 (got %d)", who, shift);
+    return PS_E_INVALID;
+  }
+  StateGateTable tab{};
+  int64_t most = 0;
+  for (int p = 0; p < n_states; ++p) {
+    const ps_state_rows& q = states_host[p];
+    if (!q.x || ((uintptr_t)q.x & 15) || q.rows <= 0 || q.rows > ((int64_t)1 << 40)) {
+      set_error("%s: state %d: a 16-byte aligned x and rows >= 1 (got %lld)", who, p, (long long)q.rows);
+      return PS_E_INVALID;
+    }
+    tab.s[p] = q;
+    if (q.rows > most) most = q.rows;
+  }
+  const int64_t chunks = (most + kGateRows - 1) / kGateRows;
+  const int strips = (B + 255) / 256;
+  if (chunks > 0x7fffffffLL || strips > 65535) {
+    set_error("%s: state too large", who);
+    return PS_E_INVALID;
+  }
+  LaunchTimer timer("state_gate_slots", (hipStream_t)stream);
+  hipLaunchKernelGGL(state_gate_kernel, dim3((unsigned)chunks, (unsigned)strips, (unsigned)n_states), dim3(256), 0,
+                     (hipStream_t)stream, tab, counter, span, shift, B, ld);
+  return launch_status(who);
+}
+
+static int stream_commit(const char* who,const ps_ring_pair* pairs_host, int n_pairs, int* counter, int advance,
                          void* stream) {
   if (!pairs_host || n_pairs <= 0 || n_pairs > PS_MAX_RING_PAIRS) {
     set_error("%s: 1 .. %d pairs (got %d)", who, PS_MAX_RING_PAIRS, n_pairs);

@@ -14,8 +14,8 @@ from typing import Optional, Sequence
 import torch
 
 from . import _abi
-from ._abi import (F16x2Range, LstmArgs, Prologue, RingPair, TcnBlock, check, lib, padded_frames, ptr, require_device,
-                   require_weight, stream_ptr)
+from ._abi import (F16x2Range, LstmArgs, Prologue, RingPair, StateRows, TcnBlock, check, lib, padded_frames, ptr,
+                   require_device, require_weight, stream_ptr)
 
 
 def pack_wt(w: torch.Tensor) -> torch.Tensor:
@@ -1061,6 +1061,29 @@ def stream_commit_frames(table: "C.Array[RingPair]", counter: torch.Tensor, fram
     """ps_stream_commit_f32 with the frame counter advanced by `frames` (ps_stream_commit_frames_f32)."""
     check(lib().ps_stream_commit_frames_f32(table, len(table), ptr(counter), int(frames), stream_ptr(device)),
           "ps_stream_commit_frames_f32")
+
+
+def state_gate(states: Sequence[torch.Tensor], counter: torch.Tensor, span: torch.Tensor, b: int, shift: int = 1,
+               ld: Optional[int] = None) -> None:
+    """The span rule for carried states (ps_state_gate_slots_f32): every tensor of `states` is contiguous rows of ld columns
+    (ld = padded_frames(b) unless given; [1, H, F * ld] is H * F rows) with the b streams as the first b columns of a row;
+    column i of every row becomes an exact 0 unless frame counter[0] - shift is live in stream i (span int32 [b, 2]).  Live
+    columns and the pad columns b..ld are left as they are, nothing is read."""
+    if not 0 < len(states) <= _abi.PS_MAX_RING_PAIRS:
+        raise RuntimeError(f"state_gate: 1 .. {_abi.PS_MAX_RING_PAIRS} states")
+    first = states[0]
+    require_device(first, "state_gate")
+    ld = padded_frames(int(b)) if ld is None else int(ld)
+    tab = (StateRows * len(states))()
+    for e, x in zip(tab, states):
+        if x.dtype != torch.float32 or not x.is_contiguous() or ld <= 0 or x.numel() % ld or x.device != first.device:
+            raise RuntimeError(f"state_gate: contiguous fp32 states of whole rows of ld = {ld} columns on one device expected")
+        e.x, e.rows = ptr(x), x.numel() // ld
+    _check_span(span, b, first, "state_gate")
+    if counter is None or counter.dtype != torch.int32 or counter.device != first.device:
+        raise RuntimeError("state_gate: the int32 frame counter on the states' device expected")
+    check(lib().ps_state_gate_slots_f32(tab, len(tab), ptr(counter), ptr(span), int(shift), int(b), ld,
+                                        stream_ptr(first.device)), "ps_state_gate_slots_f32")
 
 
 def _check_span(span: torch.Tensor, streams: int, like: torch.Tensor, who: str) -> None:

@@ -17,7 +17,7 @@ state and leaves the overlap-add tail, the window sum and its synthesis counter 
 latency_samples grow by D hops, and flush() first lets the streamer run the hops that are still inside the model (the
 streamer's `_flush_into(out)` fills min(frames, D) * hop + window - hop samples).  D = 0: nothing of this happens.
 
-Slots (tcn.py, dprnn.py, skim.py): a session of fixed capacity whose columns begin and end streams of their own while it runs.  The
+Slots (all five streamers): a session of fixed capacity whose columns begin and end streams of their own while it runs.  The
 model-independent half lives here: the device span [B, 2] of (birth, death) frame indices and the host record per slot, the
 slot checks, open / end / close, the hops each slot was fed, the frame limit, and the rules that a slot session has no
 priming phase and no flush().  A streamer with slots calls `_begin` and then `_make_slots` in its init_slots, passes
@@ -31,7 +31,8 @@ delay is not part of the birth, the model's state is live from that frame on -- 
 streamer's kernels read every tensor with the shift of its layer, so a frame is live or dead by its own index.  The D hops
 of the session after a slot's last input hop carry its last frames out (the slot's input in those hops is ignored);
 close() before they were stepped raises, as does close() without an earlier end(): end(slot, 0), D hops, close(slot).  The
-tail is flushed per slot through `_flush_slot(out, slot)`, by default `_flush_into(out, tail row)`.
+tail is flushed per slot through `_flush_slot(out, slot)`, by default `_flush_into(out, tail row)`.  spectral.py is the same
+rule with delay_frames = 0; its carried LSTM states are read through the span too (ps_state_gate_slots_f32).
 """
 import contextlib
 from typing import Dict, List, Optional

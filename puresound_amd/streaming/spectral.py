@@ -20,6 +20,22 @@ plans and swaps them into the masker's modules only while it builds or runs a ho
 are left as they were.
 The session around the kernels (priming, step / step_chunk / flush, eager run or graph replay, the capture) is HopSession's:
 streaming/_session.py.
+
+Slots (init_slots / open / end / close, HopSession's): streams that join and leave a running session, with StreamingUnetTcn's
+one rule and no new state: frame g of a tensor is read as an exact 0 for stream b unless birth_b <= g < death_b.  The down
+path, the up path and the synthesis are the *_slots_f32 kernels (ps_conv2d_step_slots_f32, ps_istft_step_slots_f32) with the
+session's span [B, 2], the one counter and shift 0: the model has no delay, a stream's last frame leaves with its last input
+hop and close() may follow it directly.  The one tensor that remembers earlier frames outside a ring is the carried state of
+the inter LSTM: the state a stream reads at frame t is "the tensor at frame t - 1", so ps_state_gate_slots_f32 (one launch at
+the top of each hop, shift 1, all four states of both blocks) stores zeros into the columns whose frame t - 1 is dead -- zeros
+at a stream's birth, as offline, and through the n_fft / hop - 1 hops between open() and the birth, in which the LSTM steps
+on dead frames (a convolution of zeros plus its bias is not zero).  The gate is on the read side, not in the commit: the
+commit advances the counter from one thread while its other workgroups copy, so nothing in that launch may read it.  So a
+slot session has no priming and no flushing pass, open() clears nothing on the device but the slot's window queue and tail
+row, and step() returns [capacity, hop] from the first hop on.  The intra passes work inside one frame of one stream and
+need nothing.  A slot's samples are the bits of row `slot` of an init_streams(capacity) session fed its stream from frame
+0: the reused GEMM and recurrence kernels pick their tiling from the column count, so the identity holds at the session's
+width.
 """
 import contextlib
 from typing import List
@@ -93,6 +109,10 @@ class StreamingSeparator(HopSession):
 
     s = StreamingSeparator(model); s.init_streams(B); s.step(hop [B, hop]) -> [B, hop] or None while the analysis window
     fills; s.step_chunk([B, k*hop]) -> what k step() calls return, concatenated; s.flush() -> the last n_fft - hop samples.
+
+    Streams that join and leave: s.init_slots(capacity); s.open(slot); s.step / s.step_chunk([capacity, k*hop]) ->
+    [capacity, k*hop] from the first hop on (an idle slot: constrain(0), whatever its input row holds); s.end(slot, hops)
+    when the stream has `hops` more hops of input; s.close(slot) -> the last n_fft - hop samples.
     """
 
     def __init__(self, model: SoTaskWrapModule):
@@ -143,10 +163,33 @@ class StreamingSeparator(HopSession):
         """Start `streams` new streams (every state zeroed)."""
         if int(streams) < 1:
             raise ValueError("init_streams: streams >= 1")
-        m = self.model.masker
         dev = next(self.model.parameters()).device
         b = int(streams)
         self._begin(b, dev, use_graph)
+        self._allocate(b, dev)
+
+    @torch.no_grad()
+    def init_slots(self, capacity: int, use_graph: bool = True) -> None:
+        """Start a slot session of `capacity` columns, every slot idle (every state zeroed); open() starts a stream."""
+        if int(capacity) < 1:
+            raise ValueError("init_slots: capacity >= 1")
+        b, dev = int(capacity), next(self.model.parameters()).device
+        self._begin(b, dev, use_graph)
+        self._make_slots()
+        self._ready()
+        self._allocate(b, dev)
+
+    def _enrolment_rule(self) -> tuple:
+        return False, "iff the model has a speaker_net (a noise suppressor has none: pass no enroll)"
+
+    def _open_slot(self, slot: int, seed) -> None:
+        """Nothing is reset or cleared: what the slot's predecessor left in the rings and the carried states are dead frames,
+        which the kernels read as zeros through the span."""
+        self._ready()
+
+    def _allocate(self, b: int, dev: torch.device) -> None:
+        """Geometry of every convolution (unet.py:219-281), the frame buffers, the rings and the carried LSTM states."""
+        m = self.model.masker
         self._ldb = ldb = hip.padded_frames(b)
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
         n = m.n_cnn
@@ -207,12 +250,14 @@ class StreamingSeparator(HopSession):
         """[1, rows, ldB] features -> ([1, rows, ldB] mask, {tensor name: this frame}) through the U-Net and the two
         bottleneck blocks."""
         m, b, pk = self.model.masker, self.streams, self._packs
+        # a slot session: every tensor of this hop is frame counter - 0, a tap reads it through the span
+        live = {} if self._span is None else dict(counter=self._counter, span=self._span, shift=0)
         cur = dict(self._cur)
         cur["in"] = feats.view(self._in_shape)
         for i, (c, lay) in enumerate(zip(self._down, pk["down"])):
             hip.conv2d_step(cur[c["src"]], self._rings[c["src"]], None, None, lay["wt"], lay["bias"], lay["M"], b, c["f_out"],
                             c["kf"], c["kt"], c["sf"], c["df"], c["dt"], c["pf"], False, lay["act"], lay["slope"],
-                            out=cur[f"d{i}"])
+                            out=cur[f"d{i}"], **live)
         y = cur[f"d{m.n_cnn - 1}"]
         for blk, (h0, c0, h1, c1) in zip((m.dprnn_block1, m.dprnn_block2), self._lstm):
             y = blk.forward_step(y, b, h0, c0, (h1, c1))
@@ -220,7 +265,7 @@ class StreamingSeparator(HopSession):
         for j, (c, lay) in enumerate(zip(self._up, pk["up"])):
             hip.conv2d_step(cur[c["src"]], self._rings[c["src"]], cur[c["skip"]], self._rings[c["skip"]], lay["wt"],
                             lay["bias"], lay["M"], b, c["f_out"], c["kf"], c["kt"], c["sf"], c["df"], c["dt"], c["pf"], True,
-                            lay["act"], lay["slope"], out=self._upout[j])
+                            lay["act"], lay["slope"], out=self._upout[j], **live)
         return self._upout[-1].view(1, -1, self._ldb), cur
 
     def _body(self, hops: int) -> None:
@@ -232,12 +277,19 @@ class StreamingSeparator(HopSession):
             frames, _ = hip.frame(wins[i:i + 1], self.n_fft, self.n_fft)               # [1, n_fft, ldB]: streams = frames
             feats, _ = hip.conv1x1(frames, b, pk["wt_a"], pk["rows"],
                                    out=torch.empty(1, pk["rows"], self._ldb, dtype=torch.float32, device=self.device))
+            if self._span is not None:     # the carried states are frame counter - 1: zeros where that frame is dead
+                hip.state_gate([t for h0, c0, _, _ in self._lstm for t in (h0, c0)], self._counter, self._span, b, shift=1)
             mask, cur = self._masker_step(feats)
             enh = (hip.complex_mask(feats, mask, self._mask_act) if self._pairing == "complex"
                    else hip.real_mask(feats, mask, self._mask_act))
             syn, _ = hip.conv1x1(enh, b, pk["wt_s"], self.n_fft,
                                  out=torch.empty(1, self.n_fft, self._ldb, dtype=torch.float32, device=self.device))
-            hip.istft_step(syn, pk["window"], self._tail, out[:, i * hop:(i + 1) * hop], self._counter, hop, self._out_mode)
+            if self._span is not None:
+                hip.istft_step(syn, pk["window"], self._tail, out[:, i * hop:(i + 1) * hop], self._counter, hop,
+                               self._out_mode, span=self._span, shift=0)
+            else:
+                hip.istft_step(syn, pk["window"], self._tail, out[:, i * hop:(i + 1) * hop], self._counter, hop,
+                               self._out_mode)
             pairs = [(cur[k], r) for k, r in self._rings.items() if r is not None]
             pairs += [(h1, h0) for h0, _, h1, _ in self._lstm] + [(c1, c0) for _, c0, _, c1 in self._lstm]
             if i == hops - 1:
@@ -246,3 +298,8 @@ class StreamingSeparator(HopSession):
 
     def _flush_into(self, out: torch.Tensor) -> None:
         hip.istft_step(None, self._packs["window"], self._tail, out, self._counter, self.hop_length, self._out_mode, flush=True)
+
+    def _flush_slot(self, out: torch.Tensor, slot: int) -> None:
+        """close(): the tail of one slot, with the window sum of its own frames (B = 1 on its tail row and span row)."""
+        hip.istft_step(None, self._packs["window"], self._tail[slot:slot + 1], out, self._counter, self.hop_length,
+                       self._out_mode, flush=True, span=self._span[slot:slot + 1], shift=0)
