@@ -1053,6 +1053,33 @@ int ps_conv_tasnet_ragged_f32(const ps_tcn_block* blocks, int n_blocks, const fl
                               int embed_norm, int N, int T, int ldt, const int* t_rows, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batches of utterances of unequal length through the DPCRN / DPARN noise suppressors behind the conv-STFT encoder
+ * (csrc/conv2d.hip, csrc/stft.hip).  Rows and t_rows as above: row n holds T_n = clamp(t_rows[n], 0, T) valid frames and
+ * ANYTHING behind them, a NaN included.  In these models frames meet each other in the time taps of the 2-D convolutions
+ * (down layers read kt - delay - 1 frames back and `delay` ahead, transpose_delay up layers one frame ahead, in both
+ * sources) and in the iSTFT's overlap-add with its per-sample window sum: these two entries stand there.  The analysis and
+ * synthesis GEMMs, the complex mask, the intra pass along frequency, the LayerNorms and the forward inter LSTM work column
+ * by column or forward in time and run as they are over all T frames; behind the first down layer every frame >= T_n is an
+ * exact zero, so they see finite values only.
+ *
+ * ps_conv2d_ragged_f32: ps_conv2d_f32 (same argument rules, routes and summation order; no statistics form) with t_rows in
+ *   place of T_in.  For row n, on frames t < T_n: what ps_conv2d_f32 writes for that row alone with T_in = T = T_n, bit for
+ *   bit; a tap on an input frame outside [0, T_n) reads as 0 by a select, never a product, in x1 and x2 alike.
+ *   y[n][m][fo][t] = 0.0 for T_n <= t < ld.  A workgroup whose frame tile (128 frames of the implicit GEMM, 512 of the
+ *   row-block kernel for M <= 4) lies at or behind T_n stores zeros and loads nothing.
+ * ps_istft_ola_ragged_f32: ps_istft_ola_f32 with t_rows.  out [N][(T-1)*hop + n_fft]; row n's samples
+ *   g < (T_n - 1) * hop + n_fft sum the frames t <= min(g / hop, T_n - 1) in numerator and window sum (ps_istft_ola_f32
+ *   with T = T_n, bit for bit), the samples behind them are exact 0.0, written after the output constraint (in
+ *   PS_OUT_SIGMOID too); frames >= T_n are never loaded; T_n = 0 gives a zero row.
+ * ------------------------------------------------------------------------------------------- */
+int ps_conv2d_ragged_f32(const float* x1, int C1, const float* x2, int C2, const float* wt, const float* bias, float* y,
+                         int N, int M, int Fin, const int* t_rows, int T, int ld, int kf, int kt, int stride_f, int dil_f,
+                         int dil_t, int pad_f, int pad_t, int Fout, int transposed, int act, const float* slope,
+                         void* stream);
+int ps_istft_ola_ragged_f32(const float* frames, const float* window, float* out, const int* t_rows, int N, int n_fft,
+                            int hop, int T, int ldt, int out_mode, void* stream);
+
 /* Five moments of an (estimate, reference) waveform pair per row -- sum a, sum b, sum a^2, sum b^2, sum ab over L
  * samples, fp64 -- as per-workgroup partials [N][ps_wave_moments_chunks(L)][5] (the caller adds them up).  Every
  * SDR / SI-SNR variant of the reference's SDRLoss.forward (puresound/nnet/loss/sdr.py:104-183), si_snr (:263-299) and

@@ -267,6 +267,9 @@ SIGNATURES = {
     "ps_align_rows_f32": (C.c_int, [_vp] * 4 + [C.c_int] * 4 + [_vp]),
     "ps_conv_tasnet_ragged_f32": (C.c_int, [C.POINTER(TcnBlock), C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
                                             C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "ps_conv2d_ragged_f32": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp] + [C.c_int] * 3 + [_vp] + [C.c_int] * 12
+                             + [_vp, _vp]),
+    "ps_istft_ola_ragged_f32": (C.c_int, [_vp] * 4 + [C.c_int] * 6 + [_vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -90,8 +90,12 @@ __device__ __forceinline__ void c2d_block(int& bx, int& fo, int& bz) {
   }
 }
 
-template <int MB>
-__global__ __launch_bounds__(256) void conv2d_lds_kernel(Conv2dArgs a) {
+// RAGGED (ps_conv2d_ragged_f32): row n holds T_n = clamp(t_rows[n], 0, T) frames and anything behind them; T_n stands where
+// T_in and T stand otherwise (a tap outside [0, T_n) is a zero by the select below, y is 0.0 on [T_n, ld)), and a frame tile
+// at or behind T_n stores its zeros before anything is loaded.  No statistics.  A compile-time switch (t_rows is the one
+// Extra argument): the instantiations without it are the kernels they were.
+template <int MB, bool RAGGED = false, typename... Extra>
+__global__ __launch_bounds__(256) void conv2d_lds_kernel(Conv2dArgs a, Extra... extra) {
   constexpr int AS = 32 * MB + (MB > 1 ? 32 : 0);  // floats per k row: rows k, k + 1 (the two half-waves) 32 banks apart
   extern __shared__ int c2d_tab[];
   __shared__ int nk_s;
@@ -107,6 +111,19 @@ __global__ __launch_bounds__(256) void conv2d_lds_kernel(Conv2dArgs a) {
   const int t0 = bx * 128;
   const int mtiles = (a.M + 32 * MB - 1) / (32 * MB);
   const int n = bz / mtiles, m0 = (bz % mtiles) * 32 * MB;
+  int Tn = 0;
+  if constexpr (RAGGED) {
+    const int* const ex[] = {extra...};  // t_rows [N]
+    const int tn = ex[0][n];
+    Tn = tn < 0 ? 0 : tn > a.T ? a.T : tn;
+    if (t0 >= Tn) {  // (uniform in the workgroup, before the first barrier)
+      for (int i = tid; i < 32 * MB * 128; i += 256) {
+        const int m = m0 + (i >> 7), t = t0 + (i & 127);
+        if (m < a.M && t < a.ld) a.y[(((size_t)n * a.M + m) * a.Fout + fo) * a.ld + t] = 0.f;
+      }
+      return;
+    }
+  }
 
   if (w == 0) {
     int count = 0;
@@ -162,7 +179,7 @@ __global__ __launch_bounds__(256) void conv2d_lds_kernel(Conv2dArgs a) {
       const int k = 2 * (bi * C2D_UN + u) + lk;
       const int off = tab_off[k];
       const int ti = tcol + tab_shift[k];
-      const bool ok = off >= 0 && ti >= 0 && ti < a.Tin;
+      const bool ok = off >= 0 && ti >= 0 && ti < (RAGGED ? Tn : a.Tin);
       const float* src = (off & (1 << 30)) ? x2n : x1n;
       const int idx = ok ? (off & ((1 << 30) - 1)) + ti : 0;
       const float v = src[idx];  // unconditional load of a valid address, masked afterwards
@@ -206,13 +223,13 @@ __global__ __launch_bounds__(256) void conv2d_lds_kernel(Conv2dArgs a) {
         const int m = m0 + 32 * mb + (r & 3) + 8 * (r >> 2) + 4 * lk;
         if (m < a.M) {
           float v = acc[mb][r] + (a.bias ? a.bias[m] : 0.f);
-          if (tcol < a.T) fsum += v, fsq += v * v;  // (statistics of the pre-activation output: the gLN that follows)
+          if (tcol < (RAGGED ? Tn : a.T)) fsum += v, fsq += v * v;  // (statistics of the pre-activation output: the gLN that follows)
           v = act_apply(v, a.act, s);
-          a.y[(((size_t)n * a.M + m) * a.Fout + fo) * a.ld + tcol] = tcol < a.T ? v : 0.f;
+          a.y[(((size_t)n * a.M + m) * a.Fout + fo) * a.ld + tcol] = tcol < (RAGGED ? Tn : a.T) ? v : 0.f;
         }
       }
   }
-  if (a.stats) {  // one partial per workgroup, in the workgroup's own slot: deterministic
+  if (!RAGGED && a.stats) {  // one partial per workgroup, in the workgroup's own slot: deterministic
     __shared__ double red[2][4];
     const double ws = wave_sum((double)fsum), wq = wave_sum((double)fsq);
     __syncthreads();
@@ -414,8 +431,9 @@ __global__ __launch_bounds__(256) void conv2d_f16x2_kernel(Conv2dF16Args fa) {
 // the results differ from it in the last bits only.
 constexpr int C2D_R = 8;
 
-template <int MM>
-__global__ __launch_bounds__(256) void conv2d_rows_kernel(Conv2dArgs a, int span, int nent) {
+// RAGGED: as in conv2d_lds_kernel; a workgroup's 512 frames at or behind T_n are stored as zeros before the table is built.
+template <int MM, bool RAGGED = false, typename... Extra>
+__global__ __launch_bounds__(256) void conv2d_rows_kernel(Conv2dArgs a, int span, int nent, Extra... extra) {
   extern __shared__ int c2d_tab[];
   int* const ent_off = c2d_tab;           // element offset of the input row (bit 30: second source), -1: outside the input
   int* const ent_shift = c2d_tab + nent;  // frame shift of the tap
@@ -423,6 +441,21 @@ __global__ __launch_bounds__(256) void conv2d_rows_kernel(Conv2dArgs a, int span
   constexpr int W4 = C2D_R * MM / 4;
   const int tid = threadIdx.x;
   const int fo0 = blockIdx.y * C2D_R, n = blockIdx.z;
+  int Tn = 0;
+  if constexpr (RAGGED) {
+    const int* const ex[] = {extra...};  // t_rows [N]
+    const int tn = ex[0][n];
+    Tn = tn < 0 ? 0 : tn > a.T ? a.T : tn;
+    const int tb0 = (int)blockIdx.x * 512;
+    if (tb0 >= Tn) {  // (uniform in the workgroup, before the first barrier)
+      for (int r = 0; r < C2D_R && fo0 + r < a.Fout; ++r)
+        for (int m = 0; m < a.M; ++m) {
+          float* row = a.y + (((size_t)n * a.M + m) * a.Fout + fo0 + r) * a.ld;
+          for (int t = tb0 + tid; t < tb0 + 512 && t < a.ld; t += 256) row[t] = 0.f;
+        }
+      return;
+    }
+  }
   int fi_lo;
   if (!a.transposed) {
     fi_lo = fo0 * a.sf - a.pf;
@@ -476,7 +509,7 @@ __global__ __launch_bounds__(256) void conv2d_rows_kernel(Conv2dArgs a, int span
       const float* src = (off & (1 << 30)) ? x2n : x1n;
       const int o = off & ((1 << 30) - 1);
       const int ia = ta + sh, ib = tb + sh;
-      const bool oka = off >= 0 && ia >= 0 && ia < a.Tin, okb = off >= 0 && ib >= 0 && ib < a.Tin;
+      const bool oka = off >= 0 && ia >= 0 && ia < (RAGGED ? Tn : a.Tin), okb = off >= 0 && ib >= 0 && ib < (RAGGED ? Tn : a.Tin);
       const float xa = src[oka ? o + ia : 0], xb = src[okb ? o + ib : 0];
       va[u] = oka ? xa : 0.f;
       vb[u] = okb ? xb : 0.f;
@@ -505,12 +538,13 @@ __global__ __launch_bounds__(256) void conv2d_rows_kernel(Conv2dArgs a, int span
         if (m < a.M) {
           const float b = a.bias ? a.bias[m] : 0.f;
           float* row = a.y + (((size_t)n * a.M + m) * a.Fout + fo) * a.ld;
-          if (ta < a.ld) row[ta] = ta < a.T ? act_apply(acc0[r * MM + m] + b, a.act, s) : 0.f;
-          if (tb < a.ld) row[tb] = tb < a.T ? act_apply(acc1[r * MM + m] + b, a.act, s) : 0.f;
+          if (ta < a.ld) row[ta] = ta < (RAGGED ? Tn : a.T) ? act_apply(acc0[r * MM + m] + b, a.act, s) : 0.f;
+          if (tb < a.ld) row[tb] = tb < (RAGGED ? Tn : a.T) ? act_apply(acc1[r * MM + m] + b, a.act, s) : 0.f;
         }
     }
   }
 }
+
 
 }  // namespace ps
 
@@ -569,7 +603,9 @@ static void with_mb(int mb, F&& f) {
 
 // The fp32 entries: the row-block kernel for <= 4 output channels when its table fits (span = input rows feeding 8 output
 // rows), otherwise the implicit GEMM.
-static int conv2d_launch(const Conv2dArgs& a, int N, hipStream_t stream) {
+// t_rows: NULL, or the per-row frame limits of ps_conv2d_ragged_f32 (the same routes, their RAGGED instantiations).
+static int conv2d_launch(const Conv2dArgs& a, int N, hipStream_t stream, const int* t_rows = nullptr) {
+  const char* who = t_rows ? "ps_conv2d_ragged_f32" : "ps_conv2d_f32";
   LaunchTimer timer("conv2d", stream);
   const int span = a.transposed ? ((C2D_R - 1) + (a.kf - 1) * a.df) / a.sf + 2 : (C2D_R - 1) * a.sf + (a.kf - 1) * a.df + 1;
   const long long nent = (long long)(a.C1 + a.C2) * span * a.kt;
@@ -582,18 +618,31 @@ static int conv2d_launch(const Conv2dArgs& a, int N, hipStream_t stream) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_rows_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       lds_raised = true;
     }
-    hipLaunchKernelGGL(mm == 2 ? conv2d_rows_kernel<2> : conv2d_rows_kernel<4>, dim3((a.ld + 511) / 512, (a.Fout + C2D_R - 1) / C2D_R, N),
-                       dim3(256), rows_lds, stream, a, span, (int)nent);
-    return launch_status("ps_conv2d_f32");
+    const dim3 grid((a.ld + 511) / 512, (a.Fout + C2D_R - 1) / C2D_R, N);
+    if (t_rows) {
+      static bool ragged_lds_raised = false;
+      if (!ragged_lds_raised) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_rows_kernel<2, true, const int*>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_rows_kernel<4, true, const int*>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        ragged_lds_raised = true;
+      }
+      hipLaunchKernelGGL((mm == 2 ? conv2d_rows_kernel<2, true, const int*> : conv2d_rows_kernel<4, true, const int*>), grid, dim3(256), rows_lds, stream, a, span,
+                         (int)nent, t_rows);
+    } else {
+      hipLaunchKernelGGL(mm == 2 ? conv2d_rows_kernel<2> : conv2d_rows_kernel<4>, grid, dim3(256), rows_lds, stream, a, span, (int)nent);
+    }
+    return launch_status(who);
   }
   const Conv2dTiles t = conv2d_tiles(a.M);
   const int Kq = (a.Kp + 31) / 32 * 32;
   const size_t as = 32 * t.mb + (t.mb > 1 ? 32 : 0);
   const size_t lds = (size_t)3 * Kq * sizeof(int) + 2 * C2D_KC * as * sizeof(float);
   with_mb(t.mb, [&](auto MB) {
-    hipLaunchKernelGGL(conv2d_lds_kernel<MB()>, dim3(a.ld / 128, a.Fout, N * t.mtiles), dim3(256), lds, stream, a);
+    const dim3 grid(a.ld / 128, a.Fout, N * t.mtiles);
+    if (t_rows) hipLaunchKernelGGL((conv2d_lds_kernel<MB(), true, const int*>), grid, dim3(256), lds, stream, a, t_rows);
+    else hipLaunchKernelGGL(conv2d_lds_kernel<MB()>, grid, dim3(256), lds, stream, a);
   });
-  return launch_status("ps_conv2d_f32");
+  return launch_status(who);
 }
 
 // ---- entries -----------------------------------------------------------------------------------------------------------------
@@ -611,6 +660,22 @@ extern "C" int ps_conv2d_f32(const float* x1, int C1, const float* x2, int C2, c
                                  dil_f, dil_t, pad_f, pad_t, Fout, transposed, act, slope, nullptr))
     return rc;
   return conv2d_launch(a, N, (hipStream_t)stream);
+}
+
+// ps_conv2d_f32 with a per-row frame limit in place of T_in (include/puresound_hip.h): the same rules, T_in = T.
+extern "C" int ps_conv2d_ragged_f32(const float* x1, int C1, const float* x2, int C2, const float* wt, const float* bias,
+                                    float* y, int N, int M, int Fin, const int* t_rows, int T, int ld, int kf, int kt,
+                                    int stride_f, int dil_f, int dil_t, int pad_f, int pad_t, int Fout, int transposed, int act,
+                                    const float* slope, void* stream) {
+  if (!t_rows) {
+    set_error("ps_conv2d_ragged_f32: t_rows is NULL");
+    return PS_E_INVALID;
+  }
+  Conv2dArgs a;
+  if (const int rc = conv2d_args("ps_conv2d_ragged_f32", a, x1, C1, x2, C2, wt, wt != nullptr, bias, y, N, M, Fin, T, T, ld, kf, kt,
+                                 stride_f, dil_f, dil_t, pad_f, pad_t, Fout, transposed, act, slope, nullptr))
+    return rc;
+  return conv2d_launch(a, N, (hipStream_t)stream, t_rows);
 }
 
 // (no activation; the shared rules report under ps_conv2d_f32's name)

@@ -115,13 +115,9 @@ __global__ __launch_bounds__(256) void real_mask_kernel(const float* __restrict_
 // window and divided by n_fft, overlapping samples are summed, then divided by the overlap-added squared window
 // wherever that exceeds 1e-10 (the reference does this with a boolean-mask index, i.e. a host sync; here the
 // window sum is recomputed per sample in the same loop).  One thread per output sample.
-__global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ frames,
-                                                        const float* __restrict__ window, float* __restrict__ out,
-                                                        int n_fft, int hop, int T, int ldt, int out_mode) {
-  const int n = blockIdx.y;
-  const int Lout = (T - 1) * hop + n_fft;
-  const int g = blockIdx.x * 256 + threadIdx.x;
-  if (g >= Lout) return;
+// (one output sample g of a row of T frames: shared by the two kernels below, so that they sum in the same order)
+__device__ __forceinline__ float istft_ola_sample(const float* __restrict__ frames, const float* __restrict__ window, int n,
+                                                  int g, int n_fft, int hop, int T, int ldt, int out_mode) {
   int t_hi = g / hop;
   if (t_hi > T - 1) t_hi = T - 1;
   const int t_lo = (g - n_fft + 1 <= 0) ? 0 : (g - n_fft + 1 + hop - 1) / hop;
@@ -136,7 +132,34 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict_
   if (wsum > 1e-10f) acc = acc / wsum;
   if (out_mode == PS_OUT_CLAMP) acc = clamp1_keep_nan(acc);
   if (out_mode == PS_OUT_SIGMOID) acc = 1.f / (1.f + expf(-acc));
-  out[(size_t)n * Lout + g] = acc;
+  return acc;
+}
+
+__global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ frames,
+                                                        const float* __restrict__ window, float* __restrict__ out,
+                                                        int n_fft, int hop, int T, int ldt, int out_mode) {
+  const int n = blockIdx.y;
+  const int Lout = (T - 1) * hop + n_fft;
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= Lout) return;
+  out[(size_t)n * Lout + g] = istft_ola_sample(frames, window, n, g, n_fft, hop, T, ldt, out_mode);
+}
+
+// ps_istft_ola_ragged_f32: row n holds T_n = clamp(t_rows[n], 0, T) frames; its first (T_n - 1) hop + n_fft samples are the
+// overlap-add of those frames alone (numerator and window sum), everything behind them is 0.0 whatever the output constraint,
+// and no frame >= T_n is loaded.
+__global__ __launch_bounds__(256) void istft_ola_ragged_kernel(const float* __restrict__ frames,
+                                                               const float* __restrict__ window, float* __restrict__ out,
+                                                               const int* __restrict__ t_rows, int n_fft, int hop, int T,
+                                                               int ldt, int out_mode) {
+  const int n = blockIdx.y;
+  const int Lout = (T - 1) * hop + n_fft;
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= Lout) return;
+  const int tr = t_rows[n];
+  const int Tn = tr < 0 ? 0 : tr > T ? T : tr;
+  const int Ln = Tn > 0 ? (Tn - 1) * hop + n_fft : 0;
+  out[(size_t)n * Lout + g] = g < Ln ? istft_ola_sample(frames, window, n, g, n_fft, hop, Tn, ldt, out_mode) : 0.f;
 }
 
 }  // namespace ps
@@ -221,6 +244,20 @@ extern "C" int ps_istft_ola_f32(const float* frames, const float* window, float*
   hipLaunchKernelGGL(istft_ola_kernel, dim3((Lout + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, frames,
                      window, out, n_fft, hop, T, ldt, out_mode);
   return launch_status("ps_istft_ola_f32");
+}
+
+extern "C" int ps_istft_ola_ragged_f32(const float* frames, const float* window, float* out, const int* t_rows, int N,
+                                       int n_fft, int hop, int T, int ldt, int out_mode, void* stream) {
+  if (!frames || !window || !out || !t_rows || N <= 0 || N > 65535 || n_fft <= 0 || hop <= 0 || T <= 0 || ldt < T ||
+      out_mode < PS_OUT_CLAMP || out_mode > PS_OUT_NONE) {
+    set_error("ps_istft_ola_ragged_f32: bad argument (N=%d n_fft=%d hop=%d T=%d)", N, n_fft, hop, T);
+    return PS_E_INVALID;
+  }
+  const int Lout = (T - 1) * hop + n_fft;
+  LaunchTimer timer("istft_ola", (hipStream_t)stream);
+  hipLaunchKernelGGL(istft_ola_ragged_kernel, dim3((Lout + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, frames,
+                     window, out, t_rows, n_fft, hop, T, ldt, out_mode);
+  return launch_status("ps_istft_ola_ragged_f32");
 }
 
 // Magnitude lobe (lobe/trivial.py:21-59) on the [re rows; im rows] channel layout: y[h] = sqrt(re[h+d]^2 + im[h+d]^2 + 1e-8)

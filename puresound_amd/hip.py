@@ -1764,6 +1764,38 @@ def zero_tail(x: torch.Tensor, limits: torch.Tensor) -> torch.Tensor:
     return x
 
 
+def conv2d_ragged(x1: torch.Tensor, x2: Optional[torch.Tensor], wt: torch.Tensor, bias: Optional[torch.Tensor], m: int, t: int,
+                  t_rows: torch.Tensor, f_out: int, kf: int, kt: int, stride_f: int, dil_f: int, dil_t: int, pad_f: int,
+                  pad_t: int, transposed: bool, act: str = "none", slope: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv2d with a per-row frame limit (t_rows int32 [N] on the device) in place of t_in: row n on its first t_rows[n]
+    frames is conv2d of that row alone with t = t_in = t_rows[n], 0.0 behind them; what the sources hold behind a row's
+    end is not read as data (ps_conv2d_ragged_f32)."""
+    n, c1, c2, f_in, ld = _conv2d_sources("conv2d_ragged", x1, x2)
+    _require_operand("conv2d_ragged", x1.device, wt=wt, bias=bias, slope=slope)
+    _require_limits("conv2d_ragged", t_rows, n, x1.device)
+    y = torch.empty(n, m, f_out, ld, dtype=torch.float32, device=x1.device)
+    check(lib().ps_conv2d_ragged_f32(ptr(x1), c1, ptr(x2), c2, ptr(wt), ptr(bias), ptr(y), n, m, f_in, ptr(t_rows), t, ld, kf,
+                                     kt, stride_f, dil_f, dil_t, pad_f, pad_t, f_out, int(transposed), ACT_KINDS[act],
+                                     ptr(slope), stream_ptr(x1.device)), "ps_conv2d_ragged_f32")
+    return y
+
+
+def istft_ola_ragged(frames: torch.Tensor, t: int, t_rows: torch.Tensor, window: torch.Tensor, hop: int,
+                     out_mode: str = "none") -> torch.Tensor:
+    """istft_ola with a per-row frame limit: frames padded [N,n_fft,ldt] -> waveform [N,(t-1)*hop+n_fft]; row n's first
+    (t_rows[n]-1)*hop+n_fft samples are istft_ola of its first t_rows[n] frames, 0.0 behind them (ps_istft_ola_ragged_f32)."""
+    require_device(frames, "istft_ola_ragged")
+    _require_operand("istft_ola_ragged", frames.device, window=window)
+    n, n_fft, ldt = frames.shape
+    _require_limits("istft_ola_ragged", t_rows, n, frames.device)
+    if not frames.is_contiguous() or window.numel() != n_fft:
+        raise RuntimeError(f"istft_ola_ragged: contiguous frames [N, n_fft, ldt] and a window of n_fft = {n_fft} values")
+    out = torch.empty(n, (t - 1) * hop + n_fft, dtype=torch.float32, device=frames.device)
+    check(lib().ps_istft_ola_ragged_f32(ptr(frames), ptr(window), ptr(out), ptr(t_rows), n, n_fft, hop, t, ldt,
+                                        _abi.PS_OUT[out_mode], stream_ptr(frames.device)), "ps_istft_ola_ragged_f32")
+    return out
+
+
 def align_rows(ref: torch.Tensor, a_len: torch.Tensor, b_len: torch.Tensor, length: int) -> torch.Tensor:
     """align_reference per row: ref [N, L_ref] (last-dim contiguous) -> [N, length] with row n's b_len[n] reference samples
     aligned to a_len[n] valid output samples -- left-padded with zeros when shorter, cut when longer -- and exact 0.0 behind

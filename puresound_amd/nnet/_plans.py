@@ -4,6 +4,7 @@ A plan holds the packed / transposed fp32 copies of a module's parameters that t
 fingerprint of the parameters so that load_state_dict / .to(device) / in-place edits invalidate it.  Plans hold
 raw device pointers through the tensors they keep alive; they are never pickled.
 """
+import contextlib
 import os
 from collections import namedtuple
 from typing import Optional
@@ -126,6 +127,25 @@ class PlanCache:
             if hasattr(m, "gemm_precision"):
                 m.gemm_precision = name
         return self
+
+
+@contextlib.contextmanager
+def own_plans(mods: list, own: list):
+    """Inside the block the plan-cached modules `mods` compute with the caller's own precision and plans, own[i] = {"gemm_precision":
+    ..., "_plans": ...} of mods[i] (start: {"gemm_precision": "fp32"}); the modules' own are put back after it and what was built
+    inside is kept in `own` for the next time.  How a path with exact fp32 products (the streamers, the ragged batches of the
+    noise suppressors) leaves the model's plans, and so plain inference, untouched."""
+    swap = ("gemm_precision", "_plans")
+    saved = []
+    for m, mine in zip(mods, own):
+        saved.append({k: m.__dict__.pop(k) for k in swap if k in m.__dict__})
+        m.__dict__.update(mine)
+    try:
+        yield
+    finally:
+        for i, m in enumerate(mods):
+            own[i] = {k: m.__dict__.pop(k) for k in swap if k in m.__dict__}
+            m.__dict__.update(saved[i])
 
 
 class GemmPlanCache(PlanCache):

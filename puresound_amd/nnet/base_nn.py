@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from .. import hip
 from .._abi import TcnBlock
-from ._plans import PlanCache
+from ._plans import PlanCache, own_plans
 from .conv_tasnet import TCN, ConvTasNet, GatedTCN
 from .lobe.trivial import Magnitude, SpecAugment
 from .dprnn import DPRNN
@@ -212,8 +212,9 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         on.  Row n of the result is, on its first output_lengths(lengths)[n] samples, what inference(noisy[n:n+1,
         :lengths[n]], enroll[n:n+1, :enroll_lengths[n]]) returns for that utterance alone, and exact 0.0 behind them.  Exact
         fp32 products whatever gemm_precision says, one lane (hip_streams is ignored).  Covered: FreeEncDec + a normal-TCN
-        ConvTasNet on the fused driver, with an enrolment the td_tse_conv_tasnet_v0 speaker net; nnet/ragged.py lists the
-        refusals, all raised before any launch."""
+        ConvTasNet on the fused driver, with an enrolment the td_tse_conv_tasnet_v0 speaker net; on device tensors also the
+        conv-STFT encoder + DPCRN / DPARN (the egs/ns noise suppressors, lookahead presets included); nnet/ragged.py lists
+        the refusals, all raised before any launch."""
         if noisy.device.type == "cpu":  # BASELINE configs[0] / the recipes' --backend cpu: stock ATen (nnet/cpu_path.py)
             from . import cpu_path
             return cpu_path.wrapper_inference(self, noisy, enroll, lengths, enroll_lengths)
@@ -260,6 +261,23 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
             rel = torch.tensor(ragged.relative_lengths(rp.enroll_t_rows, rp.enroll_frames), dtype=torch.float32)
             rows += [rp.enroll_t_rows, rel.view(torch.int32).tolist()]
         limits = hip.row_limits("inference", rows + list(more_rows), dev)
+        if ragged.spectral(self):
+            # conv-STFT encoder + DPCRN / DPARN: analysis, complex mask and synthesis work column by column over all T frames
+            # of the rows as they are; the masker's convolutions and the overlap-add take the per-row limit.  Exact fp32
+            # products on plans of this path's own (the model's, and so plain inference, are untouched).
+            enc = self.encoder.encoder
+            mods = [m for m in self.masker.modules() if isinstance(m, PlanCache)]
+            own = self.scratch("ragged_fp32_plans")
+            if own is None or len(own) != len(mods):
+                own = [{"gemm_precision": "fp32"} for _ in mods]
+            feats, t = enc.encode_padded(noisy.contiguous(), self.drop_first_bin)
+            try:
+                with own_plans(mods, own):
+                    mask = self.masker.forward_padded(feats, t, None, t_rows=limits[0])
+            finally:
+                self.keep_scratch("ragged_fp32_plans", 0, own)
+            enh = hip.complex_mask(feats, mask, mask_act)
+            return enc.decode_padded(enh, t, self.drop_first_bin, out_mode, t_rows=limits[0]), limits
         dvec = None
         if enroll is not None:
             dvec = self._speaker_embedding(enroll.contiguous(), 0, limits[2], limits[3].view(torch.float32))
@@ -719,7 +737,7 @@ class SiMoTaskWrapModule(EncDecMaskerBaseModel):
         wrapper's ragged batches) are not covered here."""
         if lengths is not None:
             raise NotImplementedError("SiMoTaskWrapModule.inference: per-row lengths are not covered (any masker with the "
-                                      "reference contract runs here; only SoTaskWrapModule has the ragged Conv-TasNet path)")
+                                      "reference contract runs here; only SoTaskWrapModule has the ragged paths)")
         return self._inference(noisy, None)
 
     def _inference(self, noisy: torch.Tensor, ref: Optional[torch.Tensor]):

@@ -106,15 +106,15 @@ class DPARN(Unet):
         self.dprnn_block1 = DPARNblock2D(input_size=channels[-1], hidden_size=rnn_hidden, nhead=nhead, dropout=dropout)
         self.dprnn_block2 = DPARNblock2D(input_size=channels[-1], hidden_size=rnn_hidden, nhead=nhead, dropout=dropout)
 
-    def forward_padded4(self, x4: torch.Tensor, t: int, dvec=None, lane: int = 0) -> torch.Tensor:
+    def forward_padded4(self, x4: torch.Tensor, t: int, dvec=None, lane: int = 0, t_rows=None) -> torch.Tensor:
         if self.spectral_compress:
             raise NotImplementedError("DPARN on HIP: spectral_compress (it returns a complex tensor in the reference)")
         p = self._plan_get(x4.device, self._build_unet)
-        skip = self._down(x4, t, p)
+        skip = self._down(x4, t, p, t_rows)
         amax = [None]
         y = self.dprnn_block1.forward_padded(skip[-1], t, amax, lane=lane)
         y = self.dprnn_block2.forward_padded(y, t, amax, lane=lane)
-        return self._up(y, skip, t, p, self.transpose_delay)
+        return self._up(y, skip, t, p, self.transpose_delay, t_rows)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x [N, C, T] -> [N, C, T] (dparn.py:170-226)."""

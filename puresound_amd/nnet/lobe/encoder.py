@@ -220,14 +220,18 @@ class ConvSTFT(PlanCache, nn.Module):
         y, _ = hip.conv1x1(frames, t, wt, m, out=torch.empty(x.shape[0], m, frames.shape[-1], device=x.device))
         return y, t
 
-    def decode_padded(self, spec_pad: torch.Tensor, t: int, drop_first_bin: bool, out_mode: str = "none"):
-        """[re;im] channel layout padded [N,2*bins,ldt] -> waveform [N,(T-1)*hop+n_fft]."""
+    def decode_padded(self, spec_pad: torch.Tensor, t: int, drop_first_bin: bool, out_mode: str = "none",
+                      t_rows: Optional[torch.Tensor] = None):
+        """[re;im] channel layout padded [N,2*bins,ldt] -> waveform [N,(T-1)*hop+n_fft].  t_rows (int32 [N] on the device):
+        row n holds that many frames; its overlap-add and window sum take those alone, 0.0 behind their last sample."""
         if not hasattr(self, "kernel_sin_inv") or not hasattr(self, "kernel_cos_inv"):
             raise NameError("Please activate the iSTFT module by setting `iSTFT=True` if you want to use `inverse`")
         wt, window = self._synthesis_plan(drop_first_bin)
         frames, _ = hip.conv1x1(spec_pad, t, wt, self.n_fft,
                                 out=torch.empty(spec_pad.shape[0], self.n_fft, spec_pad.shape[-1],
                                                 device=spec_pad.device))
+        if t_rows is not None:
+            return hip.istft_ola_ragged(frames, t, t_rows, window, self.stride, out_mode)
         return hip.istft_ola(frames, t, window, self.stride, out_mode)
 
     # -- reference API ----------------------------------------------------------------------------------

@@ -7,8 +7,11 @@ that utterance alone, and exact 0.0 behind them.  Everything here runs on the ho
 HIP path (base_nn.py) and the CPU path (cpu_path.py), which loops over the rows and so defines the semantics without a GPU.
 
 Covered: FreeEncDec encoder, the normal-TCN ConvTasNet masker on the fused driver (no cLN), and for `enroll_lengths` a
-speaker net of plain TCN blocks -> AttentiveStatisticsPooling -> k=1 projection(s) (td_tse_conv_tasnet_v0[_causal]).
-Everything else raises NotImplementedError.  Scoring such a batch: SoTaskWrapModule.inference_scored_ragged (base_nn.py), whose
+speaker net of plain TCN blocks -> AttentiveStatisticsPooling -> k=1 projection(s) (td_tse_conv_tasnet_v0[_causal]).  On
+the HIP path also the noise suppressors of egs/ns: the conv-STFT encoder (ConvEncDec, Complex output, (complex, complex)
+masks) in front of a DPCRN or DPARN with bN2d norms on the implicit-GEMM convolution, either transpose_delay, any delay,
+no enrolment (ns_dpcrn_v0[_causal], ns_dparn_v0[_causal]); the CPU path has no stock-ATen DPCRN / DPARN and keeps refusing
+them.  Everything else raises NotImplementedError.  Scoring such a batch: SoTaskWrapModule.inference_scored_ragged (base_nn.py), whose
 model refusals are check_model's and whose length values -- like the `lengths` of the scores in nnet/loss/ -- go through
 host_lengths."""
 from typing import List, NamedTuple, Optional, Sequence
@@ -62,19 +65,60 @@ def _plain_speaker_net(net) -> bool:
     return all(isinstance(m, nn.Conv1d) and m.kernel_size == (1,) and m.bias is None for m in layers[i + 1:])
 
 
-def check_model(w, enroll: Optional[torch.Tensor], enroll_lengths) -> None:
-    """What the lengths path does not cover: raised before any launch, each with its reason."""
+def spectral(w) -> bool:
+    """Whether `w` is of the conv-STFT family (check_model's second branch; _ragged_forward's)."""
+    from .lobe.encoder import ConvEncDec
+    return isinstance(w.encoder, ConvEncDec)
+
+
+def _check_spectral(w, enroll: Optional[torch.Tensor], hip_path: bool, who: str) -> None:
+    """The conv-STFT encoder in front of a DPCRN / DPARN: frames meet in the time taps of the 2-D convolutions and in the
+    iSTFT's overlap-add, which have a per-row form on the HIP path (ps_conv2d_ragged_f32, ps_istft_ola_ragged_f32)."""
+    from .conv_tasnet import ConvTasNet
+    from .dparn import DPARN
+    from .dpcrn import DPCRN
+    m = w.masker
+    if isinstance(m, ConvTasNet):
+        raise NotImplementedError(f"{who}: an STFT encoder in front of a ConvTasNet is not covered (FreeEncDec + ConvTasNet, or "
+                                  f"ConvEncDec + DPCRN / DPARN)")
+    if type(m) not in (DPCRN, DPARN):
+        raise NotImplementedError(f"{who}: behind the STFT encoder a DPCRN or DPARN masker only (got {type(m).__name__}; Unet, "
+                                  f"UnetTcn, DPARN_Mout, DPRNN and SkiM have no per-row frame limit)")
+    if not hip_path:
+        raise NotImplementedError(f"{who}: {type(m).__name__} behind the STFT encoder is covered on the HIP path only (the CPU "
+                                  f"path has no stock-ATen {type(m).__name__})")
+    stft = w.encoder.encoder
+    if stft.output_format != "Complex" or not hasattr(stft, "kernel_sin_inv"):
+        raise NotImplementedError(f"{who}: the STFT encoder's Complex output with its iSTFT only")
+    if w.check_mask_pairing(w.mask_type, w.f_type) != "complex":
+        raise NotImplementedError(f"{who}: STFT encoder with (complex, complex) masks only (got ({w.mask_type}, {w.f_type}))")
+    if getattr(m, "spectral_compress", False) or m.multi_output != 1:
+        raise NotImplementedError(f"{who}: spectral_compress / multi_output maskers are not covered")
+    reason = m.per_row_refusal()
+    if reason:
+        raise NotImplementedError(f"{who}: {type(m).__name__}: {reason}")
+    if w.embedding_free_tse:
+        raise NotImplementedError(f"{who}: embedding_free_tse is not covered")
+    if enroll is not None:
+        raise NotImplementedError(f"{who}: an enrolment is not covered behind the STFT encoder")
+
+
+def check_model(w, enroll: Optional[torch.Tensor], enroll_lengths, hip_path: bool = False) -> None:
+    """What the lengths path does not cover: raised before any launch, each with its reason.  hip_path: the call is on device
+    tensors (the noise suppressors behind the STFT encoder have no CPU form)."""
     from .conv_tasnet import ConvTasNet
     from .lobe.encoder import FreeEncDec
     if enroll_lengths is not None and enroll is None:
         raise ValueError("inference: enroll_lengths was given without enroll")
     who = "inference with lengths"
+    if spectral(w):
+        return _check_spectral(w, enroll, hip_path, who)
     if not isinstance(w.encoder, FreeEncDec):
-        raise NotImplementedError(f"{who}: the FreeEncDec encoder only (got {type(w.encoder).__name__}; the STFT encoders' "
-                                  f"overlap-add and window normalisation have no per-row form)")
+        raise NotImplementedError(f"{who}: the FreeEncDec encoder, or the conv-STFT encoder in front of a DPCRN / DPARN "
+                                  f"(got {type(w.encoder).__name__})")
     if not isinstance(w.masker, ConvTasNet):
-        raise NotImplementedError(f"{who}: the Conv-TasNet masker only (got {type(w.masker).__name__}; the DPRNN, SkiM and "
-                                  f"Unet-family maskers have no per-row frame limit)")
+        raise NotImplementedError(f"{who}: behind the FreeEncDec encoder the Conv-TasNet masker only (got "
+                                  f"{type(w.masker).__name__}; the DPRNN, SkiM and U-Net maskers have no per-row frame limit there)")
     if w.masker.tcn_layer.lower() != "normal":
         raise NotImplementedError(f'{who}: tcn_layer="{w.masker.tcn_layer}" is not covered (normal TCN blocks only)')
     if not all(m.fused_norms() for stack in w.masker.tcn_list for m in stack):
@@ -102,9 +146,11 @@ class Plan(NamedTuple):
     enroll_frames: int           # T' of the enrolment rows (0 without one)
 
 
-def plan(w, noisy: torch.Tensor, enroll: Optional[torch.Tensor], lengths, enroll_lengths) -> Plan:
-    """Refusals first, then the limits: everything a ragged call needs from the host."""
-    check_model(w, enroll, enroll_lengths)
+def plan(w, noisy: torch.Tensor, enroll: Optional[torch.Tensor], lengths, enroll_lengths,
+         hip_path: Optional[bool] = None) -> Plan:
+    """Refusals first, then the limits: everything a ragged call needs from the host.  hip_path: see check_model (None: whether
+    `noisy` is a device tensor)."""
+    check_model(w, enroll, enroll_lengths, noisy.device.type != "cpu" if hip_path is None else hip_path)
     if noisy.dim() != 2:
         raise ValueError(f"inference with lengths: noisy must be [N, L] (got {tuple(noisy.shape)})")
     n, length = noisy.shape

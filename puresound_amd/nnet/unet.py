@@ -190,11 +190,18 @@ class Unet(GemmPlanCache, nn.Module):
         return hip.norm_activation_(y, t, pro, lay["bias_sum"] * pad, lay["bias_sq"] * pad, lay["act"], lay["slope"])
 
     def _conv(self, x, x2, lay: dict, t: int, f_out: int, kf: int, kt: int, sf: int, df: int, dt: int, pf: int, pt: int,
-              transposed: bool, t_in=None):
+              transposed: bool, t_in=None, t_rows: Optional[torch.Tensor] = None):
         """One implicit-GEMM convolution of the stack with its epilogue (activation, or the statistics of a gLN that follows):
         the fp16x2 kernel when the module's arithmetic is "fp16x2" and the layer suits it (K >= 32, more than 4 output
-        channels, no stride-2 transposed taps to compact), else the exact-fp32 kernels."""
+        channels, no stride-2 transposed taps to compact), else the exact-fp32 kernels.  t_rows (int32 [N] on the device: a
+        batch of utterances of unequal length, nnet/ragged.py): the per-row form of the exact-fp32 kernels, whatever the
+        module's arithmetic."""
         gln = "gln" in lay
+        if t_rows is not None:
+            if gln or t_in is not None:
+                raise NotImplementedError("U-Net on HIP: a gLN's statistics span the frames; no per-row frame limit")
+            return hip.conv2d_ragged(x, x2, lay["wt"], lay["bias"], lay["M"], t, t_rows, f_out, kf, kt, sf, df, dt, pf, pt,
+                                     transposed, lay["act"], lay["slope"])
         k = (x.shape[1] + (0 if x2 is None else x2.shape[1])) * kf * kt
         if self.gemm_precision == "fp16x2" and k >= 32 and lay["M"] > 4 and (F16X2_STRIDED or not (transposed and sf > 1)):
             if "f16x2" not in lay:
@@ -219,8 +226,9 @@ class Unet(GemmPlanCache, nn.Module):
         pro = hip.make_prologue(PS_NORM_GLOBAL, False, stats, float(lay["M"] * f_out * t), gln[2], gln[0], gln[1], None)
         return hip.norm_activation_(y, t, pro, 0.0, 0.0, lay["act"], lay["slope"])
 
-    def _down(self, x4: torch.Tensor, t: int, p: dict) -> List[torch.Tensor]:
-        """[N, CH0, F, ld] -> skip list (input first), unet.py:235-246."""
+    def _down(self, x4: torch.Tensor, t: int, p: dict, t_rows: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+        """[N, CH0, F, ld] -> skip list (input first), unet.py:235-246.  t_rows: see _conv (every layer must be on the
+        implicit-GEMM route: ragged.check_model refuses the others beforehand)."""
         skip = [x4]
         x = x4
         for i, lay in enumerate(p["down"]):
@@ -233,15 +241,21 @@ class Unet(GemmPlanCache, nn.Module):
             if IMPLICIT_CONV and x.shape[1] * kf * kt <= 4096:
                 # (a gLN behind the convolution gets its statistics from the convolution's epilogue: round 3 built the tap
                 #  matrix for these layers, 43 + 47 ms per forward of tse_unet_tcn_v0 at 32 x 4 s)
-                x = self._conv(x, None, lay, t, f_out, kf, kt, sf, df, dt, pf, kt - self.delay[i] - 1, False)
+                x = self._conv(x, None, lay, t, f_out, kf, kt, sf, df, dt, pf, kt - self.delay[i] - 1, False, t_rows=t_rows)
+            elif t_rows is not None:
+                raise NotImplementedError(f"U-Net on HIP: no per-row frame limit: {self.per_row_refusal()}")
             else:
                 taps = hip.unfold2d(x, None, t, f_out, kf, kt, sf, df, dt, pf, kt - self.delay[i] - 1, False)
                 x = self._gemm_act(taps, lay, f_out, x.shape[3], t)
             skip.append(x)
         return skip
 
-    def _up(self, x: torch.Tensor, skip: List[torch.Tensor], t: int, p: dict, transpose_delay: bool) -> torch.Tensor:
-        """CNN-up stack (unet.py:248-256, 514-528) -> [N, CH0*multi_output, F, ld]."""
+    def _up(self, x: torch.Tensor, skip: List[torch.Tensor], t: int, p: dict, transpose_delay: bool,
+            t_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """CNN-up stack (unet.py:248-256, 514-528) -> [N, CH0*multi_output, F, ld].  t_rows: see _conv (no skip_conv, no gLN,
+        every layer on the implicit-GEMM route)."""
+        if t_rows is not None and self.per_row_refusal():
+            raise NotImplementedError(f"U-Net on HIP: no per-row frame limit: {self.per_row_refusal()}")
         for j, i in enumerate(reversed(range(self.n_cnn))):
             lay = p["up"][j]
             s = skip[-j - 1]
@@ -276,12 +290,30 @@ class Unet(GemmPlanCache, nn.Module):
                     x = hip.unfold2d(x, None, t, f_out, 1, 1, 1, 1, 1, 0, -ext, False, t_in=t + ext).view(
                         n, lay["M"], f_out, ld)
             elif IMPLICIT_CONV and (x.shape[1] + (0 if x2 is None else x2.shape[1])) * kf * self.t_kernel <= 4096:
-                x = self._conv(x, x2, lay, t, f_out, kf, self.t_kernel, sf, df, dt, pf, ext if transpose_delay else 0, True)
+                x = self._conv(x, x2, lay, t, f_out, kf, self.t_kernel, sf, df, dt, pf, ext if transpose_delay else 0, True,
+                               t_rows=t_rows)
             else:
                 shift = ext if transpose_delay else 0
                 taps = hip.unfold2d(x, x2, t, f_out, kf, self.t_kernel, sf, df, dt, pf, shift, True)
                 x = self._gemm_act(taps, lay, f_out, ld, t)
         return x
+
+    def per_row_refusal(self) -> Optional[str]:
+        """Why the stack has no per-row frame limit (t_rows of _down / _up), or None: host values only, so that
+        ragged.check_model can ask before any launch.  Covered: eval bN2d layers (folded into the weights) without skip_conv,
+        every layer on the implicit-GEMM route; any delay, either transpose_delay."""
+        if self.norm_type.lower() != "bn2d":
+            return f'norm_type="{self.norm_type}" is not covered (bN2d only: the statistics of a gLN span the frames)'
+        if self.skip_conv:
+            return "skip_conv=True is not covered"
+        if any(st != 1 for _, st in self.stride):
+            return "stride_t must be 1"
+        skip_double = 1 if self.skip_conv else 2
+        ks = [self.channels[i] * kf * kt for i, (kf, kt) in enumerate(self.kernel)]
+        ks += [self.channels[i + 1] * skip_double * kf * self.t_kernel for i, (kf, _) in enumerate(self.kernel)]
+        if not IMPLICIT_CONV or max(ks) > 4096:
+            return f"a layer with Cin*kf*kt = {max(ks)} is off the implicit-GEMM convolution (K <= 4096)"
+        return None
 
     def frames_needed(self, t: int) -> int:
         """Row length the decoder needs: gLN layers hold their untrimmed T + transpose_t_size - 1 frames."""
@@ -314,11 +346,13 @@ class Unet(GemmPlanCache, nn.Module):
         return self._up(skip[-1], skip, t, p, False)
 
     def forward_padded(self, x_pad: torch.Tensor, t: int, dvec: Optional[torch.Tensor] = None,
-                       lane: int = 0) -> torch.Tensor:
-        """Wrapper entry: padded [N, C, ld] -> padded [N, C, ld] (RI halves are the two CH0 planes: no data moves)."""
+                       lane: int = 0, t_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Wrapper entry: padded [N, C, ld] -> padded [N, C, ld] (RI halves are the two CH0 planes: no data moves).  t_rows: the
+        per-row frame limits of a batch of utterances of unequal length (DPCRN / DPARN: nnet/ragged.py)."""
         if self.multi_output != 1:
             raise NotImplementedError("multi_output U-Net behind the single-output wrapper")
-        y = self.forward_padded4(self._rows4(x_pad), t, dvec, lane)   # (lane: the recurrent bottlenecks keep rows per lane)
+        kw = {} if t_rows is None else dict(t_rows=t_rows)
+        y = self.forward_padded4(self._rows4(x_pad), t, dvec, lane, **kw)   # (lane: the recurrent bottlenecks keep rows per lane)
         return y.reshape(y.shape[0], -1, y.shape[3])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

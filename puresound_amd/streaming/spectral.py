@@ -43,14 +43,12 @@ from typing import List
 import torch
 
 from .. import hip
-from ..nnet._plans import PlanCache
+from ..nnet._plans import PlanCache, own_plans
 from ..nnet.base_nn import _MASK_ACTS, SoTaskWrapModule
 from ..nnet.dparn import DPARN
 from ..nnet.dpcrn import DPCRN
 from ..nnet.lobe.encoder import ConvEncDec
 from ._session import HopSession, check_on_device
-
-_SWAP = ("gemm_precision", "_plans")
 
 
 def check_streamable(model) -> None:
@@ -136,16 +134,8 @@ class StreamingSeparator(HopSession):
     def _fp32_plans(self):
         """The masker's plan-cached modules compute with the streamer's own exact-fp32 plans inside this block; their own
         precision and plans are put back after it."""
-        saved = []
-        for m, own in zip(self._plan_mods, self._own):
-            saved.append({k: m.__dict__.pop(k) for k in _SWAP if k in m.__dict__})
-            m.__dict__.update(own)
-        try:
+        with own_plans(self._plan_mods, self._own):
             yield
-        finally:
-            for i, m in enumerate(self._plan_mods):
-                self._own[i] = {k: m.__dict__.pop(k) for k in _SWAP if k in m.__dict__}
-                m.__dict__.update(saved[i])
 
     def _build_packs(self, dev: torch.device) -> None:
         """Conv weights (eval BatchNorm2d folded, packed for the GEMM kernels) and the STFT tables, held by the streamer:

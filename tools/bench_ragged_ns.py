@@ -1,0 +1,105 @@
+"""Timing of ragged batches through the egs/ns noise suppressors (not the bench.py headline): ns_dpcrn_v0_causal, ns_dpcrn_v0,
+ns_dparn_v0_causal and ns_dparn_v0 (the two presets of tests/golden/cases.py and a copy of each with transpose_delay=True), 32
+rows, lengths spaced evenly over 1 - 4 s.
+
+  (a) ragged        one inference(noisy, lengths=lengths) call (exact fp32 products whatever gemm_precision says),
+  (b) one_by_one    the 32 rows through inference(noisy[n:n+1, :lengths[n]]) one after the other in fp32: what a user who wants
+                    the reference's result for every utterance runs without (a),
+  (c) padded_fp32 / padded_fp16x2   the plain inference(noisy) call over the padded batch in either arithmetic: its results
+                    are WRONG for the short rows (the iSTFT's window sum and, with transpose_delay, the up layers see the
+                    padding); time references only.
+
+Every figure is the median over --steps calls after --warmup, each call bracketed by device synchronisation, repeated --runs
+times; the (b) loop is timed as a whole.  --tree DIR imports puresound_amd from another checkout (the parent commit, built):
+a tree that refuses these models with lengths gets (b) and (c) only.  One JSON line per model and run."""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+MODELS = {"ns_dpcrn_v0_causal": ("ns_dpcrn_short", False), "ns_dpcrn_v0": ("ns_dpcrn_short", True),
+          "ns_dparn_v0_causal": ("ns_dparn_short", False), "ns_dparn_v0": ("ns_dparn_short", True)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tree", default=os.path.join(HERE, ".."), help="checkout to import puresound_amd and the cases from")
+    ap.add_argument("--models", nargs="+", default=list(MODELS), choices=list(MODELS))
+    ap.add_argument("--rows", type=int, default=32)
+    ap.add_argument("--seconds", type=float, nargs=2, default=(1.0, 4.0), help="shortest and longest utterance")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--runs", type=int, default=3)
+    args = ap.parse_args()
+    tree = os.path.abspath(args.tree)
+    sys.path[:0] = [tree, os.path.join(tree, "tests", "golden")]
+    import cases
+    import puresound_amd.nnet as PA
+    from detweights import det_wave
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_ragged_ns.py measures on the GPU; there is none here")
+    dev = torch.device("cuda:0")
+
+    n, rate = args.rows, 16000
+    lo, hi = (int(s * rate) for s in args.seconds)
+    lengths = [lo + (hi - lo) * i // max(n - 1, 1) for i in range(n)]
+    noisy = (det_wave(1234, n, hi) * 0.05).to(dev)
+    rows = [noisy[i:i + 1, :lengths[i]].contiguous() for i in range(n)]
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        ms = []
+        for _ in range(args.steps):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ms)
+
+    for name in args.models:
+        base, lookahead = MODELS[name]
+        c = copy.deepcopy(cases.CASES[base])
+        c["masker"]["kw"]["transpose_delay"] = lookahead
+        torch.manual_seed(0)
+        model = PA.SoTaskWrapModule(encoder=cases.build_encoder(PA.NS, c["enc"]), masker=cases.build_masker(PA.NS, c["masker"]),
+                                    verbose=False, **c["wrap"]).eval().to(dev)
+        try:
+            model.inference(noisy[:2, :lo], lengths=[lo, lo])
+            has_ragged = True
+        except (NotImplementedError, TypeError):
+            has_ragged = False
+
+        def in_precision(precision, fn):
+            def call():
+                model.set_gemm_precision(precision)
+                return fn()
+            return call
+
+        calls = {"one_by_one": in_precision("fp32", lambda: [model.inference(r) for r in rows]),
+                 "padded_fp32": in_precision("fp32", lambda: model.inference(noisy)),
+                 "padded_fp16x2": in_precision("fp16x2", lambda: model.inference(noisy))}
+        if has_ragged:
+            calls["ragged"] = in_precision("fp16x2", lambda: model.inference(noisy, lengths=lengths))
+        for run in range(args.runs):
+            ms = {k: round(timed(fn), 3) for k, fn in calls.items()}
+            line = {"tree": os.path.relpath(tree, os.getcwd()), "model": name, "run": run, "rows": n,
+                    "samples_valid": sum(lengths), "samples_padded": n * hi, "ms": ms}
+            if has_ragged:
+                line["speedup_ragged_over_one_by_one"] = round(ms["one_by_one"] / ms["ragged"], 2)
+                line["ragged_over_padded_fp32"] = round(ms["ragged"] / ms["padded_fp32"], 3)
+                line["ragged_over_padded_fp16x2"] = round(ms["ragged"] / ms["padded_fp16x2"], 3)
+            print(json.dumps(line), flush=True)
+        del model
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
