@@ -40,6 +40,9 @@ def det_tensor(name: str, ref: torch.Tensor, mode: str = "plain") -> torch.Tenso
                 for r, e in zip(rows, (9.0, -9.0, 6.0, -7.0)):
                     v[r] *= 2.0 ** e
         return torch.tensor(np.asarray(v), dtype=ref.dtype).reshape(shape)
+    if mode == "trained" and name.startswith(("masker.", "speaker_net.")) and leaf not in (
+            "num_batches_tracked", "running_mean", "running_var"):
+        return _trained(name, det_tensor(name, ref), leaf, shape)
     if leaf == "num_batches_tracked":
         return torch.zeros(shape, dtype=ref.dtype)
     if leaf == "running_mean":
@@ -57,6 +60,28 @@ def det_tensor(name: str, ref: torch.Tensor, mode: str = "plain") -> torch.Tenso
         b = 1.0 / np.sqrt(max(fan_in, 1))
         v = g.uniform(-b, b, shape)
     return torch.tensor(np.asarray(v), dtype=ref.dtype).reshape(shape)
+
+
+def _trained(name: str, plain: torch.Tensor, leaf: str, shape: tuple) -> torch.Tensor:
+    """mode "trained": the law every model family stays finite and well conditioned under ("wild" sends the masks of the
+    recurrent and 2-D convolutional maskers to 1e16 and beyond) -- norm gains log-uniform over 2^-2 .. 2^2, biases in +-1,
+    PReLU slopes in 0.05 .. 1.5, and in every weight matrix of 16 rows or more four rows scaled by 2^4, 2^-4, 2^3, 2^-3 on
+    top of the plain values.  Its generator is keyed "trained:" + name: independent of the plain draw."""
+    g = _gen("trained:" + name)
+    if leaf in ("gamma",) or (leaf == "weight" and len(shape) == 1 and shape[0] > 1):
+        v = np.exp2(g.uniform(-2.0, 2.0, shape))
+    elif leaf in ("beta",) or (leaf == "bias" and len(shape) == 1):
+        v = g.uniform(-1.0, 1.0, shape)
+    elif leaf == "weight" and shape == (1,):
+        v = g.uniform(0.05, 1.5, shape)
+    elif len(shape) > 1 and shape[0] >= 16:
+        v = plain.double().numpy().copy()
+        rows = g.choice(shape[0], size=4, replace=False)
+        for r, e in zip(rows, (4.0, -4.0, 3.0, -3.0)):
+            v[r] *= 2.0 ** e
+    else:
+        return plain
+    return torch.tensor(np.asarray(v), dtype=plain.dtype).reshape(shape)
 
 
 # buffers that are constants of the algorithm, never randomised

@@ -336,6 +336,8 @@ def dump_state_dict_keys():
     for name, c in cases.CASES.items():
         if c["kind"] in ("loss", "func"):  # functions of tensors, no parameters
             continue
+        if c.get("weights") == "trained":  # a preset already listed, with other parameter values: the same keys and shapes
+            continue
         model = cases.build(REF, name)
         out[name] = {k: list(v.shape) for k, v in model.state_dict().items()}
     with open(os.path.join(HERE, "state_dict_keys.json"), "w") as f:

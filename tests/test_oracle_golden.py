@@ -59,7 +59,7 @@ def test_wrapper_inference_matches_reference(golden_dir, name):
             assert rel_max(taps["feats"][:, ::7, ::5].numpy(), g["feats_sub"]) < TOL
         if "block0_sub" in g:
             assert rel_max(taps["block0"][:, ::7, ::5].numpy(), g["block0_sub"]) < TOL
-    # fixtures must exercise the clamp but not be saturated
+    # fixtures must exercise the clamp but not be saturated (cfg3_causal_trained_short stays below it on purpose, cases.py)
     if c["wrap"].get("output_constraint", "linear") == "linear":
         frac = float((np.abs(g["wav_preclamp"]) > 1).mean())
         assert frac < 0.9
