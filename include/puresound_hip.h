@@ -396,6 +396,19 @@ typedef struct {
   int N, H, D, Q, q_stride, steps, step_stride, ldt, ldq, state_shift;
 } ps_lstm_args;
 int ps_lstm_f32(const ps_lstm_args* args, void* stream);
+/* ps_lstm_f32 with a step count per utterance: a batch of utterances of unequal length (SkiM's bidirectional Mem-LSTM over
+ * each row's own segments, the bidirectional speaker LSTM over each enrolment's own frames).  steps_rows: int32 [N] on the
+ * device; every sequence (n, q) runs s_n = clamp(steps_rows[n], 0, steps) steps -- direction 0 walks the steps 0 .. s_n - 1,
+ * direction 1 walks s_n - 1 .. 0 -- so row n holds on those steps what ps_lstm_f32 computes for that utterance alone with
+ * steps = s_n (the same kernel at H > 64: the same bits).  hout is exact 0.0 at the frames of the steps [s_n, steps) of every
+ * sequence; frames no step of the walk touches are not written.  gx at a step >= s_n is never read (it may hold NaN).
+ * h_last / c_last hold the state after the row's own last step: with s_n = 0 that is h0 / c0 (zeros when NULL).  The
+ * thread-per-gate-row kernel at every H <= 256, exact fp32.
+ * Refusals: NULL args ("ps_lstm_rows_f32: null args") or NULL steps_rows ("ps_lstm_rows_f32: steps_rows is NULL") and
+ * state_shift != 0 ("ps_lstm_rows_f32: state_shift must be 0") are PS_E_INVALID; sizes, strides and ldq are refused as
+ * ps_lstm_f32 refuses them, under this entry's name: "bad argument (...)", "the last frame .. lies outside the row (ldt=..)",
+ * "ldq=.. < Q=.." PS_E_INVALID, "hidden size .. > 256 is not supported" PS_E_UNSUPPORTED. */
+int ps_lstm_rows_f32(const ps_lstm_args* args, const int* steps_rows, void* stream);
 /* The recurrences of nn.RNN (tanh) and nn.GRU (num_layers = 1) -- SingleRNN(rnn_type = "RNN" | "GRU"),
  * /root/reference/puresound/nnet/lobe/rnn.py:19-35; no recipe builds them, the kernel is the plain one.  ps_lstm_args with
  * G = H (RNN) or 3H (GRU: gates r, z, n) gate rows per direction in gx [N][D*G][ldt] and whh_t [D][H][G]; c0 / c_last must be

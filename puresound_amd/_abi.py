@@ -165,6 +165,7 @@ SIGNATURES = {
     "ps_row_stats_f64": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "ps_attn_weights_f32": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "ps_lstm_f32": (C.c_int, [C.POINTER(LstmArgs), _vp]),
+    "ps_lstm_rows_f32": (C.c_int, [C.POINTER(LstmArgs), _vp, _vp]),
     "ps_rnn_f32": (C.c_int, [C.POINTER(LstmArgs), C.c_int, _vp, _vp]),
     "ps_lstm_f16x2_f32": (C.c_int, [C.POINTER(LstmArgs), _vp]),
     "ps_lstm_fmajor_ok": (C.c_int, [C.POINTER(LstmArgs), C.c_int]),

@@ -2,6 +2,8 @@
 // 1x1 conv already produced (W_ih x + b_ih + b_hh); hout on the library's padded channel-major layout [N][D*H][ldt]:
 //
 //   ps_lstm_f32, ps_lstm_f16x2_f32   a 1-layer nn.LSTM (both directions), gx channel-major; dprnn.py:155-171, skim.py:215-222
+//   ps_lstm_rows_f32                 ps_lstm_f32 with a step count per utterance (ragged batches: SkiM's bidirectional Mem-LSTM
+//                                    over each row's own segments, the speaker LSTM over each enrolment's own frames)
 //   ps_rnn_f32                       nn.RNN (tanh) / nn.GRU the same way; lobe/rnn.py:19-35
 //   ps_lstm_fmajor_*                 gx FRAME-MAJOR: H = 128 (lstm_fm.inc; dpcrn.py:34-81), H = 256 / 192 with W_hh streamed from its
 //                                    packed image (lstm_fm256.inc) or resident in the registers of several CUs (lstm_coop.inc)
@@ -28,8 +30,13 @@ struct LstmK {
   ps_lstm_args a;
 };
 
-template <bool WREG>
-__global__ __launch_bounds__(WREG ? 256 : 1024) void lstm_kernel(LstmK k) {
+// ROWS (ps_lstm_rows_f32): utterance n runs s_n = clamp(steps_rows[n], 0, a.steps) steps, not a.steps: s_n stands where
+// a.steps stands in the walk of both directions (direction 1 starts at step s_n - 1), in the prefetch ring's guards (a
+// pre-activation at a step >= s_n is never loaded) and in front of the final states; the frames of the steps [s_n, a.steps)
+// then get exact zeros.  A workgroup holds one utterance, so s_n is uniform.  A compile-time switch (steps_rows is the one
+// extra argument): the plain instantiations keep their instructions.
+template <bool WREG, bool ROWS = false, typename... Extra>
+__global__ __launch_bounds__(WREG ? 256 : 1024) void lstm_kernel(LstmK k, Extra... extra) {
   extern __shared__ float smem[];
   const ps_lstm_args& a = k.a;
   const int H = a.H, G = 4 * H;
@@ -66,7 +73,12 @@ __global__ __launch_bounds__(WREG ? 256 : 1024) void lstm_kernel(LstmK k) {
   // gate pre-activation addressing of row g
   const float* grow = a.gx + ((size_t)n * a.D * G + (size_t)d * G + g) * a.ldt;
   float* hrow = a.hout + ((size_t)n * DH + d * H + j) * a.ldt;
-  const int steps = a.steps;
+  int steps = a.steps;
+  if constexpr (ROWS) {
+    const int* const ex[] = {extra...};  // steps_rows [N]
+    const int sn = ex[0][n];
+    steps = sn < 0 ? 0 : (sn < a.steps ? sn : a.steps);
+  }
   const bool rev = d == 1;
   float pre[LSTM_PF][LS];
 #pragma unroll
@@ -131,6 +143,10 @@ __global__ __launch_bounds__(WREG ? 256 : 1024) void lstm_kernel(LstmK k) {
         __syncthreads();
       }
     }
+  }
+  if constexpr (ROWS) {
+    if (cell)
+      for (int s = steps; s < a.steps; ++s) hrow[(size_t)(q0 + i) * a.q_stride + (size_t)s * a.step_stride] = 0.f;
   }
   if (cell) {
     const size_t off = ((size_t)n * DH + d * H + j) * a.ldq + q0 + i;
@@ -1165,42 +1181,61 @@ static LstmPlan lstm_plan(const ps_lstm_args& a, bool f16x2) {
 }
 
 // ---- entries -------------------------------------------------------------------------------------------------------------
-static int lstm_launch(const ps_lstm_args* args, void* stream, bool f16x2) {
+// steps_rows: NULL, or the per-utterance step counts of ps_lstm_rows_f32 (`who`), which runs the thread-per-gate-row kernel's
+// ROWS instantiations at every H and takes no state_shift.
+static int lstm_launch(const ps_lstm_args* args, void* stream, bool f16x2, const int* steps_rows = nullptr,
+                       const char* who = "ps_lstm_f32") {
   if (!args) {
-    set_error("ps_lstm_f32: null args");
+    set_error("%s: null args", who);
     return PS_E_INVALID;
   }
   const ps_lstm_args& a = *args;
   if (!sizes_ok(a) || a.N > 65535) {
-    set_error("ps_lstm_f32: bad argument (N=%d H=%d D=%d Q=%d steps=%d)", a.N, a.H, a.D, a.Q, a.steps);
+    set_error("%s: bad argument (N=%d H=%d D=%d Q=%d steps=%d)", who, a.N, a.H, a.D, a.Q, a.steps);
     return PS_E_INVALID;
   }
   if (4 * a.H > 1024) {
-    set_error("ps_lstm_f32: hidden size %d > 256 is not supported", a.H);
+    set_error("%s: hidden size %d > 256 is not supported", who, a.H);
     return PS_E_UNSUPPORTED;
   }
   if (last_frame(a) >= a.ldt) {
-    set_error("ps_lstm_f32: the last frame %lld lies outside the row (ldt=%d)", last_frame(a), a.ldt);
+    set_error("%s: the last frame %lld lies outside the row (ldt=%d)", who, last_frame(a), a.ldt);
     return PS_E_INVALID;
   }
   if (!states_ok(a)) {
-    set_error("ps_lstm_f32: ldq=%d < Q=%d", a.ldq, a.Q);
+    set_error("%s: ldq=%d < Q=%d", who, a.ldq, a.Q);
     return PS_E_INVALID;
   }
-  if (!shift_ok(a, 1)) {
-    set_error("ps_lstm_f32: state_shift must be 0 or 1");
+  if (!shift_ok(a, steps_rows ? 0 : 1)) {
+    set_error(steps_rows ? "%s: state_shift must be 0" : "%s: state_shift must be 0 or 1", who);
     return PS_E_INVALID;
   }
-  const LstmPlan p = lstm_plan(a, f16x2);
-  {
+  if (steps_rows) {
+    const dim3 grid((a.Q + LS - 1) / LS, a.N, a.D), block((4 * a.H + 63) / 64 * 64);
+    const size_t lds = (size_t)5 * a.H * sizeof(f32x4);
+    LaunchTimer timer("lstm", (hipStream_t)stream);
+    if (a.H <= LSTM_WREG)
+      hipLaunchKernelGGL((lstm_kernel<true, true, const int*>), grid, block, lds, (hipStream_t)stream, LstmK{a}, steps_rows);
+    else
+      hipLaunchKernelGGL((lstm_kernel<false, true, const int*>), grid, block, lds, (hipStream_t)stream, LstmK{a}, steps_rows);
+  } else {
+    const LstmPlan p = lstm_plan(a, f16x2);
     LaunchTimer timer("lstm", (hipStream_t)stream);
     hipLaunchKernelGGL(p.kernel, p.grid, p.block, p.lds, (hipStream_t)stream, LstmK{a});
   }
-  return launch_status("ps_lstm_f32");
+  return launch_status(who);
 }
 
 extern "C" int ps_lstm_f32(const ps_lstm_args* args, void* stream) { return lstm_launch(args, stream, false); }
 extern "C" int ps_lstm_f16x2_f32(const ps_lstm_args* args, void* stream) { return lstm_launch(args, stream, true); }
+
+extern "C" int ps_lstm_rows_f32(const ps_lstm_args* args, const int* steps_rows, void* stream) {
+  if (!steps_rows) {
+    set_error("ps_lstm_rows_f32: steps_rows is NULL");
+    return PS_E_INVALID;
+  }
+  return lstm_launch(args, stream, false, steps_rows, "ps_lstm_rows_f32");
+}
 
 extern "C" int ps_rnn_f32(const ps_lstm_args* args, int kind, const float* bhn, void* stream) {
   if (!args || (kind != PS_RNN_TANH && kind != PS_RNN_GRU)) {

@@ -560,6 +560,26 @@ def lstm(gx: torch.Tensor, whh_t: torch.Tensor, hidden: int, dirs: int, q: int, 
     return hout, state
 
 
+def lstm_rows(gx: torch.Tensor, whh_t: torch.Tensor, hidden: int, dirs: int, q: int, q_stride: int, steps: int,
+              step_stride: int, steps_rows: torch.Tensor, h0: Optional[torch.Tensor] = None,
+              c0: Optional[torch.Tensor] = None, want_state: bool = False, state_out: Optional[tuple] = None,
+              out: Optional[torch.Tensor] = None):
+    """ps_lstm_rows_f32: lstm() with a step count per utterance (steps_rows int32 [N] on the device, clamped to [0, steps]):
+    row n is, on its first steps_rows[n] steps, lstm() of that utterance alone with that many steps -- direction 1 starts at
+    the row's own last step -- and hout is 0.0 at the frames of the steps behind them; gx there is never read.  Final states:
+    after the row's own last step."""
+    require_device(gx, "lstm_rows")
+    n, rows, ldt = gx.shape
+    if rows != dirs * 4 * hidden or tuple(whh_t.shape) != (dirs, hidden, 4 * hidden):
+        raise RuntimeError("lstm_rows: gx must be [N, D*4H, ldt] and whh_t [D, H, 4H]")
+    _require_operand("lstm_rows", gx.device, gx=gx)
+    _require_limits("lstm_rows", steps_rows, n, gx.device)
+    a, hout, state = _lstm_args("lstm_rows", gx, n, ldt, whh_t, out, hidden, dirs, (q, q_stride, steps, step_stride), h0, c0,
+                                want_state, 0, state_out)
+    check(lib().ps_lstm_rows_f32(C.byref(a), ptr(steps_rows), stream_ptr(gx.device)), "ps_lstm_rows_f32")
+    return hout, state
+
+
 def rnn(gx: torch.Tensor, whh_t: torch.Tensor, kind: str, hidden: int, dirs: int, q: int, q_stride: int, steps: int,
         step_stride: int, bhn: Optional[torch.Tensor] = None, h0: Optional[torch.Tensor] = None, want_state: bool = False):
     """ps_rnn_f32: the recurrence of nn.RNN (tanh) / nn.GRU over pre-activations gx padded [N, D*G, ldt] (G = H or 3H) ->

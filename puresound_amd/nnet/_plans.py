@@ -280,7 +280,8 @@ H_ROWS_KEPT = 8
 H_ROWS_BYTES = 256 << 20
 
 
-def _h_rows(rnn: dict, x: torch.Tensor, t: int, q: int, q_stride: int, steps: int, step_stride: int, lane: int = 0):
+def _h_rows(rnn: dict, x: torch.Tensor, t: int, q: int, q_stride: int, steps: int, step_stride: int, lane: int = 0,
+            per_row: bool = False):
     """Output rows of a recurrence.  When the sequences do not cover the span of t frames (the 2-D maps of DPCRN / DPARN:
     F rows of ld frames, pad frames between them) the recurrence never writes the pad frames, and what follows it --
     projection, LayerNorm, the next GEMM's range maximum -- runs over the whole span: the rows then come from a zeroed
@@ -295,12 +296,13 @@ def _h_rows(rnn: dict, x: torch.Tensor, t: int, q: int, q_stride: int, steps: in
     A lane keeps its most recently used buffers, H_ROWS_KEPT at most and H_ROWS_BYTES together (the one in use always stays); an
     older one is dropped from the plan, never cleared or handed out again, so a captured graph that pinned it
     (graphs._cached_tensors) keeps it, with its pads, to itself, and an eager caller pays one fill per change of geometry.
+    per_row: the walk of hip.lstm_rows, keyed apart from the plain walk of the same geometry.
     None = let the kernel wrapper allocate (every frame is written)."""
     if q * steps >= t:
         return None
     n, _, ldt = x.shape
     shape = (n, rnn["D"] * rnn["H"], ldt)
-    key = (shape, str(x.device), (t, q, q_stride, steps, step_stride))
+    key = (shape, str(x.device), (t, q, q_stride, steps, step_stride) + (("rows",) if per_row else ()))
     bufs = rnn.setdefault("h_rows", {}).setdefault(lane, {})
     buf = bufs.pop(key, None)
     if buf is None:
@@ -372,10 +374,17 @@ def lstm_gates(x: torch.Tensor, t: int, rnn: dict, route: Route, x_amax: Optiona
 
 
 def lstm_recurrence(gx: torch.Tensor, x: torch.Tensor, t: int, rnn: dict, kernel: str, walk: tuple, h0=None, c0=None,
-                    want_state: bool = False, state_shift: int = 0, state_out=None, lane: int = 0):
+                    want_state: bool = False, state_shift: int = 0, state_out=None, lane: int = 0, steps_rows=None):
     """The recurrence entry `kernel` (Route.kernel) over lstm_gates' pre-activations -> (hout [N, D*H, ldt], final states or
-    None); x: the pass's input rows (with the walk they decide where the output rows come from, see _h_rows)."""
+    None); x: the pass's input rows (with the walk they decide where the output rows come from, see _h_rows).  steps_rows
+    (int32 [N] on the device): a step count per utterance -- hip.lstm_rows whatever `kernel` says, channel-major
+    pre-activations and no state_shift."""
     states = (h0, c0, want_state, state_shift, state_out)
+    if steps_rows is not None:
+        if gx.dim() != 3 or gx.shape[1] != rnn["rows"] or state_shift:
+            raise RuntimeError("lstm_recurrence: a per-row step count takes channel-major pre-activations and no state_shift")
+        return hip.lstm_rows(gx, rnn["whh_t"], rnn["H"], rnn["D"], *walk, steps_rows, h0, c0, want_state, state_out,
+                             out=_h_rows(rnn, x, t, *walk, lane, per_row=True))
     if kernel == "fmajor256":
         image, scales = packed(rnn, "whh_h256", hip.pack_whh_h256, rnn["whh_t"])
     out = _h_rows(rnn, x, t, *walk, lane)
@@ -392,8 +401,9 @@ def lstm_recurrence(gx: torch.Tensor, x: torch.Tensor, t: int, rnn: dict, kernel
 
 def lstm_path(x: torch.Tensor, t: int, rnn: dict, proj: dict, norm: dict, q: int, q_stride: int, steps: int,
               step_stride: int, h0=None, c0=None, want_state: bool = False, state_shift: int = 0, state_out=None,
-              amax: Optional[list] = None, skip: bool = True, lane: int = 0):
+              amax: Optional[list] = None, skip: bool = True, lane: int = 0, steps_rows=None):
     """x + LN(proj(LSTM(x))) on padded [N,C,ldt] (dprnn.py:154-172, skim.py:215-227) -> (x', final states).
+    `steps_rows`: lstm_recurrence's (a ragged batch; the caller's plans are exact fp32, whose pre-activations are channel-major).
     `amax`: a one-element list carried from recurrence to recurrence in the fp16x2 arithmetic -- on entry the partial maxima
     of |x| per utterance (or None: measured here), on return those of x' (None when the kernel that made x' has none).
     `lane`: which of the caller's concurrent HIP streams this is (selects the kept output rows, see _h_rows)."""
@@ -404,5 +414,6 @@ def lstm_path(x: torch.Tensor, t: int, rnn: dict, proj: dict, norm: dict, q: int
     route = lstm_route(rnn, x.shape[0], x.shape[2], t, walk,
                        h0 is not None or c0 is not None or want_state or state_out is not None, state_shift)
     gx = lstm_gates(x, t, rnn, route, x_amax)
-    hseq, state = lstm_recurrence(gx, x, t, rnn, route.kernel, walk, h0, c0, want_state, state_shift, state_out, lane)
+    hseq, state = lstm_recurrence(gx, x, t, rnn, route.kernel, walk, h0, c0, want_state, state_shift, state_out, lane,
+                                  steps_rows)
     return _proj_norm(x, hseq, t, rnn, proj, norm, amax, skip), state

@@ -213,8 +213,9 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         :lengths[n]], enroll[n:n+1, :enroll_lengths[n]]) returns for that utterance alone, and exact 0.0 behind them.  Exact
         fp32 products whatever gemm_precision says, one lane (hip_streams is ignored).  Covered: FreeEncDec + a normal-TCN
         ConvTasNet on the fused driver, with an enrolment the td_tse_conv_tasnet_v0 speaker net; on device tensors also the
-        conv-STFT encoder + DPCRN / DPARN (the egs/ns noise suppressors, lookahead presets included); nnet/ragged.py lists
-        the refusals, all raised before any launch."""
+        conv-STFT encoder + DPCRN / DPARN (the egs/ns noise suppressors, lookahead presets included) and FreeEncDec + SkiM
+        without segment overlap (tse_skim_v0[_causal], _v0_causal_vad, _v1_causal: a row never starts from the row above's
+        last segment, as rows of a plain causal batch do); nnet/ragged.py lists the refusals, all raised before any launch."""
         if noisy.device.type == "cpu":  # BASELINE configs[0] / the recipes' --backend cpu: stock ATen (nnet/cpu_path.py)
             from . import cpu_path
             return cpu_path.wrapper_inference(self, noisy, enroll, lengths, enroll_lengths)
@@ -260,6 +261,8 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
         if enroll is not None:
             rel = torch.tensor(ragged.relative_lengths(rp.enroll_t_rows, rp.enroll_frames), dtype=torch.float32)
             rows += [rp.enroll_t_rows, rel.view(torch.int32).tolist()]
+        if rp.seg_rows is not None:   # (SkiM's segments per row: the last of the call's own rows)
+            rows += [rp.seg_rows]
         limits = hip.row_limits("inference", rows + list(more_rows), dev)
         if ragged.spectral(self):
             # conv-STFT encoder + DPCRN / DPARN: analysis, complex mask and synthesis work column by column over all T frames
@@ -278,6 +281,27 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
                 self.keep_scratch("ragged_fp32_plans", 0, own)
             enh = hip.complex_mask(feats, mask, mask_act)
             return enc.decode_padded(enh, t, self.drop_first_bin, out_mode, t_rows=limits[0]), limits
+        if ragged.skim(self):
+            # FreeEncDec + SkiM: encoder, FiLM, projections and the decoder work frame by frame and the Seg-LSTMs segment by
+            # segment over all T frames of the rows as they are, once the features are zero behind T_n; the Mem-LSTMs and a
+            # recurrent speaker net take the per-row limits.  Exact fp32 products on plans of this path's own.
+            spk = [] if enroll is None or self.speaker_net is None else list(self.speaker_net.modules())
+            mods = [m for m in list(self.masker.modules()) + spk if isinstance(m, PlanCache) and not isinstance(m, TCN)]
+            own = self.scratch("ragged_fp32_plans")
+            if own is None or len(own) != len(mods):
+                own = [{"gemm_precision": "fp32"} for _ in mods]
+            try:
+                with own_plans(mods, own):
+                    dvec = None
+                    if enroll is not None:
+                        dvec = self._speaker_embedding(enroll.contiguous(), 0, limits[2], limits[3].view(torch.float32))
+                    feats, t = self.encoder.encode_padded(noisy.contiguous(), self.masker.padded_frames_needed)
+                    mask = self.masker.forward_padded(feats, t, dvec, t_rows=limits[0], seg_rows=limits[-1 - len(more_rows)])
+            finally:
+                self.keep_scratch("ragged_fp32_plans", 0, own)
+            hip.zero_tail(mask, limits[0])
+            wav = self.encoder.decode_padded(feats, t, mask, mask_act, out_mode)
+            return hip.zero_tail(wav, limits[1]), limits
         dvec = None
         if enroll is not None:
             dvec = self._speaker_embedding(enroll.contiguous(), 0, limits[2], limits[3].view(torch.float32))
@@ -595,7 +619,9 @@ class SoTaskWrapModule(EncDecMaskerBaseModel):
                 x = lay.forward_padded(x, t, None)
                 i += 1
             elif isinstance(lay, SingleRNN):                                    # tse_skim_v1_causal
-                x = lay.forward_padded(x, t)
+                if t_rows is not None:   # (the junk behind a row's end may be NaN: nothing multiplies it)
+                    hip.zero_tail(x, t_rows)
+                x = lay.forward_padded(x, t, t_rows)
                 i += 1
             elif isinstance(lay, AttentiveStatisticsPooling):
                 pooled = lay.forward_padded(x, t, rel_lengths, exact_fp32=t_rows is not None)   # [N, 2C]

@@ -33,11 +33,16 @@ class SingleRNN(GemmPlanCache, nn.Module):
             return dict(rnn=rnn_plan(self.rnn, device), proj=linear_plan(self.proj, device))
         return dict(rnn=lstm_plan(self.rnn, device, self.gemm_precision), proj=linear_plan(self.proj, device))
 
-    def forward_padded(self, x: torch.Tensor, t: int) -> torch.Tensor:
-        """padded [N, C, ldt] -> [N, C, ldt]: proj(LSTM(x)) over the t frames of each utterance (lobe/rnn.py:37-55)."""
+    def forward_padded(self, x: torch.Tensor, t: int, t_rows=None) -> torch.Tensor:
+        """padded [N, C, ldt] -> [N, C, ldt]: proj(LSTM(x)) over the t frames of each utterance (lobe/rnn.py:37-55).
+        t_rows (int32 [N] on the device; a ragged batch, LSTM only): utterance n holds t_rows[n] frames and anything behind
+        them, which is never read as data: the recurrence is hip.lstm_rows, whose backward pass starts at the row's own last
+        frame, and row n's first t_rows[n] frames are the utterance's own (behind them: the projection's bias)."""
         p = self._plan_get(x.device, self._build)
         rnn, proj = p["rnn"], p["proj"]
         n, _, ldt = x.shape
+        if t_rows is not None and self.rnn_type != "LSTM":
+            raise NotImplementedError("SingleRNN: a per-row frame limit for the LSTM only")
         if self.rnn_type != "LSTM":
             gx, _ = hip.conv1x1(x, t, rnn["wih"], rnn["rows"], None, rnn["bias"],
                                 out=torch.empty(n, rnn["rows"], ldt, dtype=torch.float32, device=x.device))
@@ -49,7 +54,7 @@ class SingleRNN(GemmPlanCache, nn.Module):
         # of tse_skim_v1: 4000 dependent steps); _plans.lstm_route(standalone=True) says which kernels run
         route = lstm_route(rnn, n, ldt, t, (1, ldt, t, 1), standalone=True)
         gx = lstm_gates(x, t, rnn, route)
-        hseq, _ = lstm_recurrence(gx, x, t, rnn, route.kernel, (1, ldt, t, 1))
+        hseq, _ = lstm_recurrence(gx, x, t, rnn, route.kernel, (1, ldt, t, 1), steps_rows=t_rows)
         y = torch.empty(n, proj["M"], ldt, dtype=torch.float32, device=x.device)
         if route.layout == "fmajor":   # the fp16x2 arithmetic all the way: h is an LSTM output, |h| < 1 is its range
             wf, we = packed(proj, "f16x2", hip.pack_wt_f16x2, proj["w_rows"])

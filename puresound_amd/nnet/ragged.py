@@ -11,8 +11,10 @@ speaker net of plain TCN blocks -> AttentiveStatisticsPooling -> k=1 projection(
 the HIP path also the noise suppressors of egs/ns: the conv-STFT encoder (ConvEncDec, Complex output, (complex, complex)
 masks) in front of a DPCRN or DPARN with bN2d norms on the implicit-GEMM convolution, either transpose_delay, any delay,
 no enrolment (ns_dpcrn_v0[_causal], ns_dparn_v0[_causal]); the CPU path has no stock-ATen DPCRN / DPARN and keeps refusing
-them.  Everything else raises NotImplementedError.  Scoring such a batch: SoTaskWrapModule.inference_scored_ragged (base_nn.py), whose
-model refusals are check_model's and whose length values -- like the `lengths` of the scores in nnet/loss/ -- go through
+them.  On the HIP path also FreeEncDec + SkiM without segment overlap, causal or not, FiLM fusion or no embedding, with the
+plain-TCN speaker net above or SingleRNN(LSTM) -> AttentiveStatisticsPooling -> k=1 projection(s) (tse_skim_v0[_causal],
+tse_skim_v0_causal_vad, tse_skim_v1_causal); the CPU path has no SkiM.  Everything else raises NotImplementedError.
+Scoring such a batch: SoTaskWrapModule.inference_scored_ragged (base_nn.py), whose model refusals are check_model's and whose length values -- like the `lengths` of the scores in nnet/loss/ -- go through
 host_lengths."""
 from typing import List, NamedTuple, Optional, Sequence
 
@@ -65,6 +67,65 @@ def _plain_speaker_net(net) -> bool:
     return all(isinstance(m, nn.Conv1d) and m.kernel_size == (1,) and m.bias is None for m in layers[i + 1:])
 
 
+def _lstm_speaker_net(net) -> bool:
+    """SingleRNN(LSTM) -> AttentiveStatisticsPooling -> Conv1d(k=1, bias=False) projection(s) (tse_skim_v1_causal)"""
+    from .lobe.pooling import AttentiveStatisticsPooling
+    from .lobe.rnn import SingleRNN
+    if not isinstance(net, (nn.ModuleList, nn.Sequential)):
+        return False
+    layers = list(net)
+    if len(layers) < 3 or not isinstance(layers[0], SingleRNN) or layers[0].rnn_type != "LSTM":
+        return False
+    if not isinstance(layers[1], AttentiveStatisticsPooling):
+        return False
+    return all(isinstance(m, nn.Conv1d) and m.kernel_size == (1,) and m.bias is None for m in layers[2:])
+
+
+def skim(w) -> bool:
+    """Whether `w` is of the FreeEncDec + SkiM family (check_model's third branch; _ragged_forward's)."""
+    from .lobe.encoder import FreeEncDec
+    from .skim import SkiM
+    return isinstance(w.encoder, FreeEncDec) and isinstance(w.masker, SkiM)
+
+
+def _check_skim(w, enroll: Optional[torch.Tensor], hip_path: bool, who: str) -> None:
+    """FreeEncDec + SkiM: frames meet in the segment LSTMs (inside one segment: no limit needed once the features are zero
+    behind T_n), in the Mem-LSTM over a row's segments and in a recurrent speaker net over the enrolment's frames, which
+    have a per-row form on the HIP path (ps_lstm_rows_f32; the causal hand-over is shifted inside each row)."""
+    from .lobe.encoder import FreeEncDec
+    from .lobe.rnn import SingleRNN
+    from .lobe.trivial import Gate, SpecAugment
+    m = w.masker
+    if not hip_path:
+        raise NotImplementedError(f"{who}: SkiM behind the FreeEncDec encoder is covered on the HIP path only (the CPU path has "
+                                  f"no stock-ATen SkiM)")
+    if m.seg_overlap:
+        raise NotImplementedError(f"{who}: SkiM with seg_overlap=True is not covered (the split's padding differs per row)")
+    if any(isinstance(f, Gate) for f in getattr(m, "seg_input_fusion", [])):
+        raise NotImplementedError(f"{who}: SkiM with Gate fusion is not covered (FiLM fusion or no embedding)")
+    if w.embedding_free_tse:
+        raise NotImplementedError(f"{who}: embedding_free_tse is not covered")
+    if w.check_mask_pairing(w.mask_type, w.f_type) != "real":
+        raise NotImplementedError(f"{who}: FreeEncDec encoder with (real, real) masks")
+    if enroll is not None:
+        if w.speaker_net is None:
+            raise NotImplementedError(f"{who}: an enrolment needs a speaker_net")
+        enc = w.encoder_spk if w.encoder_spk is not None else w.encoder
+        layers = list(w.speaker_net) if isinstance(w.speaker_net, (nn.ModuleList, nn.Sequential)) else []
+        if any(isinstance(lay, SpecAugment) for lay in layers):
+            raise NotImplementedError(f"{who}: a speaker net with a SpecAugment layer is not covered (its random draws have no "
+                                      f"per-row meaning)")
+        if not isinstance(enc, FreeEncDec):
+            raise NotImplementedError(f"{who}: with an enrolment in front of SkiM, a FreeEncDec enrolment encoder only (got "
+                                      f"{type(enc).__name__})")
+        if any(isinstance(lay, SingleRNN) and lay.rnn_type != "LSTM" for lay in layers):
+            raise NotImplementedError(f"{who}: a SingleRNN speaker net that is not an LSTM is not covered (the per-row "
+                                      f"recurrence is the LSTM's)")
+        if not (_plain_speaker_net(w.speaker_net) or _lstm_speaker_net(w.speaker_net)):
+            raise NotImplementedError(f"{who}: with an enrolment in front of SkiM, a speaker net of plain TCN blocks or "
+                                      f"SingleRNN(LSTM) -> AttentiveStatisticsPooling -> k=1 projection(s) only")
+
+
 def spectral(w) -> bool:
     """Whether `w` is of the conv-STFT family (check_model's second branch; _ragged_forward's)."""
     from .lobe.encoder import ConvEncDec
@@ -113,12 +174,14 @@ def check_model(w, enroll: Optional[torch.Tensor], enroll_lengths, hip_path: boo
     who = "inference with lengths"
     if spectral(w):
         return _check_spectral(w, enroll, hip_path, who)
+    if skim(w):
+        return _check_skim(w, enroll, hip_path, who)
     if not isinstance(w.encoder, FreeEncDec):
         raise NotImplementedError(f"{who}: the FreeEncDec encoder, or the conv-STFT encoder in front of a DPCRN / DPARN "
                                   f"(got {type(w.encoder).__name__})")
     if not isinstance(w.masker, ConvTasNet):
-        raise NotImplementedError(f"{who}: behind the FreeEncDec encoder the Conv-TasNet masker only (got "
-                                  f"{type(w.masker).__name__}; the DPRNN, SkiM and U-Net maskers have no per-row frame limit there)")
+        raise NotImplementedError(f"{who}: behind the FreeEncDec encoder the Conv-TasNet or SkiM masker only (got "
+                                  f"{type(w.masker).__name__}; the DPRNN and U-Net maskers have no per-row frame limit there)")
     if w.masker.tcn_layer.lower() != "normal":
         raise NotImplementedError(f'{who}: tcn_layer="{w.masker.tcn_layer}" is not covered (normal TCN blocks only)')
     if not all(m.fused_norms() for stack in w.masker.tcn_list for m in stack):
@@ -144,6 +207,7 @@ class Plan(NamedTuple):
     enroll_lengths: Optional[List[int]]
     enroll_t_rows: Optional[List[int]]
     enroll_frames: int           # T' of the enrolment rows (0 without one)
+    seg_rows: Optional[List[int]] = None   # SkiM: S_n = T_n // K + 1 segments per row
 
 
 def plan(w, noisy: torch.Tensor, enroll: Optional[torch.Tensor], lengths, enroll_lengths,
@@ -168,7 +232,8 @@ def plan(w, noisy: torch.Tensor, enroll: Optional[torch.Tensor], lengths, enroll
                               enc.win_length)
         e_rows = [frames(v, enc.win_length, enc.hop_length) for v in e_lens]
         e_frames = frames(e_len, enc.win_length, enc.hop_length)
-    return Plan(lens, t_rows, [(t - 1) * hop + win for t in t_rows], e_lens, e_rows, e_frames)
+    seg_rows = [t // w.masker.seg_size + 1 for t in t_rows] if skim(w) else None
+    return Plan(lens, t_rows, [(t - 1) * hop + win for t in t_rows], e_lens, e_rows, e_frames, seg_rows)
 
 
 def relative_lengths(t_rows: Sequence[int], t: int) -> List[float]:

@@ -66,10 +66,13 @@ class MemLSTM(GemmPlanCache, nn.Module):
         return p["units"]
 
     def forward_state(self, h: torch.Tensor, c: torch.Tensor, s: int, h_states=None, c_states=None,
-                      want_states: bool = False, per_frame_sequences: bool = False):
+                      want_states: bool = False, per_frame_sequences: bool = False, seg_rows: Optional[torch.Tensor] = None):
         """h, c: state layout [N, D*H, ldS] with S frames.  Offline: every utterance is one sequence over its S
         segments.  per_frame_sequences (streaming): every frame is its own one-step sequence with carried LSTM
-        states.  Returns (h', c', h_states', c_states'); the causal shift is left to the consumer."""
+        states.  Returns (h', c', h_states', c_states'); the causal shift is left to the consumer.
+        seg_rows (int32 [N] on the device; a ragged batch): utterance n holds seg_rows[n] segments.  The bidirectional net
+        then runs hip.lstm_rows, whose backward pass starts at the row's own last segment; the causal net needs no limit
+        (nothing behind a row's last segment reaches a segment in front of it) and runs as it is."""
         p = self._plan_get(h.device, self._build)
         outs, states = [], []
         for key, v, st in (("h", h, h_states), ("c", c, c_states)):
@@ -79,7 +82,7 @@ class MemLSTM(GemmPlanCache, nn.Module):
                                    want_state=True)
             else:
                 y, new = lstm_path(v, s, *p[key], q=1, q_stride=0, steps=s, step_stride=1, h0=h0, c0=c0,
-                                   want_state=want_states)
+                                   want_state=want_states, steps_rows=seg_rows if self.bi_direct else None)
             outs.append(y)
             states.append(new)
         return outs[0], outs[1], states[0], states[1]
@@ -161,6 +164,13 @@ class SegLSTM(GemmPlanCache, nn.Module):
         return hip.unpad_rows(y, k).transpose(1, 2).contiguous(), back(hl), back(cl)
 
 
+def _shift_segments(v: torch.Tensor, s: int) -> torch.Tensor:
+    """state layout [N, D*H, ldS] with S segments -> the same with segment q holding segment q - 1 and zeros in segment 0"""
+    out = torch.zeros_like(v)
+    out[..., 1:s] = v[..., :s - 1]
+    return out
+
+
 def _out_size(ctor, x, aux, params):
     return (x[0], ctor["output_size"], x[2])
 
@@ -230,8 +240,21 @@ class SkiM(GemmPlanCache, nn.Module):
         return y
 
     def forward_padded(self, x_pad: torch.Tensor, t: int, embed: Optional[torch.Tensor] = None,
-                       lane: int = 0) -> torch.Tensor:
-        """padded [N,C,ldt] (zero beyond T, ldt >= padded_frames_needed(T)), embed [N,E] -> mask logits padded."""
+                       lane: int = 0, t_rows: Optional[torch.Tensor] = None,
+                       seg_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """padded [N,C,ldt] (zero beyond T, ldt >= padded_frames_needed(T)), embed [N,E] -> mask logits padded.
+        t_rows, seg_rows (int32 [N] on the device, both or neither; a ragged batch, nnet/ragged.py): utterance n holds
+        t_rows[n] frames in seg_rows[n] = t_rows[n] // K + 1 segments and anything behind them.  x_pad is cleared behind
+        t_rows[n] IN PLACE (the utterance alone sees zeros up to its last segment's end; it removes every NaN), each Mem-LSTM
+        takes the rows' segment counts, and the causal hand-over is per row: segment 0 of every utterance starts from zeros
+        (the plain call hands it utterance n - 1's last segment, as the reference does).  Row n's logits are the utterance's own
+        on its first t_rows[n] frames and finite junk behind them."""
+        if (t_rows is None) != (seg_rows is None):
+            raise ValueError("SkiM.forward_padded: t_rows and seg_rows come together")
+        if t_rows is not None:
+            if self.seg_overlap:
+                raise NotImplementedError("SkiM.forward_padded: seg_overlap=True has no per-row frame limit")
+            hip.zero_tail(x_pad, t_rows)
         if self.seg_overlap:
             x_pad, tp = hip.segment_split(x_pad, t, self.seg_size)     # SkiM.split (skim.py:334-369)
         else:
@@ -247,8 +270,11 @@ class SkiM(GemmPlanCache, nn.Module):
             x = self._fuse(i, x, tp, embed)
             x, (h, c) = self.seg_lstm[i].forward_padded(x, tp, s, k, h, c, shift)
             if i < self.n_blocks - 1:
-                h, c, _, _ = self.mem_lstm[i].forward_state(h, c, s)
+                h, c, _, _ = self.mem_lstm[i].forward_state(h, c, s, seg_rows=seg_rows)
                 shift = 1 if self.causal else 0
+                if shift and seg_rows is not None:
+                    # the hand-over inside each row: the states move one segment back, zeros in front (two small tensors)
+                    h, c, shift = _shift_segments(h, s), _shift_segments(c, s), 0
         if self.seg_overlap:
             x = hip.segment_merge(x, tp, t, self.seg_size)              # SkiM.merge (skim.py:371-408)
         return self._output(x, t)
